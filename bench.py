@@ -12,7 +12,7 @@ conversion) and -- for N > 1 -- the RCCL gather of the finished tiles to the roo
 (RayTracerImpl.cu:236-315 without the GUI hand-off).  Workload at N=1: BASELINE.json configs[2] = C3
 (Cornell-box 32 triangles, thin-lens DoF, 1920x1080, 16 spp), the configuration the metric is quoted
 on.  For N > 1 the headline record keeps per-GPU work fixed ("weak": the frame grows to 1920 x (1080*N),
-one 1080-row band per GPU) and the same line carries a second record, `c5_strong`: BASELINE.json
+one 1080-row band per GPU) and with --full the same line carries a second record, `c5_strong`: BASELINE.json
 configs[4], the 10k-triangle scene at 3840x2160x256 spp as ONE frame in N row bands.  If the box has
 fewer devices than N (a 1-GPU box), the single-process form places the bands round-robin on what is
 there and says so (`config.devices`).
@@ -21,29 +21,40 @@ Before the W warmup steps every device is brought to its steady clocks with the 
 record (`clock_preheat`, 150 ms, no step of the path in it: a cold MI355X needs ~25 ms of load to ramp, which is longer than
 a short run's whole timed region; tools/clock_ramp.py, --no-preheat).
 
+A plain run does only what the headline needs: set up, one untimed step and one untimed batch of the W + K steps (the
+device work the timed steps have always followed; the batch sizes the library's pool of timing events, see main()), preheat,
+W warmup steps, the K timed steps, --dump-outputs DIR if given, the line.  Every record below marked (--full) is measured only
+with --full, which runs them beside the headline as before.
+
+  --dump-outputs DIR  after the timed steps, what the last of them computed, as DIR/<name>.npy (float32, or float64 where
+                      float32 would round): `image` (the BGRA8 frame a caller receives, channels B, G, R, A), `render` (the fp32
+                      accumulators), `counts` (samples per pixel) and `rng` (the persisted RNG states {d, v0..v4}).  When the
+                      whole of it exceeds 60 MiB, every array holds the same fixed, seeded sample of its pixels, listed as flat
+                      pixel indices in DIR/<name>_pixels.npy.  Same arguments, same inputs: two builds compare output for output.
+
 Prints ONE JSON line on rank 0 with
   roofline      HBM: algorithmic bytes per launch / live HIP-event kernel time vs 8 TB/s (contractual
                 bound), frac_wall = the same bytes / wall time per step, and the R = 48 accounting beside it
-  valu          the binding bound: VALU instructions issued per launch (PMC pass, stamped with the kernel
+  valu          (--full) the binding bound: VALU instructions issued per launch (PMC pass, stamped with the kernel
                 source hash: null + stale when the loaded library is a different build) against the wave64
                 issue rate this device sustains (calibrated live); `algorithmic` = the reference's
                 full-scan flops for context (a ratio, not a utilisation)
   gather_ms     N > 1: device time of one tile gather on the root's gather stream
-  group         N > 1: transport, RCCL version, the ranks and device of every communicator of this process (ncclCommCount /
+  group         (--full) N > 1: transport, RCCL version, the ranks and device of every communicator of this process (ncclCommCount /
                 ncclCommCuDevice: what RCCL itself says it spans), and gather_only_ms = one exchange without tracing
-  c5_strong     N > 1: the strong-scaling record; measured after the headline under a watchdog (RT_MI355X_C5_TIMEOUT, 300 s):
+  c5_strong     (--full) N > 1: the strong-scaling record; measured after the headline under a watchdog (RT_MI355X_C5_TIMEOUT, 300 s):
                 if it or the final barrier blocks, rank 0 still prints the line, with the reason in c5_strong.error
                 (a sharded run that makes no progress before the headline is measured ends after RT_MI355X_BENCH_TIMEOUT,
                 900 s, with value null and the phase it was in)
-  warm_lists    NOT the headline: the same steps with the library's default list reuse across Traces
-  full_path_all_tiles  NOT the headline: the same steps with certain-winner tiles switched off (every tile traces its rays)
-  cpu_baseline  the oracle (scalar CPU port of the reference kernel) timed on this box's cores, N = 1 only: 16 threads,
+  warm_lists    (--full) NOT the headline: the same steps with the library's default list reuse across Traces
+  full_path_all_tiles  (--full) NOT the headline: the same steps with certain-winner tiles switched off (every tile traces its rays)
+  cpu_baseline  (--full) the oracle (scalar CPU port of the reference kernel) timed on this box's cores, N = 1 only: 16 threads,
                 one thread, and every core of the process's affinity mask, with the CPU model string
-  parity_check  N = 1: ONE untimed headline step on the fresh tracer, before anything else runs, compared (CRC32 of render /
+  parity_check  (--full) N = 1: ONE untimed headline step on the fresh tracer, before anything else runs, compared (CRC32 of render /
                 counts / RNG states / image) with the committed golden frame of the same configuration
                 (tests/golden/frames.json: data, generated by the oracle in the build container)
-  cold          NOT the headline: the same W + K steps measured BEFORE the clock preheat (what --no-preheat gives)
-  full_scan     NOT the headline: the same steps with RT_FLAG_NO_BINNING -- every ray tests every triangle, the reference's
+  cold          (--full) NOT the headline: the same W + K steps measured BEFORE the clock preheat (what --no-preheat gives)
+  full_scan     (--full) NOT the headline: the same steps with RT_FLAG_NO_BINNING -- every ray tests every triangle, the reference's
                 algorithm (Kernels.cuh:75-92) -- and, `reference_order`, with the wave-uniform early-outs off as well
 Exit codes: 0 ok; 2 the job could not be set up; 3 no progress before the headline was measured; 4 the headline was printed
 but the extra N > 1 record or the final barrier blocked (the phase and the rank are on stderr).
@@ -351,6 +362,48 @@ def api_end_to_end(cfg, tris, traces=200):
     return rec
 
 
+DUMP_BYTES = 60 * 2 ** 20      # --dump-outputs: at most this much in all, beyond it a seeded sample of the pixels
+DUMP_SEED = 1234
+
+
+def dump_outputs(dirname, job, n_parts, rank):
+    """--dump-outputs: the buffers of the last timed step as DIR/<name>.npy (module docstring).  Called on every rank (a rank
+    other than 0 only waits for its part of the gather); rank 0 writes and returns what it wrote for the line."""
+    t = job.tracer
+    if job.world > 1:
+        frame = job.exchange.frame(job)              # rank 0: the gathered frame, None elsewhere
+    elif n_parts > 1:
+        frame = t.Frame()
+    else:
+        frame = t.Image()
+    if rank != 0:
+        return None
+    # name: (pixels-first array, dtype written).  float32 holds the BGRA8 bytes and the counts (< 2^24) exactly; the RNG
+    # words are uint32 and need float64.  N > 1 in several processes: render / counts / rng are rank 0's band.
+    arrays = {"image": (np.ascontiguousarray(frame).view(np.uint8).reshape(frame.shape[0], frame.shape[1], 4), np.float32),
+              "render": (t.RenderBuffer(), np.float32),
+              "counts": (t.SampleCounts(), np.float32),
+              "rng": (t.RngStates(), np.float64)}
+    os.makedirs(dirname, exist_ok=True)
+    full = sum(a.size * np.dtype(dt).itemsize for a, dt in arrays.values())
+    # every array keeps the same fraction of its pixels (+ a float64 index per kept pixel), so that the whole fits DUMP_BYTES
+    frac = 1.0 if full <= DUMP_BYTES else DUMP_BYTES / float(full + sum(8 * a.shape[0] * a.shape[1] for a, _ in arrays.values()))
+    rec = {"dir": dirname, "arrays": {}, "bytes": 0}
+    for name, (a, dt) in arrays.items():
+        n_pix = a.shape[0] * a.shape[1]
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pix, int(n_pix * frac), replace=False))
+            a = a.reshape((n_pix,) + a.shape[2:])[idx]
+            np.save(os.path.join(dirname, name + "_pixels.npy"), idx.astype(np.float64))
+            rec["bytes"] += idx.size * 8
+        a = a.astype(dt)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        rec["arrays"][name] = list(a.shape)
+        rec["bytes"] += a.nbytes
+    rec["sampled"] = frac < 1.0
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -372,7 +425,15 @@ def main():
                          "(a rehearsal of the sharded path, NOT a scaling measurement: n_gpus on the line stays the number of distinct devices)")
     ap.add_argument("--samples-in-flight", type=int, default=0)
     ap.add_argument("--lds-chunk", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every record beside the headline (parity_check, cold, group, warm_lists, full_path_all_tiles, "
+                         "full_scan, c4, api_end_to_end, valu, cpu_baseline, c5_strong); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    if not args.full:                  # the --no-* switches below select among the --full records
+        args.no_warm = args.no_valu = args.no_c4 = args.no_e2e = args.no_c5 = True
+        args.cpu_rows = 0
 
     import raytracertest_amd as R
     from raytracertest_amd import api, scenes
@@ -442,16 +503,22 @@ def main():
     job.tracer.SetListReuse(False)
     phase["name"] = "measuring the headline steps"
     # Parity accompanies the timing: the very first step of the fresh tracer -- the launch shape the timed
-    # steps use -- is compared with the committed golden frame before anything else runs.  Untimed.
+    # steps use -- is compared (--full) with the committed golden frame before anything else runs.  Untimed; a plain run
+    # takes the step as well, so that its device work before the timed steps is the same.
     parity = None
     if n_parts == 1 and not args.no_parity:
         job.step()
         job.finish()
-        parity = parity_check(args.config, job.tracer)
-    # the same W + K steps on the device as it is found (clocks not ramped): reported as `cold`, never as `value`
+        if args.full:
+            parity = parity_check(args.config, job.tracer)
+    # Part of the headline's warm-up: the same W + K steps once on the device as it is found.  The library takes a new
+    # timing-event pair whenever its pool is empty, and that pool grows with the launches in flight: the first batch of K
+    # launches pays for the growth (K = 1000: 1 % per step when the timed batch is the first).  With --full the batch is
+    # measured and reported as `cold` (clocks not ramped), never as `value`.
     cold = None
     if not args.no_preheat and n_parts == 1:
         rc = timed_steps(job, args.steps, args.warmup)
+    if args.full and not args.no_preheat and n_parts == 1:
         cold = {"value": round(cfg["width"] * cfg["height"] * cfg["samples"] * cfg["iterations"] * args.steps / rc["elapsed"] / 1e6, 2),
                 "unit": "Mray/s", "ms_per_step": round(rc["elapsed"] / args.steps * 1e3, 5),
                 "kernel_us": round(rc["kernel_ms"] / max(rc["launches"], 1) * 1e3, 2),
@@ -459,8 +526,12 @@ def main():
                         "reports (a cold MI355X needs ~25 ms of load to reach its steady clocks)" % (args.warmup, args.steps)}
     heat = {} if args.no_preheat else preheat(devices if devices else [local_rank])
     res = timed_steps(job, args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs:
+        phase["name"] = "reading back the outputs of the last step"
+        dumped = dump_outputs(args.dump_outputs, job, n_parts, rank)
     group = None
-    if n_parts > 1:
+    if n_parts > 1 and args.full:
         # what the exchange is made of (transport, RCCL version, how many ranks the communicator really has, on which devices)
         # and what it costs on its own: five gathers of the tiles as they are, no tracing
         phase["name"] = "measuring the gather on its own"
@@ -570,12 +641,15 @@ def main():
                 if n_parts > 1:
                     out["config"]["devices"] = [b["device"] for b in bands] if bands and len(bands) > 1 else list(range(n_parts))
                     out["gather_ms"] = round(res["gather_ms"] / res["gathers"], 4) if res["gathers"] else 0.0
-                    out["group"] = group
+                    if group is not None:
+                        out["group"] = group
                     out["gather_note"] = ("device time of one gather on the root's gather stream (HIP events around the grouped ncclSend/ncclRecv; "
                                           "includes waiting for the slowest peer's tile); it overlaps the next step's tracing.  0 with every band "
                                           "on the root device: those tiles are written in place by the trace kernel")
                     if c5 is not None:
                         out["c5_strong"] = c5
+                if dumped is not None:
+                    out["dump_outputs"] = dumped
                 if warm is not None:
                     out["warm_lists"] = warm
                 if cold is not None:

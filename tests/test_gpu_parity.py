@@ -679,7 +679,8 @@ def test_two_rank_rehearsal_of_the_multi_gpu_driver(rt):
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"],
                              capture_output=True, text=True, timeout=600, env=env)
         assert out.returncode == 2 and "--allow-alias" in out.stderr and not out.stdout.strip(), out.stdout[-2000:] + out.stderr[-2000:]
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--allow-alias"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--allow-alias",
+                          "--full"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

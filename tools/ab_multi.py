@@ -1,5 +1,5 @@
 import os, subprocess, sys, json
-root = "/root/repo"
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 libs = sys.argv[2:]
 rounds = int(sys.argv[1])
 res = {l: [] for l in libs}

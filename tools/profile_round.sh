@@ -24,9 +24,9 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$S/pmc_write_c
 grep '^{"metric"' "$O/stats.log" > "$O/bench_c3_under_rocprof.json"
 python3 tools/step_periods.py "$S/stats" > "profiles/${TAG}_c3_step_periods.txt" 2>&1 || true
 echo "summary";   python3 tools/pmc_summary.py "$TAG" "$S" > "$O/pmc_summary.log" 2>&1 || { cat "$O/pmc_summary.log"; exit 1; }
-echo "bench";     python3 bench.py > "profiles/${TAG}_bench_c3.json" 2> "$O/bench_c3_final.err" || exit 1
-python3 bench.py --steps 20 --warmup 5 > "profiles/${TAG}_bench_c3_steps20.json" 2>> "$O/bench_c3_final.err" || exit 1
-python3 bench.py --config C4 --steps 30 --warmup 5 > "profiles/${TAG}_bench_c4.json" 2> "$O/bench_c4_final.err" || exit 1
+echo "bench";     python3 bench.py --full > "profiles/${TAG}_bench_c3.json" 2> "$O/bench_c3_final.err" || exit 1
+python3 bench.py --full --steps 20 --warmup 5 > "profiles/${TAG}_bench_c3_steps20.json" 2>> "$O/bench_c3_final.err" || exit 1
+python3 bench.py --full --config C4 --steps 30 --warmup 5 > "profiles/${TAG}_bench_c4.json" 2> "$O/bench_c4_final.err" || exit 1
 mkdir -p "$O/profiles"
 cp profiles/${TAG}_* profiles/hbm_traffic.json profiles/valu_issue.json "$O/profiles/"
 cat "$O/pmc_summary.log"
