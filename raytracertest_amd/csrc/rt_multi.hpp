@@ -1,5 +1,5 @@
 // rt_multi.hpp -- one frame sharded in contiguous row bands over several GPUs.
-// Included by rt_tracer.hip behind the definition of struct rt_tracer (same translation unit).
+// Included by rt_tracer.hpp behind the definition of struct rt_tracer.
 //
 // The reference drives ONE rt::RayTracer on device 0 (OpenGLView/MainFrame.cpp:44-45,
 // OpenGLView/GLCanvas.cpp:259-260).  Pixels are independent and a pixel's RNG stream is keyed by its
@@ -24,7 +24,7 @@
 
 #include "rt_rccl.hpp"
 
-namespace {
+namespace rtr {
 
 #define RCCL_CHECK(expr)                                                                              \
   do {                                                                                                \
@@ -32,7 +32,7 @@ namespace {
     if (r_ != ncclSuccess) throw HipFail{fmt("%s failed: %s", #expr, rtc::Rccl::get().GetErrorString(r_))}; \
   } while (0)
 
-rtc::Rccl& need_rccl() {
+inline rtc::Rccl& need_rccl() {
   rtc::Rccl& r = rtc::Rccl::get();
   if (!r.ok()) throw HipFail{"RCCL is needed for a frame sharded over several devices and could not be loaded: " + r.why};
   return r;
@@ -340,4 +340,4 @@ struct MultiState {
   }
 };
 
-}  // namespace
+}  // namespace rtr

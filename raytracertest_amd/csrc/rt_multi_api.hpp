@@ -3,7 +3,7 @@
 // block; the C functions there dispatch here when the handle is one of the two.
 #pragma once
 
-namespace {
+namespace rtr {
 
 bool env_on(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
 
@@ -18,11 +18,7 @@ void multi_sync_all(rt_tracer* t) {
   MultiState& m = *t->mg;
   for (rt_tracer* b : m.bands) {
     b->use_device();
-    const uint64_t seen = b->event_seq_now();        // a running render thread may enqueue more meanwhile
-    HIP_CHECK(hipStreamSynchronize(b->main_stream()));
-    b->sync_list_stream();
-    b->stagger_next = true;
-    b->drain_events_before(seen);
+    b->sync_all();
   }
   m.group.sync();
 }
@@ -510,4 +506,4 @@ size_t member_band_index(rt_tracer* t) {
   return 0;
 }
 
-}  // namespace
+}  // namespace rtr
