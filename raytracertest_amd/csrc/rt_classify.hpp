@@ -229,12 +229,6 @@ __device__ __forceinline__ TileFamily make_family(const TraceParams& p, const Fo
 #ifndef RT_LISTS_WAVES
 #define RT_LISTS_WAVES 5      // region_lists_kernel: waves per SIMD the allocator must allow (its VGPRs are taken from the trace waves it runs beside)
 #endif
-#ifndef RT_TRACE_THIRD_BLOCK
-#define RT_TRACE_THIRD_BLOCK true
-#endif
-#ifndef RT_TRACE_THIRD_WAVE
-#define RT_TRACE_THIRD_WAVE (!PRE)
-#endif
 template <bool FORMS = false, bool SURE = false, class SL = SlackProduct, bool THIRD = !FORMS>
 __device__ __forceinline__ bool tile_misses_triangle(const TileFamily& f, V3 v0, V3 e1, V3 e2, float* forms = nullptr,
                                                      bool* sure_hit = nullptr, float* q = nullptr, float* dbg = nullptr,

@@ -1,12 +1,12 @@
 // rt_dense.hpp -- dense scenes (4 096 ... 50 000 triangles, the per-sample forms): the per-wave candidate lists as a structure of
-// their own in HBM, built by wave_lists_kernel, read by trace_kernel<.., PRE, HBM> (rt_trace.hpp).
+// their own in HBM, built by wave_lists_kernel, read by trace_kernel<.., TracePath::DenseLists> (rt_trace.hpp).
 //
 // rt::Radiance tests every triangle for every ray (RayTracer/Kernels.cuh:75-92).  Rounds 1-3 classified inside the trace kernel:
 // every wave of EVERY launch walked macro list -> block list -> its own list and kept the survivors' records and per-sample
 // forms in LDS.  The lists depend on camera, scene and frame, not on the samples -- like the macro lists and the small scenes'
 // tile lists they are an acceleration structure -- so wave_lists_kernel runs that three-level classification once per key (the
 // same focal_bounds, make_family, block pre-cull and tile_misses_triangle calls, the same forms) and writes per 8x8 tile a
-// header and the survivors, ascending, 64 bytes each; the trace kernel's HBM instantiation contains no classification and no
+// header and the survivors, ascending, 64 bytes each; the trace kernel's DenseLists instantiation contains no classification and no
 // barrier: a wave copies its tile's records into its LDS slot and runs the candidate loop of round 3.  Accumulating launches
 // of a Trace (and, with list reuse across Traces, every launch of an unchanged view) skip the build.
 // A tile whose survivors exceed the list's capacity is marked and falls back to the exact tests over its macro tile's list

@@ -304,79 +304,16 @@ hipError_t launch_prep_triangles(bool fma, bool edges, const float4* verts, uint
   return hipGetLastError();
 }
 
-// small-scene kernels (BIN && ONEPASS): a block of four tiles is 4 / RT_SMALL_WG_WAVES workgroups (trace_kernel)
-constexpr uint32_t kSmallWgWaves = RT_SMALL_WG_WAVES;
-static_assert(kSmallWgWaves == 1u || kSmallWgWaves == 2u || kSmallWgWaves == 4u, "waves per small-scene workgroup");
-
-uint32_t trace_lds_bytes(const TraceParams& p, bool bin) {
-  if (bin) {
-    const bool large = p.n_tris > p.bin_list;
-    const uint32_t per_candidate = (large && (p.flags & TRACE_PRETEST)) ? 104u : 40u;
-    return (large ? 4u : kSmallWgWaves) * p.bin_list * per_candidate + (large ? p.block_list * 4u + 160u : 0u);
-  }
-  const uint32_t staged = p.n_tris < p.chunk ? p.n_tris : p.chunk;
-  return staged * 36u;
-}
-
-template <bool FMA, bool FILTER, bool STATS, bool BIN, bool ONEPASS>
-static void launch_trace_o(const TraceParams& p, int K, dim3 grid, size_t lds, hipStream_t st) {
-  dim3 blk(256);
-  if (BIN && ONEPASS) { grid.x *= 4u / kSmallWgWaves; blk.x = 64u * kSmallWgWaves; }
-  switch (K) {
-    case 1: hipLaunchKernelGGL((trace_kernel<FMA, 1, FILTER, STATS, BIN, ONEPASS>), grid, blk, lds, st, p); break;
-    case 2: hipLaunchKernelGGL((trace_kernel<FMA, 2, FILTER, STATS, BIN, ONEPASS>), grid, blk, lds, st, p); break;
-    default: hipLaunchKernelGGL((trace_kernel<FMA, 4, FILTER, STATS, BIN, ONEPASS>), grid, blk, lds, st, p); break;
+uint32_t trace_lds_bytes(const TraceParams& p, TracePath path) {
+  switch (path) {
+    case TracePath::FullScan: return (p.n_tris < p.chunk ? p.n_tris : p.chunk) * 36u;
+    case TracePath::SmallLists: return 4u * p.bin_list * 40u;
+    case TracePath::DenseLists: return 4u * p.bin_list * 116u;        // four waves' records + forms + colours; no block list
+    default: return 4u * p.bin_list * (path == TracePath::ClassifyForms ? 104u : 40u) + p.block_list * 4u + 160u;
   }
 }
 
-template <bool FMA, bool FILTER, bool STATS, bool BIN>
-static void launch_trace_k(const TraceParams& p, int K, dim3 grid, size_t lds, hipStream_t st) {
-  // one classification pass suffices when the whole scene fits the per-wave candidate list
-  if (BIN && p.n_tris <= p.bin_list) launch_trace_o<FMA, FILTER, STATS, BIN, BIN>(p, K, grid, lds, st);
-  else launch_trace_o<FMA, FILTER, STATS, BIN, false>(p, K, grid, lds, st);
-}
-
-template <bool FMA, bool FILTER, bool STATS>
-static void launch_trace_b(const TraceParams& p, bool bin, int K, dim3 grid, size_t lds, hipStream_t st) {
-  if (bin) launch_trace_k<FMA, FILTER, STATS, true>(p, K, grid, lds, st);
-  else launch_trace_k<FMA, FILTER, STATS, false>(p, K, grid, lds, st);
-}
-
-template <bool FMA, bool STATS>
-static void launch_trace_f(const TraceParams& p, bool filter, bool bin, int K, dim3 grid, size_t lds, hipStream_t st) {
-  if (filter) launch_trace_b<FMA, true, STATS>(p, bin, K, grid, lds, st);
-  else launch_trace_b<FMA, false, STATS>(p, bin, K, grid, lds, st);
-}
-
-// Large-scene kernels with the per-sample forms (TRACE_PRETEST): filtered + classified only; STATS and FUSE variants
-template <bool FMA, bool STATS, bool FUSE>
-static void launch_trace_pre(const TraceParams& p, int K, dim3 grid, size_t lds, hipStream_t st) {
-#define RT_PRE(KK) hipLaunchKernelGGL((trace_kernel<FMA, KK, true, STATS, true, false, FUSE, true>), grid, dim3(256), lds, st, p)
-  if (K == 1) RT_PRE(1); else if (K == 2) RT_PRE(2); else RT_PRE(4);
-#undef RT_PRE
-}
-
-template <bool FMA>
-static void launch_trace_fused(const TraceParams& p, int K, dim3 grid, size_t lds, hipStream_t st) {
-  const bool onepass = p.n_tris <= p.bin_list;
-  if (!onepass && (p.flags & TRACE_PRETEST)) { launch_trace_pre<FMA, false, true>(p, K, grid, lds, st); return; }
-#define RT_FUSED(KK, OP) hipLaunchKernelGGL((trace_kernel<FMA, KK, true, false, true, OP, true>), grid, blk, lds, st, p)
-  dim3 blk(256);
-  if (onepass) { grid.x *= 4u / kSmallWgWaves; blk.x = 64u * kSmallWgWaves; }
-  if (onepass) { if (K == 1) RT_FUSED(1, true); else if (K == 2) RT_FUSED(2, true); else RT_FUSED(4, true); }
-  else { if (K == 1) RT_FUSED(1, false); else if (K == 2) RT_FUSED(2, false); else RT_FUSED(4, false); }
-#undef RT_FUSED
-}
-
-bool trace_can_fuse(bool filter, bool bin) { return filter && bin; }
-
-// dense scenes with lists in HBM (rt_dense.hpp): default, un-instrumented launches only
-template <bool FMA, bool FUSE>
-static void launch_dense(const TraceParams& p, int K, dim3 grid, size_t lds, hipStream_t st) {
-#define RT_DENSE(KK) hipLaunchKernelGGL((trace_kernel<FMA, KK, true, false, true, false, FUSE, true, true>), grid, dim3(256), lds, st, p)
-  if (K == 1) RT_DENSE(1); else if (K == 2) RT_DENSE(2); else RT_DENSE(4);
-#undef RT_DENSE
-}
+bool trace_can_fuse(TracePath path, bool filter) { return filter && path != TracePath::FullScan; }
 
 hipError_t launch_wave_lists(const TraceParams& p, bool fma, hipStream_t st) {
   if (p.wave_lists == nullptr || p.rows == 0u || p.W == 0u) return hipSuccess;
@@ -387,54 +324,80 @@ hipError_t launch_wave_lists(const TraceParams& p, bool fma, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, bool bin, int K, hipStream_t st) {
+// One launch of path P with K samples per pass.  Only the variants the host asks for exist, each a kernel of its own: every
+// path filtered or not and instrumented or not -- the forms paths filtered only, DenseLists never instrumented -- and the
+// filtered, un-instrumented kernels of every path but FullScan with fused iterations too (launch_trace checks the rest).
+template <bool FMA, int K, TracePath P>
+static void launch_trace_kernel(const TraceParams& p, bool filter, dim3 grid, size_t lds, hipStream_t st) {
+  constexpr bool FORMS = P == TracePath::ClassifyForms || P == TracePath::DenseLists;
+  if constexpr (P != TracePath::FullScan) {
+    if (p.iters > 1u) { hipLaunchKernelGGL((trace_kernel<FMA, K, true, false, P, true>), grid, dim3(256), lds, st, p); return; }
+  }
+  if constexpr (!FORMS) {
+    if (!filter) {
+      if (p.stats != nullptr) hipLaunchKernelGGL((trace_kernel<FMA, K, false, true, P>), grid, dim3(256), lds, st, p);
+      else hipLaunchKernelGGL((trace_kernel<FMA, K, false, false, P>), grid, dim3(256), lds, st, p);
+      return;
+    }
+  }
+  if constexpr (P != TracePath::DenseLists) {
+    if (p.stats != nullptr) { hipLaunchKernelGGL((trace_kernel<FMA, K, true, true, P>), grid, dim3(256), lds, st, p); return; }
+  }
+  hipLaunchKernelGGL((trace_kernel<FMA, K, true, false, P>), grid, dim3(256), lds, st, p);
+}
+
+static constexpr int variant(TracePath path, int K) { return static_cast<int>(path) * 8 + K; }
+
+hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, TracePath path, int K, hipStream_t st) {
   // samples == 0 is a real launch, as in the reference (TraceKernel with sampleCount 0: counts += 0,
   // render += 0, RNG written back, Kernels.cuh:133-146): the fused clear / BGRA8 emit / list store of the
   // launch still have to happen
   if (p.rows == 0 || p.W == 0) return hipSuccess;
+  const bool forms = path == TracePath::ClassifyForms || path == TracePath::DenseLists;
+  if ((forms && !filter) || (path == TracePath::SmallLists && p.n_tris > p.bin_list) ||
+      (path == TracePath::DenseLists && (p.wave_lists == nullptr || p.stats != nullptr)) ||
+      (p.iters > 1u && (!trace_can_fuse(path, filter) || p.stats != nullptr)) ||
+      (p.row_il != 0u && (path != TracePath::SmallLists || p.stats != nullptr))) return hipErrorInvalidValue;
   dim3 grid(cdiv(p.W, 32), cdiv(p.rows, 8));
   if (p.row_il != 0u) {                                  // every second block row (small-scene kernels only)
-    if (!(bin && p.n_tris <= p.bin_list) || p.stats != nullptr) return hipErrorInvalidValue;
     const uint32_t R = grid.y, G = p.row_il, full = R / (2u * G), rest = R % (2u * G);      // groups of G block rows, alternating
     grid.y = full * G + (p.row_phase == 0u ? (rest < G ? rest : G) : (rest > G ? rest - G : 0u));
     if (grid.y == 0u) return hipSuccess;
   }
-  if (p.wave_lists != nullptr) {     // dense scenes, lists in HBM: no LDS, no classification in the trace kernel
-    if (!((p.flags & TRACE_PRETEST) && filter && bin && p.n_tris > p.bin_list) || p.stats != nullptr) return hipErrorInvalidValue;
-    const size_t lds_d = 4u * p.bin_list * 116u;                       // four waves' records + forms + colours; no block list
-    if (p.iters > 1u) { if (fma) launch_dense<true, true>(p, K, grid, lds_d, st); else launch_dense<false, true>(p, K, grid, lds_d, st); }
-    else { if (fma) launch_dense<true, false>(p, K, grid, lds_d, st); else launch_dense<false, false>(p, K, grid, lds_d, st); }
-    return hipGetLastError();
-  }
-  const size_t lds = trace_lds_bytes(p, bin);
-  if (p.iters > 1u) {                // fused iterations: default (filtered, classified, un-instrumented) kernels only
-    if (!trace_can_fuse(filter, bin) || p.stats != nullptr) return hipErrorInvalidValue;
-    if (fma) launch_trace_fused<true>(p, K, grid, lds, st);
-    else launch_trace_fused<false>(p, K, grid, lds, st);
-    return hipGetLastError();
-  }
-  if ((p.flags & TRACE_PRETEST) && filter && bin && p.n_tris > p.bin_list) {   // large-scene kernels with the per-sample forms
-    if (p.stats != nullptr) { if (fma) launch_trace_pre<true, true, false>(p, K, grid, lds, st); else launch_trace_pre<false, true, false>(p, K, grid, lds, st); }
-    else { if (fma) launch_trace_pre<true, false, false>(p, K, grid, lds, st); else launch_trace_pre<false, false, false>(p, K, grid, lds, st); }
-    return hipGetLastError();
-  }
-  if (p.stats != nullptr) {          // instrumented build of the same kernel (not the timed path)
-    if (fma) launch_trace_f<true, true>(p, filter, bin, K, grid, lds, st);
-    else launch_trace_f<false, true>(p, filter, bin, K, grid, lds, st);
-  } else {
-    if (fma) launch_trace_f<true, false>(p, filter, bin, K, grid, lds, st);
-    else launch_trace_f<false, false>(p, filter, bin, K, grid, lds, st);
-  }
+  const size_t lds = trace_lds_bytes(p, path);
+  auto launch = [&](auto fma_c) {
+    constexpr bool F = decltype(fma_c)::value;
+    using P = TracePath;
+    switch (variant(path, K == 1 || K == 2 ? K : 4)) {
+      case variant(P::FullScan, 1): return launch_trace_kernel<F, 1, P::FullScan>(p, filter, grid, lds, st);
+      case variant(P::FullScan, 2): return launch_trace_kernel<F, 2, P::FullScan>(p, filter, grid, lds, st);
+      case variant(P::FullScan, 4): return launch_trace_kernel<F, 4, P::FullScan>(p, filter, grid, lds, st);
+      case variant(P::SmallLists, 1): return launch_trace_kernel<F, 1, P::SmallLists>(p, filter, grid, lds, st);
+      case variant(P::SmallLists, 2): return launch_trace_kernel<F, 2, P::SmallLists>(p, filter, grid, lds, st);
+      case variant(P::SmallLists, 4): return launch_trace_kernel<F, 4, P::SmallLists>(p, filter, grid, lds, st);
+      case variant(P::Classify, 1): return launch_trace_kernel<F, 1, P::Classify>(p, filter, grid, lds, st);
+      case variant(P::Classify, 2): return launch_trace_kernel<F, 2, P::Classify>(p, filter, grid, lds, st);
+      case variant(P::Classify, 4): return launch_trace_kernel<F, 4, P::Classify>(p, filter, grid, lds, st);
+      case variant(P::ClassifyForms, 1): return launch_trace_kernel<F, 1, P::ClassifyForms>(p, filter, grid, lds, st);
+      case variant(P::ClassifyForms, 2): return launch_trace_kernel<F, 2, P::ClassifyForms>(p, filter, grid, lds, st);
+      case variant(P::ClassifyForms, 4): return launch_trace_kernel<F, 4, P::ClassifyForms>(p, filter, grid, lds, st);
+      case variant(P::DenseLists, 1): return launch_trace_kernel<F, 1, P::DenseLists>(p, filter, grid, lds, st);
+      case variant(P::DenseLists, 2): return launch_trace_kernel<F, 2, P::DenseLists>(p, filter, grid, lds, st);
+      case variant(P::DenseLists, 4): return launch_trace_kernel<F, 4, P::DenseLists>(p, filter, grid, lds, st);
+    }
+  };
+  if (fma) launch(std::true_type{}); else launch(std::false_type{});
   return hipGetLastError();
 }
 
-// blocks of the default (fma, filtered, binned) trace kernel the occupancy API admits per CU
+// blocks of the default (fma, filtered) trace kernel the occupancy API admits per CU: the small scenes' at K = 1, 2,
+// the classifying one at K = 4
 int trace_occupancy(int K, size_t lds) {
   int n = 0;
   hipError_t e;
-  if (K == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_kernel<true, 1, true, false, true, true>, 64 * kSmallWgWaves, lds);
-  else if (K == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_kernel<true, 2, true, false, true, true>, 64 * kSmallWgWaves, lds);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_kernel<true, 4, true, false, true, false>, 256, lds);
+  if (K == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_kernel<true, 1, true, false, TracePath::SmallLists>, 256, lds);
+  else if (K == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_kernel<true, 2, true, false, TracePath::SmallLists>, 256, lds);
+  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_kernel<true, 4, true, false, TracePath::Classify>, 256, lds);
   return e == hipSuccess ? n : -1;
 }
 

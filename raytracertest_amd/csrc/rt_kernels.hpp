@@ -88,22 +88,30 @@ constexpr uint32_t TRACE_PRETEST = 32u;
 // small-scene kernels: do not skip the intersection tests of tiles whose list is one certainly-hit triangle (A/B, tests)
 constexpr uint32_t TRACE_NO_SURE_HIT = 64u;
 
+// How the waves of a trace launch get their candidate triangles: trace_kernel's Path.  The host picks it per (half-)launch
+// in one place (rt_tracer::trace_path).
+enum class TracePath : uint32_t {
+  FullScan,        // RT_FLAG_NO_BINNING: the block stages the scene into LDS in chunks and every ray scans all of it
+  SmallLists,      // n_tris <= bin_list: each tile's list comes from tile_lists_kernel (p.tile_lists)
+  Classify,        // larger scenes: each wave classifies the scene (or its block's and macro tile's survivors) into LDS
+  ClassifyForms,   // Classify with the per-sample forms of TRACE_PRETEST: instrumented launches, no macro lists, large frames
+  DenseLists,      // forms and lists from HBM (p.wave_lists, wave_lists_kernel): no classification in the trace kernel
+};
+
 // jump: J^(2^k), k < 32, 160 columns x 8 words; win: the 4-bit window tables of J^(2^m), m < 6 (rt_rng_host.hpp)
 hipError_t launch_rng_init(uint32_t* rng, uint32_t npix, uint32_t p0, const uint32_t seeded[6],
                            const uint32_t* jump, const uint32_t* win, hipStream_t st);
 hipError_t launch_prep_triangles(bool fma, bool edges, const float4* verts, uint32_t n, float4* tri_a, float* tri_b,
                                  float4* color, float4* normals, hipStream_t st);
-uint32_t trace_lds_bytes(const TraceParams& p, bool bin);
-// bin: per-tile triangle classification + per-wave LDS candidate lists (rt_trace.hpp);
-// !bin: every ray scans the whole list, staged into LDS in chunks of p.chunk.
-hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, bool bin, int K, hipStream_t st);
+uint32_t trace_lds_bytes(const TraceParams& p, TracePath path);
+hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, TracePath path, int K, hipStream_t st);
 int trace_occupancy(int K, size_t lds);
 hipError_t launch_convert(const float4* render, const uint32_t* counts, uint32_t* image, uint32_t npix,
                           hipStream_t st);
 
 hipError_t launch_dbg_hit_triangle(bool fma, uint32_t n, const float* rays, const float* tris, int eps_mode,
                                    int* hit, float* tuv, float* normal, float* point, hipStream_t st);
-bool trace_can_fuse(bool filter, bool bin);      // launches with TraceParams::iters > 1 are available
+bool trace_can_fuse(TracePath path, bool filter);   // launches with TraceParams::iters > 1 are available
 hipError_t launch_macro_bin(const TraceParams& p, bool fma, hipStream_t st);
 // the level above: p.super_lists (before launch_macro_bin)
 hipError_t launch_super_bin(const TraceParams& p, bool fma, hipStream_t st);

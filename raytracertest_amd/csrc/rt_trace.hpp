@@ -12,29 +12,15 @@
 //     Kernels.cuh:84);
 //   * __ballot-driven wave-uniform early-outs after the culling test, the u test and the v
 //     test (FILTER); the IEEE division only runs for triangles some lane may really hit;
-//   * BIN: before tracing, each wave classifies the whole triangle list against the ray
-//     family of its tile (lane = triangle, interval bounds) and compacts the survivors with
-//     __ballot + mbcnt into a per-wave LDS candidate list, so the exact tests run only on
-//     triangles some ray of the tile could hit.  Without BIN the block stages the list into
-//     LDS in chunks and every ray scans all of it.
+//   * every path but TracePath::FullScan tests each ray against a per-wave LDS candidate list of
+//     its tile: the triangles some ray of the tile could hit, in ascending order (the paths differ
+//     in where the list comes from, rt_kernels.hpp).  FullScan stages the whole triangle list
+//     into LDS in chunks and every ray scans all of it.
 #pragma once
 #include "rt_lists.hpp"          // -> rt_classify.hpp -> rt_rays.hpp -> rt_device_math.hpp, rt_kernels.hpp
 
 namespace rtk {
 
-#ifndef RT_TRACE_MIN_WAVES
-#define RT_TRACE_MIN_WAVES 4     // __launch_bounds__ 2nd argument: waves per SIMD the allocator must allow
-                                 // (<= 128 VGPRs; measured C3 213 -> 193 us, C4 27.2 -> 24.3 ms vs the 136-VGPR build)
-#endif
-#ifndef RT_TRACE_WAVES
-#define RT_TRACE_WAVES(K) RT_TRACE_MIN_WAVES
-#endif
-#ifndef RT_HBM_WAVES
-#define RT_HBM_WAVES 4           // the dense-scene kernels that read their lists from HBM (A/B: 5 = at most 102 VGPRs)
-#endif
-#ifndef RT_SMALL_WG_WAVES
-#define RT_SMALL_WG_WAVES 4      // small-scene trace kernels: waves per workgroup (4, 2 or 1; see trace_kernel)
-#endif
 // candidate records per wave in LDS (40 bytes each): TraceParams::bin_list, a multiple of 64
 
 // ------------------------------------------------------------------------------------
@@ -149,40 +135,38 @@ __device__ __forceinline__ void test_triangle(const float4 A0, const float4 A1, 
 
 // ------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------
-// The trace kernel.  grid = (ceil(W/32), ceil(rows/8)), block = 256 threads.
-// Dynamic LDS: BIN ? 4 waves * bin_list * 40 bytes (104 with the per-sample forms, PRE) + block_list * 4
-// + 160 bytes for the block-level pre-cull : min(n_tris, chunk) * 36 bytes  (trace_lds_bytes()).
+// The trace kernel.  grid = (ceil(W/32), ceil(rows/8)), block = 256 threads, one wave per 8x8 tile.
+// Dynamic LDS (trace_lds_bytes()): FullScan min(n_tris, chunk) * 36 bytes; otherwise 4 waves * bin_list * 40 bytes
+// (104 with the per-sample forms, 116 on DenseLists), + block_list * 4 + 160 bytes for the block-level pre-cull of
+// the classifying paths.
+// Waves per SIMD the register allocator must allow (__launch_bounds__): 4, i.e. <= 128 VGPRs (measured C3 213 -> 193 us,
+// C4 27.2 -> 24.3 ms against the 136-VGPR build; DenseLists was A/B'd at 5 = at most 102 VGPRs); 5 for SmallLists at K = 2.
 // ------------------------------------------------------------------------------------
 // FUSE: the launch runs p.iters consecutive iterations of the host loop (RayTracerImpl.cu:246-249)
 // of p.samples samples each: the per-iteration `render += accu` (:141-143) keeps its order of
 // additions, so the buffers end bit-identical to p.iters separate launches -- without their
 // state traffic, tile family and classification.  Used between two update points of a Trace.
-// PRE: large-scene kernels (BIN && !ONEPASS) with the per-sample forms; a separate instantiation because
-// the first classification then moves in front of the sample loop and the forms cost registers and code
-// that sparser scenes do not earn back (300-1000 triangles at 1080p: +6-10 % with them, C4: -13 %).
-// HBM (PRE kernels only): the tiles' candidate lists + forms come from p.wave_lists (wave_lists_kernel, rt_dense.hpp) -- this
+// ClassifyForms: the classifying kernel with the per-sample forms; a path of its own because the first
+// classification then moves in front of the sample loop and the forms cost registers and code that sparser
+// scenes do not earn back (300-1000 triangles at 1080p: +6-10 % with them, C4: -13 %).
+// DenseLists: the tiles' candidate lists + forms come from p.wave_lists (wave_lists_kernel, rt_dense.hpp) -- this
 // instantiation contains no classification and no barrier; a tile marked as overflowing tests its macro tile's list.
 constexpr uint32_t kWaveRec = 16u;                 // dwords per record of p.wave_lists
 constexpr uint32_t kWaveOverflow = 0xFFFFFFFFu;
-template <bool FMA, int K, bool FILTER, bool STATS, bool BIN, bool ONEPASS, bool FUSE = false, bool PRE = false, bool HBM = false>
-__global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (ONEPASS && K == 2) ? 5 : HBM ? RT_HBM_WAVES : RT_TRACE_WAVES(K)) void trace_kernel(const TraceParams p) {
-  static_assert(!HBM || (PRE && BIN && !ONEPASS && FILTER && !STATS), "lists from HBM: the default dense-scene kernels only");
+template <bool FMA, int K, bool FILTER, bool STATS, TracePath Path, bool FUSE = false>
+__global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 : 4) void trace_kernel(const TraceParams p) {
+  static_assert(Path != TracePath::DenseLists || (FILTER && !STATS), "lists from HBM: the default dense-scene kernels only");
   using M = Math<FMA>;
   extern __shared__ float4 s_mem[];
-  // Small scenes: a 32 x 8 block of four tiles is traced by 4 / WGW workgroups of WGW waves (no wave of these kernels talks to
-  // another one).  A CU holds at most 16 multi-wave workgroups (one barrier resource each, kept until the LAST wave of the
-  // workgroup ends): in a frame that mixes short certain-winner waves with long ray-generating ones a four-wave workgroup is
-  // soon down to its slowest wave and 16 of them leave wave slots empty.
-  constexpr uint32_t WGW = (BIN && ONEPASS) ? RT_SMALL_WG_WAVES : 4u, WGS = 4u / WGW;
-
   // (workgroup shape, measured at C3 with the lists rebuilt: 256 threads = one block of four tiles 62.5 us per step; one wave
-  //  per workgroup 85.0; two / four blocks per workgroup 67.2 / 75.2; 8 instead of 7 waves per SIMD at 64 VGPRs 63.2)
-  const uint32_t lane = threadIdx.x & 63u, wl = threadIdx.x >> 6;   // wl: wave within its workgroup
-  const uint32_t wave = (blockIdx.x % WGS) * WGW + wl;             // tile within the block of 32 x 8 pixels
-  const uint32_t bx = blockIdx.x / WGS;                            // the block this workgroup traces (a part of)
+  //  per workgroup 85.0; two / four blocks per workgroup 67.2 / 75.2; 8 instead of 7 waves per SIMD at 64 VGPRs 63.2;
+  //  two- or one-wave workgroups of the small scenes: DESIGN.md 4.1)
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = threadIdx.x >> 6;                          // tile within the block of 32 x 8 pixels
+  const uint32_t bx = blockIdx.x;
   uint32_t by = blockIdx.y;
-  const uint32_t gxb = gridDim.x / WGS;                            // blocks per block row
-  if constexpr (BIN && ONEPASS) {
+  const uint32_t gxb = gridDim.x;                                  // blocks per block row
+  if constexpr (Path == TracePath::SmallLists) {
     if (p.row_il != 0u) by = (blockIdx.y / p.row_il) * (2u * p.row_il) + p.row_phase * p.row_il + blockIdx.y % p.row_il;
   }
   const uint32_t px = bx * 32u + wave * 8u + (lane & 7u);
@@ -219,27 +203,28 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
     rng.v3 = p.rng[4 * static_cast<size_t>(p.npix) + pix];
     rng.v4 = p.rng[5 * static_cast<size_t>(p.npix) + pix];
   };
-  // Dense-scene kernels with the per-sample forms (PRE) classify BEFORE any ray exists; six state registers held across the
+  constexpr bool FORMS = Path == TracePath::ClassifyForms || Path == TracePath::DenseLists;   // candidates with the per-sample forms
+  // Dense-scene kernels with the per-sample forms classify BEFORE any ray exists; six state registers held across the
   // block- and wave-level classification are what made the 128-VGPR kernel spill (32 bytes of scratch per lane): their state
   // is requested behind the classification instead (one exposed load latency per wave, hidden by the other three waves).
-  constexpr bool RNG_LATE = PRE && BIN && !ONEPASS;
+  constexpr bool RNG_LATE = FORMS;
   // The third-edge rules of tile_misses_triangle inside this kernel (block and wave level of dense scenes; the macro level and the
   // small scenes' list builders always have them): at the block level always; at the wave level of the instantiations with the
   // per-sample forms not inside the forms call (K = 4: 24 -> 92 bytes of scratch per lane) but as a separate call in front
   // of it.  C4, interleaved on one device: macro level only 3.97 ms, + block level 3.75 ms, + wave level inside the forms
   // call 4.55 ms, as a call of its own 3.68 ms.
-  constexpr bool THIRD_BLOCK = RT_TRACE_THIRD_BLOCK, THIRD_WAVE = RT_TRACE_THIRD_WAVE;
+  constexpr bool THIRD_BLOCK = true, THIRD_WAVE = !FORMS;
   if constexpr (!RNG_LATE) load_rng();
 
 
-  // Small scenes (ONEPASS): the tile's candidate list and its certain-winner verdict were built ahead of this launch by
+  // Small scenes (SmallLists): the tile's candidate list and its certain-winner verdict were built ahead of this launch by
   // tile_lists_kernel (p.tile_lists; null only for a scene without triangles), so the wave knows the verdict before
   // anything else: a tile with a certain winner needs no pinhole ray either (its samples keep their RNG draws and
   // additions only).
-  const bool sure_ok = BIN && ONEPASS && (p.flags & (TRACE_NEAREST_HIT | TRACE_NO_SURE_HIT)) == 0u && p.n_spheres == 0u && p.tri_n == nullptr;
+  const bool sure_ok = Path == TracePath::SmallLists && (p.flags & (TRACE_NEAREST_HIT | TRACE_NO_SURE_HIT)) == 0u && p.n_spheres == 0u && p.tri_n == nullptr;
   bool loaded_sure = false;
   uint32_t list_word = 0u;                                          // count | winner << 10 | certain << 31
-  if constexpr (BIN && ONEPASS) {
+  if constexpr (Path == TracePath::SmallLists) {
     if (p.tile_lists != nullptr) {
       const size_t slot0 = (static_cast<size_t>(by) * gxb + bx) * 4u + wave;
       // wave-uniform by construction; readfirstlane tells the compiler (scalar loop control below)
@@ -263,12 +248,12 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
   unsigned long long st_bin[2] = {0, 0};                           // STATS: candidates kept, classification rounds
   unsigned long long st_pre = 0;                                   // STATS: candidate tests of a sample batch skipped by the per-sample forms
 
-  // ---- full-scan staging (BIN == false) --------------------------------------------------
+  // ---- full-scan staging (FullScan) --------------------------------------------------------
   const uint32_t cap = n < p.chunk ? n : p.chunk;                  // triangles resident in LDS
   float4* const sA = s_mem;                                        // 2 float4 per triangle
   float* const sB = reinterpret_cast<float*>(s_mem + 2u * cap);    // 1 float per triangle
   const bool single_chunk = n <= p.chunk;
-  if constexpr (!BIN) {
+  if constexpr (Path == TracePath::FullScan) {
     if (single_chunk) {
       for (uint32_t i = threadIdx.x; i < 2u * n; i += 256u) sA[i] = p.tri_a[i];
       for (uint32_t i = threadIdx.x; i < n; i += 256u) sB[i] = p.tri_b[i];
@@ -276,20 +261,20 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
     }
   }
 
-  // ---- per-wave candidate list (BIN == true) ---------------------------------------------
+  // ---- per-wave candidate list (every other path) ----------------------------------------
   const uint32_t L = p.bin_list;
-  float4* const cA = s_mem + static_cast<size_t>(wl) * (2u * L);                           // 2 float4 per candidate
-  float* const cB = reinterpret_cast<float*>(s_mem + WGW * 2u * L) + wl * L;
-  int* const cI = reinterpret_cast<int*>(s_mem + WGW * 2u * L) + WGW * L + wl * L;
-  // PRETEST (large-scene kernels, TRACE_PRETEST): one 64-byte block more per candidate behind the index
+  float4* const cA = s_mem + static_cast<size_t>(wave) * (2u * L);                         // 2 float4 per candidate
+  float* const cB = reinterpret_cast<float*>(s_mem + 4u * 2u * L) + wave * L;
+  int* const cI = reinterpret_cast<int*>(s_mem + 4u * 2u * L) + 4u * L + wave * L;
+  // PRETEST (forms paths, TRACE_PRETEST): one 64-byte block more per candidate behind the index
   // array -- the three per-sample forms of tile_misses_triangle<true> (9 floats) and their focal-point
   // gradients (9 fp16 in 5 dwords), contiguous so that one address register and four ds_read_b128
   // with immediate offsets fetch them.  L is a multiple of 2 here.
-  constexpr bool PRETEST = PRE && BIN && !ONEPASS;
+  constexpr bool PRETEST = FORMS;
   const bool pretest = PRETEST && (p.flags & TRACE_PRETEST) != 0u;   // wave-uniform
   float4* const cP = s_mem + 4u * 2u * L + 2u * L + static_cast<size_t>(wave) * (4u * L);   // after cA (8L float4), cB + cI (2L float4)
   const uint32_t list_floats4 = pretest ? (4u * 2u * L + 2u * L + 16u * L) : (4u * 2u * L + 2u * L);   // float4 units before the block list
-  // HBM: the candidates' colours travel with them (3 floats each, behind the forms: this instantiation has no block list).  A
+  // DenseLists: the candidates' colours travel with them (3 floats each, behind the forms: this instantiation has no block list).  A
   // hit is remembered as its SLOT in the wave's list -- ascending like the triangle indices, so ties break the same way -- and
   // shaded from LDS: the per-sample gather p.tri_color[winner] was an exposed global-memory round trip per sample batch
   // (24 % of the dense-scene kernel's wave cycles sat in s_waitcnt: profiles/r04_c4_stalls.txt).
@@ -298,7 +283,7 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
   TileFamily fam;
   bool list_complete = false;       // the list in LDS covers the whole scene (classification done once)
   uint32_t list_count = 0;
-  // ONEPASS: one triangle that every ray of the tile's family certainly hits is certainly the farthest hit of every ray
+  // SmallLists: one triangle that every ray of the tile's family certainly hits is certainly the farthest hit of every ray
   // (wave-uniform): the sample loop then needs neither rays nor tests (tile_misses_triangle<.., SURE>)
   bool sure_hit_tile = false;
   uint32_t sure_winner = 0;         // triangle index of the certain winner
@@ -314,7 +299,7 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
   bool src_is_block_list = false;
   // macro level: this block's macro tile already excludes most of the scene (macro_bin_kernel)
   const uint32_t* mI = nullptr;     // ascending triangle indices of the macro tile, or null = whole scene
-  if constexpr (BIN && !ONEPASS) {
+  if constexpr (Path != TracePath::FullScan && Path != TracePath::SmallLists) {
     if (p.macro_lists != nullptr) {
       const uint32_t mt = (blockIdx.y * 8u / p.macro_h) * p.macro_nx + (blockIdx.x * 32u / p.macro_w);
       const uint32_t* const ml = p.macro_lists + static_cast<size_t>(mt) * (p.macro_cap + 1u);
@@ -324,9 +309,9 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
   }
   const uint32_t n_src = src_count;  // triangles the block-level pre-cull walks over
   // (small-scene kernels load their tiles' lists and need no ray family at all)
-  if constexpr (BIN && ONEPASS) fam.usable = false;
-  bool hbm_overflow = false;        // HBM: the tile's list did not fit its slot -> exact tests over the macro tile's list
-  if constexpr (HBM) {
+  if constexpr (Path == TracePath::SmallLists) fam.usable = false;
+  bool hbm_overflow = false;        // DenseLists: the tile's list did not fit its slot -> exact tests over the macro tile's list
+  if constexpr (Path == TracePath::DenseLists) {
     const size_t slot = (static_cast<size_t>(by) * gxb + bx) * 4u + wave;
     const float4* const rec = reinterpret_cast<const float4*>(p.wave_lists) + slot * (1u + p.wave_cap) * (kWaveRec / 4u);
     const float4 hdr = rec[0];
@@ -351,7 +336,7 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
     __builtin_amdgcn_wave_barrier();
     list_complete = true;
   }
-  if constexpr (BIN && !ONEPASS && !HBM) {
+  if constexpr (Path == TracePath::Classify || Path == TracePath::ClassifyForms) {
     tl_mark(8);                                                    // loads issued, pinhole + focal point done
     const FocalBounds wb = focal_bounds(p, focal, inside);
     tl_mark(9);
@@ -459,10 +444,10 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
     return base < src_count ? base : src_count;
   };
 
-  // ONEPASS: the scene has no more triangles than the list holds (host-checked).  The tile's list -- a function of the
+  // SmallLists: the scene has no more triangles than the list holds (host-checked).  The tile's list -- a function of the
   // tile's ray family only, not of the samples -- comes from tile_lists_kernel: the wave gathers the records of the listed
   // triangles into its LDS slot; a tile with a certain winner needs no records at all.
-  if constexpr (BIN && ONEPASS) {
+  if constexpr (Path == TracePath::SmallLists) {
     const size_t slot = (static_cast<size_t>(by) * gxb + bx) * 4u + wave;
     const uint32_t count = list_word & 0x3FFu;                         // bit 31: the tile has a certain winner, bits 10..19: its triangle
     sure_hit_tile = loaded_sure;
@@ -491,18 +476,18 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
   // all of them -- never classifies again; one that overflows falls back to rounds inside the
   // sample loop (lists rebuilt per batch, without forms).
   bool forms_ready = false;
-  if constexpr (PRETEST && !HBM) {
+  if constexpr (Path == TracePath::ClassifyForms) {
     const uint32_t next0 = classify(0u, std::true_type{});
     list_complete = next0 >= src_count;
     forms_ready = pretest && list_complete;
   }
-  if constexpr (HBM) forms_ready = true;
+  if constexpr (Path == TracePath::DenseLists) forms_ready = true;
   if constexpr (RNG_LATE) load_rng();
   tl_mark(1);                                                      // family + classification done
   float4 sure_col = make_float4(0.0f, 0.0f, 0.0f, 0.0f);           // the winner's colour -- or, with the table, its p.samples-fold sum
-  const bool sure_sums = BIN && ONEPASS && p.sure_table != nullptr;
-  if constexpr (BIN && ONEPASS) { if (sure_hit_tile) sure_col = sure_sums ? p.sure_table[sure_winner] : p.tri_color[sure_winner]; }
-  if constexpr (STATS && BIN && ONEPASS) {                         // tiles with a certain winner; the others by list length: 0, 1, 2, more
+  const bool sure_sums = Path == TracePath::SmallLists && p.sure_table != nullptr;
+  if constexpr (Path == TracePath::SmallLists) { if (sure_hit_tile) sure_col = sure_sums ? p.sure_table[sure_winner] : p.tri_color[sure_winner]; }
+  if constexpr (STATS && Path == TracePath::SmallLists) {        // tiles with a certain winner; the others by list length: 0, 1, 2, more
     if (lane == 0u && p.stats != nullptr)
       atomicAdd(p.stats + (sure_hit_tile ? 13 : list_count == 0u ? 11 : list_count == 1u ? 12 : list_count == 2u ? 14 : 15), 1ull);
   }
@@ -512,7 +497,7 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
   for (uint32_t it = 0; it < iters; ++it) {                        // FUSE: the host loop's iterations, :246
   if constexpr (FUSE) { ax = 0.0f; ay = 0.0f; az = 0.0f; }          // accu, :133
   uint32_t traced_samples = p.samples;
-  if constexpr (BIN && ONEPASS) {
+  if constexpr (Path == TracePath::SmallLists) {
     // The tile's winner is hit by every ray of its family: every sample's radiance is that triangle's colour
     // (Kernels.cuh:95-99), whatever the lens sample -- no ray, no test.  What the samples still do to the state is kept
     // exactly: the three draws of each lens sample (Random.cuh:15-16) and the additions of :137 in sample order.
@@ -549,20 +534,20 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
       for (int k = 0; k < K; ++k) { dox[k] = o[k].x - p.cam[9]; doy[k] = o[k].y - p.cam[10]; }
       dFx = focal.x - fam.fc[0]; dFy = focal.y - fam.fc[1]; dFz = focal.z - fam.fc[2];
     }
-    if constexpr (BIN && ONEPASS) {
+    if constexpr (Path == TracePath::SmallLists) {
       for (uint32_t j = 0; j < list_count; ++j) {                  // ascending triangle order
         const float4 A0 = cA[2u * j], A1 = cA[2u * j + 1u];
         test_triangle<FMA, K, FILTER, STATS>(A0, A1, [&] { return cB[j]; }, cI[j], o, d, best_t, best_i,
                                              nearest, inside, valid_k, st_exit, st_skip);
       }
-    } else if constexpr (BIN) {
+    } else if constexpr (Path != TracePath::FullScan) {
       uint32_t base = 0;
       do {
         uint32_t next = src_count;
-        if constexpr (!HBM) {
+        if constexpr (Path != TracePath::DenseLists) {
           if (!list_complete) {
             next = classify(base, std::false_type{});
-            if (base == 0u && next >= src_count) list_complete = true;     // (!PRE: the first classification happens here)
+            if (base == 0u && next >= src_count) list_complete = true;     // (Classify: the first classification happens here)
           }
         }
         // does ANY ray of the wave survive the per-sample forms of candidate j?  (wave-uniform)
@@ -595,7 +580,7 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
         auto forms_alive = [&](uint32_t j) -> bool { return forms_eval(cP[4u * j], cP[4u * j + 1u], cP[4u * j + 2u], cP[4u * j + 3u]); };
         auto run_tests = [&](uint32_t j) {
           const float4 A0 = cA[2u * j], A1 = cA[2u * j + 1u];
-          test_triangle<FMA, K, FILTER, STATS>(A0, A1, [&] { return cB[j]; }, HBM ? static_cast<int>(j) : cI[j], o, d, best_t, best_i,
+          test_triangle<FMA, K, FILTER, STATS>(A0, A1, [&] { return cB[j]; }, Path == TracePath::DenseLists ? static_cast<int>(j) : cI[j], o, d, best_t, best_i,
                                                nearest, inside, valid_k, st_exit, st_skip);
         };
         if (forms_ready) {
@@ -616,7 +601,7 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
         base = next;
         if (!list_complete) __builtin_amdgcn_wave_barrier();       // list is rewritten by the next round
       } while (!list_complete && base < src_count);
-      if constexpr (HBM) {
+      if constexpr (Path == TracePath::DenseLists) {
         if (hbm_overflow) {                                        // (wave-uniform, rare) every triangle of the macro tile's list, ascending
           for (uint32_t e = 0; e < n_src; ++e) {
             const uint32_t tri = mI != nullptr ? static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(mI[e]))) : e;
@@ -650,8 +635,8 @@ __global__ __launch_bounds__((BIN && ONEPASS) ? 64 * RT_SMALL_WG_WAVES : 256, (O
       if (static_cast<uint32_t>(k) < valid_k) {
         float dist = best_t[k];
         int win = best_i[k];
-        // (HBM: a triangle hit is its slot in the wave's list -- unless the tile overflowed and tested triangles by index)
-        const bool by_slot = HBM && !hbm_overflow;                  // wave-uniform
+        // (DenseLists: a triangle hit is its slot in the wave's list -- unless the tile overflowed and tested triangles by index)
+        const bool by_slot = Path == TracePath::DenseLists && !hbm_overflow;   // wave-uniform
         const int first_sphere = by_slot ? 0x40000000 : static_cast<int>(n);
         for (uint32_t si = 0; si < p.n_spheres; ++si) {
           float t = 0.0f;

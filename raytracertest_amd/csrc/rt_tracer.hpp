@@ -662,11 +662,13 @@ struct rt_tracer {
     p.image_host = host_image;
     p.flags = flags | mode_flags(p);
     p.image = d_image.get();
+    const rtk::TracePath path = trace_path(p);
     bool have_lists = false;
-    const bool build_lists = prepare_tile_lists(p, (flags & rtk::TRACE_ZERO_ACC) != 0u, have_lists);
+    const bool build_lists = prepare_tile_lists(p, path, (flags & rtk::TRACE_ZERO_ACC) != 0u, have_lists);
     attach_sure_table(p, have_lists);
     last_k = K; last_chunk = p.chunk;
-    last_lds = rtk::trace_lds_bytes(p, bin);
+    // (DenseLists: the LDS of the classifying kernel, what rt_tracer_info has always reported for dense scenes)
+    last_lds = rtk::trace_lds_bytes(p, path == rtk::TracePath::DenseLists ? rtk::TracePath::ClassifyForms : path);
     // Tall frames: upper half on the primary stream, lower half on stream_b (see the fields' comment).
     // The split row is a multiple of 8, each half is a row band of its own (own tile / macro lists).
     const uint32_t r0 = allow_split ? split_row(p.rows) : 0u;
@@ -678,8 +680,8 @@ struct rt_tracer {
       lists.attach(p, row0, have_lists);
       if (timed) HIP_CHECK(hipEventRecord(e.a, stream));
       if (have_lists) lists.wait(stream, 0);
-      attach_macro_lists(p, 0, stream, (flags & rtk::TRACE_ZERO_ACC) != 0u);   // part of the launch: timed with it
-      HIP_CHECK(rtk::launch_trace(p, fma, filter, bin, K, stream));
+      attach_macro_lists(p, path, 0, stream, (flags & rtk::TRACE_ZERO_ACC) != 0u);   // part of the launch: timed with it
+      HIP_CHECK(rtk::launch_trace(p, fma, filter, path, K, stream));
       if (timed) HIP_CHECK(hipEventRecord(e.b, stream));
     } else {
       fork_b();
@@ -713,8 +715,9 @@ struct rt_tracer {
           if (us >= 5u) HIP_CHECK(rtk::launch_delay(us, stream_b));
           else HIP_CHECK(hipStreamWaitEvent(stream_b, stagger_event, 0));
         }
-        attach_macro_lists(half[h], h, st[h], (flags & rtk::TRACE_ZERO_ACC) != 0u);
-        HIP_CHECK(rtk::launch_trace(half[h], fma, filter, bin, K, st[h]));
+        const rtk::TracePath half_path = trace_path(half[h]);
+        attach_macro_lists(half[h], half_path, h, st[h], (flags & rtk::TRACE_ZERO_ACC) != 0u);
+        HIP_CHECK(rtk::launch_trace(half[h], fma, filter, half_path, K, st[h]));
         if (h == 0 && stagger) HIP_CHECK(hipEventRecord(stagger_event, stream));
       }
       if (timed) { HIP_CHECK(hipEventRecord(e.b, stream)); HIP_CHECK(hipEventRecord(e.c, stream_b)); }
@@ -763,7 +766,7 @@ struct rt_tracer {
     HIP_CHECK(hipStreamSynchronize(main_stream()));                             // :259,:287
   }
 
-  // Candidate lists (ONEPASS scenes) are kept across launches: the launch that clears the
+  // Candidate lists (SmallLists scenes) are kept across launches: the launch that clears the
   // accumulators (the first of a Trace) classifies as usual and stores nothing, so one-launch
   // passes -- bench.py's step -- neither pay for nor profit from the cache; the first
   // accumulating launch classifies and stores its tiles' lists, later ones load them as long as
@@ -820,8 +823,8 @@ struct rt_tracer {
   // be (re)built first -- camera snapshot, scene, frame, list length or arithmetic mode changed; or this is the first launch
   // of a Trace and the lists are not kept across Traces (rt_tracer_set_list_reuse(t, 0): bench.py's headline, every step
   // builds its own) -- and makes sure the buffer holds the whole band's lists.  have = the scene uses lists at all.
-  bool prepare_tile_lists(const rtk::TraceParams& p, bool first_launch_of_trace, bool& have) {
-    have = bin && p.n_tris != 0u && p.n_tris <= p.bin_list;
+  bool prepare_tile_lists(const rtk::TraceParams& p, rtk::TracePath path, bool first_launch_of_trace, bool& have) {
+    have = path == rtk::TracePath::SmallLists && p.n_tris != 0u;
     if (!have) return false;
     const size_t tiles = static_cast<size_t>((W + 31u) / 32u) * ((rows + 7u) / 8u + 1u) * 4u;   // (+1: a split adds a partial block row)
     return lists.prepare(tiles * (1u + p.bin_list), make_key(p, p.bin_list), !(first_launch_of_trace && !reuse_across_traces),
@@ -866,13 +869,14 @@ struct rt_tracer {
   // One synchronous launch of `p` on the primary stream, its lists built in-stream into the current slot (the
   // instrumented launches of rt_tracer_trace_stats and rt_dbg_trace_timeline).
   void launch_instrumented(rtk::TraceParams& p, uint32_t samples) {
+    const rtk::TracePath path = trace_path(p);
     bool have_lists = false;
-    (void)prepare_tile_lists(p, true, have_lists);
+    (void)prepare_tile_lists(p, path, true, have_lists);
     sync_list_stream();
     lists.attach(p, row0, have_lists);
     if (have_lists) HIP_CHECK(rtk::launch_tile_lists(p, fma, main_stream()));
-    attach_macro_lists(p, 0, main_stream());
-    HIP_CHECK(rtk::launch_trace(p, fma, filter, bin, pick_k(samples), main_stream()));
+    attach_macro_lists(p, path, 0, main_stream());
+    HIP_CHECK(rtk::launch_trace(p, fma, filter, path, pick_k(samples), main_stream()));
     HIP_CHECK(hipStreamSynchronize(main_stream()));
   }
 
@@ -903,9 +907,9 @@ struct rt_tracer {
   // and the lists are not kept across Traces (bench.py's headline: every step bins afresh) -- and reads the kept lists
   // otherwise (accumulating launches of a progressive Trace: macro_bin_kernel is 0.15 ms per half at C4, 7 % of a launch).
   // (Growing a buffer frees the old one first: hipFree waits for the device, safe while the other half runs.)
-  void attach_macro_lists(rtk::TraceParams& p, int half, hipStream_t st, bool first_launch_of_trace = true) {
+  void attach_macro_lists(rtk::TraceParams& p, rtk::TracePath path, int half, hipStream_t st, bool first_launch_of_trace = true) {
     p.macro_lists = nullptr;
-    if (!bin || !macro || p.n_tris <= p.bin_list) return;
+    if (!macro || path == rtk::TracePath::FullScan || path == rtk::TracePath::SmallLists) return;
     rtr::HalfLists& h = half_lists[half];
     p.macro_w = kMacroW; p.macro_h = kMacroH;
     p.macro_nx = (p.W + p.macro_w - 1u) / p.macro_w;
@@ -932,28 +936,37 @@ struct rt_tracer {
       if (p.super_lists != nullptr) HIP_CHECK(rtk::launch_super_bin(p, fma, st));
       HIP_CHECK(rtk::launch_macro_bin(p, fma, st));
     }
-    attach_wave_lists(p, h, st, !same);
+    attach_wave_lists(p, path, h, st, !same);
   }
 
   // Dense scenes with the per-sample forms: the tiles' candidate lists (forms + triangle index, 64 bytes per candidate) live in HBM,
   // built by wave_lists_kernel behind the macro lists -- same key, same reuse rule -- and read by dense_trace_kernel through the
   // scalar cache (rt_dense.hpp).  Sized for the list capacity, (1 + cap) x 64 bytes per tile: 0.7 GB for a 4K frame at cap 84
   // (what a launch touches is the survivors: ~75 MB at C4); frames whose lists would exceed kWaveListsMaxBytes per half
-  // and instrumented launches keep the classification inside the trace kernel.
+  // and instrumented launches keep the classification inside the trace kernel (trace_path).
   static constexpr size_t kWaveListsMaxBytes = size_t(6) << 30;
-  void attach_wave_lists(rtk::TraceParams& p, rtr::HalfLists& h, hipStream_t st, bool macro_rebuilt) {
+  static size_t wave_list_tiles(const rtk::TraceParams& p) { return static_cast<size_t>((p.W + 31u) / 32u) * ((p.rows + 7u) / 8u) * 4u; }
+  static size_t wave_list_words(const rtk::TraceParams& p) { return wave_list_tiles(p) * (1u + p.bin_list) * 16u; }
+  void attach_wave_lists(rtk::TraceParams& p, rtk::TracePath path, rtr::HalfLists& h, hipStream_t st, bool macro_rebuilt) {
     p.wave_lists = nullptr; p.wave_cap = 0u;
     if (macro_rebuilt) h.wave_valid = false;                            // (also when this launch does not use them: they follow the macro lists' key)
-    if (!p.pretest_on || p.stats != nullptr || p.macro_lists == nullptr) return;
-    const size_t tiles = static_cast<size_t>((p.W + 31u) / 32u) * ((p.rows + 7u) / 8u) * 4u;
-    const size_t words = tiles * (1u + p.bin_list) * 16u;
-    if (words * sizeof(uint32_t) > kWaveListsMaxBytes) return;
-    if (h.wave.ensure(words)) h.wave_valid = false;
+    if (path != rtk::TracePath::DenseLists) return;
+    if (h.wave.ensure(wave_list_words(p))) h.wave_valid = false;
     p.wave_lists = h.wave.get(); p.wave_cap = p.bin_list;
     if (!h.wave_valid) {
       HIP_CHECK(rtk::launch_wave_lists(p, fma, st));
-      h.wave_valid = true; h.wave_cap = p.bin_list; h.wave_tiles = tiles;
+      h.wave_valid = true; h.wave_cap = p.bin_list; h.wave_tiles = wave_list_tiles(p);
     }
+  }
+
+  // Which kernel the (half-)launch `p` runs: the one place that decides it.  Evaluated per half: a half's rows decide whether
+  // its wave lists fit.  (p.pretest_on, params(): the forms need the filter, binning, pretest and 4 096 ... 50 000 triangles.)
+  rtk::TracePath trace_path(const rtk::TraceParams& p) const {
+    if (!bin) return rtk::TracePath::FullScan;
+    if (p.n_tris <= p.bin_list) return rtk::TracePath::SmallLists;
+    if (!p.pretest_on || !filter) return rtk::TracePath::Classify;
+    if (p.stats != nullptr || !macro || wave_list_words(p) * sizeof(uint32_t) > kWaveListsMaxBytes) return rtk::TracePath::ClassifyForms;
+    return rtk::TracePath::DenseLists;
   }
 
   static constexpr int kWindow = 4;
@@ -982,8 +995,8 @@ struct rt_tracer {
   // RayTracerImpl::TraceFunct, RayTracerImpl.cu:236-315 (runs on the render thread)
   // How many consecutive iterations one launch may run (1 = no fusing): bounded so that a launch
   // stays short (<= 64 samples per pixel) and a Stop() takes effect within a few launches.
-  uint32_t fused_iterations(uint32_t samplesPerIteration) const {
-    if (!rtk::trace_can_fuse(filter, bin) || samplesPerIteration == 0u) return 1u;
+  uint32_t fused_iterations(uint32_t samplesPerIteration) {
+    if (samplesPerIteration == 0u || !rtk::trace_can_fuse(trace_path(params(samplesPerIteration)), filter)) return 1u;
     const uint32_t n = 64u / samplesPerIteration;
     return n < 1u ? 1u : n;
   }

@@ -6,7 +6,7 @@ import re
 import sys
 
 path = sys.argv[1] if len(sys.argv) > 1 else "raytracertest_amd/csrc/_build/rt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s"
-want = sys.argv[2] if len(sys.argv) > 2 else "trace_kernelILb1ELi2ELb1ELb0ELb1ELb1ELb0ELb0E"
+want = sys.argv[2] if len(sys.argv) > 2 else "trace_kernelILb1ELi2ELb1ELb0ELNS_9TracePathE1ELb0E"   # <true, 2, true, false, SmallLists, false>
 inside = False
 count = collections.Counter()
 for line in open(path):
