@@ -7,7 +7,8 @@ the HIP path and the oracle are then both checked against the same bytes on any 
 Outputs (small, data only):
   rng_kats.json      curand_init/curand/curand_uniform restatement: states + first outputs
   sincos_kats.json   build-owned sincos at fixed arguments (bit patterns)
-  frames.json        CRC32 of render/counts/rng/image buffers for small and full-size configs
+  frames.json        CRC32 of render/counts/rng/image buffers for small and full-size configs (both arithmetic
+                     modes; the C4 / C5 bands in FMA, those of STRICT_BANDS in strict arithmetic too)
   frames_crops.npz   16x16 pixel crops (float bit patterns) of the same frames
 """
 import json
@@ -79,6 +80,10 @@ for _r in (0, 62, 377, 707, 1022, 1533, 1899, 2156):
     FRAMES["C4_rows%04d" % _r] = dict(W=3840, H=2160, row0=_r, rows=4, scene="rand10k", it=1, spp=64, fov=70.0, focal=3.0, aperture=0.05)
 for _r in (133, 1700, 2156):
     FRAMES["C5_rows%04d" % _r] = dict(W=3840, H=2160, row0=_r, rows=4, scene="rand10k", it=1, spp=256, fov=70.0, focal=3.0, aperture=0.05)
+# The full-size dense-scene bands that are also pinned in strict arithmetic (RT_MATH_STRICT, no contraction): the frame's
+# first and last rows, a macro-tile seam, the split row of the default launch, and one C5 band.  The other C4 / C5 bands
+# stay FMA-only (each strict band costs as much oracle time as its FMA twin).
+STRICT_BANDS = ("C4_rows0000", "C4_rows1022", "C4_band4", "C4_rows2156", "C5_rows2156")
 
 
 def scene_arrays(name):
@@ -114,7 +119,7 @@ def frames(only=None):
     for name, spec in FRAMES.items():
         if only and name not in only:
             continue
-        modes = (1, 0) if not name.startswith(("C4_", "C5_")) else (1,)
+        modes = (1, 0) if not name.startswith(("C4_", "C5_")) or name in STRICT_BANDS else (1,)
         for contract in modes:
             key = "%s/%s" % (name, "fma" if contract else "strict")
             o = render(spec, contract)

@@ -170,3 +170,53 @@ def test_harness_has_teeth_on_decisions(rt, orc):
     t = cc.run(g, o, all_tiles(96, 64), 0, lens, ladder=(1000,), tag="moved scene")
     g.close()
     assert t.bad[1000]["drop_hit"] > 0 and t.bad[1000]["sure_miss"] > 0 and t.contain_bad > 0
+
+
+def test_c4_forms_in_strict_arithmetic(rt, orc):
+    """The C4 per-sample forms probe of test_c4_scene_all_three_levels_and_the_forms in RT_MATH_STRICT (the kernels' FMA=false
+    instantiations, the oracle without contraction): the same 12 wave tiles, the full lens set."""
+    from raytracertest_amd import scenes
+    cfg = scenes.CONFIGS["C4"]
+    cam = dict(angles=cfg["angles"], fov=cfg["fov"], focal=cfg["focal"], aperture=cfg["aperture"])
+    tris, _ = scenes.scene_for("C4")
+    g, o = pair(rt, orc, cfg["width"], cfg["height"], tris, cam, 1, seed=cfg["seed"])
+    rng = np.random.default_rng(404)
+    W, H = cfg["width"], cfg["height"]
+    tiles = [(int(rng.integers(0, W // 8)) * 8, int(rng.integers(0, H // 8)) * 8) for _ in range(20)]
+    lens = cc.lens_samples(orc, seed=1, pixel_index=0)
+    t = cc.run(g, o, tiles[:12], 0, lens, forms=True, ladder=(1000, 0), tag="C4 strict forms")
+    g.close()
+    REPORT["C4_strict_wave_tiles_with_forms"] = clean(t, "C4 wave tiles, forms, strict")
+    assert t.form_rejects > 0.5 * t.form_tests > 0, "the forms should skip most candidate tests of a tile"
+
+
+def test_adversarial_dense_scenes_per_tile_and_triangle(rt, orc):
+    """adversarial_config(large=True): 4 096 ... 9 000 triangles, 400 of them aimed at the tiles' decision boundaries, six
+    configurations at fixed seeds, three in each arithmetic mode -- a sample of wave tiles with the per-sample forms, blocks
+    and macro tiles, each level's drops against the rays of its own region."""
+    from raytracertest_amd import scenes
+    lens = cc.lens_samples(orc, seed=3, pixel_index=5)
+    small = np.concatenate([lens[:1], lens[1:113:2], lens[-8:]])
+    waves, blocks, macros = cc.Tally(), cc.Tally(), cc.Tally()
+    modes = []
+    for k in range(6):
+        rng = np.random.default_rng(7100 + k)
+        c = adversarial_config(rng, large=True)
+        c["mode"] = k % 2
+        modes.append(c["mode"])
+        W, H = c["W"], c["H"]
+        g, o = pair(rt, orc, W, H, scenes._tri_rows(c["tris"]), c["cam"], c["mode"], seed=c["seed"])
+        tag = "adv-dense%d(n=%d, scale=%.3g, mode=%d)" % (k, c["tris"].shape[0], c["scale"], c["mode"])
+        tiles = all_tiles(W, H)
+        pick = rng.permutation(len(tiles))[:8]
+        waves.merge(cc.run(g, o, [tiles[i] for i in sorted(pick)], 0, small, forms=True, ladder=(1000, 0), tag=tag + " forms"))
+        blocks.merge(cc.run(g, o, [(x, y) for y in range(0, H, 8) for x in range(0, W, 32)][:4], 1, small, ladder=(1000, 0),
+                            max_pixels=128, tag=tag + " blocks"))
+        macros.merge(cc.run(g, o, [(0, 0)], 2, small, ladder=(1000, 0), max_pixels=192, tag=tag + " macro"))
+        g.close()
+    assert sorted(modes) == [0, 0, 0, 1, 1, 1]
+    REPORT["adversarial_dense_wave_tiles_with_forms"] = clean(waves, "adversarial dense scenes, wave tiles, forms")
+    REPORT["adversarial_dense_blocks"] = clean(blocks, "adversarial dense scenes, blocks")
+    REPORT["adversarial_dense_macro_tiles"] = clean(macros, "adversarial dense scenes, macro tiles")
+    assert waves.form_tests > 0 and waves.pairs > 0 and blocks.pairs > 0 and macros.pairs > 0
+    assert waves.dropped + blocks.dropped + macros.dropped > 0

@@ -38,14 +38,14 @@ def buffers(g):
     return g.RenderBuffer(), g.SampleCounts(), g.RngStates(), g.Image()
 
 
-def check_bands(golden, prefix, bufs, row_offset=0, first_row=0, n_rows=None):
-    """every committed `prefix`* band that lies inside rows [first_row, first_row + n_rows) of the frame against `bufs`
+def check_bands(golden, prefix, bufs, row_offset=0, first_row=0, n_rows=None, suffix="/fma"):
+    """every committed `prefix`*`suffix` band that lies inside rows [first_row, first_row + n_rows) of the frame against `bufs`
     (arrays whose row 0 is frame row `row_offset`); returns the bands checked"""
     frames, crops = golden
     render, counts, rng, image = bufs
     n_rows = render.shape[0] if n_rows is None else n_rows
     done = []
-    for key in sorted(k for k in frames if k.startswith(prefix) and k.endswith("/fma")):
+    for key in sorted(k for k in frames if k.startswith(prefix) and k.endswith(suffix)):
         m = frames[key]
         r0, n = m["spec"]["row0"], m["spec"]["rows"]
         if r0 < first_row or r0 + n > first_row + n_rows:
@@ -84,6 +84,34 @@ def test_c4_full_frame_default_launch_equals_the_full_scan_and_the_oracle_rows(r
     for name, a, b in zip(("render", "counts", "rng", "image"), base, ref):
         same = np.ascontiguousarray(a).view(np.uint32) == np.ascontiguousarray(b).view(np.uint32)
         assert same.all(), "%s: the default launch differs from the full scan in %d words, first at %s" % (
+            name, int((~same).sum()), np.argwhere(~same)[0].tolist())
+
+
+def test_c4_full_frame_strict_default_launch_equals_the_full_scan_and_the_oracle_rows(rt, golden):
+    """The same frame in RT_MATH_STRICT (the FMA=false kernels: wave lists, super / macro binning, the forms, split halves):
+    the default launch == the full scan in all four buffers of the whole frame, and the committed strict bands of the oracle
+    -- rows 0-3, 1022-1025 (a macro-tile seam), 1078-1081 (the split row), 2156-2159."""
+    from raytracertest_amd import scenes
+    cfg = scenes.CONFIGS["C4"]
+    tris, _ = scenes.scene_for("C4")
+
+    def full(**kw):
+        g = rt.RayTracer((cfg["width"], cfg["height"]), (0, 0, 0), cfg["angles"], cfg["fov"], cfg["focal"], cfg["aperture"], seed=cfg["seed"],
+                         math_mode=rt.MATH_STRICT, **kw)
+        assert g.UploadScene(tris)
+        g.SetListReuse(False)
+        g.TraceEnqueue(1, cfg["samples"]); g.Sync()
+        out = buffers(g)
+        g.close()
+        return out
+    base = full()
+    bands = check_bands(golden, "C4_", base, suffix="/strict")
+    assert len(bands) >= 4, bands
+    assert (base[1] == cfg["samples"]).all() and not base[0][..., 3].any()
+    ref = full(no_binning=True)
+    for name, a, b in zip(("render", "counts", "rng", "image"), base, ref):
+        same = np.ascontiguousarray(a).view(np.uint32) == np.ascontiguousarray(b).view(np.uint32)
+        assert same.all(), "%s: the strict default launch differs from the full scan in %d words, first at %s" % (
             name, int((~same).sum()), np.argwhere(~same)[0].tolist())
 
 
