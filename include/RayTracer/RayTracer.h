@@ -103,6 +103,27 @@ public:
     counts.resize(rt_tracer_buffer_bytes(mImpl, RT_BUF_COUNTS) / sizeof(uint32_t));
     return rt_tracer_read_buffer(mImpl, RT_BUF_COUNTS, counts.data(), counts.size() * sizeof(uint32_t)) == RT_OK;
   }
+  // Ray queries (rt_mi355x.h "ray queries"): the tracer's arithmetic and hit rule; rays are origin, direction pairs used as
+  // given.  hits[i].prim = triangle index, n_tris + sphere index, or RT_PRIM_NONE.
+  bool Intersect(const std::vector<math::vec3>& rays, std::vector<rt_hit>& hits) {
+    static_assert(sizeof(math::vec3) == 3 * sizeof(float), "vec3 layout");
+    hits.resize(rays.size() / 2);
+    return mImpl && rays.size() % 2 == 0 &&
+           rt_tracer_intersect(mImpl, reinterpret_cast<const float*>(rays.data()), hits.size(), hits.data()) == RT_OK;
+  }
+  // The pinhole ray of a full-image pixel; `ray` (origin, direction) when asked for: the hit point is o + t * d.
+  bool Pick(const math::uvec2& pixel, rt_hit& hit) { return Pick(pixel, hit, nullptr); }
+  bool Pick(const math::uvec2& pixel, rt_hit& hit, math::vec3 ray[2]) {
+    const uint32_t px[2] = {pixel.x, pixel.y};
+    float r[6];
+    if (!mImpl || rt_tracer_pick(mImpl, px, 1, &hit, r) != RT_OK) return false;
+    if (ray) { ray[0] = math::vec3(r[0], r[1], r[2]); ray[1] = math::vec3(r[3], r[4], r[5]); }
+    return true;
+  }
+  // Click to focus: the focal length becomes the distance to what the pixel sees (fov and aperture unchanged).
+  bool FocusAt(const math::uvec2& pixel, float* focalLength = nullptr) {
+    return mImpl && rt_tracer_focus_at(mImpl, pixel.x, pixel.y, focalLength) == RT_OK;
+  }
   std::string LastError() const { return mImpl ? rt_tracer_last_error(mImpl) : rt_last_error(); }
   rt_tracer* Handle() const { return mImpl; }
 

@@ -228,6 +228,40 @@ const char* rt_last_error(void);          /* for failures before a tracer exists
 int  rt_device_count(void);
 const char* rt_version(void);
 
+/* ---- ray queries ---------------------------------------------------------------------------
+ * What a ray hits in the tracer's scene, under the tracer's own rules: its arithmetic (RT_MATH_FMA / RT_MATH_STRICT) and
+ * its hit rule (the reference's farthest hit incl. negative t, or RT_FLAG_NEAREST_HIT).  The answer is exactly what the
+ * renderer computes for that ray (HitTriangle, Kernels.cuh:29-65, the scan of :73-92).
+ *   rays    n x 6 floats: origin xyz, direction xyz, used as given (Ray(o, d, false): nothing is normalised).
+ *   scan    triangles in upload order, then spheres; ties keep the first one scanned (Kernels.cuh:84).  Edge-format scenes
+ *           (rt_tracer_upload_scene_edges) are intersected with their uploaded rows.  No scene: every ray misses.
+ *   prim    a triangle index in [0, n_tris); n_tris + i for sphere i; RT_PRIM_NONE for no hit.
+ *   t u v   a triangle's t, u, v exactly as HitTriangle computes them (:50,:57,:63; t may be negative under the reference
+ *           rule); a sphere's t with u = v = 0; no hit: all 0.  NaN, infinite and zero-length rays get whatever the
+ *           reference arithmetic gives them.
+ * n = 0 is a no-op.  Queries never cancel or join a running Trace (a pick during a progressive render leaves it unchanged):
+ * they are serialised with the other calls and read only the scene and the camera.  A query sees the scene of the last
+ * upload that returned; uploads and destroy wait for the queries in flight before they replace the scene.  A multi-device
+ * handle (rt_tracer_create_multi) answers from its first band; a band tracer of a process group answers locally. */
+typedef struct rt_hit { float t, u, v; int32_t prim; } rt_hit;   /* 16 bytes */
+#define RT_PRIM_NONE (-1)
+/* Host arrays: rays n*6, hits n.  Returns with the hits in host memory. */
+int  rt_tracer_intersect(rt_tracer* t, const float* rays, size_t n, rt_hit* hits);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  hits must be 16-byte aligned. */
+int  rt_tracer_intersect_device(rt_tracer* t, const float* rays, size_t n, rt_hit* hits, void* stream);
+/* n (x, y) pixels in FULL-image coordinates (a band tracer may pick rows outside its band) through their pinhole rays
+ * (ThinLensCamera.cuh:111-130) of the camera the tracer holds at the call, computed on the device as the trace kernel does.
+ * rays (n*6, or NULL) receives those rays, for the hit point o + t*d.  A pixel outside the image: RT_ERR_INVALID, nothing
+ * written.  Returns with the results in host memory. */
+int  rt_tracer_pick(rt_tracer* t, const uint32_t* pixels, size_t n, rt_hit* hits, float* rays);
+/* Click to focus: picks (x, y); when the hit has prim >= 0 and 0 < t < inf, sets ONLY the focal length to t (for the
+ * normalised pinhole direction the focal point sits at focalLength along it, ThinLensCamera.cuh:45) and returns it through
+ * focal_length (or NULL).  fov and aperture keep their bits.  Otherwise RT_ERR_INVALID (background, or the hit is not in
+ * front of the camera; rt_tracer_last_error says which) and the camera is unchanged.  Like SetCameraParameters it does not
+ * join a running Trace. */
+int  rt_tracer_focus_at(rt_tracer* t, uint32_t x, uint32_t y, float* focal_length);
+
 /* ---- one frame sharded over several GPUs --------------------------------------
  * The reference builds ONE rt::RayTracer pinned to device 0 (OpenGLView/MainFrame.cpp:44-45,
  * OpenGLView/GLCanvas.cpp:259-260).  Pixels are independent and a pixel's RNG stream is keyed by its

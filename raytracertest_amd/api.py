@@ -4,7 +4,8 @@ the reference class, so that the parity tests read like a caller of the referenc
 (OpenGLView/MainFrame.cpp:45,219-256).
 
 There is NO fallback: if librt_mi355x.so is missing or no HIP device is usable this
-module raises.  PyTorch is not involved here at all.
+module raises.  PyTorch is not involved here, except that RayTracer.Intersect also takes a torch tensor on the
+tracer's device (torch is imported only then).
 """
 import ctypes as C
 import os
@@ -47,11 +48,17 @@ ABI_SYMBOLS = [
     "rt_tracer_gather_time", "rt_tracer_band_count", "rt_tracer_band_info",
     "rt_tracer_join_group_bands", "rt_balance_rows", "rt_tracer_rebalance", "rt_tracer_set_band", "rt_dbg_read_tile_lists", "rt_dbg_wave_list_counts", "rt_dbg_focal_boxes", "rt_dbg_classify",
     "rt_tracer_gather_only", "rt_tracer_group_info",
+    "rt_tracer_intersect", "rt_tracer_intersect_device", "rt_tracer_pick", "rt_tracer_focus_at",
 ]
 
 
 class RtError(RuntimeError):
     pass
+
+
+PRIM_NONE = -1
+# rt_hit: one ray query's answer (include/rt_mi355x.h)
+HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("prim", np.int32)])
 
 
 class Options(C.Structure):
@@ -191,6 +198,10 @@ def load_library():
         L.rt_tracer_gather_only.argtypes = [vp]
         L.rt_tracer_group_info.argtypes = [vp, C.c_char_p, C.c_size_t]
         L.rt_dbg_classify.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32, f32p, C.c_size_t]
+        L.rt_tracer_intersect.argtypes = [vp, vp, C.c_size_t, vp]
+        L.rt_tracer_intersect_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.rt_tracer_pick.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.rt_tracer_focus_at.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
         _lib = L
         return _lib
 
@@ -525,6 +536,49 @@ class RayTracer:
         out = np.zeros((reg.shape[0], per), np.float32)
         self._check(self._lib.rt_dbg_classify(self._h, level, 1 if forms else 0, slack_milli, _u32p(reg), reg.shape[0], _f32p(out), out.size))
         return out[:, :16], out[:, 16:].reshape(reg.shape[0], n_tris, 32 if forms else 12)
+
+    # ---- ray queries (rt_tracer_intersect / _device, rt_tracer_pick, rt_tracer_focus_at) -----------------------------
+    def Intersect(self, rays):
+        """What each ray hits, under the tracer's arithmetic and hit rule.  rays: (n, 6) float32 {origin, direction}, used as
+        given.  A numpy array -> structured array HIT_DTYPE (t, u, v, prim), on return.  A contiguous torch float32 tensor
+        on the tracer's device -> (n, 4) float32 tensor {t, u, v, prim bits} (column 3 .view(torch.int32)), enqueued on
+        torch.cuda.current_stream() without a host synchronisation.  prim: triangle index, n_tris + sphere index, or -1."""
+        if type(rays).__module__.startswith("torch"):
+            return self._intersect_tensor(rays)
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        hits = np.zeros(r.shape[0], HIT_DTYPE)
+        self._check(self._lib.rt_tracer_intersect(self._h, r.ctypes.data, r.shape[0], hits.ctypes.data))
+        return hits
+
+    def _intersect_tensor(self, rays):
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6 or not rays.is_contiguous():
+            raise ValueError("Intersect: expected a contiguous (n, 6) float32 tensor")
+        dev = self.Bands()[0]["device"]
+        if rays.device.type != "cuda" or rays.device.index != dev:
+            raise ValueError("Intersect: the rays are on %s, the tracer on cuda:%d" % (rays.device, dev))
+        hits = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
+        stream = torch.cuda.current_stream(rays.device).cuda_stream
+        self._check(self._lib.rt_tracer_intersect_device(self._h, rays.data_ptr(), rays.shape[0], hits.data_ptr(),
+                                                         C.c_void_p(stream)))
+        return hits
+
+    def Pick(self, pixels, return_rays=False):
+        """Pinhole rays of full-image (x, y) pixels (one pair or (n, 2)) against the scene: structured array HIT_DTYPE,
+        and with return_rays the (n, 6) rays as well."""
+        pix = np.ascontiguousarray(pixels, np.uint32).reshape(-1, 2)
+        hits = np.zeros(pix.shape[0], HIT_DTYPE)
+        rays = np.zeros((pix.shape[0], 6), np.float32) if return_rays else None
+        self._check(self._lib.rt_tracer_pick(self._h, pix.ctypes.data, pix.shape[0], hits.ctypes.data,
+                                             None if rays is None else rays.ctypes.data))
+        return (hits, rays) if return_rays else hits
+
+    def FocusAt(self, x, y):
+        """Sets the focal length to the distance the pinhole ray of pixel (x, y) travels to its hit; returns it.  Raises
+        RtError (camera unchanged) on a background pixel or a hit that is not in front of the camera."""
+        f = C.c_float()
+        self._check(self._lib.rt_tracer_focus_at(self._h, x, y, C.byref(f)))
+        return np.float32(f.value)
 
     def DebugGetRay(self, pixels, states):
         pix = np.ascontiguousarray(pixels, np.uint32).reshape(-1, 2)

@@ -1,6 +1,6 @@
 """Headless front end: `python -m raytracertest_amd.cli`.  The reference's command line
 (OpenGLView/App.cpp:62-184: -w -h -s -i -u -cx -cy -cz -cxa -cya -f -l -a, integer values,
-defaults App.cpp:11-23) without the GUI, plus scene/seed/output options; the image is saved
+defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --focus; the image is saved
 in the reference's BMP format (Common/Bitmap.h).  Same options as tools/rt_cli.cpp."""
 import argparse
 import math
@@ -36,7 +36,15 @@ def build_parser():
     p.add_argument("-o", default="image0.bmp", dest="out")
     p.add_argument("-q", action="store_true", dest="quiet")
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--pick", type=_xy, default=None, metavar="X,Y", help="print `pick x y prim t u v` for the pixel's pinhole ray")
+    p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
+                   help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
     return p
+
+
+def _xy(s):
+    x, y = s.split(",")
+    return int(x), int(y)
 
 
 def load_scene(name):
@@ -73,6 +81,15 @@ def main(argv=None):
         sys.exit("scene '%s' has %d float4 (need a positive multiple of 3)" % (a.scene, tris.shape[0]))
     if spheres.shape[0]:
         g.UploadSpheres(spheres)
+    if a.pick is not None:
+        h = g.Pick(a.pick)[0]
+        print("pick %d %d %d %.9g %.9g %.9g" % (a.pick[0], a.pick[1], h["prim"], h["t"], h["u"], h["v"]))
+    if a.focus is not None:
+        try:
+            f = g.FocusAt(*a.focus)
+        except Exception as e:
+            sys.exit("--focus: %s" % e)
+        print("focus %d %d focal %.9g" % (a.focus[0], a.focus[1], f))
     state = {"updates": 0, "image": None}
     g.SetUpdateCallback(lambda img, size: state.__setitem__("updates", state["updates"] + 1))
     g.SetFinishedCallback(lambda img, size: state.__setitem__("image", img.copy()))

@@ -109,6 +109,13 @@ int trace_occupancy(int K, size_t lds);
 hipError_t launch_convert(const float4* render, const uint32_t* counts, uint32_t* image, uint32_t npix,
                           hipStream_t st);
 
+// Ray queries (rt_query.hpp): n rays {origin xyz, direction xyz} -- or, when `pixels` is not null, the pinhole rays of n
+// full-image (x, y) pairs, also written to rays_out when that is not null -- against p's scene under p.flags' hit rule; hits[i] =
+// {t, u, v, bits of the int32 primitive}.  K in {1, 2, 4} rays per lane.
+uint32_t query_lds_bytes(uint32_t n_tris, int K);
+hipError_t launch_query(const TraceParams& p, bool fma, int K, uint32_t n, const float* rays, const uint32_t* pixels,
+                        float* rays_out, float4* hits, hipStream_t st);
+
 hipError_t launch_dbg_hit_triangle(bool fma, uint32_t n, const float* rays, const float* tris, int eps_mode,
                                    int* hit, float* tuv, float* normal, float* point, hipStream_t st);
 bool trace_can_fuse(TracePath path, bool filter);   // launches with TraceParams::iters > 1 are available

@@ -323,6 +323,7 @@ static int upload_scene_impl(rt_tracer* t, const rt_float4* hostData, size_t cou
     t->use_device();
     HIP_CHECK(hipStreamSynchronize(t->main_stream()));
     t->sync_list_stream();                                               // (a list build may still be reading the old records)
+    t->wait_queries();                                                   // (and so may a query)
     t->d_tri.reset(); t->d_tri_b.reset(); t->d_tri_color.reset(); t->d_tri_n.reset();   // :128-137
     t->n_tris = 0;
     const uint32_t n = static_cast<uint32_t>(count / 3);                 // :139
@@ -381,6 +382,7 @@ int rt_tracer_upload_spheres(rt_tracer* t, const rt_float4* spheres, size_t coun
     t->cancel_and_join();
     t->use_device();
     HIP_CHECK(hipStreamSynchronize(t->main_stream()));
+    t->wait_queries();
     t->d_spheres.reset();
     t->n_spheres = 0;
     if (count == 0) return;
@@ -723,3 +725,5 @@ int rt_tracer_band_info(rt_tracer* t, uint32_t band, uint32_t out[4]) {
 }
 
 }  // extern "C"
+
+#include "rt_query_api.hpp"

@@ -425,6 +425,7 @@ struct rt_tracer {
   // because its half always uses the same stream.  main_stream() is the ordering point for everything else.
   rtr::Stream stream_b;
   rtr::Stream stream_l;               // the small scenes' list builds (highest priority; TileListRing)
+  rtr::Stream stream_q;               // ray queries (rt_query_api.hpp): created by the first query, highest priority
   rtr::Event join_event, fork_event;
   bool b_dirty = false;               // work on stream_b the primary stream has not waited for yet
   bool a_dirty = false;               // non-launch work on the primary stream that stream_b has not waited for yet
@@ -466,6 +467,13 @@ struct rt_tracer {
   uint32_t n_tris = 0;
   rtr::DevArray<float4> d_spheres;
   uint32_t n_spheres = 0;
+  // ray queries: grow-only staging of the host-array entry points, and an event behind every query enqueued (on stream_q or
+  // a caller's stream) that covers all earlier ones -- what uploads and destroy wait for before they free the scene's records
+  rtr::DevArray<float> d_q_rays;
+  rtr::DevArray<uint32_t> d_q_pixels;
+  rtr::DevArray<float4> d_q_hits;
+  rtr::Event query_done;
+  void wait_queries() { if (query_done) HIP_CHECK(hipEventSynchronize(query_done)); }
 
   // camera + callbacks (guarded by state_mu; snapshotted per launch like the by-value kernel argument)
   std::mutex state_mu;
@@ -507,7 +515,8 @@ struct rt_tracer {
   // every stream idle and every sampled launch accounted (destruction: the owning members release the rest)
   void quiesce() {
     (void)hipSetDevice(device);
-    for (const rtr::Stream* s : {&stream_b, &stream, &stream_l}) if (*s) (void)hipStreamSynchronize(*s);
+    for (const rtr::Stream* s : {&stream_b, &stream, &stream_l, &stream_q}) if (*s) (void)hipStreamSynchronize(*s);
+    if (query_done) (void)hipEventSynchronize(query_done);
     clock.drain();
   }
 

@@ -27,7 +27,21 @@ struct Args {
   uint64_t seed = 0; bool have_seed = false;
   std::string scene = "demo3", scene_file, out = "image0.bmp";
   bool quiet = false, edges = false, smooth = false, nearest = false;
+  bool pick = false, focus = false;
+  uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0};
 };
+
+// "X,Y" -> two pixel coordinates
+bool parse_xy(const char* s, uint32_t xy[2]) {
+  char* end = nullptr;
+  const unsigned long x = std::strtoul(s, &end, 10);
+  if (end == s || *end != ',') return false;
+  const char* s2 = end + 1;
+  const unsigned long y = std::strtoul(s2, &end, 10);
+  if (end == s2 || *end != 0) return false;
+  xy[0] = static_cast<uint32_t>(x); xy[1] = static_cast<uint32_t>(y);
+  return true;
+}
 
 std::vector<float4> demo3() {                   // MainFrame.cpp:230-232
   return {make_float4(0, 0, 10, 1), make_float4(0, 1, 10, 0), make_float4(1, 0, 10, 0),
@@ -52,7 +66,9 @@ void usage() {
             "       [-cxa deg] [-cya deg] [-f fovDeg] [-l focalLength] [-a aperture]      (reference flags, integers)\n"
             "       [--focal F] [--aperture A] [--fov F]                                  (float forms)\n"
             "       [--scene demo3|<file.f4>] [--seed N] [-o out.bmp] [-q]\n"
-            "       [--edges] (file holds (v0,e0,e1) rows, packed vertex normals in .w)  [--smooth] [--nearest]");
+            "       [--edges] (file holds (v0,e0,e1) rows, packed vertex normals in .w)  [--smooth] [--nearest]\n"
+            "       [--pick X,Y]  (prints `pick x y prim t u v` for the pixel's pinhole ray)\n"
+            "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)");
 }
 
 }  // namespace
@@ -88,6 +104,11 @@ int main(int argc, char** argv) {
     else if (k == "--edges") a.edges = true;
     else if (k == "--smooth") a.smooth = true;
     else if (k == "--nearest") a.nearest = true;
+    else if (k == "--pick" || k == "--focus") {
+      const bool pk = k == "--pick";
+      if (!parse_xy(next(k.c_str()), pk ? a.pick_xy : a.focus_xy)) { std::fprintf(stderr, "%s wants X,Y\n", k.c_str()); return 2; }
+      (pk ? a.pick : a.focus) = true;
+    }
     else if (k == "-o") a.out = next("-o");
     else if (k == "-q") a.quiet = true;
     else if (k == "-v") a.quiet = false;
@@ -112,6 +133,24 @@ int main(int argc, char** argv) {
   }
   if (a.edges) tracer.UploadSceneEdges(scene);
   else tracer.UploadScene(scene);
+
+  if (a.pick) {
+    rt_hit hit;
+    if (!tracer.Pick(math::uvec2(a.pick_xy[0], a.pick_xy[1]), hit)) {
+      std::fprintf(stderr, "rt_cli: --pick: %s\n", tracer.LastError().c_str());
+      return 1;
+    }
+    std::printf("pick %u %u %d %.9g %.9g %.9g\n", a.pick_xy[0], a.pick_xy[1], hit.prim, static_cast<double>(hit.t),
+                static_cast<double>(hit.u), static_cast<double>(hit.v));
+  }
+  if (a.focus) {
+    float focal = 0.0f;
+    if (!tracer.FocusAt(math::uvec2(a.focus_xy[0], a.focus_xy[1]), &focal)) {
+      std::fprintf(stderr, "rt_cli: --focus: %s\n", tracer.LastError().c_str());
+      return 1;
+    }
+    std::printf("focus %u %u focal %.9g\n", a.focus_xy[0], a.focus_xy[1], static_cast<double>(focal));
+  }
 
   uint32_t updates = 0;
   std::vector<rt::Color> finalImage;
