@@ -124,6 +124,15 @@ public:
   bool FocusAt(const math::uvec2& pixel, float* focalLength = nullptr) {
     return mImpl && rt_tracer_focus_at(mImpl, pixel.x, pixel.y, focalLength) == RT_OK;
   }
+  // Opt-in BVH for Intersect / Pick / FocusAt (rt_tracer_set_query_accel; false = the default scan).  Same answers for every
+  // ray whose scan winner is well conditioned (rt_mi355x.h, "ray queries"); the tree is built by the next query.
+  bool SetQueryAcceleration(bool bvh) { return mImpl && rt_tracer_set_query_accel(mImpl, bvh ? RT_QUERY_BVH : RT_QUERY_SCAN) == RT_OK; }
+  struct QueryAccel { bool bvh, valid; uint64_t nodes, leaves, depth, alwaysTested, buildMicroseconds, deviceBytes; };
+  QueryAccel QueryAccelInfo() const {
+    uint64_t o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (mImpl) (void)rt_tracer_query_accel_info(mImpl, o);
+    return QueryAccel{o[0] == RT_QUERY_BVH, o[1] != 0, o[2], o[3], o[4], o[5], o[6], o[7]};
+  }
   std::string LastError() const { return mImpl ? rt_tracer_last_error(mImpl) : rt_last_error(); }
   rt_tracer* Handle() const { return mImpl; }
 

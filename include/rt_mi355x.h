@@ -262,6 +262,25 @@ int  rt_tracer_pick(rt_tracer* t, const uint32_t* pixels, size_t n, rt_hit* hits
  * join a running Trace. */
 int  rt_tracer_focus_at(rt_tracer* t, uint32_t x, uint32_t y, float* focal_length);
 
+/* Opt-in acceleration of the four entry points above: a bounding volume hierarchy (BVH) over the uploaded triangles, built on the
+ * host by the first query after an upload (UploadScene / UploadSceneEdges invalidate it, UploadSpheres does not; the build waits
+ * for no Trace) and walked per ray on the device.  RT_QUERY_SCAN is the default and launches exactly the kernels described
+ * above.  A multi-device handle forwards both calls to its first band.
+ * With RT_QUERY_BVH the answer is the scan's -- same prim, and t, u, v with the same bits, under both hit rules, both arithmetic
+ * modes, both scene layouts, with spheres (scanned after the triangles as before) -- for every ray whose scan winner is WELL
+ * CONDITIONED: in float64, det / (|d| |e1| |e2|) >= 2^-10, det = e1 . (d x e2) of the record the kernel intersects.  The
+ * reason: the boxes prune by geometry, and for a ray within rounding of a triangle's plane the fp32 test's det, u and v are
+ * noise, so that the scan may report a hit the line passes nowhere near; no finite padding of a box covers that.  For a ray
+ * whose scan winner is not well conditioned the BVH mode may return another primitive that the exact test accepts, or none; it
+ * never returns a primitive the exact test rejects.  Rays with a non-finite component, a zero direction, or for which the box
+ * arithmetic yields a NaN take no pruning decision and get the scan's answer unconditionally. */
+#define RT_QUERY_SCAN 0u   /* default: every ray scans every triangle */
+#define RT_QUERY_BVH  1u
+int  rt_tracer_set_query_accel(rt_tracer* t, uint32_t mode);
+/* out = {mode, tree valid (0/1), nodes, leaves, max depth (levels of nodes), triangles in the always-tested list, host build
+ * time in us, device bytes of the tree}; the last six are 0 while no valid tree exists. */
+int  rt_tracer_query_accel_info(rt_tracer* t, uint64_t out[8]);
+
 /* ---- one frame sharded over several GPUs --------------------------------------
  * The reference builds ONE rt::RayTracer pinned to device 0 (OpenGLView/MainFrame.cpp:44-45,
  * OpenGLView/GLCanvas.cpp:259-260).  Pixels are independent and a pixel's RNG stream is keyed by its
@@ -370,6 +389,22 @@ int rt_dbg_focal_boxes(rt_tracer* t, float curv_scale, float* boxes, size_t boxe
  *   forms {F1.c0, cx, cy, F2..., F3..., g1.xyz, g2.xyz, g3.xyz} each form scaled by its power of two, the gradients the fp16 values the kernel stores, 2 x 0. */
 int rt_dbg_classify(rt_tracer* t, uint32_t level, uint32_t forms, uint32_t slack_milli, const uint32_t* regions, uint32_t n_regions,
                     float* out, size_t capacity_floats);
+/* The BVH builder of RT_QUERY_BVH on its own; needs no device.  rows: count float4 as rt_tracer_upload_scene takes them, or
+ * (edges_layout != 0) as rt_tracer_upload_scene_edges does.  Writes the node array and the record array exactly as a tracer
+ * uploads them; info = {depth bound the traversal stack is sized from, 1, nodes, leaves, max depth, always-tested, build us,
+ * bytes}.  With both capacities 0 only info is written (nodes * 128 and count / 3 * 48 bytes are needed).
+ *   node, 128 bytes:   float lo_x[4], lo_y[4], lo_z[4], hi_x[4], hi_y[4], hi_z[4] (the four children's boxes); uint32 child[4];
+ *                      float cmax[4] (largest |coordinate| of the child's box).  child: 0xFFFFFFFF = none (lo = +inf, hi = -inf);
+ *                      bit 31 set = leaf, bits 28-29 = triangles - 1 (1..4), bits 0-27 = its first record; else a node index.
+ *                      Node 0 is the root; no node at all when no triangle is finite.
+ *   record, 48 bytes:  float e2[3], e1[3], v0[3]; uint32 upload index; 2 x uint32 0.  The leaves' records come first (a leaf's
+ *                      ascending by upload index), then the always-tested list: the triangles with a non-finite record, which
+ *                      are in no box and which every ray tests. */
+int rt_dbg_bvh_build(const rt_float4* rows, size_t count, int edges_layout, void* nodes, size_t node_capacity_bytes,
+                     void* leaf_records, size_t leaf_capacity_bytes, uint64_t info[8]);
+/* Multiplies the box test's inflation rho for this tracer's following queries in RT_QUERY_BVH mode (1000 = the product; 300,
+ * 100, 30, 10, 0 exist so that the margin can be measured in the shipped library, tools/bvh_margin.py). */
+int rt_dbg_query_accel_slack(rt_tracer* t, uint32_t slack_milli);
 /* states n*6 {d,v0..v4} advanced in place, out n*m uniforms in (0,1] */
 int rt_dbg_uniform(int device, uint32_t n, uint32_t m, uint32_t* states, float* out);
 /* thin-lens rays of the tracer's current camera for n (x, y) pixels with given RNG states */

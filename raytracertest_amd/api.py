@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "rt_tracer_join_group_bands", "rt_balance_rows", "rt_tracer_rebalance", "rt_tracer_set_band", "rt_dbg_read_tile_lists", "rt_dbg_wave_list_counts", "rt_dbg_focal_boxes", "rt_dbg_classify",
     "rt_tracer_gather_only", "rt_tracer_group_info",
     "rt_tracer_intersect", "rt_tracer_intersect_device", "rt_tracer_pick", "rt_tracer_focus_at",
+    "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
 ]
 
 
@@ -57,6 +58,30 @@ class RtError(RuntimeError):
 
 
 PRIM_NONE = -1
+QUERY_SCAN, QUERY_BVH = 0, 1
+# the arrays of rt_dbg_bvh_build (include/rt_mi355x.h): a 4-wide node and a leaf record
+BVH_NODE_DTYPE = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("child", np.uint32, 4), ("cmax", np.float32, 4)])
+BVH_RECORD_DTYPE = np.dtype([("e2", np.float32, 3), ("e1", np.float32, 3), ("v0", np.float32, 3), ("index", np.uint32), ("pad", np.uint32, 2)])
+BVH_EMPTY, BVH_LEAF = 0xFFFFFFFF, 0x80000000
+_ACCEL_KEYS = ("mode", "valid", "nodes", "leaves", "depth", "always_tested", "build_us", "device_bytes")
+
+
+def bvh_build(rows, edges=False):
+    """rt_dbg_bvh_build: the query BVH of upload rows (3N, 4), built on the host (no device needed) -> (nodes
+    BVH_NODE_DTYPE, records BVH_RECORD_DTYPE, info dict; info["depth_bound"] is what the traversal stack is sized from)."""
+    L = load_library()
+    r = np.ascontiguousarray(rows, np.float32).reshape(-1, 4)
+    info = (C.c_uint64 * 8)()
+    if L.rt_dbg_bvh_build(r.ctypes.data, r.shape[0], int(bool(edges)), None, 0, None, 0, info) != 0:
+        raise RtError("rt_dbg_bvh_build: " + L.rt_last_error().decode())
+    nodes = np.zeros(int(info[2]), BVH_NODE_DTYPE)
+    recs = np.zeros(r.shape[0] // 3, BVH_RECORD_DTYPE)
+    if L.rt_dbg_bvh_build(r.ctypes.data, r.shape[0], int(bool(edges)), nodes.ctypes.data, max(nodes.nbytes, 1), recs.ctypes.data,
+                          max(recs.nbytes, 1), info) != 0:
+        raise RtError("rt_dbg_bvh_build: " + L.rt_last_error().decode())
+    d = dict(zip(_ACCEL_KEYS, (int(x) for x in info)))
+    d["depth_bound"] = d.pop("mode")
+    return nodes, recs, d
 # rt_hit: one ray query's answer (include/rt_mi355x.h)
 HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("prim", np.int32)])
 
@@ -202,6 +227,10 @@ def load_library():
         L.rt_tracer_intersect_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.rt_tracer_pick.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.rt_tracer_focus_at.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
+        L.rt_tracer_set_query_accel.argtypes = [vp, C.c_uint32]
+        L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_dbg_query_accel_slack.argtypes = [vp, C.c_uint32]
+        L.rt_dbg_bvh_build.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint64)]
         _lib = L
         return _lib
 
@@ -579,6 +608,21 @@ class RayTracer:
         f = C.c_float()
         self._check(self._lib.rt_tracer_focus_at(self._h, x, y, C.byref(f)))
         return np.float32(f.value)
+
+    def SetQueryAcceleration(self, mode):
+        """How Intersect / Pick / FocusAt find their hits: QUERY_SCAN (0 / False, the default: every ray scans every triangle)
+        or QUERY_BVH (1 / True: a bounding volume hierarchy over the uploaded scene, built by the next query).  Same answer
+        for every ray whose scan winner is well conditioned (include/rt_mi355x.h, "ray queries")."""
+        self._check(self._lib.rt_tracer_set_query_accel(self._h, int(mode)))
+
+    def QueryAccelInfo(self):
+        """rt_tracer_query_accel_info as a dict: mode, valid, nodes, leaves, depth, always_tested, build_us, device_bytes."""
+        out = (C.c_uint64 * 8)()
+        self._check(self._lib.rt_tracer_query_accel_info(self._h, out))
+        return dict(zip(_ACCEL_KEYS, (int(x) for x in out)))
+
+    def DebugQueryAccelSlack(self, slack_milli):
+        self._check(self._lib.rt_dbg_query_accel_slack(self._h, int(slack_milli)))
 
     def DebugGetRay(self, pixels, states):
         pix = np.ascontiguousarray(pixels, np.uint32).reshape(-1, 2)

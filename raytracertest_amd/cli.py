@@ -37,6 +37,7 @@ def build_parser():
     p.add_argument("-q", action="store_true", dest="quiet")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--pick", type=_xy, default=None, metavar="X,Y", help="print `pick x y prim t u v` for the pixel's pinhole ray")
+    p.add_argument("--accel", action="store_true", help="--pick / --focus through the scene's BVH instead of the scan")
     p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
                    help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
     return p
@@ -81,6 +82,8 @@ def main(argv=None):
         sys.exit("scene '%s' has %d float4 (need a positive multiple of 3)" % (a.scene, tris.shape[0]))
     if spheres.shape[0]:
         g.UploadSpheres(spheres)
+    if a.accel:
+        g.SetQueryAcceleration(True)
     if a.pick is not None:
         h = g.Pick(a.pick)[0]
         print("pick %d %d %d %.9g %.9g %.9g" % (a.pick[0], a.pick[1], h["prim"], h["t"], h["u"], h["v"]))

@@ -6,11 +6,13 @@
 //                         (rt_trace.hpp; RayTracer/Kernels.cuh:29-147, ThinLensCamera.cuh:30-52,111-130)
 //   convert_kernel     <- rt::ConverterKernel              (RayTracer/Kernels.cuh:149-169)
 //   query_kernel       <- Radiance's hit scan for caller rays / pixels (rt_query.hpp)
+//   query_bvh_kernel   <- the same answer through a bounding volume hierarchy (rt_bvh.hpp)
 //   dbg_* kernels      <- single-function harnesses used by the parity tests
 #include <stdlib.h>
 
 #include "rt_dense.hpp"
 #include "rt_query.hpp"
+#include "rt_bvh.hpp"
 
 namespace rtk {
 

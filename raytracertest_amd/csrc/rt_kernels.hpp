@@ -116,6 +116,22 @@ uint32_t query_lds_bytes(uint32_t n_tris, int K);
 hipError_t launch_query(const TraceParams& p, bool fma, int K, uint32_t n, const float* rays, const uint32_t* pixels,
                         float* rays_out, float4* hits, hipStream_t st);
 
+// The same through the scene's bounding volume hierarchy (rt_bvh.hpp; the tree: rt_bvh_host.hpp), one ray per lane.
+#define RT_BVH_RHO 0.00390625f      // 2^-8: DESIGN.md 4.3b derives it
+
+struct BvhParams {
+  const float4* nodes;      // 8 float4 per node
+  const float4* records;    // 3 float4 per record: (e2.xyz, e1.x), (e1.yz, v0.xy), (v0.z, upload index, 0, 0)
+  uint32_t n_nodes;         // 0: no tree (no finite triangle)
+  uint32_t n_leaf_records;  // records [0, n_leaf_records) are the leaves', [n_leaf_records, + n_always) the always-tested list
+  uint32_t n_always;
+  uint32_t stack_cap;       // entries per lane
+  float rho;                // RT_BVH_RHO x the tracer's slack
+};
+uint32_t query_bvh_lds_bytes(uint32_t stack_cap);
+hipError_t launch_query_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* rays, const uint32_t* pixels,
+                            float* rays_out, float4* hits, hipStream_t st);
+
 hipError_t launch_dbg_hit_triangle(bool fma, uint32_t n, const float* rays, const float* tris, int eps_mode,
                                    int* hit, float* tuv, float* normal, float* point, hipStream_t st);
 bool trace_can_fuse(TracePath path, bool filter);   // launches with TraceParams::iters > 1 are available

@@ -8,6 +8,8 @@
 #pragma once
 #include <cmath>
 
+#include "rt_bvh_host.hpp"
+
 namespace rtr {
 
 constexpr size_t kQueryMaxRays = 0xFFFFFFFFu;
@@ -29,14 +31,56 @@ inline hipStream_t query_stream(rt_tracer* t) {
   return t->stream_q;
 }
 
+// RT_QUERY_BVH: the tree of the current scene, built on the host from the records the kernel intersects (read back from the
+// device: for either upload layout they are what prep_triangles_kernel stored) and uploaded, all on the query stream -- the
+// upload that made the records has returned, so the build waits for no Trace.  Queries in flight may still read the old
+// tree: they are waited for before its buffers are rewritten.
+inline void ensure_query_tree(rt_tracer* t) {
+  if (t->bvh_valid()) return;
+  const hipStream_t st = query_stream(t);
+  t->wait_queries();
+  const size_t n = t->n_tris;
+  if (n > rtb::kBvhMaxTris) throw HipFail{fmt("RT_QUERY_BVH: %zu triangles (at most %zu)", n, rtb::kBvhMaxTris)};
+  std::vector<float> a(n * 8u), b(n);
+  if (n != 0u) {
+    HIP_CHECK(hipMemcpyAsync(a.data(), t->d_tri.get(), n * 8u * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(b.data(), t->d_tri_b.get(), n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  }
+  const std::vector<float> rec = rtb::records_of_device(a.data(), b.data(), n);
+  const rtb::Tree tree = rtb::build(rec.data(), n);
+  t->d_bvh_nodes.ensure(std::max<size_t>(tree.nodes.size(), 1u) * 8u);
+  t->d_bvh_records.ensure(std::max<size_t>(tree.records.size(), 1u) * 3u);
+  if (!tree.nodes.empty()) HIP_CHECK(hipMemcpyAsync(t->d_bvh_nodes.get(), tree.nodes.data(), tree.nodes.size() * sizeof(rtb::Node), hipMemcpyHostToDevice, st));
+  if (!tree.records.empty()) HIP_CHECK(hipMemcpyAsync(t->d_bvh_records.get(), tree.records.data(), tree.records.size() * sizeof(rtb::Record), hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipStreamSynchronize(st));                                   // (the host vectors go away; a caller's stream may run the query)
+  t->bvh_info[0] = tree.nodes.size(); t->bvh_info[1] = tree.leaves; t->bvh_info[2] = tree.depth; t->bvh_info[3] = tree.always;
+  t->bvh_info[4] = tree.build_us; t->bvh_info[5] = tree.bytes();
+  t->bvh_leaf_records = static_cast<uint32_t>(tree.records.size() - tree.always);
+  t->bvh_scene = t->scene_generation;
+  t->bvh_built = true;
+}
+
 // rays (or pixels) -> hits on `st`, behind every earlier query: query_done then covers this one and all before it
 inline void enqueue_query(rt_tracer* t, size_t n, const float* rays, const uint32_t* pixels, float* rays_out, float4* hits,
                           hipStream_t st) {
   rtk::TraceParams p = t->params(1);                                     // the launches' camera snapshot and scene
   p.flags = t->nearest_hit ? rtk::TRACE_NEAREST_HIT : 0u;
+  const bool bvh = t->query_accel == RT_QUERY_BVH;
+  if (bvh) ensure_query_tree(t);
   if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
   else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
-  HIP_CHECK(rtk::launch_query(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st));
+  if (bvh) {
+    rtk::BvhParams b;
+    b.nodes = t->d_bvh_nodes.get(); b.records = t->d_bvh_records.get();
+    b.n_nodes = static_cast<uint32_t>(t->bvh_info[0]); b.n_leaf_records = t->bvh_leaf_records;
+    b.n_always = static_cast<uint32_t>(t->bvh_info[3]);
+    b.stack_cap = rtb::stack_capacity(static_cast<uint32_t>(t->bvh_info[2]));
+    b.rho = RT_BVH_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f);
+    HIP_CHECK(rtk::launch_query_bvh(p, b, t->fma, static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st));
+  } else {
+    HIP_CHECK(rtk::launch_query(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st));
+  }
   HIP_CHECK(hipEventRecord(t->query_done, st));
 }
 
@@ -50,6 +94,59 @@ inline bool query_args_ok(rt_tracer* t, size_t n, const void* a, const void* b) 
 }  // namespace rtr
 
 extern "C" {
+
+int rt_tracer_set_query_accel(rt_tracer* t, uint32_t mode) {
+  if (!t) return RT_ERR_INVALID;
+  if (mode != RT_QUERY_SCAN && mode != RT_QUERY_BVH) { t->set_error(fmt("rt_tracer_set_query_accel: unknown mode %u", mode)); return RT_ERR_INVALID; }
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_set_query_accel(t->mg->bands[0], mode);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  t->query_accel = mode;
+  return RT_OK;
+}
+
+int rt_tracer_query_accel_info(rt_tracer* t, uint64_t out[8]) {
+  if (!t || !out) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_query_accel_info(t->mg->bands[0], out);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  const bool valid = t->bvh_valid();
+  out[0] = t->query_accel; out[1] = valid ? 1u : 0u;
+  for (int i = 0; i < 6; ++i) out[2 + i] = valid ? t->bvh_info[i] : 0u;
+  return RT_OK;
+}
+
+int rt_dbg_query_accel_slack(rt_tracer* t, uint32_t slack_milli) {
+  if (!t) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) return rt_dbg_query_accel_slack(t->mg->bands[0], slack_milli);
+  t->query_slack_milli = slack_milli;
+  return RT_OK;
+}
+
+int rt_dbg_bvh_build(const rt_float4* rows, size_t count, int edges_layout, void* nodes, size_t node_capacity_bytes,
+                     void* leaf_records, size_t leaf_capacity_bytes, uint64_t info[8]) {
+  if (!rows || !info || count < 3u || count % 3u != 0u || count / 3u > rtb::kBvhMaxTris) return RT_ERR_INVALID;
+  return guarded(nullptr, [&] {
+    const size_t n = count / 3u;
+    const std::vector<float> rec = rtb::records_of_rows(&rows[0].x, n, edges_layout != 0);
+    const rtb::Tree tree = rtb::build(rec.data(), n);
+    const size_t nb = tree.nodes.size() * sizeof(rtb::Node), rb = tree.records.size() * sizeof(rtb::Record);
+    info[0] = rtb::kBvhMaxDepth; info[1] = 1u; info[2] = tree.nodes.size(); info[3] = tree.leaves; info[4] = tree.depth;
+    info[5] = tree.always; info[6] = tree.build_us; info[7] = tree.bytes();
+    if (node_capacity_bytes == 0u && leaf_capacity_bytes == 0u) return;  // sizes only
+    if (!nodes || !leaf_records || node_capacity_bytes < nb || leaf_capacity_bytes < rb)
+      throw HipFail{fmt("rt_dbg_bvh_build: the tree needs %zu + %zu bytes", nb, rb)};
+    if (nb) memcpy(nodes, tree.nodes.data(), nb);
+    if (rb) memcpy(leaf_records, tree.records.data(), rb);
+  });
+}
 
 int rt_tracer_intersect(rt_tracer* t, const float* rays, size_t n, rt_hit* hits) {
   if (!t) return RT_ERR_INVALID;

@@ -474,6 +474,16 @@ struct rt_tracer {
   rtr::DevArray<float4> d_q_hits;
   rtr::Event query_done;
   void wait_queries() { if (query_done) HIP_CHECK(hipEventSynchronize(query_done)); }
+  // RT_QUERY_BVH (rt_bvh_host.hpp, rt_bvh.hpp): the tree of the scene of generation bvh_scene, built by the first query in
+  // that mode after an upload (rt_query_api.hpp, under api_mu).  The buffers are grow-only; a rebuild waits for the queries.
+  uint32_t query_accel = RT_QUERY_SCAN;
+  uint32_t query_slack_milli = 1000u;                 // rt_dbg_query_accel_slack: multiplies the box test's rho
+  rtr::DevArray<float4> d_bvh_nodes, d_bvh_records;
+  bool bvh_built = false;
+  uint32_t bvh_scene = 0;                             // scene_generation the tree was built for
+  uint64_t bvh_info[6] = {0, 0, 0, 0, 0, 0};          // nodes, leaves, depth, always-tested, build us, device bytes
+  uint32_t bvh_leaf_records = 0;
+  bool bvh_valid() const { return bvh_built && bvh_scene == scene_generation; }
 
   // camera + callbacks (guarded by state_mu; snapshotted per launch like the by-value kernel argument)
   std::mutex state_mu;

@@ -27,7 +27,7 @@ struct Args {
   uint64_t seed = 0; bool have_seed = false;
   std::string scene = "demo3", scene_file, out = "image0.bmp";
   bool quiet = false, edges = false, smooth = false, nearest = false;
-  bool pick = false, focus = false;
+  bool pick = false, focus = false, accel = false;
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0};
 };
 
@@ -68,7 +68,8 @@ void usage() {
             "       [--scene demo3|<file.f4>] [--seed N] [-o out.bmp] [-q]\n"
             "       [--edges] (file holds (v0,e0,e1) rows, packed vertex normals in .w)  [--smooth] [--nearest]\n"
             "       [--pick X,Y]  (prints `pick x y prim t u v` for the pixel's pinhole ray)\n"
-            "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)");
+            "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
+            "       [--accel]     (--pick / --focus through the scene's BVH instead of the scan)");
 }
 
 }  // namespace
@@ -104,6 +105,7 @@ int main(int argc, char** argv) {
     else if (k == "--edges") a.edges = true;
     else if (k == "--smooth") a.smooth = true;
     else if (k == "--nearest") a.nearest = true;
+    else if (k == "--accel") a.accel = true;
     else if (k == "--pick" || k == "--focus") {
       const bool pk = k == "--pick";
       if (!parse_xy(next(k.c_str()), pk ? a.pick_xy : a.focus_xy)) { std::fprintf(stderr, "%s wants X,Y\n", k.c_str()); return 2; }
@@ -134,6 +136,10 @@ int main(int argc, char** argv) {
   if (a.edges) tracer.UploadSceneEdges(scene);
   else tracer.UploadScene(scene);
 
+  if (a.accel && !tracer.SetQueryAcceleration(true)) {
+    std::fprintf(stderr, "rt_cli: --accel: %s\n", tracer.LastError().c_str());
+    return 1;
+  }
   if (a.pick) {
     rt_hit hit;
     if (!tracer.Pick(math::uvec2(a.pick_xy[0], a.pick_xy[1]), hit)) {
