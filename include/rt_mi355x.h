@@ -218,6 +218,11 @@ void* rt_tracer_stream(rt_tracer* t);
  * orders its OWN work behind a launch without blocking either stream records one event on each and
  * waits for both (raytracertest_amd/dist.py), or calls rt_tracer_sync. */
 void* rt_tracer_stream_b(rt_tracer* t);
+/* The device address of one of the tracer's buffers.  The Weyl word d of the RNG states (plane 0 of RT_BUF_RNG) and the
+ * sample count are the same for every pixel of a tracer, so the launches carry them as scalars and do not write these
+ * two planes: the read and copy entry points above fill them first, and a pointer obtained here for RT_BUF_RNG or
+ * RT_BUF_COUNTS holds d / the counts AS OF THIS CALL (filled on rt_tracer_stream: order behind it or call
+ * rt_tracer_sync; ask again after later launches).  Planes 1..5 of RT_BUF_RNG and the other buffers are always current. */
 void* rt_tracer_device_pointer(rt_tracer* t, int which);
 size_t rt_tracer_buffer_bytes(rt_tracer* t, int which);
 /* Launch geometry actually used: out[0]=K, out[1]=lds_chunk, out[2]=dynamic LDS bytes,

@@ -57,12 +57,12 @@ __global__ __launch_bounds__(256) void prep_triangles_kernel(const float4* __res
 // rt::ConverterKernel, Kernels.cuh:149-169: BGRA8 = pack(255 * sum / count)
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void convert_kernel(const float4* __restrict__ render,
-                                                       const uint32_t* __restrict__ counts,
+                                                       uint32_t count,
                                                        uint32_t* __restrict__ image, uint32_t npix) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= npix) return;
   const float4 s = render[i];
-  const float cnt = static_cast<float>(counts[i]);                  // :164
+  const float cnt = static_cast<float>(count);                      // :164 (the same for every pixel)
   image[i] = rtd::pack_color(255.0f * (s.x / cnt), 255.0f * (s.y / cnt), 255.0f * (s.z / cnt));
 }
 
@@ -405,10 +405,9 @@ int trace_occupancy(int K, size_t lds) {
   return e == hipSuccess ? n : -1;
 }
 
-hipError_t launch_convert(const float4* render, const uint32_t* counts, uint32_t* image, uint32_t npix,
-                          hipStream_t st) {
+hipError_t launch_convert(const float4* render, uint32_t count, uint32_t* image, uint32_t npix, hipStream_t st) {
   if (npix == 0) return hipSuccess;
-  hipLaunchKernelGGL(convert_kernel, dim3(cdiv(npix, 256)), dim3(256), 0, st, render, counts, image, npix);
+  hipLaunchKernelGGL(convert_kernel, dim3(cdiv(npix, 256)), dim3(256), 0, st, render, count, image, npix);
   return hipGetLastError();
 }
 

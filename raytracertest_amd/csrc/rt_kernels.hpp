@@ -12,8 +12,12 @@ constexpr uint32_t kSuperChunk = 1024u, kSuperMaxChunks = 64u;   // super tiles:
 
 struct TraceParams {
   float4*   render;    // rows*W RGBA float accumulators (mRenderBuffer)
-  uint32_t* counts;    // rows*W sample counts          (mSampleCountBuffer)
-  uint32_t* rng;       // 6 planes of rows*W u32: d, v0..v4 (mRandomStates, SoA)
+  uint32_t* rng;       // 6 planes of rows*W u32: d, v0..v4 (mRandomStates, SoA); the launches read and write v0..v4 only
+  // The two state words that are the same for every pixel of the band travel as scalars (rt_tracer::take_uniform_state):
+  // the XORWOW Weyl word d at the start of the launch (every pixel makes 3 draws per sample on every path, a draw adds
+  // 362437) and the sample count before it (mSampleCountBuffer; 0 with TRACE_ZERO_ACC).  Plane 0 of `rng` and the count
+  // buffer are filled from them when somebody reads them (rt_tracer::materialise).
+  uint32_t  weyl, count;
   uint32_t  W, H;      // full image size (camera uses the full height)
   uint32_t  row0, rows;
   uint32_t  npix;      // rows*W
@@ -98,7 +102,8 @@ enum class TracePath : uint32_t {
   DenseLists,      // forms and lists from HBM (p.wave_lists, wave_lists_kernel): no classification in the trace kernel
 };
 
-// jump: J^(2^k), k < 32, 160 columns x 8 words; win: the 4-bit window tables of J^(2^m), m < 6 (rt_rng_host.hpp)
+// jump: J^(2^k), k < 32, 160 columns x 8 words; win: the 4-bit window tables of J^(2^m), m < 6 (rt_rng_host.hpp).
+// Writes planes 1..5 (v0..v4); the Weyl word seeded[0] is every pixel's and stays with the host (TraceParams::weyl).
 hipError_t launch_rng_init(uint32_t* rng, uint32_t npix, uint32_t p0, const uint32_t seeded[6],
                            const uint32_t* jump, const uint32_t* win, hipStream_t st);
 hipError_t launch_prep_triangles(bool fma, bool edges, const float4* verts, uint32_t n, float4* tri_a, float* tri_b,
@@ -106,8 +111,7 @@ hipError_t launch_prep_triangles(bool fma, bool edges, const float4* verts, uint
 uint32_t trace_lds_bytes(const TraceParams& p, TracePath path);
 hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, TracePath path, int K, hipStream_t st);
 int trace_occupancy(int K, size_t lds);
-hipError_t launch_convert(const float4* render, const uint32_t* counts, uint32_t* image, uint32_t npix,
-                          hipStream_t st);
+hipError_t launch_convert(const float4* render, uint32_t count, uint32_t* image, uint32_t npix, hipStream_t st);
 
 // Ray queries (rt_query.hpp): n rays {origin xyz, direction xyz} -- or, when `pixels` is not null, the pinhole rays of n
 // full-image (x, y) pairs, also written to rays_out when that is not null -- against p's scene under p.flags' hit rule; hits[i] =

@@ -434,6 +434,8 @@ void multi_read_buffer(rt_tracer* t, int which, void* dst, size_t bytes) {
     rt_tracer* band = m.bands[k];
     band->use_device();
     const size_t band_px = band->npix(), off_px = static_cast<size_t>(g.bands[k].row0) * t->W;
+    band->materialise(which);                                          // each band keeps its own Weyl word and count
+    HIP_CHECK(hipStreamSynchronize(band->main_stream()));
     for (size_t p = 0; p < planes; ++p)
       HIP_CHECK(hipMemcpy(static_cast<char*>(dst) + (p * frame_px + off_px) * per_px,
                           static_cast<const char*>(buffer_ptr(band, which)) + p * band_px * per_px, band_px * per_px,

@@ -126,7 +126,6 @@ __global__ __launch_bounds__(kRngInitThreads, 4) void rng_init_kernel(uint32_t* 
     }
     const uint32_t i = base + lane;
     if (i < npix) {
-      rng[0 * static_cast<size_t>(npix) + i] = seeded.d;
       rng[1 * static_cast<size_t>(npix) + i] = v[0];
       rng[2 * static_cast<size_t>(npix) + i] = v[1];
       rng[3 * static_cast<size_t>(npix) + i] = v[2];

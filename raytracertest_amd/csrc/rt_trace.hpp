@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 
 #endif
   Rng rng;                                                         // :131
   auto load_rng = [&] {
-    rng.d = p.rng[0 * static_cast<size_t>(p.npix) + pix];
+    rng.d = p.weyl;                                                // wave-uniform: the Weyl step runs on the scalar unit
     rng.v0 = p.rng[1 * static_cast<size_t>(p.npix) + pix];
     rng.v1 = p.rng[2 * static_cast<size_t>(p.npix) + pix];
     rng.v2 = p.rng[3 * static_cast<size_t>(p.npix) + pix];
@@ -493,7 +493,6 @@ __global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 
   }
   const uint32_t iters = FUSE ? p.iters : 1u;
   float rx = 0.0f, ry = 0.0f, rz = 0.0f, rw = 0.0f;                // FUSE: the pixel's RenderBuffer value so far
-  uint32_t cnt_first = 0u;
   for (uint32_t it = 0; it < iters; ++it) {                        // FUSE: the host loop's iterations, :246
   if constexpr (FUSE) { ax = 0.0f; ay = 0.0f; az = 0.0f; }          // accu, :133
   uint32_t traced_samples = p.samples;
@@ -704,7 +703,6 @@ __global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 
     if (it == 0u && !(p.flags & TRACE_ZERO_ACC) && inside) {        // wave-uniform but for `inside`
       const float4 r0 = p.render[pix];
       rx = r0.x; ry = r0.y; rz = r0.z; rw = r0.w;
-      cnt_first = p.counts[pix];
     }
     rx += ax; ry += ay; rz += az;
   }
@@ -720,15 +718,10 @@ __global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 
     // the whole kernel cost more (spills at the 96-VGPR budget of 5 waves/SIMD) than the exposed
     // read latency of a finished wave (measured C3 169.4 -> 164.9 us, progressive launches equal).
     float4 acc_in = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    uint32_t cnt_in = 0u;
     if constexpr (!FUSE) {
-      if (!(p.flags & TRACE_ZERO_ACC)) {                            // wave-uniform
-        acc_in = p.render[pix_e];
-        cnt_in = p.counts[pix_e];
-      }
+      if (!(p.flags & TRACE_ZERO_ACC)) acc_in = p.render[pix_e];    // wave-uniform
     }
-    const uint32_t cnt = FUSE ? cnt_first + iters * p.samples : cnt_in + p.samples;   // :140
-    p.counts[pix_e] = cnt;
+    const uint32_t cnt = p.count + iters * p.samples;               // :140 (p.count: 0 with TRACE_ZERO_ACC; the host keeps the sum)
     float4 acc = acc_in;
     if constexpr (FUSE) {
       acc = make_float4(rx, ry, rz, rw);
@@ -747,8 +740,7 @@ __global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 
       // PCIe writes, one 256-byte row segment per wave store) -- no device-to-host copy afterwards
       if (p.image_host != nullptr) p.image_host[pix_e] = bgra;
     }
-    p.rng[0 * static_cast<size_t>(p.npix) + pix_e] = rng.d;           // :146
-    p.rng[1 * static_cast<size_t>(p.npix) + pix_e] = rng.v0;
+    p.rng[1 * static_cast<size_t>(p.npix) + pix_e] = rng.v0;          // :146 (d: the host advances it, rt_tracer::take_uniform_state)
     p.rng[2 * static_cast<size_t>(p.npix) + pix_e] = rng.v1;
     p.rng[3 * static_cast<size_t>(p.npix) + pix_e] = rng.v2;
     p.rng[4 * static_cast<size_t>(p.npix) + pix_e] = rng.v3;

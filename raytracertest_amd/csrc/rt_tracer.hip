@@ -544,7 +544,13 @@ int rt_tracer_launch_time(rt_tracer* t, double* total_ms, uint64_t* launches, in
 }
 
 size_t rt_tracer_buffer_bytes(rt_tracer* t, int which) { return t ? buffer_bytes(t, which) : 0; }
-void* rt_tracer_device_pointer(rt_tracer* t, int which) { return t ? buffer_ptr(t, which) : nullptr; }
+void* rt_tracer_device_pointer(rt_tracer* t, int which) {
+  if (!t) return nullptr;
+  // plane 0 of the RNG states / the counts as of this call, filled on the primary stream (rt_tracer::materialise)
+  if (!t->mg && (which == RT_BUF_RNG || which == RT_BUF_COUNTS) &&
+      guarded(t, [&] { t->use_device(); t->materialise(which); }) != RT_OK) return nullptr;
+  return buffer_ptr(t, which);
+}
 
 int rt_tracer_read_buffer(rt_tracer* t, int which, void* dst, size_t bytes) {
   if (!t || !dst) return RT_ERR_INVALID;
@@ -555,6 +561,7 @@ int rt_tracer_read_buffer(rt_tracer* t, int which, void* dst, size_t bytes) {
   if (buffer_ptr(t, which) == nullptr || bytes > buffer_bytes(t, which)) return RT_ERR_INVALID;
   return guarded(t, [&] {
     t->use_device();
+    t->materialise(which);
     HIP_CHECK(hipStreamSynchronize(t->main_stream()));
     if (t->grp) t->grp->sync();
     HIP_CHECK(hipMemcpy(dst, buffer_ptr(t, which), bytes, hipMemcpyDeviceToHost));
@@ -571,6 +578,7 @@ int rt_tracer_copy_buffer_to_device(rt_tracer* t, int which, void* dst_device, s
   return guarded(t, [&] {
     t->use_device();
     if (t->grp && which == RT_BUF_FRAME) t->grp->sync();
+    t->materialise(which);
     HIP_CHECK(hipMemcpyAsync(dst_device, buffer_ptr(t, which), bytes, hipMemcpyDeviceToDevice, t->main_stream()));
     HIP_CHECK(hipStreamSynchronize(t->main_stream()));
   });
@@ -581,6 +589,7 @@ int rt_tracer_copy_buffer_to_device_async(rt_tracer* t, int which, void* dst_dev
   if (t->mg || which == RT_BUF_FRAME) { t->set_error("rt_tracer_copy_buffer_to_device_async: per-stream copies are for plain tracers' own buffers"); return RT_ERR_STATE; }
   return guarded(t, [&] {
     t->use_device();
+    t->materialise(which);
     HIP_CHECK(hipMemcpyAsync(dst_device, buffer_ptr(t, which), bytes, hipMemcpyDeviceToDevice, t->main_stream()));
   });
 }

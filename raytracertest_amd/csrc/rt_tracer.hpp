@@ -433,10 +433,11 @@ struct rt_tracer {
 
   // The ordering state is shared by the render thread and by entry points that do not join it
   // (rt_tracer_sync, rt_tracer_read_buffer, the device copies): order_mu serialises the dirty flags and the
-  // re-recording of the two shared events.
-  std::mutex order_mu;
+  // re-recording of the two shared events -- and the uniform state words below with the launches that advance them
+  // (recursive: a launch is enqueued under it and asks for main_stream() / fork_b() on the way).
+  std::recursive_mutex order_mu;
   hipStream_t main_stream() {         // primary stream, made to wait for everything enqueued on stream_b
-    std::lock_guard<std::mutex> lk(order_mu);
+    std::lock_guard<std::recursive_mutex> lk(order_mu);
     if (b_dirty) {
       HIP_CHECK(hipEventRecord(join_event, stream_b));
       HIP_CHECK(hipStreamWaitEvent(stream, join_event, 0));
@@ -446,15 +447,47 @@ struct rt_tracer {
     return stream;
   }
   void fork_b() {                     // stream_b waits for the non-launch work enqueued on the primary stream
-    std::lock_guard<std::mutex> lk(order_mu);
+    std::lock_guard<std::recursive_mutex> lk(order_mu);
     if (!a_dirty) return;
     HIP_CHECK(hipEventRecord(fork_event, stream));
     HIP_CHECK(hipStreamWaitEvent(stream_b, fork_event, 0));
     a_dirty = false;
   }
-  void mark_b_dirty() { std::lock_guard<std::mutex> lk(order_mu); b_dirty = true; }
+  void mark_b_dirty() { std::lock_guard<std::recursive_mutex> lk(order_mu); b_dirty = true; }
   rtr::DevArray<float4> d_render;
   rtr::DevArray<uint32_t> d_counts, d_image, d_rng;
+  // Two words of the per-pixel state are the same for every pixel of the band, so the tracer keeps them and the launches
+  // get them as scalars (TraceParams::weyl, ::count) instead of loading and storing them per pixel:
+  //   weyl_now  -- the XORWOW Weyl word d: seeded[0] when the states are created (the subsequence jump acts on v0..v4
+  //                only), + 362437 per draw, 3 draws per sample on every path (get_ray, or rng_discard for certain winners);
+  //   count_now -- the samples accumulated since the accumulators were cleared.
+  // Plane 0 of d_rng and d_counts hold them only after materialise(), which every reader of the two buffers calls first;
+  // *_plane is the word the plane was last filled with.  All guarded by order_mu.
+  uint32_t weyl_now = 0, count_now = 0;
+  uint32_t weyl_plane = 0, count_plane = 0;
+  bool weyl_plane_ok = false, count_plane_ok = false;
+  // Once per launch of `p.samples` x `p.iters` samples (not per half of a split one), with order_mu held until the
+  // launch is enqueued: hands the launch the two words and advances them by what it will do to every pixel.
+  void take_uniform_state(rtk::TraceParams& p) {
+    if (p.flags & rtk::TRACE_ZERO_ACC) count_now = 0u;
+    p.weyl = weyl_now; p.count = count_now;
+    const uint32_t done = p.samples * (p.iters > 1u ? p.iters : 1u);
+    weyl_now += 362437u * 3u * done;
+    count_now += done;
+  }
+  // RT_BUF_RNG / RT_BUF_COUNTS are about to be read: plane 0 / the counts get the current word, on the stream that
+  // orders behind both trace streams (no launch touches either plane).  Skipped when the plane already holds it.
+  void materialise(int which) {
+    std::lock_guard<std::recursive_mutex> lk(order_mu);
+    if (which == RT_BUF_RNG && !(weyl_plane_ok && weyl_plane == weyl_now) && d_rng.get() != nullptr) {
+      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_rng.get()), static_cast<int>(weyl_now), npix(), main_stream()));
+      weyl_plane = weyl_now; weyl_plane_ok = true;
+    }
+    if (which == RT_BUF_COUNTS && !(count_plane_ok && count_plane == count_now) && d_counts.get() != nullptr) {
+      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_counts.get()), static_cast<int>(count_now), npix(), main_stream()));
+      count_plane = count_now; count_plane_ok = true;
+    }
+  }
   rtr::PinnedArray<uint32_t> h_image;       // handed to callbacks
   rtr::PinnedArray<uint32_t> h_image_alt;   // second image: update i+1 is produced while the callback reads update i
   uint32_t* image_mirror = nullptr; // rt_tracer_set_image_mirror: second target of emitting rt_tracer_launch* / trace_enqueue launches
@@ -536,7 +569,9 @@ struct rt_tracer {
     const uint32_t p0 = row0 * W;                                        // subsequence of the band's first pixel
     if (static_cast<uint64_t>(W) * H > 0xFFFFFFFFull) throw rtr::HipFail{"frames above 2^32 pixels are not supported (32-bit pixel index, Kernels.cuh:128)"};
     uint32_t* const tables = rtr::jump_device(device);
+    std::lock_guard<std::recursive_mutex> lk(order_mu);
     HIP_CHECK(rtk::launch_rng_init(d_rng.get(), npix(), p0, seeded, tables, tables + rtr::kJumpWords, main_stream()));
+    weyl_now = seeded[0]; weyl_plane_ok = false;                         // (the kernel writes v0..v4)
   }
 
   void create_buffers() {                                                // ctor :33-40, Resize :96-102
@@ -546,10 +581,10 @@ struct rt_tracer {
     memset(h_image.get(), 0, n * sizeof(uint32_t));
     memset(h_image_alt.get(), 0, n * sizeof(uint32_t));
     // the reference leaves new buffers uninitialised until the first Trace clears them; we
-    // zero them so that reading before a Trace is defined
+    // zero them so that reading before a Trace is defined (the counts: materialise())
     HIP_CHECK(hipMemsetAsync(d_render.get(), 0, n * sizeof(float4), main_stream()));
-    HIP_CHECK(hipMemsetAsync(d_counts.get(), 0, n * sizeof(uint32_t), main_stream()));
     HIP_CHECK(hipMemsetAsync(d_image.get(), 0, n * sizeof(uint32_t), main_stream()));
+    { std::lock_guard<std::recursive_mutex> lk(order_mu); count_now = 0u; count_plane_ok = false; }
     create_states();
     HIP_CHECK(hipStreamSynchronize(main_stream()));
   }
@@ -613,7 +648,7 @@ struct rt_tracer {
     memset(&p, 0, sizeof p);
     rtr::Camera c;
     { std::lock_guard<std::mutex> lk(state_mu); c = cam; }               // *mCamera by value, :221
-    p.render = d_render.get(); p.counts = d_counts.get(); p.rng = d_rng.get();
+    p.render = d_render.get(); p.rng = d_rng.get();             // (weyl, count: take_uniform_state)
     p.W = W; p.H = H; p.row0 = row0; p.rows = rows; p.npix = npix(); p.samples = samples;
     for (int col = 0; col < 4; ++col)
       for (int r = 0; r < 3; ++r) p.cam[col * 3 + r] = c.M[col * 4 + r];
@@ -693,6 +728,8 @@ struct rt_tracer {
     const uint32_t r0 = allow_split ? split_row(p.rows) : 0u;
     rtr::EventPair e;                                                    // sampled launches: timing events (LaunchClock)
     const bool timed = clock.start(sync_after == 1, r0 != 0u, e);
+    std::unique_lock<std::recursive_mutex> uniform_lk(order_mu);          // the state words and the launch that advances them
+    take_uniform_state(p);
     if (r0 == 0u) {
       (void)main_stream();                                               // a launch on one stream orders behind both
       if (build_lists) build_tile_lists_ahead(p);
@@ -742,6 +779,7 @@ struct rt_tracer {
       if (timed) { HIP_CHECK(hipEventRecord(e.b, stream)); HIP_CHECK(hipEventRecord(e.c, stream_b)); }
       mark_b_dirty();
     }
+    uniform_lk.unlock();
     if (timed) clock.enqueued(std::move(e), sync_after);
   }
 
@@ -750,19 +788,21 @@ struct rt_tracer {
     rtk::TraceParams q = p;
     const size_t px = static_cast<size_t>(off) * p.W;
     q.row0 = p.row0 + off; q.rows = n;
-    q.render = p.render + px; q.counts = p.counts + px; q.rng = p.rng + px;    // npix stays the RNG planes' stride
+    q.render = p.render + px; q.rng = p.rng + px;                              // npix stays the RNG planes' stride
     q.image = p.image + px;
     if (p.image_host != nullptr) q.image_host = p.image_host + px;
     return q;
   }
 
   void clear_accumulators() {                                            // :242-243
+    std::lock_guard<std::recursive_mutex> lk(order_mu);
     HIP_CHECK(hipMemsetAsync(d_render.get(), 0, static_cast<size_t>(npix()) * sizeof(float4), main_stream()));
-    HIP_CHECK(hipMemsetAsync(d_counts.get(), 0, static_cast<size_t>(npix()) * sizeof(uint32_t), main_stream()));
+    count_now = 0u;                                                      // (the count buffer: materialise())
   }
 
   void convert() {                                                       // RunConverterKernel :189-202
-    HIP_CHECK(rtk::launch_convert(d_render.get(), d_counts.get(), d_image.get(), npix(), main_stream()));
+    std::lock_guard<std::recursive_mutex> lk(order_mu);
+    HIP_CHECK(rtk::launch_convert(d_render.get(), count_now, d_image.get(), npix(), main_stream()));
   }
 
   // Waits for a stream with the host polling: the end of a Trace is latency, not throughput (the reference's caller re-traces
@@ -895,7 +935,11 @@ struct rt_tracer {
     lists.attach(p, row0, have_lists);
     if (have_lists) HIP_CHECK(rtk::launch_tile_lists(p, fma, main_stream()));
     attach_macro_lists(p, path, 0, main_stream());
-    HIP_CHECK(rtk::launch_trace(p, fma, filter, path, pick_k(samples), main_stream()));
+    {
+      std::lock_guard<std::recursive_mutex> lk(order_mu);
+      take_uniform_state(p);
+      HIP_CHECK(rtk::launch_trace(p, fma, filter, path, pick_k(samples), main_stream()));
+    }
     HIP_CHECK(hipStreamSynchronize(main_stream()));
   }
 

@@ -1,0 +1,56 @@
+"""The premise of carrying two words of the per-pixel state as scalars (rt_tracer.hpp: weyl_now, count_now), pinned to
+the reference's arithmetic on the CPU oracle:
+
+  * the XORWOW Weyl word d (word 0 of a pixel's RNG state) is the same for every pixel of a band and equals
+    seed word + 362437 * 3 * (samples traced since the states were created)  (mod 2^32): the subsequence jump of
+    random::CreateStates acts on v0..v4 only, and every pixel makes exactly three draws per sample whatever its rays hit;
+  * the sample count is the same for every pixel and equals the samples traced since the last clear.
+"""
+import numpy as np
+import pytest
+
+from raytracertest_amd import scenes
+
+WEYL_STEP = 362437
+W, H = 96, 72
+CAMERA = dict(angles=(0.0, 0.0), fov_deg=70.0, focal=3.0, aperture=0.05)
+LAUNCHES = (16, 0, 3, 1)
+
+
+def _tracer(orc, scene, band):
+    row0, rows = band
+    o = orc.OracleTracer(W, H, seed=7, row0=row0, rows=rows, nthreads=4, **CAMERA)
+    if scene == "triangles":
+        assert o.upload_scene(scenes.cornell32())
+    else:
+        o.upload_spheres(scenes.sphere1()[1])
+    return o
+
+
+def _check(o, weyl, count):
+    d = o.rng[..., 0]
+    assert d.min() == d.max() == weyl % (1 << 32), "plane 0 of the RNG states is not the predicted constant"
+    assert o.counts.min() == o.counts.max() == count, "the sample counts are not the predicted constant"
+
+
+@pytest.mark.parametrize("band", [(0, None), (24, 16)], ids=["frame", "rows24to39"])
+@pytest.mark.parametrize("scene", ["triangles", "spheres"])
+def test_weyl_word_and_counts_are_uniform(orc, scene, band):
+    o = _tracer(orc, scene, band)
+    seed_word = int(orc.rng_seed(7)[0])
+    # a pixel's state is the seeded one jumped ahead by whole subsequences: the jump leaves d alone
+    far = orc.rng_init(7, W * H - 1)
+    assert int(far[0]) == seed_word and not np.array_equal(far[1:], orc.rng_seed(7)[1:])
+    traced = 0
+    _check(o, seed_word, 0)                                   # fresh states, no launch yet
+    for samples in LAUNCHES:                                  # accumulating launches, one of them of 0 samples
+        o.launch(samples)
+        traced += samples
+        _check(o, seed_word + WEYL_STEP * 3 * traced, traced)
+    o.trace(3, 2)                                             # a Trace clears the accumulators, not the states
+    traced += 6
+    _check(o, seed_word + WEYL_STEP * 3 * traced, 6)
+    o.trace(0, 5)                                             # no iteration: only the clear
+    _check(o, seed_word + WEYL_STEP * 3 * traced, 0)
+    # the other five words do differ from pixel to pixel (the check above is not vacuous)
+    assert len(np.unique(o.rng[..., 1])) == o.rng[..., 1].size

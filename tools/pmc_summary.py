@@ -105,8 +105,8 @@ def config(prefix, W, H, spp, n_tris):
 i3, t3 = config("", 1920, 1080, 16, 32)
 i4, t4 = config("_c4", 3840, 2160, 64, 10000)
 if t3:
-    t3["note"] = ("trace kernels + the list builder; bench launches treat the accumulators as zero (no accumulator read): reads = 24 B/pixel RNG state, "
-                  "writes = 24 B RNG + 16 B RGBA + 4 B count + 4 B BGRA8, + the tiles' lists written and read once")
+    t3["note"] = ("trace kernels + the list builder; bench launches treat the accumulators as zero (no accumulator read): reads = 20 B/pixel RNG state "
+                  "(v0..v4; the Weyl word and the sample count are scalars of the launch), writes = 20 B RNG + 16 B RGBA + 4 B BGRA8, + the tiles' lists written and read once")
 if t4:
     t4["note"] = "trace kernels + macro_bin_kernel: the macro / block list traffic and the dense-scene kernel's scratch on top of the per-pixel state"
 method = ("rocprofv3 --kernel-trace --pmc <counter> in separate passes around `python3 bench.py --steps 5 --warmup 1 --cpu-rows 0 --no-valu --no-warm --no-parity` "
