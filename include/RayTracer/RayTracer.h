@@ -111,6 +111,12 @@ public:
     return mImpl && rays.size() % 2 == 0 &&
            rt_tracer_intersect(mImpl, reinterpret_cast<const float*>(rays.data()), hits.size(), hits.data()) == RT_OK;
   }
+  // Visibility (rt_mi355x.h, rt_tracer_occluded): segs holds 8 floats per ray -- origin, direction (used as given), tmin, tmax;
+  // occluded[i] = 1 when anything in the scene is hit with tmin <= t <= tmax.  Independent of the hit rule.
+  bool Occluded(const std::vector<float>& segs, std::vector<uint8_t>& occluded) {
+    occluded.resize(segs.size() / 8);
+    return mImpl && segs.size() % 8 == 0 && rt_tracer_occluded(mImpl, segs.data(), occluded.size(), occluded.data()) == RT_OK;
+  }
   // The pinhole ray of a full-image pixel; `ray` (origin, direction) when asked for: the hit point is o + t * d.
   bool Pick(const math::uvec2& pixel, rt_hit& hit) { return Pick(pixel, hit, nullptr); }
   bool Pick(const math::uvec2& pixel, rt_hit& hit, math::vec3 ray[2]) {

@@ -286,6 +286,32 @@ int  rt_tracer_set_query_accel(rt_tracer* t, uint32_t mode);
  * time in us, device bytes of the tree}; the last six are 0 while no valid tree exists. */
 int  rt_tracer_query_accel_info(rt_tracer* t, uint64_t out[8]);
 
+/* Visibility (shadow rays, line of sight, ambient occlusion): is ray i blocked within its own t interval?
+ *   segs      n x 8 floats: origin xyz, direction xyz (used as given, nothing normalised), tmin, tmax.
+ *   occluded  occluded[i] = 1 when some primitive of the tracer's scene is hit by ray i with tmin <= t <= tmax, else 0.
+ *   hit       HitTriangle (Kernels.cuh:29-65) returns true in the tracer's arithmetic mode (RT_MATH_FMA / RT_MATH_STRICT) for
+ *             the record the renderer intersects (edge-format scenes: their uploaded rows); t is the value of :63, exactly as
+ *             rt_tracer_intersect reports it.  A sphere counts with the one t its ray-sphere test computes.
+ *   interval  closed, compared in plain fp32: tmin <= t && t <= tmax.  A NaN t or a NaN bound never occludes; tmin > tmax never
+ *             occludes; +-inf bounds are allowed, and [-inf, +inf] means any hit at all, negative t included.
+ * The answer is an OR over the primitives: it does not depend on RT_FLAG_NEAREST_HIT nor on the order of the tests.  No scene:
+ * every ray is unoccluded; spheres alone are enough to occlude; n = 0 is a no-op.  NaN, infinite and zero-length rays get
+ * whatever the reference arithmetic gives them.  Scheduling is that of the other queries: never cancels or joins a running
+ * Trace, serialised with the other calls, waited for by uploads and destroy; a multi-device handle answers from its first
+ * band, a band tracer locally.
+ * RT_QUERY_SCAN (default): exact, the OR described above.  RT_QUERY_BVH: the same tree and box inflation as the other
+ * queries, under the any-hit form of their contract.  Call an accepted in-interval triangle WELL CONDITIONED when, in float64,
+ * det / (|d| |e1| |e2|) >= 2^-10.  Then BVH = 1 implies scan = 1 (never an occluder the exact test rejects); BVH = scan when
+ * scan = 0; BVH = scan when at least one in-interval occluder of the ray is well conditioned or is a sphere.  The two may
+ * differ only when every in-interval occluder of a ray is ill conditioned.  A ray with a non-finite component, a zero
+ * direction or a NaN in its box arithmetic takes no pruning decision and gets the scan's answer; triangles with a non-finite
+ * record are always tested. */
+/* Host arrays: segs n*8, occluded n.  Returns with the answers in host memory. */
+int  rt_tracer_occluded(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  segs must be 16-byte aligned (a ray is two 16-byte loads); otherwise RT_ERR_INVALID. */
+int  rt_tracer_occluded_device(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded, void* stream);
+
 /* ---- one frame sharded over several GPUs --------------------------------------
  * The reference builds ONE rt::RayTracer pinned to device 0 (OpenGLView/MainFrame.cpp:44-45,
  * OpenGLView/GLCanvas.cpp:259-260).  Pixels are independent and a pixel's RNG stream is keyed by its

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "rt_tracer_join_group_bands", "rt_balance_rows", "rt_tracer_rebalance", "rt_tracer_set_band", "rt_dbg_read_tile_lists", "rt_dbg_wave_list_counts", "rt_dbg_focal_boxes", "rt_dbg_classify",
     "rt_tracer_gather_only", "rt_tracer_group_info",
     "rt_tracer_intersect", "rt_tracer_intersect_device", "rt_tracer_pick", "rt_tracer_focus_at",
+    "rt_tracer_occluded", "rt_tracer_occluded_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
 ]
 
@@ -227,6 +228,8 @@ def load_library():
         L.rt_tracer_intersect_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.rt_tracer_pick.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.rt_tracer_focus_at.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
+        L.rt_tracer_occluded.argtypes = [vp, vp, C.c_size_t, vp]
+        L.rt_tracer_occluded_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.rt_tracer_set_query_accel.argtypes = [vp, C.c_uint32]
         L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_dbg_query_accel_slack.argtypes = [vp, C.c_uint32]
@@ -608,6 +611,46 @@ class RayTracer:
         f = C.c_float()
         self._check(self._lib.rt_tracer_focus_at(self._h, x, y, C.byref(f)))
         return np.float32(f.value)
+
+    def Occluded(self, segs):
+        """Visibility: is each ray blocked within its own interval?  segs: (n, 8) float32 {origin, direction (used as given),
+        tmin, tmax}; the answer is 1 when some primitive is hit with tmin <= t <= tmax (closed, fp32; NaN never occludes),
+        whatever the tracer's hit rule.  A numpy array -> bool array, on return.  A contiguous torch float32 tensor on the
+        tracer's device -> uint8 tensor, enqueued on torch.cuda.current_stream() without a host synchronisation."""
+        if type(segs).__module__.startswith("torch"):
+            return self._occluded_tensor(segs)
+        s = np.asarray(segs, np.float32)
+        if s.ndim == 0 or s.shape[-1] != 8:                                # (an (n, 6) ray array is not silently reinterpreted)
+            raise ValueError("Occluded: expected (n, 8) float32 segments, got shape %s" % (s.shape,))
+        s = np.ascontiguousarray(s).reshape(-1, 8)
+        out = np.zeros(s.shape[0], np.uint8)
+        self._check(self._lib.rt_tracer_occluded(self._h, s.ctypes.data, s.shape[0], out.ctypes.data))
+        return out.view(np.bool_)
+
+    def _occluded_tensor(self, segs):
+        import torch
+        if segs.dtype != torch.float32 or segs.dim() != 2 or segs.shape[1] != 8 or not segs.is_contiguous():
+            raise ValueError("Occluded: expected a contiguous (n, 8) float32 tensor")
+        dev = self.Bands()[0]["device"]
+        if segs.device.type != "cuda" or segs.device.index != dev:
+            raise ValueError("Occluded: the segments are on %s, the tracer on cuda:%d" % (segs.device, dev))
+        out = torch.empty((segs.shape[0],), dtype=torch.uint8, device=segs.device)
+        stream = torch.cuda.current_stream(segs.device).cuda_stream
+        self._check(self._lib.rt_tracer_occluded_device(self._h, segs.data_ptr(), segs.shape[0], out.data_ptr(),
+                                                        C.c_void_p(stream)))
+        return out
+
+    def Visible(self, a, b, tmin=0.0, tmax=1.0):
+        """Line of sight between the points a[i] and b[i] ((n, 3) each): ~Occluded of the rays o = a, d = b - a (fp32, on the
+        host) over [tmin, tmax] in units of the segment.  A convenience: the caller chooses the interval that keeps the end
+        points' own surfaces out (e.g. tmin=1e-3, tmax=1 - 1e-3)."""
+        a = np.asarray(a, np.float32).reshape(-1, 3)
+        b = np.asarray(b, np.float32).reshape(-1, 3)
+        if a.shape != b.shape:
+            raise ValueError("Visible: %d start points, %d end points" % (a.shape[0], b.shape[0]))
+        segs = np.empty((a.shape[0], 8), np.float32)
+        segs[:, :3], segs[:, 3:6], segs[:, 6], segs[:, 7] = a, b - a, np.float32(tmin), np.float32(tmax)
+        return ~self.Occluded(segs)
 
     def SetQueryAcceleration(self, mode):
         """How Intersect / Pick / FocusAt find their hits: QUERY_SCAN (0 / False, the default: every ray scans every triangle)

@@ -13,6 +13,7 @@
 #include "rt_dense.hpp"
 #include "rt_query.hpp"
 #include "rt_bvh.hpp"
+#include "rt_occluded.hpp"
 
 namespace rtk {
 

@@ -136,6 +136,15 @@ uint32_t query_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_query_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* rays, const uint32_t* pixels,
                             float* rays_out, float4* hits, hipStream_t st);
 
+// The visibility query (rt_occluded.hpp): n segments {origin xyz, direction xyz, tmin, tmax}, 16-byte aligned; occluded[i] = 1
+// when some primitive of p's scene is hit by ray i with tmin <= t <= tmax (closed, plain fp32 comparisons), else 0.  p.flags'
+// hit rule plays no part.  The scan with K in {1, 2, 4} rays per lane, or the any-hit walk of the tree, one ray per lane.
+uint32_t occluded_lds_bytes(uint32_t n_tris);
+hipError_t launch_occluded(const TraceParams& p, bool fma, int K, uint32_t n, const float* segs, uint8_t* occluded, hipStream_t st);
+uint32_t occluded_bvh_lds_bytes(uint32_t stack_cap);
+hipError_t launch_occluded_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint8_t* occluded,
+                               hipStream_t st);
+
 hipError_t launch_dbg_hit_triangle(bool fma, uint32_t n, const float* rays, const float* tris, int eps_mode,
                                    int* hit, float* tuv, float* normal, float* point, hipStream_t st);
 bool trace_can_fuse(TracePath path, bool filter);   // launches with TraceParams::iters > 1 are available

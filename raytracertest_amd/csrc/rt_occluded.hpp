@@ -1,0 +1,280 @@
+// rt_occluded.hpp -- the visibility query (rt_tracer_occluded*): is ray i blocked by ANY primitive of the
+// scene with tmin <= t <= tmax?  Included by rt_kernels.hip only, behind rt_bvh.hpp.  Nothing of rt_query.hpp or rt_bvh.hpp is
+// shared beyond the renderer's device functions (hit_triangle_exact, hit_sphere, Math<FMA>): the triangle stages and the box
+// test are stated here again, because query_kernel and query_bvh_kernel keep their schedule only while their text is theirs
+// alone (rt_bvh.hpp).
+//
+// A "hit" is the reference's HitTriangle returning true (Kernels.cuh:29-65) and its t is the value of :63, a sphere's the one t
+// of hit_sphere; the interval is closed and compared in plain fp32 (a NaN t or bound, or tmin > tmax, never occludes).  The
+// answer is an OR over the primitives: no winner, no order, no tie rule, and a ray is finished at its first accepted hit.
+//
+// occluded_kernel (RT_QUERY_SCAN): query_kernel's outer shape -- 256-thread blocks, K rays per lane (ray k * 256 + lane of the
+// block), the triangles staged through LDS in ascending chunks of 36-byte records -- with the early exit on top: a finished ray
+// leaves the ballots of the triangle stages, a wave skips a chunk's loop once every ray of it is finished, and the block stops
+// staging once that holds for all its waves (decided by __syncthreads_or in place of the barrier between two chunks: block-
+// uniform, never under divergent control flow).  Rays are two 16-byte loads each, the answers one byte per ray (a wave's 64
+// lanes store 64 consecutive bytes).  Padding lanes (ray index >= n) start finished.
+//
+// occluded_bvh_kernel (RT_QUERY_BVH): query_bvh_kernel's walk -- one wave per block, lane = ray, the lane's stack in LDS at
+// entry * 64 + lane -- as an any-hit traversal.  The box test is that kernel's (same pad, same operations, same NaN rule); a
+// child is skipped when  exit < enter,  exit < tmin  or  enter > tmax  (strictly: a tie is visited).  There is no best t, so a
+// stack entry is the child's reference alone and no popped entry is judged again.  The child whose span overlaps [tmin, tmax]
+// most is entered first.  The always-tested list comes before the tree (it may end the walk before it starts); a ray with a
+// non-finite component or a zero direction, or a child with a NaN in its box arithmetic, takes no pruning decision.
+#pragma once
+#include "rt_bvh.hpp"
+
+namespace rtk {
+
+// One triangle against the unfinished rays of every lane: test_triangle's stages A-D (rt_trace.hpp: the same conservative
+// wave-uniform rejections, the same operations in stage D, so t has the renderer's bits), a finished ray counting as rejected.
+template <bool FMA, int K>
+__device__ __forceinline__ void occluded_test_triangle(const float4 A0, const float4 A1, const float v0z, const V3 (&o)[K],
+                                                       const V3 (&d)[K], const float (&tmin)[K], const float (&tmax)[K],
+                                                       bool (&done)[K]) {
+  using M = Math<FMA>;
+  const V3 e2 = {A0.x, A0.y, A0.z}, e1 = {A0.w, A1.x, A1.y};
+  // stage A: pv = cross(dir, e2), det = dot(e1, pv), culling (:39-45)
+  V3 pv[K];
+  float det[K];
+  unsigned long long mk[K];
+  unsigned long long live = 0ull;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    pv[k] = M::cross(d[k], e2);
+    det[k] = M::dot(e1, pv[k]);
+    mk[k] = __builtin_amdgcn_ballot_w64(!done[k] && !(det[k] < RT_EPS));
+    live |= mk[k];
+  }
+  if (live == 0ull) return;
+  // stage B: U = dot(origin - v0, pv) (:49-50), conservative u rejection
+  const V3 v0 = {A1.z, A1.w, v0z};
+  V3 tv[K];
+  float U[K], thi[K], tlo[K];
+  live = 0ull;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    tv[k] = rtd::sub(o[k], v0);
+    U[k] = M::dot(tv[k], pv[k]);
+    thi[k] = det[k] * 1.0001f;
+    tlo[k] = det[k] * -1e-6f;
+    mk[k] &= __builtin_amdgcn_ballot_w64(!(U[k] > thi[k])) & __builtin_amdgcn_ballot_w64(!(U[k] < tlo[k]));
+    live |= mk[k];
+  }
+  if (live == 0ull) return;
+  // stage C: V = dot(dir, cross(tv, e1)) (:56-57), conservative v rejection
+  V3 qv[K];
+  float V[K];
+  live = 0ull;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    qv[k] = M::cross(tv[k], e1);
+    V[k] = M::dot(d[k], qv[k]);
+    mk[k] &= __builtin_amdgcn_ballot_w64(!(V[k] < tlo[k])) & __builtin_amdgcn_ballot_w64(!((U[k] + V[k]) > thi[k]));
+    live |= mk[k];
+  }
+  if (live == 0ull) return;
+  // stage D: the reference's exact tests (:42-63) wherever a ray may hit, then the closed interval
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (mk[k] != 0ull) {
+      const float inv = 1.0f / det[k];                             // :47
+      const float u = U[k] * inv;                                  // :50
+      const float v = V[k] * inv;                                  // :57
+      const float t = M::dot(e2, qv[k]) * inv;                     // :63
+      const bool miss = (det[k] < RT_EPS) | (u < 0.0f) | (u > 1.0f) | (v < 0.0f) | (u + v > 1.0f);
+      done[k] = done[k] | ((!miss) & (tmin[k] <= t) & (t <= tmax[k]));
+    }
+  }
+}
+
+template <bool FMA, int K>
+__global__ __launch_bounds__(256, 4) void occluded_kernel(const TraceParams p, uint32_t n, const float4* __restrict__ segs,
+                                                           uint8_t* __restrict__ occluded) {
+  extern __shared__ float4 s_mem[];
+  const uint32_t tid = threadIdx.x;
+  const size_t base = static_cast<size_t>(blockIdx.x) * (256u * K);      // first ray of the block
+  const uint32_t nb = (n - base < 256u * K) ? static_cast<uint32_t>(n - base) : 256u * K;
+
+  V3 o[K], d[K];
+  float tmin[K], tmax[K];
+  bool done[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const uint32_t r = static_cast<uint32_t>(k) * 256u + tid;
+    float4 s0 = {0.0f, 0.0f, 0.0f, 0.0f}, s1 = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (r < nb) { s0 = segs[2u * (base + r)]; s1 = segs[2u * (base + r) + 1u]; }
+    o[k] = {s0.x, s0.y, s0.z};
+    d[k] = {s0.w, s1.x, s1.y};
+    tmin[k] = s1.z; tmax[k] = s1.w;
+    done[k] = !(r < nb);                                           // padding lanes start finished
+  }
+
+  // the spheres first: they are few (hit_sphere's one t)
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    for (uint32_t si = 0; si < p.n_spheres; ++si) {
+      float t = 0.0f;
+      if (!done[k] && hit_sphere<FMA>(o[k], d[k], p.spheres[si], t) && tmin[k] <= t && t <= tmax[k]) done[k] = true;
+    }
+  }
+
+  // the triangles, staged into LDS chunk by chunk, until every ray of the block is finished
+  const uint32_t nt = p.n_tris;
+  const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
+  float4* const sA = s_mem;                                        // 2 float4 per triangle
+  float* const sB = reinterpret_cast<float*>(s_mem + 2u * cap);    // v0.z
+  for (uint32_t c0 = 0; c0 < nt; c0 += kQueryChunk) {
+    const uint32_t cn = (nt - c0 < kQueryChunk) ? nt - c0 : kQueryChunk;
+    bool open = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) open = open || !done[k];
+    // the barrier between two chunks (the previous one is read) carries the block's verdict: every thread gets the same
+    if (__syncthreads_or(open ? 1 : 0) == 0) break;
+    for (uint32_t i = tid; i < 2u * cn; i += 256u) sA[i] = p.tri_a[2u * c0 + i];
+    for (uint32_t i = tid; i < cn; i += 256u) sB[i] = p.tri_b[c0 + i];
+    __syncthreads();
+    if (__builtin_amdgcn_ballot_w64(open) == 0ull) continue;       // this wave is finished; it still helps staging
+    for (uint32_t j = 0; j < cn; ++j) {
+      const float4 A0 = sA[2u * j], A1 = sA[2u * j + 1u];
+      occluded_test_triangle<FMA, K>(A0, A1, sB[j], o, d, tmin, tmax, done);
+    }
+  }
+
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const uint32_t r = static_cast<uint32_t>(k) * 256u + tid;
+    if (r < nb) occluded[base + r] = done[k] ? 1u : 0u;
+  }
+}
+
+// one record against one ray: the exact test, then the closed interval
+template <bool FMA>
+__device__ __forceinline__ bool occluded_test_record(const float4* __restrict__ rec, V3 o, V3 d, float tmin, float tmax) {
+  const float4 A0 = rec[0], A1 = rec[1], B = rec[2];
+  float t = 0.0f, u = 0.0f, v = 0.0f;
+  int stage;
+  if (!hit_triangle_exact<FMA>(o, d, {A1.z, A1.w, B.x}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, RT_EPS, t, u, v, stage)) return false;
+  return tmin <= t && t <= tmax;
+}
+
+template <bool FMA>
+__global__ __launch_bounds__(64) void occluded_bvh_kernel(const TraceParams p, const BvhParams b, uint32_t n,
+                                                           const float4* __restrict__ segs, uint8_t* __restrict__ occluded) {
+  extern __shared__ float4 s_mem[];
+  const uint32_t lane = threadIdx.x;
+  const size_t i = static_cast<size_t>(blockIdx.x) * 64u + lane;
+  if (i >= n) return;                                              // (no barrier and no cross-lane operation below)
+  const float4 s0 = segs[2u * i], s1 = segs[2u * i + 1u];
+  const V3 o = {s0.x, s0.y, s0.z}, d = {s0.w, s1.x, s1.y};
+  const float tmin = s1.z, tmax = s1.w;
+  bool done = false;
+
+  for (uint32_t si = 0; si < p.n_spheres && !done; ++si) {
+    float t = 0.0f;
+    done = hit_sphere<FMA>(o, d, p.spheres[si], t) && tmin <= t && t <= tmax;
+  }
+  for (uint32_t j = 0; j < b.n_always && !done; ++j)
+    done = occluded_test_record<FMA>(b.records + 3u * (b.n_leaf_records + j), o, d, tmin, tmax);
+
+  uint32_t* const stack = reinterpret_cast<uint32_t*>(s_mem) + lane;   // entry e at stack[e * 64]
+  const float inf = __builtin_inff();
+  const bool finite = fabsf(o.x) < inf && fabsf(o.y) < inf && fabsf(o.z) < inf && fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf;
+  const bool prunes = finite && !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f);
+  const V3 inv = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+  const float omax = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
+  uint32_t sp = 0u;
+  uint32_t cur = (b.n_nodes != 0u && !done) ? 0u : kBvhEmpty;
+  bool overflow = false;
+  while (!done) {
+    if (cur == kBvhEmpty) {
+      if (sp == 0u) break;
+      --sp;
+      cur = stack[sp * 64u];
+    }
+    if ((cur & kBvhLeaf) != 0u) {
+      const uint32_t first = cur & 0x0FFFFFFFu, count = ((cur >> 28) & 3u) + 1u;
+      for (uint32_t j = 0; j < count && !done; ++j) done = occluded_test_record<FMA>(b.records + 3u * (first + j), o, d, tmin, tmax);
+      cur = kBvhEmpty;
+      continue;
+    }
+    const float4* const nd = b.nodes + 8u * static_cast<size_t>(cur);
+    const float4 lox = nd[0], loy = nd[1], loz = nd[2], hix = nd[3], hiy = nd[4], hiz = nd[5], refs = nd[6], cm = nd[7];
+    const float L[3][4] = {{lox.x, lox.y, lox.z, lox.w}, {loy.x, loy.y, loy.z, loy.w}, {loz.x, loz.y, loz.z, loz.w}};
+    const float Hh[3][4] = {{hix.x, hix.y, hix.z, hix.w}, {hiy.x, hiy.y, hiy.z, hiy.w}, {hiz.x, hiz.y, hiz.z, hiz.w}};
+    const float cmax[4] = {cm.x, cm.y, cm.z, cm.w};
+    uint32_t ref[4] = {__float_as_uint(refs.x), __float_as_uint(refs.y), __float_as_uint(refs.z), __float_as_uint(refs.w)};
+    float good[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float pad = b.rho * (omax + cmax[c]);
+      const float t1x = ((L[0][c] - pad) - o.x) * inv.x, t2x = ((Hh[0][c] + pad) - o.x) * inv.x;
+      const float t1y = ((L[1][c] - pad) - o.y) * inv.y, t2y = ((Hh[1][c] + pad) - o.y) * inv.y;
+      const float t1z = ((L[2][c] - pad) - o.z) * inv.z, t2z = ((Hh[2][c] + pad) - o.z) * inv.z;
+      const bool nan = __builtin_isunordered(t1x, t2x) || __builtin_isunordered(t1y, t2y) || __builtin_isunordered(t1z, t2z);
+      const float enter = fmaxf(fmaxf(fminf(t1x, t2x), fminf(t1y, t2y)), fminf(t1z, t2z));
+      const float exit = fminf(fminf(fmaxf(t1x, t2x), fmaxf(t1y, t2y)), fmaxf(t1z, t2z));
+      const bool skip = (exit < enter) || (exit < tmin) || (enter > tmax);
+      const bool decided = prunes && !nan;
+      // the overlap of the child's span with the interval (inf - inf: a NaN, which fmaxf drops)
+      float g = decided ? fmaxf(fminf(exit, tmax) - fmaxf(enter, tmin), -FLT_MAX) : inf;
+      if (ref[c] == kBvhEmpty || (decided && skip)) { ref[c] = kBvhEmpty; g = -inf; }
+      good[c] = g;
+    }
+    // largest overlap first (a 5-exchange network); an empty reference carries -inf, a visited one at least -FLT_MAX
+#define RT_OCC_CSWAP(i, j)                                                                            \
+    if (good[i] < good[j]) { const float tg = good[i]; good[i] = good[j]; good[j] = tg;               \
+                             const uint32_t tr = ref[i]; ref[i] = ref[j]; ref[j] = tr; }
+    RT_OCC_CSWAP(0, 1) RT_OCC_CSWAP(2, 3) RT_OCC_CSWAP(0, 2) RT_OCC_CSWAP(1, 3) RT_OCC_CSWAP(1, 2)
+#undef RT_OCC_CSWAP
+    cur = ref[0];
+    auto push = [&](uint32_t r) {
+      if (r == kBvhEmpty) return;
+      if (sp < b.stack_cap) { stack[sp * 64u] = r; ++sp; }
+      else overflow = true;                                        // (cannot happen: the capacity is 3 x the tree's depth)
+    };
+    push(ref[3]); push(ref[2]); push(ref[1]);                      // the better of them on top
+  }
+  if (overflow && !done) {                                         // an entry was not kept: every leaf record
+    for (uint32_t j = 0; j < b.n_leaf_records && !done; ++j) done = occluded_test_record<FMA>(b.records + 3u * j, o, d, tmin, tmax);
+  }
+  occluded[i] = done ? 1u : 0u;
+}
+
+uint32_t occluded_lds_bytes(uint32_t n_tris) {
+  return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
+}
+
+uint32_t occluded_bvh_lds_bytes(uint32_t stack_cap) {
+  return stack_cap * 64u * 4u;
+}
+
+hipError_t launch_occluded(const TraceParams& p, bool fma, int K, uint32_t n, const float* segs, uint8_t* occluded, hipStream_t st) {
+  if (n == 0u) return hipSuccess;
+  if ((K != 1 && K != 2 && K != 4) || segs == nullptr || occluded == nullptr) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 256u * K - 1u) / (256u * K)));
+  const size_t lds = occluded_lds_bytes(p.n_tris);
+  const float4* const s4 = reinterpret_cast<const float4*>(segs);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, n, s4, occluded); };
+  if (fma) {
+    if (K == 1) go(occluded_kernel<true, 1>); else if (K == 2) go(occluded_kernel<true, 2>); else go(occluded_kernel<true, 4>);
+  } else {
+    if (K == 1) go(occluded_kernel<false, 1>); else if (K == 2) go(occluded_kernel<false, 2>); else go(occluded_kernel<false, 4>);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_occluded_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint8_t* occluded,
+                               hipStream_t st) {
+  if (n == 0u) return hipSuccess;
+  if (segs == nullptr || occluded == nullptr) return hipErrorInvalidValue;
+  const uint32_t lds = occluded_bvh_lds_bytes(b.stack_cap);
+  if (lds > 65536u) return hipErrorInvalidValue;                   // (3 x kBvhMaxDepth entries are 12 KiB)
+  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
+  const float4* const s4 = reinterpret_cast<const float4*>(segs);
+  if (fma) hipLaunchKernelGGL(occluded_bvh_kernel<true>, grid, dim3(64), lds, st, p, b, n, s4, occluded);
+  else hipLaunchKernelGGL(occluded_bvh_kernel<false>, grid, dim3(64), lds, st, p, b, n, s4, occluded);
+  return hipGetLastError();
+}
+
+}  // namespace rtk

@@ -1,5 +1,5 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
-// rt_tracer_focus_at).  Included by rt_tracer.hip.
+// rt_tracer_focus_at, rt_tracer_occluded*).  Included by rt_tracer.hip.
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
 // calls by api_mu, reads only the scene and a snapshot of the camera (params(), under state_mu), and runs on a stream of its
@@ -61,6 +61,17 @@ inline void ensure_query_tree(rt_tracer* t) {
   t->bvh_built = true;
 }
 
+// the valid tree (ensure_query_tree) as the traversal kernels take it
+inline rtk::BvhParams query_bvh_params(const rt_tracer* t) {
+  rtk::BvhParams b;
+  b.nodes = t->d_bvh_nodes.get(); b.records = t->d_bvh_records.get();
+  b.n_nodes = static_cast<uint32_t>(t->bvh_info[0]); b.n_leaf_records = t->bvh_leaf_records;
+  b.n_always = static_cast<uint32_t>(t->bvh_info[3]);
+  b.stack_cap = rtb::stack_capacity(static_cast<uint32_t>(t->bvh_info[2]));
+  b.rho = RT_BVH_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f);
+  return b;
+}
+
 // rays (or pixels) -> hits on `st`, behind every earlier query: query_done then covers this one and all before it
 inline void enqueue_query(rt_tracer* t, size_t n, const float* rays, const uint32_t* pixels, float* rays_out, float4* hits,
                           hipStream_t st) {
@@ -71,15 +82,28 @@ inline void enqueue_query(rt_tracer* t, size_t n, const float* rays, const uint3
   if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
   else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
   if (bvh) {
-    rtk::BvhParams b;
-    b.nodes = t->d_bvh_nodes.get(); b.records = t->d_bvh_records.get();
-    b.n_nodes = static_cast<uint32_t>(t->bvh_info[0]); b.n_leaf_records = t->bvh_leaf_records;
-    b.n_always = static_cast<uint32_t>(t->bvh_info[3]);
-    b.stack_cap = rtb::stack_capacity(static_cast<uint32_t>(t->bvh_info[2]));
-    b.rho = RT_BVH_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f);
+    const rtk::BvhParams b = query_bvh_params(t);
     HIP_CHECK(rtk::launch_query_bvh(p, b, t->fma, static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st));
   } else {
     HIP_CHECK(rtk::launch_query(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st));
+  }
+  HIP_CHECK(hipEventRecord(t->query_done, st));
+}
+
+// segments -> one byte per ray on `st`, with enqueue_query's event discipline.  The hit rule plays no part (an OR over the
+// primitives), so p.flags stays 0.
+inline void enqueue_occluded(rt_tracer* t, size_t n, const float* segs, uint8_t* occluded, hipStream_t st) {
+  rtk::TraceParams p = t->params(1);
+  p.flags = 0u;
+  const bool bvh = t->query_accel == RT_QUERY_BVH;
+  if (bvh) ensure_query_tree(t);
+  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
+  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
+  if (bvh) {
+    const rtk::BvhParams b = query_bvh_params(t);
+    HIP_CHECK(rtk::launch_occluded_bvh(p, b, t->fma, static_cast<uint32_t>(n), segs, occluded, st));
+  } else {
+    HIP_CHECK(rtk::launch_occluded(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), segs, occluded, st));
   }
   HIP_CHECK(hipEventRecord(t->query_done, st));
 }
@@ -187,6 +211,48 @@ int rt_tracer_intersect_device(rt_tracer* t, const float* rays, size_t n, rt_hit
     if (n == 0u) return;
     t->use_device();
     enqueue_query(t, n, rays, nullptr, nullptr, reinterpret_cast<float4*>(hits), static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_occluded(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded) {
+  if (!t) return RT_ERR_INVALID;
+  if (!query_args_ok(t, n, segs, occluded)) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_occluded(t->mg->bands[0], segs, n, occluded);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    const hipStream_t st = query_stream(t);
+    t->d_q_segs.ensure(n * 8u);
+    t->d_q_occluded.ensure(n);
+    HIP_CHECK(hipMemcpyAsync(t->d_q_segs.get(), segs, n * 8u * sizeof(float), hipMemcpyHostToDevice, st));
+    enqueue_occluded(t, n, t->d_q_segs.get(), t->d_q_occluded.get(), st);
+    HIP_CHECK(hipMemcpyAsync(occluded, t->d_q_occluded.get(), n, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_occluded_device(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded, void* stream) {
+  if (!t) return RT_ERR_INVALID;
+  if (!query_args_ok(t, n, segs, occluded)) return RT_ERR_INVALID;
+  if (n != 0u && reinterpret_cast<uintptr_t>(segs) % 16u != 0u) {
+    t->set_error("rt_tracer_occluded_device: segs must be 16-byte aligned");
+    return RT_ERR_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_occluded_device(t->mg->bands[0], segs, n, occluded, stream);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_occluded(t, n, segs, occluded, static_cast<hipStream_t>(stream));
   });
 }
 

@@ -38,8 +38,8 @@ namespace rtk {
 //   U+V > fl(det*1.0001), with U,V >= -1e-6 det (not dropped above)
 //                                 => u+v > 1.0001 - 4e-6 - roundoff > 1       (miss, :58)
 // NaN/inf operands make every comparison false: the ray is kept and stage D decides.
-// tests/test_gpu_parity.py::test_filter_off_equals_filter_on checks FILTER against the
-// plain reference-order path bit for bit.
+// tests/test_gpu_parity.py::test_filter_off_equals_filter_on checks FILTER against the plain reference-order path bit for bit.
+// A SECOND COPY of stages A-D (constants and operations) is rt_occluded.hpp's occluded_test_triangle: change both together.
 // ------------------------------------------------------------------------------------
 template <bool FMA, int K, bool FILTER, bool STATS, class GetB>
 __device__ __forceinline__ void test_triangle(const float4 A0, const float4 A1, GetB get_v0z, int tri_index,

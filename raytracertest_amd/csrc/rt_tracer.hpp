@@ -505,6 +505,8 @@ struct rt_tracer {
   rtr::DevArray<float> d_q_rays;
   rtr::DevArray<uint32_t> d_q_pixels;
   rtr::DevArray<float4> d_q_hits;
+  rtr::DevArray<float> d_q_segs;      // rt_tracer_occluded: n x 8 floats in, n bytes out
+  rtr::DevArray<uint8_t> d_q_occluded;
   rtr::Event query_done;
   void wait_queries() { if (query_done) HIP_CHECK(hipEventSynchronize(query_done)); }
   // RT_QUERY_BVH (rt_bvh_host.hpp, rt_bvh.hpp): the tree of the scene of generation bvh_scene, built by the first query in

@@ -1,0 +1,53 @@
+"""CPU checks of the visibility query's boundary (rt_tracer_occluded / _device): declared, exported, argument checks that need
+no device, and the Python and C++ classes."""
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIBDIR = os.path.join(ROOT, "raytracertest_amd", "lib")
+NEW = ("rt_tracer_occluded", "rt_tracer_occluded_device")
+
+
+def test_symbols_are_declared_exported_and_reject_null_handles_and_arrays():
+    from raytracertest_amd import api
+    L = api.load_library()
+    hdr = open(os.path.join(ROOT, "include", "rt_mi355x.h")).read()
+    for name in NEW:
+        assert name in api.ABI_SYMBOLS and hasattr(L, name) and name + "(" in hdr
+    segs = np.zeros((4, 8), np.float32)
+    out = np.zeros(4, np.uint8)
+    assert L.rt_tracer_occluded(None, segs.ctypes.data, 4, out.ctypes.data) == 1
+    assert L.rt_tracer_occluded_device(None, segs.ctypes.data, 4, out.ctypes.data, None) == 1
+    assert L.rt_tracer_occluded(None, None, 0, None) == 1
+
+
+def test_python_class_has_occluded_and_visible():
+    from raytracertest_amd import api
+    for m in ("Occluded", "Visible", "_occluded_tensor"):
+        assert callable(getattr(api.RayTracer, m))
+
+
+def test_header_compiles_as_c99_with_the_new_entries(tmp_path):
+    src = tmp_path / "o.c"
+    src.write_text('#include "rt_mi355x.h"\n'
+                   'int main(void) { float s[8] = {0}; uint8_t o = 0;\n'
+                   '  return rt_tracer_occluded(NULL, s, 1, &o) == RT_ERR_INVALID &&\n'
+                   '         rt_tracer_occluded_device(NULL, s, 1, &o, NULL) == RT_ERR_INVALID ? 0 : 1; }\n')
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I" + os.path.join(ROOT, "include"),
+                    "-c", str(src), "-o", str(tmp_path / "o.o")], check=True)
+
+
+def test_cpp_class_has_occluded(tmp_path):
+    src = tmp_path / "o.cpp"
+    src.write_text('#include "RayTracer/RayTracer.h"\n'
+                   'int main() {\n'
+                   '  rt::RayTracer r(math::uvec2(8, 8), math::vec3(0, 0, 0), math::vec2(0, 0), 70.0f, 10.0f, 4.0f);\n'
+                   '  std::vector<float> segs(16, 0.0f); std::vector<uint8_t> occ;\n'
+                   '  const bool ok = r.Occluded(segs, occ);\n'
+                   '  std::vector<float> odd(9, 0.0f);\n'
+                   '  return (ok || true) && occ.size() == 2 && !r.Occluded(odd, occ) ? 0 : 1;\n}\n')
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
+                    "-L" + LIBDIR, "-lrt_mi355x", "-Wl,-rpath," + LIBDIR, "-pthread", "-o", str(tmp_path / "o")], check=True)
+
