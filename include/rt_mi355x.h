@@ -442,6 +442,14 @@ int rt_dbg_uniform(int device, uint32_t n, uint32_t m, uint32_t* states, float* 
 int rt_dbg_get_ray(rt_tracer* t, uint32_t n, const uint32_t* pixels, uint32_t* states, float* rays);
 /* host: curand_init(seed, subsequence, 0) restated -> state[6] */
 void rt_dbg_rng_init_host(uint64_t seed, uint64_t subsequence, uint32_t state[6]);
+/* host: the xorshift words v0..v4 advanced in place by n draws -- through the window table of T^n (use_table != 0: the
+ * product the settle kernel forms) or by n single steps */
+void rt_dbg_rng_advance_host(uint32_t state[5], uint32_t n, int use_table);
+/* the same for count states of 5 words each, the table built once */
+void rt_dbg_rng_advance_host_n(uint32_t* states, uint32_t count, uint32_t n, int use_table);
+/* the draws a plain tracer owes to its certain-winner tiles: out = {owed draws, owing launches since the last settle,
+ * settle kernels enqueued so far, device tables held} */
+int rt_dbg_owed_state(rt_tracer* t, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

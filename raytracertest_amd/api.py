@@ -43,7 +43,7 @@ ABI_SYMBOLS = [
     "rt_tracer_device_pointer", "rt_tracer_buffer_bytes", "rt_tracer_info",
     "rt_tracer_last_error", "rt_last_error", "rt_device_count", "rt_version",
     "rt_dbg_hit_triangle", "rt_dbg_sincos", "rt_dbg_valu_peak", "rt_dbg_check_midrange", "rt_dbg_trace_occupancy", "rt_dbg_uniform", "rt_dbg_get_ray",
-    "rt_dbg_rng_init_host",
+    "rt_dbg_rng_init_host", "rt_dbg_rng_advance_host", "rt_dbg_rng_advance_host_n", "rt_dbg_owed_state",
     "rt_tracer_create_multi", "rt_group_unique_id", "rt_tracer_join_group", "rt_tracer_leave_group",
     "rt_tracer_gather_time", "rt_tracer_band_count", "rt_tracer_band_info",
     "rt_tracer_join_group_bands", "rt_balance_rows", "rt_tracer_rebalance", "rt_tracer_set_band", "rt_dbg_read_tile_lists", "rt_dbg_wave_list_counts", "rt_dbg_focal_boxes", "rt_dbg_classify",
@@ -206,6 +206,12 @@ def load_library():
         L.rt_dbg_get_ray.argtypes = [vp, C.c_uint32, u32p, u32p, f32p]
         L.rt_dbg_rng_init_host.argtypes = [C.c_uint64, C.c_uint64, u32p]
         L.rt_dbg_rng_init_host.restype = None
+        if hasattr(L, "rt_dbg_owed_state"):               # (an older build selected by RT_MI355X_LIB for a kernel A/B has none of the three)
+            L.rt_dbg_rng_advance_host.argtypes = [u32p, C.c_uint32, C.c_int]
+            L.rt_dbg_rng_advance_host.restype = None
+            L.rt_dbg_rng_advance_host_n.argtypes = [u32p, C.c_uint32, C.c_uint32, C.c_int]
+            L.rt_dbg_rng_advance_host_n.restype = None
+            L.rt_dbg_owed_state.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_tracer_create_multi.argtypes = [u32p, f32p, f32p, C.c_float, C.c_float, C.c_float, C.POINTER(Options),
                                              C.POINTER(C.c_int32), C.c_uint32, C.POINTER(vp)]
         L.rt_group_unique_id.argtypes = [C.c_char_p]
@@ -534,6 +540,12 @@ class RayTracer:
         words = buf[:bx * by * 4 * w].reshape(by, bx * 4, w)[:, :, 0]
         return (words & 0x3FF).astype(np.int32), ((words >> 10) & 0x3FF).astype(np.int32), (words >> 31).astype(bool)
 
+    def DebugOwedState(self):
+        """rt_dbg_owed_state: dict of the RNG draws the tracer owes to its certain-winner tiles."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.rt_dbg_owed_state(self._h, out))
+        return dict(zip(("owed_draws", "owing_launches", "settles_enqueued", "tables"), (int(x) for x in out)))
+
     def DebugWaveListCounts(self, half=0):
         """(counts, capacity): candidate count per tile (grid order of the half's launch; 0xFFFFFFFF = overflow) of a dense scene's
         lists in HBM (rt_dbg_wave_list_counts)."""
@@ -782,4 +794,16 @@ def dbg_uniform(states, m, device=0):
 def dbg_rng_init_host(seed, subsequence):
     s = np.zeros(6, np.uint32)
     load_library().rt_dbg_rng_init_host(int(seed), int(subsequence), _u32p(s))
+    return s
+
+
+def dbg_rng_advance_host(state, n, use_table):
+    """v0..v4 -- one state (5,) or several (k, 5) -- advanced by n draws on the host: with the window table of T^n, or by n
+    steps (rt_dbg_rng_advance_host, _n)."""
+    s = np.ascontiguousarray(state, np.uint32).copy()
+    L = load_library()
+    if s.ndim == 1:
+        L.rt_dbg_rng_advance_host(_u32p(s.reshape(5)), int(n), int(bool(use_table)))
+    else:
+        L.rt_dbg_rng_advance_host_n(_u32p(s.reshape(-1, 5)), s.reshape(-1, 5).shape[0], int(n), int(bool(use_table)))
     return s

@@ -207,4 +207,42 @@ void rt_dbg_rng_init_host(uint64_t seed, uint64_t subsequence, uint32_t state[6]
   rth::init_state(jump_host(), seed, subsequence & 0xffffffffull, state);
 }
 
+
+// count states of v0..v4 advanced by n draws on the host: through the 4-bit window table of T^n (what rng_settle_kernel
+// does with it; built once per call) or by n single steps (all states in lockstep: the loop vectorises).  No device needed.
+void rt_dbg_rng_advance_host_n(uint32_t* states, uint32_t count, uint32_t n, int use_table) {
+  if (use_table) {
+    const std::vector<uint32_t> table = rth::build_window_table(rth::step_power(n));
+    for (uint32_t i = 0; i < count; ++i) rth::window_product(table, states + 5u * i, states + 5u * i);
+    return;
+  }
+  constexpr uint32_t kLanes = 64;
+  for (uint32_t base = 0; base < count; base += kLanes) {
+    const uint32_t m = count - base < kLanes ? count - base : kLanes;
+    uint32_t v[5][kLanes] = {};
+    for (uint32_t i = 0; i < m; ++i) for (int w = 0; w < 5; ++w) v[w][i] = states[5u * (base + i) + w];
+    auto f = [](uint32_t x, uint32_t y) -> uint32_t { const uint32_t t = x ^ (x >> 2); return (y ^ (y << 4)) ^ (t ^ (t << 1)); };
+    uint32_t k = 0;
+    for (; k + 5u <= n; k += 5u)                                        // five draws rotate the words once: in place (rtd::rng_discard)
+      for (uint32_t i = 0; i < kLanes; ++i) {
+        v[0][i] = f(v[0][i], v[4][i]); v[1][i] = f(v[1][i], v[0][i]); v[2][i] = f(v[2][i], v[1][i]);
+        v[3][i] = f(v[3][i], v[2][i]); v[4][i] = f(v[4][i], v[3][i]);
+      }
+    for (uint32_t i = 0; i < m; ++i) {
+      uint32_t one[5] = {v[0][i], v[1][i], v[2][i], v[3][i], v[4][i]};
+      for (uint32_t r = k; r < n; ++r) rth::xorshift_step(one);
+      memcpy(states + 5u * (base + i), one, sizeof one);
+    }
+  }
+}
+void rt_dbg_rng_advance_host(uint32_t state[5], uint32_t n, int use_table) { rt_dbg_rng_advance_host_n(state, 1u, n, use_table); }
+
+// out = {owed draws, owing launches since the last settle, settle kernels enqueued so far, device tables held}
+int rt_dbg_owed_state(rt_tracer* t, uint64_t out[4]) {
+  if (!t || t->mg || !out) return RT_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lk(t->order_mu);
+  out[0] = t->owed_draws; out[1] = t->owing_launches; out[2] = t->settles_enqueued; out[3] = t->settle_tables.size();
+  return RT_OK;
+}
+
 }  // extern "C"

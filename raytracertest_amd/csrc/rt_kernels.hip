@@ -363,12 +363,8 @@ hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, TracePath p
       (path == TracePath::DenseLists && (p.wave_lists == nullptr || p.stats != nullptr)) ||
       (p.iters > 1u && (!trace_can_fuse(path, filter) || p.stats != nullptr)) ||
       (p.row_il != 0u && (path != TracePath::SmallLists || p.stats != nullptr))) return hipErrorInvalidValue;
-  dim3 grid(cdiv(p.W, 32), cdiv(p.rows, 8));
-  if (p.row_il != 0u) {                                  // every second block row (small-scene kernels only)
-    const uint32_t R = grid.y, G = p.row_il, full = R / (2u * G), rest = R % (2u * G);      // groups of G block rows, alternating
-    grid.y = full * G + (p.row_phase == 0u ? (rest < G ? rest : G) : (rest > G ? rest - G : 0u));
-    if (grid.y == 0u) return hipSuccess;
-  }
+  const dim3 grid = trace_grid(p);                       // (row_il: every second block row, small-scene kernels only)
+  if (grid.y == 0u) return hipSuccess;
   const size_t lds = trace_lds_bytes(p, path);
   auto launch = [&](auto fma_c) {
     constexpr bool F = decltype(fma_c)::value;

@@ -91,6 +91,9 @@ constexpr uint32_t TRACE_NEAREST_HIT = 4u;
 constexpr uint32_t TRACE_PRETEST = 32u;
 // small-scene kernels: do not skip the intersection tests of tiles whose list is one certainly-hit triangle (A/B, tests)
 constexpr uint32_t TRACE_NO_SURE_HIT = 64u;
+// small-scene kernels: the waves of certain-winner tiles leave their pixels' xorshift words alone -- no load, no
+// rng_discard, no store; the host sums the draws they skipped and rng_settle_kernel pays them later (rt_tracer::settle)
+constexpr uint32_t TRACE_OWE_RNG = 128u;
 
 // How the waves of a trace launch get their candidate triangles: trace_kernel's Path.  The host picks it per (half-)launch
 // in one place (rt_tracer::trace_path).
@@ -106,9 +109,23 @@ enum class TracePath : uint32_t {
 // Writes planes 1..5 (v0..v4); the Weyl word seeded[0] is every pixel's and stays with the host (TraceParams::weyl).
 hipError_t launch_rng_init(uint32_t* rng, uint32_t npix, uint32_t p0, const uint32_t seeded[6],
                            const uint32_t* jump, const uint32_t* win, hipStream_t st);
+// Small scenes: advances v0..v4 of every pixel of the certain-winner tiles of the (half-)launch `p` (p.tile_lists, p.rng and
+// the grid of trace_grid(p)) by `draws` xorshift steps.  table: the window table of T^draws in device memory
+// (rth::build_window_table), or null = step.
+hipError_t launch_rng_settle(const TraceParams& p, uint32_t draws, const uint32_t* table, hipStream_t st);
 hipError_t launch_prep_triangles(bool fma, bool edges, const float4* verts, uint32_t n, float4* tri_a, float* tri_b,
                                  float4* color, float4* normals, hipStream_t st);
 uint32_t trace_lds_bytes(const TraceParams& p, TracePath path);
+// The block grid of the trace launch `p`: one block per 32 x 8 pixels; with row_il only the block rows of its phase
+// (groups of row_il block rows, alternating; y may come out 0).  launch_rng_settle walks the same grid.
+inline dim3 trace_grid(const TraceParams& p) {
+  dim3 grid((p.W + 31u) / 32u, (p.rows + 7u) / 8u);
+  if (p.row_il != 0u) {
+    const uint32_t R = grid.y, G = p.row_il, full = R / (2u * G), rest = R % (2u * G);
+    grid.y = full * G + (p.row_phase == 0u ? (rest < G ? rest : G) : (rest > G ? rest - G : 0u));
+  }
+  return grid;
+}
 hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, TracePath path, int K, hipStream_t st);
 int trace_occupancy(int K, size_t lds);
 hipError_t launch_convert(const float4* render, uint32_t count, uint32_t* image, uint32_t npix, hipStream_t st);

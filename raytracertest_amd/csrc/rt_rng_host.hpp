@@ -55,25 +55,73 @@ inline std::vector<uint32_t> build_jump_table() {
   return table;
 }
 
-// 4-bit window tables of the six lowest jump powers J^(2^m), m = 0..5 (what distinguishes the 64 pixels of a
-// wave): entry [m][g][n] = XOR of the columns g*4 + j of J^(2^m) over the set bits j of the nibble n, so that a
-// matrix-vector product is 40 table look-ups instead of 160 masked column XORs (rng_init_kernel keeps the
-// tables in LDS).  Device layout: 6*40*16 entries of words 0..3 (16 bytes each), then the same entries' word 4.
+// 4-bit window tables of `matrices` matrices whose column i of matrix m starts at cols[(m * 160 + i) * col_stride] (5 words
+// used): entry [m][g][n] = XOR of the columns g*4 + j of matrix m over the set bits j of the nibble n, so that a
+// matrix-vector product is 40 table look-ups instead of 160 masked column XORs (the kernels keep the tables in LDS).
+// Device layout: matrices*40*16 entries of words 0..3 (16 bytes each), then the same entries' word 4.
+// rng_init_kernel: the six lowest jump powers J^(2^m), m = 0..5 (what distinguishes the 64 pixels of a wave);
+// rng_settle_kernel: the one matrix T^n of the draws a tracer owes.
 constexpr uint32_t kWindowMatrices = 6, kWindowGroups = 40, kWindowEntries = kWindowMatrices * kWindowGroups * 16u;
-inline std::vector<uint32_t> build_window_tables(const std::vector<uint32_t>& jump) {
-  std::vector<uint32_t> t(static_cast<size_t>(kWindowEntries) * 5u, 0u);
-  for (uint32_t m = 0; m < kWindowMatrices; ++m)
+constexpr uint32_t kWindowEntriesOne = kWindowGroups * 16u;
+inline std::vector<uint32_t> build_window_tables(const uint32_t* cols, size_t col_stride, uint32_t matrices) {
+  const size_t entries = static_cast<size_t>(matrices) * kWindowGroups * 16u;
+  std::vector<uint32_t> t(entries * 5u, 0u);
+  for (uint32_t m = 0; m < matrices; ++m)
     for (uint32_t g = 0; g < kWindowGroups; ++g)
       for (uint32_t n = 0; n < 16u; ++n) {
         uint32_t r[5] = {0, 0, 0, 0, 0};
         for (uint32_t j = 0; j < 4u; ++j)
           if ((n >> j) & 1u)
-            for (int w = 0; w < 5; ++w) r[w] ^= jump[(static_cast<size_t>(m) * 160u + g * 4u + j) * 8u + w];
+            for (int w = 0; w < 5; ++w) r[w] ^= cols[(static_cast<size_t>(m) * 160u + g * 4u + j) * col_stride + w];
         const size_t e = (static_cast<size_t>(m) * kWindowGroups + g) * 16u + n;
         memcpy(&t[e * 4u], r, 4 * sizeof(uint32_t));
-        t[static_cast<size_t>(kWindowEntries) * 4u + e] = r[4];
+        t[entries * 4u + e] = r[4];
       }
   return t;
+}
+inline std::vector<uint32_t> build_window_tables(const std::vector<uint32_t>& jump) { return build_window_tables(jump.data(), 8u, kWindowMatrices); }
+inline std::vector<uint32_t> build_window_table(const Gf2Mat& m) { return build_window_tables(&m.col[0][0], 5u, 1u); }
+
+// out = M x through the window table of the one matrix M (what rng_settle_kernel does per lane)
+inline void window_product(const std::vector<uint32_t>& table, const uint32_t x[5], uint32_t out[5]) {
+  uint32_t r[5] = {0, 0, 0, 0, 0};
+  for (uint32_t g = 0; g < kWindowGroups; ++g) {
+    const uint32_t n = (x[g >> 3] >> ((g & 7u) * 4u)) & 15u;
+    const size_t e = static_cast<size_t>(g) * 16u + n;
+    for (int w = 0; w < 4; ++w) r[w] ^= table[e * 4u + w];
+    r[4] ^= table[static_cast<size_t>(kWindowEntriesOne) * 4u + e];
+  }
+  memcpy(out, r, sizeof r);
+}
+
+// Advancing the xorshift words by n draws is the product by T^n (T: the one-step matrix).  T^(2^j), j < 32, are built once
+// per process; T^n comes from them by square-and-multiply (all powers of T commute).
+inline Gf2Mat identity_matrix() {
+  Gf2Mat m;
+  memset(&m, 0, sizeof m);
+  for (int i = 0; i < 160; ++i) m.col[i][i >> 5] = 1u << (i & 31);
+  return m;
+}
+inline const std::vector<Gf2Mat>& step_powers() {
+  static const std::vector<Gf2Mat> powers = [] {
+    std::vector<Gf2Mat> p(32);
+    p[0] = identity_matrix();
+    for (int i = 0; i < 160; ++i) xorshift_step(p[0].col[i]);
+    for (int j = 1; j < 32; ++j) mat_mul(p[j - 1], p[j - 1], p[j]);
+    return p;
+  }();
+  return powers;
+}
+inline Gf2Mat step_power(uint32_t n) {                          // T^n
+  const std::vector<Gf2Mat>& p = step_powers();
+  Gf2Mat r = identity_matrix();
+  bool first = true;
+  for (int j = 0; j < 32; ++j) {
+    if (!((n >> j) & 1u)) continue;
+    if (first) { r = p[j]; first = false; }
+    else mat_mul(p[j], r, r);
+  }
+  return r;
 }
 
 // seed scramble of curand_init: state = {d, v0..v4}

@@ -214,8 +214,8 @@ __global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 
   // of it.  C4, interleaved on one device: macro level only 3.97 ms, + block level 3.75 ms, + wave level inside the forms
   // call 4.55 ms, as a call of its own 3.68 ms.
   constexpr bool THIRD_BLOCK = true, THIRD_WAVE = !FORMS;
-  if constexpr (!RNG_LATE) load_rng();
-
+  // (SmallLists: behind the tile's verdict below -- a wave that owes its draws requests no state at all)
+  if constexpr (!RNG_LATE && Path != TracePath::SmallLists) load_rng();
 
   // Small scenes (SmallLists): the tile's candidate list and its certain-winner verdict were built ahead of this launch by
   // tile_lists_kernel (p.tile_lists; null only for a scene without triangles), so the wave knows the verdict before
@@ -224,6 +224,9 @@ __global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 
   const bool sure_ok = Path == TracePath::SmallLists && (p.flags & (TRACE_NEAREST_HIT | TRACE_NO_SURE_HIT)) == 0u && p.n_spheres == 0u && p.tri_n == nullptr;
   bool loaded_sure = false;
   uint32_t list_word = 0u;                                          // count | winner << 10 | certain << 31
+  // TRACE_OWE_RNG: a certain-winner tile does not touch its pixels' xorshift words (no load, no rng_discard, no store): the
+  // host adds the draws to what the tracer owes and rng_settle_kernel advances the states when somebody needs them
+  bool owes_rng = false;                                            // wave-uniform
   if constexpr (Path == TracePath::SmallLists) {
     if (p.tile_lists != nullptr) {
       const size_t slot0 = (static_cast<size_t>(by) * gxb + bx) * 4u + wave;
@@ -231,6 +234,8 @@ __global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 
       list_word = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(p.tile_lists[slot0 * (1u + p.bin_list)])));
       loaded_sure = sure_ok && (list_word >> 31) != 0u;
     }
+    owes_rng = loaded_sure && (p.flags & TRACE_OWE_RNG) != 0u;
+    if (!owes_rng) load_rng();                                      // (the other waves, and a traced wave's pinhole ray, cover the latency)
   }
   V3 po = {0.0f, 0.0f, 0.0f}, pd = {0.0f, 0.0f, 0.0f}, focal = {0.0f, 0.0f, 0.0f};
   if (!loaded_sure) {                                               // wave-uniform
@@ -501,7 +506,7 @@ __global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 
     // (Kernels.cuh:95-99), whatever the lens sample -- no ray, no test.  What the samples still do to the state is kept
     // exactly: the three draws of each lens sample (Random.cuh:15-16) and the additions of :137 in sample order.
     if (sure_hit_tile) {                                           // wave-uniform
-      rtd::rng_discard(rng, 3u * p.samples);
+      if (!owes_rng) rtd::rng_discard(rng, 3u * p.samples);
       if (sure_sums) { ax = sure_col.x; ay = sure_col.y; az = sure_col.z; }      // (the same additions, done once per triangle)
       else for (uint32_t s = 0; s < p.samples; ++s) { ax += sure_col.x; ay += sure_col.y; az += sure_col.z; }
       if constexpr (STATS) st_pre += (p.samples + static_cast<uint32_t>(K) - 1u) / static_cast<uint32_t>(K);
@@ -740,11 +745,13 @@ __global__ __launch_bounds__(256, (Path == TracePath::SmallLists && K == 2) ? 5 
       // PCIe writes, one 256-byte row segment per wave store) -- no device-to-host copy afterwards
       if (p.image_host != nullptr) p.image_host[pix_e] = bgra;
     }
-    p.rng[1 * static_cast<size_t>(p.npix) + pix_e] = rng.v0;          // :146 (d: the host advances it, rt_tracer::take_uniform_state)
-    p.rng[2 * static_cast<size_t>(p.npix) + pix_e] = rng.v1;
-    p.rng[3 * static_cast<size_t>(p.npix) + pix_e] = rng.v2;
-    p.rng[4 * static_cast<size_t>(p.npix) + pix_e] = rng.v3;
-    p.rng[5 * static_cast<size_t>(p.npix) + pix_e] = rng.v4;
+    if (!owes_rng) {
+      p.rng[1 * static_cast<size_t>(p.npix) + pix_e] = rng.v0;        // :146 (d: the host advances it, rt_tracer::take_uniform_state)
+      p.rng[2 * static_cast<size_t>(p.npix) + pix_e] = rng.v1;
+      p.rng[3 * static_cast<size_t>(p.npix) + pix_e] = rng.v2;
+      p.rng[4 * static_cast<size_t>(p.npix) + pix_e] = rng.v3;
+      p.rng[5 * static_cast<size_t>(p.npix) + pix_e] = rng.v4;
+    }
   }
   tl_mark(4);                                                      // stores issued
   if constexpr (STATS) {

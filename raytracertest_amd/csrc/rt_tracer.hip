@@ -321,6 +321,7 @@ static int upload_scene_impl(rt_tracer* t, const rt_float4* hostData, size_t cou
   return guarded(t, [&] {
     t->cancel_and_join();
     t->use_device();
+    t->settle();                                                         // owed RNG draws, while the lists of the old scene say whose
     HIP_CHECK(hipStreamSynchronize(t->main_stream()));
     t->sync_list_stream();                                               // (a list build may still be reading the old records)
     t->wait_queries();                                                   // (and so may a query)
@@ -381,6 +382,7 @@ int rt_tracer_upload_spheres(rt_tracer* t, const rt_float4* spheres, size_t coun
   return guarded(t, [&] {
     t->cancel_and_join();
     t->use_device();
+    t->settle();
     HIP_CHECK(hipStreamSynchronize(t->main_stream()));
     t->wait_queries();
     t->d_spheres.reset();
@@ -451,6 +453,7 @@ int rt_tracer_set_list_reuse(rt_tracer* t, int across_traces) {
   t->cancel_and_join();
   if (t->mg) for (rt_tracer* b : t->mg->bands) (void)rt_tracer_set_list_reuse(b, across_traces);
   t->reuse_across_traces = across_traces != 0;
+  if (!t->mg) (void)guarded(t, [&] { t->use_device(); t->settle(); });   // (the lists stay in their slots; the next launch rebuilds them)
   t->lists.key.reset();
   return RT_OK;
 }

@@ -11,6 +11,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <map>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -38,6 +39,8 @@ struct Env {
   bool no_sure_table;   // RT_MI355X_NO_SURE_TABLE=1: certain-winner tiles add their samples' colours per pixel
   int row_interleave;   // RT_MI355X_ROW_INTERLEAVE=0|1: pins the halves of a split small-scene launch (-1: by the builder's counts)
   long macro_cap;       // RT_MI355X_MACRO_CAP=n: capacity of the macro lists (tests: forces the overflow fallback); 0 = default
+  bool no_owe;          // RT_MI355X_NO_OWE=1: certain-winner tiles advance their RNG states in every launch (no owed draws)
+  long owe_period;      // RT_MI355X_OWE_PERIOD=n: owing launches between two periodic settles (tests); 0 = RT_OWE_PERIOD
   static bool on(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
   Env() {
     log = getenv("RT_MI355X_LOG") != nullptr;
@@ -48,6 +51,9 @@ struct Env {
     row_interleave = (ri && (ri[0] == '0' || ri[0] == '1') && ri[1] == 0) ? ri[0] - '0' : -1;
     const char* mc = getenv("RT_MI355X_MACRO_CAP");
     macro_cap = mc ? strtol(mc, nullptr, 10) : 0;
+    no_owe = on("RT_MI355X_NO_OWE");
+    const char* op = getenv("RT_MI355X_OWE_PERIOD");
+    owe_period = op ? strtol(op, nullptr, 10) : 0;
   }
 };
 
@@ -283,6 +289,18 @@ struct ListKey {
 };
 inline bool same_key(const std::optional<ListKey>& held, const ListKey& k) { return held && memcmp(&*held, &k, sizeof k) == 0; }
 
+// What has to stay the same from one small-scene launch to the next for the certain-winner tiles to be the same tiles:
+// the lists' key, what the kernel's certain-winner condition reads, the trace path and the arithmetic mode (rt_tracer::
+// owe_key_of zeroes the padding: compared bytewise).
+struct OweKey {
+  ListKey lists;
+  uint32_t mode_flags, n_spheres, smooth, path;
+};
+#ifndef RT_OWE_PERIOD
+#define RT_OWE_PERIOD 16         // owing launches between two periodic settles (<= 20: the driver's timed region then holds one)
+#endif
+constexpr uint32_t kSettleStepMax = 96u;   // draws up to which rng_settle_kernel steps (7 VALU per draw) instead of one table product (~300 VALU + 80 LDS reads)
+
 // The small scenes' tile lists live in a small ring of buffers and are built on a stream of their own (stream_l, high priority): a build is
 // enqueued when the launch that needs it is enqueued, so it runs UNDER the trace kernels of the previous launch instead of
 // in front of its own (measured in-stream: each half-frame build took 35-45 us competing for wave slots with the other
@@ -466,6 +484,59 @@ struct rt_tracer {
   uint32_t weyl_now = 0, count_now = 0;
   uint32_t weyl_plane = 0, count_plane = 0;
   bool weyl_plane_ok = false, count_plane_ok = false;
+  // A third word of the same kind: owed_draws -- the xorshift steps the pixels of the certain-winner tiles are behind.  A
+  // small-scene launch whose owe key equals that of the launch enqueued before it runs with TRACE_OWE_RNG: its
+  // certain-winner waves neither load, advance nor store v0..v4, and the launch adds its 3 x samples x iterations here instead.
+  // settle() pays: one rng_settle_kernel over the tiles whose list header has the certain bit -- the same tiles in every
+  // owing launch, their key being the same.  Who calls it: the first launch that may not owe or has another key (before it
+  // replaces the lists), materialise(RT_BUF_RNG) -- every reader of the buffer --, the uploads, the instrumented launches,
+  // and every owe_period()-th owing launch (on the streams of its halves, so that the debt stays one table product).
+  // Where the states are created anew the debt is dropped.  All guarded by order_mu.
+  uint32_t owed_draws = 0;
+  uint32_t owing_launches = 0;                 // since the last settle
+  uint64_t settles_enqueued = 0;               // settle kernels so far (rt_dbg_owed_state)
+  std::optional<rtr::OweKey> owe_key;          // of the launch enqueued last; none: the next launch does not owe
+  rtk::TraceParams owe_p;                      // the band-wide launch the debt is settled as: planes, lists, frame
+  std::map<uint32_t, rtr::DevArray<uint32_t>> settle_tables;   // window tables of T^n by n; steady state holds one, n = period x 3 x samples
+  uint32_t owe_period() const { return env.owe_period > 0 ? static_cast<uint32_t>(env.owe_period) : static_cast<uint32_t>(RT_OWE_PERIOD); }
+  // the owe key of the launch `p` on `path`, or none: such a launch may not owe
+  std::optional<rtr::OweKey> owe_key_of(const rtk::TraceParams& p, rtk::TracePath path) const {
+    const bool sure_ok = (p.flags & (rtk::TRACE_NEAREST_HIT | rtk::TRACE_NO_SURE_HIT)) == 0u && p.n_spheres == 0u && p.tri_n == nullptr;
+    if (env.no_owe || path != rtk::TracePath::SmallLists || p.n_tris == 0u || p.stats != nullptr || !sure_ok) return std::nullopt;
+    rtr::OweKey k;
+    memset(&k, 0, sizeof k);
+    k.lists = make_key(p, p.bin_list);
+    k.mode_flags = mode_flags(p); k.n_spheres = p.n_spheres; k.smooth = p.tri_n != nullptr ? 1u : 0u;
+    k.path = static_cast<uint32_t>(path);
+    return k;
+  }
+  // the device table of T^n, or null: n draws are stepped.  A new table is in device memory when this returns.
+  const uint32_t* settle_table(uint32_t n) {
+    if (n <= rtr::kSettleStepMax) return nullptr;
+    auto it = settle_tables.find(n);
+    if (it != settle_tables.end()) return it->second.get();
+    if (settle_tables.size() >= 32u) {                                   // (earlier settles may still read theirs)
+      HIP_CHECK(hipStreamSynchronize(stream_b));
+      HIP_CHECK(hipStreamSynchronize(stream));
+      settle_tables.clear();
+    }
+    const std::vector<uint32_t> host = rth::build_window_table(rth::step_power(n));
+    rtr::DevArray<uint32_t> dev(host.size());
+    HIP_CHECK(hipMemcpy(dev.get(), host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return settle_tables.emplace(n, std::move(dev)).first->second.get();
+  }
+  // pays the debt on the stream that orders behind both trace streams; nothing owed: nothing enqueued
+  void settle() {
+    std::lock_guard<std::recursive_mutex> lk(order_mu);
+    if (owed_draws == 0u) return;
+    const uint32_t* const table = settle_table(owed_draws);
+    HIP_CHECK(rtk::launch_rng_settle(owe_p, owed_draws, table, main_stream()));
+    owed_draws = 0u; owing_launches = 0u; ++settles_enqueued;
+  }
+  void drop_debt() {                           // the states are created anew
+    std::lock_guard<std::recursive_mutex> lk(order_mu);
+    owed_draws = 0u; owing_launches = 0u; owe_key.reset();
+  }
   // Once per launch of `p.samples` x `p.iters` samples (not per half of a split one), with order_mu held until the
   // launch is enqueued: hands the launch the two words and advances them by what it will do to every pixel.
   void take_uniform_state(rtk::TraceParams& p) {
@@ -479,6 +550,7 @@ struct rt_tracer {
   // orders behind both trace streams (no launch touches either plane).  Skipped when the plane already holds it.
   void materialise(int which) {
     std::lock_guard<std::recursive_mutex> lk(order_mu);
+    if (which == RT_BUF_RNG && d_rng.get() != nullptr) settle();
     if (which == RT_BUF_RNG && !(weyl_plane_ok && weyl_plane == weyl_now) && d_rng.get() != nullptr) {
       HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_rng.get()), static_cast<int>(weyl_now), npix(), main_stream()));
       weyl_plane = weyl_now; weyl_plane_ok = true;
@@ -574,6 +646,7 @@ struct rt_tracer {
     std::lock_guard<std::recursive_mutex> lk(order_mu);
     HIP_CHECK(rtk::launch_rng_init(d_rng.get(), npix(), p0, seeded, tables, tables + rtr::kJumpWords, main_stream()));
     weyl_now = seeded[0]; weyl_plane_ok = false;                         // (the kernel writes v0..v4)
+    drop_debt();
   }
 
   void create_buffers() {                                                // ctor :33-40, Resize :96-102
@@ -719,9 +792,17 @@ struct rt_tracer {
     p.flags = flags | mode_flags(p);
     p.image = d_image.get();
     const rtk::TracePath path = trace_path(p);
+    std::unique_lock<std::recursive_mutex> uniform_lk(order_mu);          // the state words and the launch that advances them
+    // Owed draws: the launch owes when its key is that of the launch before it; otherwise the debt is paid first -- before
+    // the lists the owing launches read are replaced.
+    const std::optional<rtr::OweKey> okey = owe_key_of(p, path);
+    const bool owes = okey && owe_key && memcmp(&*okey, &*owe_key, sizeof(rtr::OweKey)) == 0;
+    if (!owes) settle();
+    owe_key = okey;
     bool have_lists = false;
     const bool build_lists = prepare_tile_lists(p, path, (flags & rtk::TRACE_ZERO_ACC) != 0u, have_lists);
     attach_sure_table(p, have_lists);
+    if (owes) p.flags |= rtk::TRACE_OWE_RNG;
     last_k = K; last_chunk = p.chunk;
     // (DenseLists: the LDS of the classifying kernel, what rt_tracer_info has always reported for dense scenes)
     last_lds = rtk::trace_lds_bytes(p, path == rtk::TracePath::DenseLists ? rtk::TracePath::ClassifyForms : path);
@@ -730,8 +811,10 @@ struct rt_tracer {
     const uint32_t r0 = allow_split ? split_row(p.rows) : 0u;
     rtr::EventPair e;                                                    // sampled launches: timing events (LaunchClock)
     const bool timed = clock.start(sync_after == 1, r0 != 0u, e);
-    std::unique_lock<std::recursive_mutex> uniform_lk(order_mu);          // the state words and the launch that advances them
     take_uniform_state(p);
+    if (owes) { owed_draws += 3u * p.samples * (p.iters > 1u ? p.iters : 1u); ++owing_launches; }   // once per launch, not per half
+    const bool settle_now = owes && owing_launches >= owe_period();       // the periodic settle, behind this launch's kernels
+    const uint32_t* const settle_tab = settle_now ? settle_table(owed_draws) : nullptr;
     if (r0 == 0u) {
       (void)main_stream();                                               // a launch on one stream orders behind both
       if (build_lists) build_tile_lists_ahead(p);
@@ -741,6 +824,8 @@ struct rt_tracer {
       attach_macro_lists(p, path, 0, stream, (flags & rtk::TRACE_ZERO_ACC) != 0u);   // part of the launch: timed with it
       HIP_CHECK(rtk::launch_trace(p, fma, filter, path, K, stream));
       if (timed) HIP_CHECK(hipEventRecord(e.b, stream));
+      if (owes) owe_p = p;
+      if (settle_now) { HIP_CHECK(rtk::launch_rng_settle(p, owed_draws, settle_tab, stream)); ++settles_enqueued; }
     } else {
       fork_b();
       if (build_lists) build_tile_lists_ahead(p);
@@ -779,8 +864,12 @@ struct rt_tracer {
         if (h == 0 && stagger) HIP_CHECK(hipEventRecord(stagger_event, stream));
       }
       if (timed) { HIP_CHECK(hipEventRecord(e.b, stream)); HIP_CHECK(hipEventRecord(e.c, stream_b)); }
+      if (owes) { owe_p = p; lists.attach(owe_p, row0, true); }          // (the band as one launch: settle() orders behind both streams)
+      // each half's tiles on that half's own stream, with the geometry of its trace kernel: no join
+      if (settle_now) for (int h = 0; h < 2; ++h) { HIP_CHECK(rtk::launch_rng_settle(half[h], owed_draws, settle_tab, st[h])); ++settles_enqueued; }
       mark_b_dirty();
     }
+    if (settle_now) { owed_draws = 0u; owing_launches = 0u; }
     uniform_lk.unlock();
     if (timed) clock.enqueued(std::move(e), sync_after);
   }
@@ -827,12 +916,10 @@ struct rt_tracer {
     HIP_CHECK(hipStreamSynchronize(main_stream()));                             // :259,:287
   }
 
-  // Candidate lists (SmallLists scenes) are kept across launches: the launch that clears the
-  // accumulators (the first of a Trace) classifies as usual and stores nothing, so one-launch
-  // passes -- bench.py's step -- neither pay for nor profit from the cache; the first
-  // accumulating launch classifies and stores its tiles' lists, later ones load them as long as
-  // camera snapshot, scene, frame, list length and arithmetic mode are unchanged (they do not
-  // depend on the samples).
+  // Candidate lists + certain-winner verdicts of the small scenes' tiles (TracePath::SmallLists): built by tile_lists_kernel
+  // on stream_l into the next slot of a ring, ahead of the launch that needs them, and kept while camera snapshot, lens,
+  // scene, frame, list length and arithmetic mode are unchanged (lists.key; they do not depend on the samples).  The first
+  // launch of a Trace rebuilds them when lists are not kept across Traces (reuse_across_traces: bench.py's headline).
   rtr::TileListRing lists;            // small scenes: the tile lists, built ahead on stream_l
   rtr::Event stagger_event;
   std::atomic<bool> stagger_next{true};   // the next split launch starts from an idle tracer: stagger its halves (enqueue_trace_launch)
@@ -931,6 +1018,7 @@ struct rt_tracer {
   // instrumented launches of rt_tracer_trace_stats and rt_dbg_trace_timeline).
   void launch_instrumented(rtk::TraceParams& p, uint32_t samples) {
     const rtk::TracePath path = trace_path(p);
+    { std::lock_guard<std::recursive_mutex> lk(order_mu); settle(); owe_key.reset(); }   // (it rebuilds the lists in place and advances every state)
     bool have_lists = false;
     (void)prepare_tile_lists(p, path, true, have_lists);
     sync_list_stream();
