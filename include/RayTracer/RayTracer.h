@@ -117,6 +117,17 @@ public:
     occluded.resize(segs.size() / 8);
     return mImpl && segs.size() % 8 == 0 && rt_tracer_occluded(mImpl, segs.data(), occluded.size(), occluded.data()) == RT_OK;
   }
+  // All hits (rt_mi355x.h, rt_tracer_intersect_all): the same segments; row i of hits (maxHits records) holds the ray's first
+  // counts[i] <= maxHits in-interval hits in ascending (t, prim) order, then records {0, 0, 0, RT_PRIM_NONE}.  counts[i] ==
+  // maxHits: there may be more.  1 <= maxHits <= RT_MAX_HITS.  A segment vector whose size is no multiple of 8: false, the
+  // outputs untouched.
+  bool IntersectAll(const std::vector<float>& segs, uint32_t maxHits, std::vector<rt_hit>& hits, std::vector<uint32_t>& counts) {
+    if (!mImpl || segs.size() % 8 != 0 || maxHits == 0 || maxHits > RT_MAX_HITS) return false;
+    const size_t n = segs.size() / 8;
+    hits.resize(n * maxHits);
+    counts.resize(n);
+    return rt_tracer_intersect_all(mImpl, segs.data(), n, maxHits, hits.data(), counts.data()) == RT_OK;
+  }
   // The pinhole ray of a full-image pixel; `ray` (origin, direction) when asked for: the hit point is o + t * d.
   bool Pick(const math::uvec2& pixel, rt_hit& hit) { return Pick(pixel, hit, nullptr); }
   bool Pick(const math::uvec2& pixel, rt_hit& hit, math::vec3 ray[2]) {

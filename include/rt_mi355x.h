@@ -312,6 +312,40 @@ int  rt_tracer_occluded(rt_tracer* t, const float* segs, size_t n, uint8_t* occl
  * synchronisation.  segs must be 16-byte aligned (a ray is two 16-byte loads); otherwise RT_ERR_INVALID. */
 int  rt_tracer_occluded_device(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded, void* stream);
 
+/* All hits along a ray (seeing through surfaces, wall thickness, point-in-solid by the parity of the crossings, the nearest hit
+ * in front of the origin under any hit rule): the first max_hits hits of ray i within its own t interval, in order.
+ *   segs      n x 8 floats, exactly as rt_tracer_occluded takes them: origin, direction used as given, tmin, tmax.
+ *   max_hits  1 .. RT_MAX_HITS; otherwise RT_ERR_INVALID.
+ *   hits      n * max_hits records.  Row i (hits + i * max_hits) holds counts[i] <= max_hits hits, then records
+ *             {0, 0, 0, RT_PRIM_NONE}.
+ *   counts    counts[i] = hits stored for ray i.  counts[i] == max_hits means there MAY be more.  To continue, call again
+ *             with tmin = the last stored t and skip the (t, prim) pairs already seen -- the interval is closed, so hits with
+ *             that same t come again, which is what keeps coincident surfaces from being lost.
+ *   hit       rt_tracer_occluded's definition word for word: HitTriangle returns true in the tracer's arithmetic mode for the
+ *             record the renderer intersects (edge-format scenes: their uploaded rows), t is the value of Kernels.cuh:63; a
+ *             sphere counts with the one t of its ray-sphere test and u = v = 0 (prim = triangle count + sphere index).  The
+ *             interval is closed and compared in plain fp32; a NaN t, a NaN bound or tmin > tmax gives no hit; [-inf, +inf]
+ *             means every hit, negative t included.
+ *   order     ascending t; equal t (==, so -0 equals +0) by ascending prim.  The rule names no visiting order and does not
+ *             depend on RT_FLAG_NEAREST_HIT.
+ *   bits      t, u and v of a stored hit are exactly what rt_tracer_intersect reports for that (ray, primitive).
+ * No scene: every count is 0; spheres alone can be hit; n = 0 is a no-op; a NULL array with n > 0 is RT_ERR_INVALID.
+ * Scheduling is that of the other queries: never cancels or joins a running Trace, serialised with the other calls, waited for
+ * by uploads and destroy; a multi-device handle answers from its first band, a band tracer locally.
+ * RT_QUERY_SCAN (default): exact.  RT_QUERY_BVH: let E be the ray's exact set of in-interval hits, and W the subset of E made
+ * of the spheres and of the WELL CONDITIONED triangles (in float64, det / (|d| |e1| |e2|) >= 2^-10).  The answer is the first
+ * max_hits elements, in the order above, of some set E' with W <= E' <= E: it never stores a hit the exact test rejects or
+ * that lies outside the interval, the bits are the scan's, only ill-conditioned hits may be lost, and what is kept is what the
+ * rule gives on the rest.  A ray with a non-finite component, a zero direction or a NaN in its box arithmetic takes no pruning
+ * decision and gets the scan's answer; triangles with a non-finite record are always tested. */
+#define RT_MAX_HITS 16u
+/* Host arrays: segs n*8, hits n*max_hits, counts n.  Returns with the results in host memory. */
+int  rt_tracer_intersect_all(rt_tracer* t, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  segs and hits must be 16-byte aligned; otherwise RT_ERR_INVALID. */
+int  rt_tracer_intersect_all_device(rt_tracer* t, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts,
+                                    void* stream);
+
 /* ---- one frame sharded over several GPUs --------------------------------------
  * The reference builds ONE rt::RayTracer pinned to device 0 (OpenGLView/MainFrame.cpp:44-45,
  * OpenGLView/GLCanvas.cpp:259-260).  Pixels are independent and a pixel's RNG stream is keyed by its

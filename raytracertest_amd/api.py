@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "rt_tracer_gather_only", "rt_tracer_group_info",
     "rt_tracer_intersect", "rt_tracer_intersect_device", "rt_tracer_pick", "rt_tracer_focus_at",
     "rt_tracer_occluded", "rt_tracer_occluded_device",
+    "rt_tracer_intersect_all", "rt_tracer_intersect_all_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
 ]
 
@@ -59,6 +60,7 @@ class RtError(RuntimeError):
 
 
 PRIM_NONE = -1
+RT_MAX_HITS = 16         # rt_tracer_intersect_all: the longest row
 QUERY_SCAN, QUERY_BVH = 0, 1
 # the arrays of rt_dbg_bvh_build (include/rt_mi355x.h): a 4-wide node and a leaf record
 BVH_NODE_DTYPE = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("child", np.uint32, 4), ("cmax", np.float32, 4)])
@@ -236,6 +238,8 @@ def load_library():
         L.rt_tracer_focus_at.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
         L.rt_tracer_occluded.argtypes = [vp, vp, C.c_size_t, vp]
         L.rt_tracer_occluded_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.rt_tracer_intersect_all.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp]
+        L.rt_tracer_intersect_all_device.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
         L.rt_tracer_set_query_accel.argtypes = [vp, C.c_uint32]
         L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_dbg_query_accel_slack.argtypes = [vp, C.c_uint32]
@@ -651,6 +655,47 @@ class RayTracer:
         self._check(self._lib.rt_tracer_occluded_device(self._h, segs.data_ptr(), segs.shape[0], out.data_ptr(),
                                                         C.c_void_p(stream)))
         return out
+
+    def IntersectAll(self, segs, max_hits=RT_MAX_HITS):
+        """All hits along each ray within its own interval, in order.  segs: (n, 8) float32 as Occluded takes them; 1 <= max_hits
+        <= RT_MAX_HITS.  Row i holds the ray's first counts[i] <= max_hits hits with tmin <= t <= tmax in ascending t (equal t by
+        ascending prim), then records {0, 0, 0, PRIM_NONE}; counts[i] == max_hits means there may be more (call again with tmin
+        = the last t and skip what was seen).  Independent of the tracer's hit rule.  A numpy array -> (hits (n, max_hits)
+        HIT_DTYPE, counts (n,) uint32), on return.  A contiguous torch float32 tensor on the tracer's device -> ((n, max_hits, 4)
+        float32 {t, u, v, prim bits}, (n,) int32), enqueued on torch.cuda.current_stream() without a host synchronisation."""
+        if type(segs).__module__.startswith("torch"):
+            return self._intersect_all_tensor(segs, max_hits)
+        s = np.asarray(segs, np.float32)
+        if s.ndim == 0 or s.shape[-1] != 8:                                # (an (n, 6) ray array is not silently reinterpreted)
+            raise ValueError("IntersectAll: expected (n, 8) float32 segments, got shape %s" % (s.shape,))
+        k = self._max_hits(max_hits)
+        s = np.ascontiguousarray(s).reshape(-1, 8)
+        hits = np.zeros((s.shape[0], k), HIT_DTYPE)
+        counts = np.zeros(s.shape[0], np.uint32)
+        self._check(self._lib.rt_tracer_intersect_all(self._h, s.ctypes.data, s.shape[0], k, hits.ctypes.data, counts.ctypes.data))
+        return hits, counts
+
+    @staticmethod
+    def _max_hits(max_hits):
+        k = int(max_hits)
+        if k != max_hits or not 1 <= k <= RT_MAX_HITS:
+            raise ValueError("IntersectAll: max_hits = %r (1 to %d)" % (max_hits, RT_MAX_HITS))
+        return k
+
+    def _intersect_all_tensor(self, segs, max_hits=RT_MAX_HITS):
+        import torch
+        if segs.dtype != torch.float32 or segs.dim() != 2 or segs.shape[1] != 8 or not segs.is_contiguous():
+            raise ValueError("IntersectAll: expected a contiguous (n, 8) float32 tensor")
+        k = self._max_hits(max_hits)
+        dev = self.Bands()[0]["device"]
+        if segs.device.type != "cuda" or segs.device.index != dev:
+            raise ValueError("IntersectAll: the segments are on %s, the tracer on cuda:%d" % (segs.device, dev))
+        hits = torch.empty((segs.shape[0], k, 4), dtype=torch.float32, device=segs.device)
+        counts = torch.empty((segs.shape[0],), dtype=torch.int32, device=segs.device)
+        stream = torch.cuda.current_stream(segs.device).cuda_stream
+        self._check(self._lib.rt_tracer_intersect_all_device(self._h, segs.data_ptr(), segs.shape[0], k, hits.data_ptr(),
+                                                             counts.data_ptr(), C.c_void_p(stream)))
+        return hits, counts
 
     def Visible(self, a, b, tmin=0.0, tmax=1.0):
         """Line of sight between the points a[i] and b[i] ((n, 3) each): ~Occluded of the rays o = a, d = b - a (fp32, on the

@@ -1,6 +1,6 @@
 """Headless front end: `python -m raytracertest_amd.cli`.  The reference's command line
 (OpenGLView/App.cpp:62-184: -w -h -s -i -u -cx -cy -cz -cxa -cya -f -l -a, integer values,
-defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --focus; the image is saved
+defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --focus; the image is saved
 in the reference's BMP format (Common/Bitmap.h).  Same options as tools/rt_cli.cpp."""
 import argparse
 import math
@@ -37,7 +37,9 @@ def build_parser():
     p.add_argument("-q", action="store_true", dest="quiet")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--pick", type=_xy, default=None, metavar="X,Y", help="print `pick x y prim t u v` for the pixel's pinhole ray")
-    p.add_argument("--accel", action="store_true", help="--pick / --focus through the scene's BVH instead of the scan")
+    p.add_argument("--hits", type=_xyk, default=None, metavar="X,Y[,K]",
+                   help="print one line `prim t u v` per hit of the pixel's pinhole ray, in order, over all t (at most K, default 8)")
+    p.add_argument("--accel", action="store_true", help="--pick / --hits / --focus through the scene's BVH instead of the scan")
     p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
                    help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
     return p
@@ -46,6 +48,13 @@ def build_parser():
 def _xy(s):
     x, y = s.split(",")
     return int(x), int(y)
+
+
+def _xyk(s):
+    v = [int(x) for x in s.split(",")]
+    if len(v) not in (2, 3):
+        raise ValueError(s)
+    return v[0], v[1], v[2] if len(v) == 3 else 8
 
 
 def load_scene(name):
@@ -87,6 +96,15 @@ def main(argv=None):
     if a.pick is not None:
         h = g.Pick(a.pick)[0]
         print("pick %d %d %d %.9g %.9g %.9g" % (a.pick[0], a.pick[1], h["prim"], h["t"], h["u"], h["v"]))
+    if a.hits is not None:
+        _, ray = g.Pick(a.hits[:2], return_rays=True)
+        seg = np.concatenate([ray[0], np.float32([-np.inf, np.inf])])[None, :]
+        try:
+            hits, counts = g.IntersectAll(seg, a.hits[2])
+        except Exception as e:
+            sys.exit("--hits: %s" % e)
+        for h in hits[0, :counts[0]]:
+            print("%d %.9g %.9g %.9g" % (h["prim"], h["t"], h["u"], h["v"]))
     if a.focus is not None:
         try:
             f = g.FocusAt(*a.focus)

@@ -1,0 +1,316 @@
+// rt_allhits.hpp -- the all-hits query (rt_tracer_intersect_all*): the first max_hits hits of ray i within its own
+// closed t interval, in ascending (t, prim) order.  Included by rt_kernels.hip only, behind rt_occluded.hpp.  As there, nothing
+// is shared with the other query kernels beyond the renderer's device functions (hit_triangle_exact, hit_sphere, Math<FMA>):
+// the triangle stages and the box test are stated here a third time, because the existing query kernels keep their schedule
+// only while their text is theirs alone (rt_bvh.hpp, rt_occluded.hpp).
+//
+// A "hit" is rt_occluded.hpp's: the reference's HitTriangle returning true (Kernels.cuh:29-65) with the t of :63, a sphere with
+// the one t of hit_sphere; tmin <= t && t <= tmax in plain fp32 (a NaN t or bound, or tmin > tmax: no hit).  Order: ascending
+// t, equal t (==, so -0 equals +0) by ascending prim (upload index; n_tris + i for sphere i).  The rule names no visiting order,
+// so the scan and the traversal cannot disagree about it.
+//
+// The list: CAP pairs (t, prim) in registers, touched with compile-time indices only (a runtime-indexed private array would
+// live in scratch).  A new hit replaces the LAST slot when it sorts before it and is bubbled up by CAP - 1 compare-exchanges.
+// max_hits <= CAP is a runtime argument: the leading CAP - max_hits slots start as (-inf, -1), which sorts before every hit and
+// is therefore never displaced, the others as (+inf, INT_MAX), which sorts behind every hit.  The wanted list is then always the
+// last max_hits slots, it is full exactly when the last slot is no longer the empty pair, and the last slot's t is the t_last
+// the traversal prunes with -- no runtime index anywhere.  u and v are recomputed from the triangle's record when a row is
+// written out (finish_query_hit's way: same operations as the scan, same bits), so the list holds 8 bytes per hit.
+//
+// allhits_kernel (RT_QUERY_SCAN): occluded_kernel's outer shape -- 256-thread blocks, two 16-byte loads per ray, the triangles
+// staged through LDS in ascending chunks of kQueryChunk 36-byte records, stages A-D with the conservative wave-uniform ballots
+// -- at one ray per lane and without the early exits: nothing is ever finished.  Padding lanes and rays whose interval is empty
+// (a NaN bound, tmin > tmax) stay out of the ballots.
+//
+// allhits_bvh_kernel (RT_QUERY_BVH): occluded_bvh_kernel's walk -- one wave per block, lane = ray -- with query_bvh_kernel's
+// stack of 8-byte {-enter, reference} entries in LDS at entry * 64 + lane.  Same pad, same operations, same NaN rule in the box
+// test; a child is skipped when  exit < enter,  exit < tmin,  enter > tmax  or, once the list is full,  enter > t_last  (strictly:
+// a tie is visited, a lower prim may be waiting in it).  The nearest child (smallest enter) is entered first; a popped entry is
+// dropped when its enter has fallen strictly behind t_last meanwhile.  The always-tested list and the spheres are tested
+// unconditionally.  A ray with a non-finite component or a zero direction, or a child with a NaN in its box arithmetic, takes no
+// pruning decision.
+#pragma once
+#include "rt_occluded.hpp"
+
+namespace rtk {
+
+constexpr int kAllHitsEmpty = 0x7FFFFFFF;      // prim of an empty slot (with t = +inf): behind every hit
+constexpr uint32_t kAllHitsMax = 16u;          // RT_MAX_HITS
+
+// (ta, pa) sorts strictly before (tb, pb)
+__device__ __forceinline__ bool allhits_before(float ta, int pa, float tb, int pb) {
+  return (ta < tb) | ((ta == tb) & (pa < pb));
+}
+
+template <int CAP>
+__device__ __forceinline__ void allhits_init(float (&lt)[CAP], int (&lp)[CAP], uint32_t max_hits) {
+  const float inf = __builtin_inff();
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) {
+    const bool wanted = static_cast<uint32_t>(s) + max_hits >= static_cast<uint32_t>(CAP);
+    lt[s] = wanted ? inf : -inf;
+    lp[s] = wanted ? kAllHitsEmpty : -1;
+  }
+}
+
+// one accepted in-interval hit into the sorted list
+template <int CAP>
+__device__ __forceinline__ void allhits_insert(float (&lt)[CAP], int (&lp)[CAP], float t, int prim) {
+  if (allhits_before(t, prim, lt[CAP - 1], lp[CAP - 1])) {
+    lt[CAP - 1] = t; lp[CAP - 1] = prim;
+#pragma unroll
+    for (int s = CAP - 1; s > 0; --s) {
+      const bool sw = allhits_before(lt[s], lp[s], lt[s - 1], lp[s - 1]);
+      const float ta = lt[s - 1], tb = lt[s];
+      const int pa = lp[s - 1], pb = lp[s];
+      lt[s - 1] = sw ? tb : ta; lt[s] = sw ? ta : tb;
+      lp[s - 1] = sw ? pb : pa; lp[s] = sw ? pa : pb;
+    }
+  }
+}
+
+// The ray's row: the last max_hits slots in order, u and v of a triangle from its record (Kernels.cuh:50,57), then records
+// {0, 0, 0, -1}; and its count.  The list is consumed from the front (slot 0 is taken, the rest moves up: compile-time indices).
+template <bool FMA, int CAP>
+__device__ __forceinline__ void allhits_store(const TraceParams& p, V3 o, V3 d, float (&lt)[CAP], int (&lp)[CAP], uint32_t max_hits,
+                                              float4* __restrict__ row, uint32_t* __restrict__ count) {
+  const uint32_t nt = p.n_tris;
+  uint32_t cnt = 0u;
+#pragma unroll 1
+  for (uint32_t s = 0; s < static_cast<uint32_t>(CAP); ++s) {
+    const float t0 = lt[0];
+    const int prim = lp[0];
+#pragma unroll
+    for (int k = 0; k + 1 < CAP; ++k) { lt[k] = lt[k + 1]; lp[k] = lp[k + 1]; }
+    if (s + max_hits < static_cast<uint32_t>(CAP)) continue;       // a leading (-inf, -1) slot (uniform: max_hits is)
+    float4 h = {0.0f, 0.0f, 0.0f, __int_as_float(-1)};
+    if (prim != kAllHitsEmpty) {
+      ++cnt;
+      h.x = t0;
+      h.w = __int_as_float(prim);
+      if (static_cast<uint32_t>(prim) < nt) {
+        const float4 A0 = p.tri_a[2 * prim], A1 = p.tri_a[2 * prim + 1];
+        float t = 0.0f, u = 0.0f, v = 0.0f;
+        int stage;
+        (void)hit_triangle_exact<FMA>(o, d, {A1.z, A1.w, p.tri_b[prim]}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, RT_EPS, t, u, v, stage);
+        h.y = u; h.z = v;
+      }
+    }
+    row[s + max_hits - static_cast<uint32_t>(CAP)] = h;
+  }
+  *count = cnt;
+}
+
+// the spheres through the same insert (hit_sphere's one t; prim = n_tris + sphere index)
+template <bool FMA, int CAP>
+__device__ __forceinline__ void allhits_spheres(const TraceParams& p, V3 o, V3 d, float tmin, float tmax, bool active,
+                                                float (&lt)[CAP], int (&lp)[CAP]) {
+  for (uint32_t si = 0; si < p.n_spheres; ++si) {
+    float t = 0.0f;
+    if (active && hit_sphere<FMA>(o, d, p.spheres[si], t) && tmin <= t && t <= tmax)
+      allhits_insert<CAP>(lt, lp, t, static_cast<int>(p.n_tris + si));
+  }
+}
+
+template <bool FMA, int CAP>
+__global__ __launch_bounds__(256, 4) void allhits_kernel(const TraceParams p, uint32_t n, const float4* __restrict__ segs,
+                                                          uint32_t max_hits, float4* __restrict__ hits, uint32_t* __restrict__ counts) {
+  using M = Math<FMA>;
+  extern __shared__ float4 s_mem[];
+  const uint32_t tid = threadIdx.x;
+  const size_t base = static_cast<size_t>(blockIdx.x) * 256u;           // first ray of the block
+  const uint32_t nb = (n - base < 256u) ? static_cast<uint32_t>(n - base) : 256u;
+
+  float4 s0 = {0.0f, 0.0f, 0.0f, 0.0f}, s1 = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (tid < nb) { s0 = segs[2u * (base + tid)]; s1 = segs[2u * (base + tid) + 1u]; }
+  const V3 o = {s0.x, s0.y, s0.z}, d = {s0.w, s1.x, s1.y};
+  const float tmin = s1.z, tmax = s1.w;
+  const bool active = (tid < nb) & (tmin <= tmax);                 // padding lanes and empty intervals take no part
+
+  float lt[CAP];
+  int lp[CAP];
+  allhits_init<CAP>(lt, lp, max_hits);
+
+  // the triangles, staged into LDS chunk by chunk; every chunk is scanned
+  const uint32_t nt = p.n_tris;
+  const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
+  float4* const sA = s_mem;                                        // 2 float4 per triangle
+  float* const sB = reinterpret_cast<float*>(s_mem + 2u * cap);    // v0.z
+  for (uint32_t c0 = 0; c0 < nt; c0 += kQueryChunk) {
+    const uint32_t cn = (nt - c0 < kQueryChunk) ? nt - c0 : kQueryChunk;
+    __syncthreads();                                               // the previous chunk is read
+    for (uint32_t i = tid; i < 2u * cn; i += 256u) sA[i] = p.tri_a[2u * c0 + i];
+    for (uint32_t i = tid; i < cn; i += 256u) sB[i] = p.tri_b[c0 + i];
+    __syncthreads();
+    if (__builtin_amdgcn_ballot_w64(active) == 0ull) continue;     // no ray of this wave can hit; it still helps staging
+    for (uint32_t j = 0; j < cn; ++j) {
+      const float4 A0 = sA[2u * j], A1 = sA[2u * j + 1u];
+      const V3 e2 = {A0.x, A0.y, A0.z}, e1 = {A0.w, A1.x, A1.y};
+      // stage A: pv = cross(dir, e2), det = dot(e1, pv), culling (:39-45)
+      const V3 pv = M::cross(d, e2);
+      const float det = M::dot(e1, pv);
+      unsigned long long mk = __builtin_amdgcn_ballot_w64(active && !(det < RT_EPS));
+      if (mk == 0ull) continue;
+      // stage B: U = dot(origin - v0, pv) (:49-50), conservative u rejection
+      const V3 v0 = {A1.z, A1.w, sB[j]};
+      const V3 tv = rtd::sub(o, v0);
+      const float U = M::dot(tv, pv);
+      const float thi = det * 1.0001f, tlo = det * -1e-6f;
+      mk &= __builtin_amdgcn_ballot_w64(!(U > thi)) & __builtin_amdgcn_ballot_w64(!(U < tlo));
+      if (mk == 0ull) continue;
+      // stage C: V = dot(dir, cross(tv, e1)) (:56-57), conservative v rejection
+      const V3 qv = M::cross(tv, e1);
+      const float V = M::dot(d, qv);
+      mk &= __builtin_amdgcn_ballot_w64(!(V < tlo)) & __builtin_amdgcn_ballot_w64(!((U + V) > thi));
+      if (mk == 0ull) continue;
+      // stage D: the reference's exact tests (:42-63), then the closed interval, then the list
+      const float inv = 1.0f / det;                                // :47
+      const float u = U * inv;                                     // :50
+      const float v = V * inv;                                     // :57
+      const float t = M::dot(e2, qv) * inv;                        // :63
+      const bool miss = (det < RT_EPS) | (u < 0.0f) | (u > 1.0f) | (v < 0.0f) | (u + v > 1.0f);
+      if (active & (!miss) & (tmin <= t) & (t <= tmax)) allhits_insert<CAP>(lt, lp, t, static_cast<int>(c0 + j));
+    }
+  }
+
+  allhits_spheres<FMA, CAP>(p, o, d, tmin, tmax, active, lt, lp);
+
+  if (tid < nb) allhits_store<FMA, CAP>(p, o, d, lt, lp, max_hits, hits + (base + tid) * max_hits, counts + base + tid);
+}
+
+// one record against one ray: the exact test, the closed interval, the list
+template <bool FMA, int CAP>
+__device__ __forceinline__ void allhits_test_record(const float4* __restrict__ rec, V3 o, V3 d, float tmin, float tmax,
+                                                    float (&lt)[CAP], int (&lp)[CAP]) {
+  const float4 A0 = rec[0], A1 = rec[1], B = rec[2];
+  float t = 0.0f, u = 0.0f, v = 0.0f;
+  int stage;
+  if (!hit_triangle_exact<FMA>(o, d, {A1.z, A1.w, B.x}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, RT_EPS, t, u, v, stage)) return;
+  if (tmin <= t && t <= tmax) allhits_insert<CAP>(lt, lp, t, __float_as_int(B.y));
+}
+
+template <bool FMA, int CAP>
+__global__ __launch_bounds__(64) void allhits_bvh_kernel(const TraceParams p, const BvhParams b, uint32_t n, const float4* __restrict__ segs,
+                                                          uint32_t max_hits, float4* __restrict__ hits, uint32_t* __restrict__ counts) {
+  extern __shared__ float4 s_mem[];
+  const uint32_t lane = threadIdx.x;
+  const size_t i = static_cast<size_t>(blockIdx.x) * 64u + lane;
+  if (i >= n) return;                                              // (no barrier and no cross-lane operation below)
+  const float4 s0 = segs[2u * i], s1 = segs[2u * i + 1u];
+  const V3 o = {s0.x, s0.y, s0.z}, d = {s0.w, s1.x, s1.y};
+  const float tmin = s1.z, tmax = s1.w;
+  const bool active = tmin <= tmax;                                // a NaN bound or tmin > tmax: nothing can be in the interval
+
+  float lt[CAP];
+  int lp[CAP];
+  allhits_init<CAP>(lt, lp, max_hits);
+
+  uint2* const stack = reinterpret_cast<uint2*>(s_mem) + lane;     // entry e at stack[e * 64]
+  const float inf = __builtin_inff();
+  const bool finite = fabsf(o.x) < inf && fabsf(o.y) < inf && fabsf(o.z) < inf && fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf;
+  const bool prunes = finite && !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f);
+  const V3 inv = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+  const float omax = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
+  uint32_t sp = 0u;
+  uint32_t cur = (b.n_nodes != 0u && active) ? 0u : kBvhEmpty;
+  bool overflow = false;
+  for (;;) {
+    if (cur == kBvhEmpty) {
+      if (sp == 0u) break;
+      --sp;
+      const uint2 e = stack[sp * 64u];
+      // -enter fell strictly behind -t_last meanwhile (an empty last slot has t = +inf: nothing is below -inf)
+      if (__uint_as_float(e.x) < -lt[CAP - 1]) continue;
+      cur = e.y;
+    }
+    if ((cur & kBvhLeaf) != 0u) {
+      const uint32_t first = cur & 0x0FFFFFFFu, count = ((cur >> 28) & 3u) + 1u;
+      for (uint32_t j = 0; j < count; ++j) allhits_test_record<FMA, CAP>(b.records + 3u * (first + j), o, d, tmin, tmax, lt, lp);
+      cur = kBvhEmpty;
+      continue;
+    }
+    const float4* const nd = b.nodes + 8u * static_cast<size_t>(cur);
+    const float4 lox = nd[0], loy = nd[1], loz = nd[2], hix = nd[3], hiy = nd[4], hiz = nd[5], refs = nd[6], cm = nd[7];
+    const float L[3][4] = {{lox.x, lox.y, lox.z, lox.w}, {loy.x, loy.y, loy.z, loy.w}, {loz.x, loz.y, loz.z, loz.w}};
+    const float Hh[3][4] = {{hix.x, hix.y, hix.z, hix.w}, {hiy.x, hiy.y, hiy.z, hiy.w}, {hiz.x, hiz.y, hiz.z, hiz.w}};
+    const float cmax[4] = {cm.x, cm.y, cm.z, cm.w};
+    uint32_t ref[4] = {__float_as_uint(refs.x), __float_as_uint(refs.y), __float_as_uint(refs.z), __float_as_uint(refs.w)};
+    float good[4];
+    const float t_last = lt[CAP - 1];                              // +inf while the list is not full: enter > +inf never holds
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float pad = b.rho * (omax + cmax[c]);
+      const float t1x = ((L[0][c] - pad) - o.x) * inv.x, t2x = ((Hh[0][c] + pad) - o.x) * inv.x;
+      const float t1y = ((L[1][c] - pad) - o.y) * inv.y, t2y = ((Hh[1][c] + pad) - o.y) * inv.y;
+      const float t1z = ((L[2][c] - pad) - o.z) * inv.z, t2z = ((Hh[2][c] + pad) - o.z) * inv.z;
+      const bool nan = __builtin_isunordered(t1x, t2x) || __builtin_isunordered(t1y, t2y) || __builtin_isunordered(t1z, t2z);
+      const float enter = fmaxf(fmaxf(fminf(t1x, t2x), fminf(t1y, t2y)), fminf(t1z, t2z));
+      const float exit = fminf(fminf(fmaxf(t1x, t2x), fmaxf(t1y, t2y)), fmaxf(t1z, t2z));
+      const bool skip = (exit < enter) || (exit < tmin) || (enter > tmax) || (enter > t_last);
+      const bool decided = prunes && !nan;
+      float g = decided ? fmaxf(-enter, -FLT_MAX) : inf;           // nearest first; an undecided child is never dropped
+      if (ref[c] == kBvhEmpty || (decided && skip)) { ref[c] = kBvhEmpty; g = -inf; }
+      good[c] = g;
+    }
+    // nearest first (a 5-exchange network); an empty reference carries -inf, a visited one at least -FLT_MAX
+#define RT_ALL_CSWAP(i, j)                                                                            \
+    if (good[i] < good[j]) { const float tg = good[i]; good[i] = good[j]; good[j] = tg;               \
+                             const uint32_t tr = ref[i]; ref[i] = ref[j]; ref[j] = tr; }
+    RT_ALL_CSWAP(0, 1) RT_ALL_CSWAP(2, 3) RT_ALL_CSWAP(0, 2) RT_ALL_CSWAP(1, 3) RT_ALL_CSWAP(1, 2)
+#undef RT_ALL_CSWAP
+    cur = ref[0];
+    auto push = [&](float g, uint32_t r) {
+      if (r == kBvhEmpty) return;
+      if (sp < b.stack_cap) { stack[sp * 64u] = make_uint2(__float_as_uint(g), r); ++sp; }
+      else overflow = true;                                        // (cannot happen: the capacity is 3 x the tree's depth)
+    };
+    push(good[3], ref[3]); push(good[2], ref[2]); push(good[1], ref[1]);   // the nearer of them on top
+  }
+  if (overflow) {                                                  // an entry was not kept: every leaf record, from an empty list
+    allhits_init<CAP>(lt, lp, max_hits);
+    for (uint32_t j = 0; j < b.n_leaf_records; ++j) allhits_test_record<FMA, CAP>(b.records + 3u * j, o, d, tmin, tmax, lt, lp);
+  }
+  if (active) {
+    for (uint32_t j = 0; j < b.n_always; ++j)
+      allhits_test_record<FMA, CAP>(b.records + 3u * (b.n_leaf_records + j), o, d, tmin, tmax, lt, lp);
+  }
+  allhits_spheres<FMA, CAP>(p, o, d, tmin, tmax, active, lt, lp);
+  allhits_store<FMA, CAP>(p, o, d, lt, lp, max_hits, hits + i * max_hits, counts + i);
+}
+
+uint32_t allhits_lds_bytes(uint32_t n_tris) {
+  return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
+}
+
+uint32_t allhits_bvh_lds_bytes(uint32_t stack_cap) {
+  return stack_cap * 64u * 8u;
+}
+
+hipError_t launch_allhits(const TraceParams& p, bool fma, uint32_t n, const float* segs, uint32_t max_hits, float4* hits,
+                          uint32_t* counts, hipStream_t st) {
+  if (n == 0u) return hipSuccess;
+  if (max_hits == 0u || max_hits > kAllHitsMax || segs == nullptr || hits == nullptr || counts == nullptr) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 255u) / 256u));
+  const size_t lds = allhits_lds_bytes(p.n_tris);
+  const float4* const s4 = reinterpret_cast<const float4*>(segs);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, n, s4, max_hits, hits, counts); };
+  if (fma) { if (max_hits <= 4u) go(allhits_kernel<true, 4>); else go(allhits_kernel<true, 16>); }
+  else { if (max_hits <= 4u) go(allhits_kernel<false, 4>); else go(allhits_kernel<false, 16>); }
+  return hipGetLastError();
+}
+
+hipError_t launch_allhits_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint32_t max_hits,
+                              float4* hits, uint32_t* counts, hipStream_t st) {
+  if (n == 0u) return hipSuccess;
+  if (max_hits == 0u || max_hits > kAllHitsMax || segs == nullptr || hits == nullptr || counts == nullptr) return hipErrorInvalidValue;
+  const uint32_t lds = allhits_bvh_lds_bytes(b.stack_cap);
+  if (lds > 65536u) return hipErrorInvalidValue;                   // (3 x kBvhMaxDepth entries are 24 KiB)
+  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
+  const float4* const s4 = reinterpret_cast<const float4*>(segs);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), lds, st, p, b, n, s4, max_hits, hits, counts); };
+  if (fma) { if (max_hits <= 4u) go(allhits_bvh_kernel<true, 4>); else go(allhits_bvh_kernel<true, 16>); }
+  else { if (max_hits <= 4u) go(allhits_bvh_kernel<false, 4>); else go(allhits_bvh_kernel<false, 16>); }
+  return hipGetLastError();
+}
+
+}  // namespace rtk

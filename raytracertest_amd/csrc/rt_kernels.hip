@@ -7,6 +7,8 @@
 //   convert_kernel     <- rt::ConverterKernel              (RayTracer/Kernels.cuh:149-169)
 //   query_kernel       <- Radiance's hit scan for caller rays / pixels (rt_query.hpp)
 //   query_bvh_kernel   <- the same answer through a bounding volume hierarchy (rt_bvh.hpp)
+//   occluded_*kernel   <- any hit within a caller's t interval (rt_occluded.hpp)
+//   allhits_*kernel    <- the first k hits within a caller's t interval, in order (rt_allhits.hpp)
 //   dbg_* kernels      <- single-function harnesses used by the parity tests
 #include <stdlib.h>
 
@@ -14,6 +16,7 @@
 #include "rt_query.hpp"
 #include "rt_bvh.hpp"
 #include "rt_occluded.hpp"
+#include "rt_allhits.hpp"
 
 namespace rtk {
 

@@ -162,6 +162,16 @@ uint32_t occluded_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_occluded_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint8_t* occluded,
                                hipStream_t st);
 
+// The all-hits query (rt_allhits.hpp): the same segments; row i of hits (max_hits records {t, u, v, bits of the int32 primitive},
+// 16-byte aligned) holds the ray's first counts[i] <= max_hits in-interval hits in ascending (t, prim) order, then records
+// {0, 0, 0, -1}.  1 <= max_hits <= 16; one ray per lane in both forms.
+uint32_t allhits_lds_bytes(uint32_t n_tris);
+hipError_t launch_allhits(const TraceParams& p, bool fma, uint32_t n, const float* segs, uint32_t max_hits, float4* hits,
+                          uint32_t* counts, hipStream_t st);
+uint32_t allhits_bvh_lds_bytes(uint32_t stack_cap);
+hipError_t launch_allhits_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint32_t max_hits,
+                              float4* hits, uint32_t* counts, hipStream_t st);
+
 hipError_t launch_dbg_hit_triangle(bool fma, uint32_t n, const float* rays, const float* tris, int eps_mode,
                                    int* hit, float* tuv, float* normal, float* point, hipStream_t st);
 bool trace_can_fuse(TracePath path, bool filter);   // launches with TraceParams::iters > 1 are available

@@ -1,5 +1,5 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
-// rt_tracer_focus_at, rt_tracer_occluded*).  Included by rt_tracer.hip.
+// rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_intersect_all*).  Included by rt_tracer.hip.
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
 // calls by api_mu, reads only the scene and a snapshot of the camera (params(), under state_mu), and runs on a stream of its
@@ -20,6 +20,18 @@ inline int query_k(const rt_tracer* t, size_t n) {
   if (t->k_req == 1 || t->k_req == 2 || t->k_req == 4) return static_cast<int>(t->k_req);
   constexpr size_t kResidentLanes = 256u * 4u * 256u;
   return n >= 4u * kResidentLanes ? 4 : n >= 2u * kResidentLanes ? 2 : 1;
+}
+
+inline bool intersect_all_args_ok(rt_tracer* t, const char* who, size_t n, const float* segs, uint32_t max_hits, const rt_hit* hits,
+                                  const uint32_t* counts) {
+  if (max_hits == 0u || max_hits > RT_MAX_HITS) {
+    t->set_error(fmt("%s: max_hits = %u (1 to %u)", who, max_hits, RT_MAX_HITS));
+    return false;
+  }
+  if (n == 0u) return true;
+  if (!segs || !hits || !counts) { t->set_error("query: null array"); return false; }
+  if (n > kQueryMaxRays) { t->set_error(fmt("query: %zu rays (at most %zu)", n, kQueryMaxRays)); return false; }
+  return true;
 }
 
 inline hipStream_t query_stream(rt_tracer* t) {
@@ -104,6 +116,25 @@ inline void enqueue_occluded(rt_tracer* t, size_t n, const float* segs, uint8_t*
     HIP_CHECK(rtk::launch_occluded_bvh(p, b, t->fma, static_cast<uint32_t>(n), segs, occluded, st));
   } else {
     HIP_CHECK(rtk::launch_occluded(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), segs, occluded, st));
+  }
+  HIP_CHECK(hipEventRecord(t->query_done, st));
+}
+
+// segments -> rows of max_hits records and one count per ray on `st`, with enqueue_query's event discipline.  The order rule
+// names no hit rule, so p.flags stays 0.
+inline void enqueue_intersect_all(rt_tracer* t, size_t n, const float* segs, uint32_t max_hits, float4* hits, uint32_t* counts,
+                                  hipStream_t st) {
+  rtk::TraceParams p = t->params(1);
+  p.flags = 0u;
+  const bool bvh = t->query_accel == RT_QUERY_BVH;
+  if (bvh) ensure_query_tree(t);
+  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
+  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
+  if (bvh) {
+    const rtk::BvhParams b = query_bvh_params(t);
+    HIP_CHECK(rtk::launch_allhits_bvh(p, b, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st));
+  } else {
+    HIP_CHECK(rtk::launch_allhits(p, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st));
   }
   HIP_CHECK(hipEventRecord(t->query_done, st));
 }
@@ -253,6 +284,52 @@ int rt_tracer_occluded_device(rt_tracer* t, const float* segs, size_t n, uint8_t
     if (n == 0u) return;
     t->use_device();
     enqueue_occluded(t, n, segs, occluded, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_intersect_all(rt_tracer* t, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts) {
+  if (!t) return RT_ERR_INVALID;
+  if (!intersect_all_args_ok(t, "rt_tracer_intersect_all", n, segs, max_hits, hits, counts)) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_intersect_all(t->mg->bands[0], segs, n, max_hits, hits, counts);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    const hipStream_t st = query_stream(t);
+    t->d_q_segs.ensure(n * 8u);
+    t->d_q_all_hits.ensure(n * max_hits);
+    t->d_q_all_counts.ensure(n);
+    HIP_CHECK(hipMemcpyAsync(t->d_q_segs.get(), segs, n * 8u * sizeof(float), hipMemcpyHostToDevice, st));
+    enqueue_intersect_all(t, n, t->d_q_segs.get(), max_hits, t->d_q_all_hits.get(), t->d_q_all_counts.get(), st);
+    HIP_CHECK(hipMemcpyAsync(hits, t->d_q_all_hits.get(), n * max_hits * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(counts, t->d_q_all_counts.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_intersect_all_device(rt_tracer* t, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts,
+                                   void* stream) {
+  if (!t) return RT_ERR_INVALID;
+  if (!intersect_all_args_ok(t, "rt_tracer_intersect_all_device", n, segs, max_hits, hits, counts)) return RT_ERR_INVALID;
+  if (n != 0u && (reinterpret_cast<uintptr_t>(segs) % 16u != 0u || reinterpret_cast<uintptr_t>(hits) % 16u != 0u ||
+                  reinterpret_cast<uintptr_t>(counts) % 4u != 0u)) {
+    t->set_error("rt_tracer_intersect_all_device: segs and hits must be 16-byte aligned, counts 4-byte aligned");
+    return RT_ERR_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_intersect_all_device(t->mg->bands[0], segs, n, max_hits, hits, counts, stream);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_intersect_all(t, n, segs, max_hits, reinterpret_cast<float4*>(hits), counts, static_cast<hipStream_t>(stream));
   });
 }
 

@@ -579,6 +579,8 @@ struct rt_tracer {
   rtr::DevArray<float4> d_q_hits;
   rtr::DevArray<float> d_q_segs;      // rt_tracer_occluded: n x 8 floats in, n bytes out
   rtr::DevArray<uint8_t> d_q_occluded;
+  rtr::DevArray<float4> d_q_all_hits; // rt_tracer_intersect_all: n x max_hits records and n counts out
+  rtr::DevArray<uint32_t> d_q_all_counts;
   rtr::Event query_done;
   void wait_queries() { if (query_done) HIP_CHECK(hipEventSynchronize(query_done)); }
   // RT_QUERY_BVH (rt_bvh_host.hpp, rt_bvh.hpp): the tree of the scene of generation bvh_scene, built by the first query in

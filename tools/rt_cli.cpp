@@ -27,8 +27,8 @@ struct Args {
   uint64_t seed = 0; bool have_seed = false;
   std::string scene = "demo3", scene_file, out = "image0.bmp";
   bool quiet = false, edges = false, smooth = false, nearest = false;
-  bool pick = false, focus = false, accel = false;
-  uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0};
+  bool pick = false, focus = false, accel = false, hits = false;
+  uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0}, hits_xy[2] = {0, 0}, hits_k = 8;
 };
 
 // "X,Y" -> two pixel coordinates
@@ -41,6 +41,18 @@ bool parse_xy(const char* s, uint32_t xy[2]) {
   if (end == s2 || *end != 0) return false;
   xy[0] = static_cast<uint32_t>(x); xy[1] = static_cast<uint32_t>(y);
   return true;
+}
+
+// "X,Y" or "X,Y,K"
+bool parse_xyk(const char* s, uint32_t xy[2], uint32_t& k) {
+  const std::string v = s;
+  const size_t c1 = v.find(','), c2 = c1 == std::string::npos ? c1 : v.find(',', c1 + 1);
+  if (c2 == std::string::npos) return parse_xy(s, xy);
+  char* end = nullptr;
+  const unsigned long kk = std::strtoul(v.c_str() + c2 + 1, &end, 10);
+  if (end == v.c_str() + c2 + 1 || *end != 0) return false;
+  k = static_cast<uint32_t>(kk);
+  return parse_xy(v.substr(0, c2).c_str(), xy);
 }
 
 std::vector<float4> demo3() {                   // MainFrame.cpp:230-232
@@ -68,8 +80,10 @@ void usage() {
             "       [--scene demo3|<file.f4>] [--seed N] [-o out.bmp] [-q]\n"
             "       [--edges] (file holds (v0,e0,e1) rows, packed vertex normals in .w)  [--smooth] [--nearest]\n"
             "       [--pick X,Y]  (prints `pick x y prim t u v` for the pixel's pinhole ray)\n"
+            "       [--hits X,Y[,K]] (prints one line `prim t u v` per hit of the pixel's pinhole ray, in order, over all t;\n"
+            "                      at most K, default 8)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
-            "       [--accel]     (--pick / --focus through the scene's BVH instead of the scan)");
+            "       [--accel]     (--pick / --hits / --focus through the scene's BVH instead of the scan)");
 }
 
 }  // namespace
@@ -111,6 +125,10 @@ int main(int argc, char** argv) {
       if (!parse_xy(next(k.c_str()), pk ? a.pick_xy : a.focus_xy)) { std::fprintf(stderr, "%s wants X,Y\n", k.c_str()); return 2; }
       (pk ? a.pick : a.focus) = true;
     }
+    else if (k == "--hits") {
+      if (!parse_xyk(next("--hits"), a.hits_xy, a.hits_k)) { std::fprintf(stderr, "--hits wants X,Y[,K]\n"); return 2; }
+      a.hits = true;
+    }
     else if (k == "-o") a.out = next("-o");
     else if (k == "-q") a.quiet = true;
     else if (k == "-v") a.quiet = false;
@@ -148,6 +166,23 @@ int main(int argc, char** argv) {
     }
     std::printf("pick %u %u %d %.9g %.9g %.9g\n", a.pick_xy[0], a.pick_xy[1], hit.prim, static_cast<double>(hit.t),
                 static_cast<double>(hit.u), static_cast<double>(hit.v));
+  }
+  if (a.hits) {
+    rt_hit first;
+    math::vec3 ray[2];
+    std::vector<rt_hit> hits;
+    std::vector<uint32_t> counts;
+    if (!tracer.Pick(math::uvec2(a.hits_xy[0], a.hits_xy[1]), first, ray)) {
+      std::fprintf(stderr, "rt_cli: --hits: %s\n", tracer.LastError().c_str());
+      return 1;
+    }
+    const std::vector<float> seg = {ray[0].x, ray[0].y, ray[0].z, ray[1].x, ray[1].y, ray[1].z, -INFINITY, INFINITY};
+    if (!tracer.IntersectAll(seg, a.hits_k, hits, counts)) {
+      std::fprintf(stderr, "rt_cli: --hits: %s\n", a.hits_k == 0 || a.hits_k > RT_MAX_HITS ? "K out of range" : tracer.LastError().c_str());
+      return 1;
+    }
+    for (uint32_t j = 0; j < counts[0]; ++j)
+      std::printf("%d %.9g %.9g %.9g\n", hits[j].prim, static_cast<double>(hits[j].t), static_cast<double>(hits[j].u), static_cast<double>(hits[j].v));
   }
   if (a.focus) {
     float focal = 0.0f;
