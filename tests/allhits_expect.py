@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from occluded_expect import conditioning_matrix
-from query_accel_expect import EMPTY, LEAF, RHO, WELL_CONDITIONED, leaf_span
+from query_accel_expect import EMPTY, LEAF, RHO, WELL_CONDITIONED, leaf_span, note_box_arithmetic
 from query_expect import HIT_DTYPE
 
 INF = np.float32(np.inf)
@@ -193,12 +193,16 @@ def check_bvh_all_hits(got, ref, E, W, max_hits, cap=None, label="", every=False
 
 # ---- the traversal, restated ---------------------------------------------------------------------------------------------
 
-def walk_tree_all_hits(orc, nodes, recs, info, segs, rows, max_hits, spheres=None, contract=None, rho=RHO):
+def walk_tree_all_hits(orc, nodes, recs, info, segs, rows, max_hits, spheres=None, contract=None, rho=RHO, tie_rule=True, strict=True,
+                       stats=None):
     """allhits_bvh_kernel in numpy: the tree with the fp32 box test of csrc/rt_allhits.hpp operation by operation -- a child is
     skipped when exit < enter, exit < tmin, enter > tmax or, once the list holds max_hits entries, enter > t_last, unless the
     ray has a non-finite component or a zero direction or the child's arithmetic holds a NaN; the nearest child is entered
     first; a popped entry whose enter fell strictly behind t_last is dropped -- then the always-tested list and the spheres,
-    with the oracle's HitTriangle on absolute rows.  Returns (hits, counts, triangle tests made)."""
+    with the oracle's HitTriangle on absolute rows.  Returns (hits, counts, triangle tests made).
+    Switches that break one rule each, for tests of the tests: tie_rule=False keeps equal t in the order of arrival; strict=False
+    also skips a child whose exit EQUALS tmin or whose enter EQUALS tmax or t_last, and drops a popped entry whose enter EQUALS
+    t_last.  stats: a dict that receives note_box_arithmetic's counters."""
     contract = orc.FMA if contract is None else contract
     L = orc.lib()
     fp = C.POINTER(C.c_float)
@@ -228,7 +232,7 @@ def walk_tree_all_hits(orc, nodes, recs, info, segs, rows, max_hits, spheres=Non
                 if not (bool(tmin <= tj) and bool(tj <= tmax)):
                     return
                 k = len(lst)
-                while k > 0 and (tj < lst[k - 1][0] or (tj == lst[k - 1][0] and prim < lst[k - 1][1])):
+                while k > 0 and (tj < lst[k - 1][0] or (tie_rule and tj == lst[k - 1][0] and prim < lst[k - 1][1])):
                     k -= 1
                 lst.insert(k, (tj, prim, uj, vj))
                 del lst[max_hits:]
@@ -244,13 +248,14 @@ def walk_tree_all_hits(orc, nodes, recs, info, segs, rows, max_hits, spheres=Non
             inv = f32(1.0) / d
             omax = np.abs(o).max()
             stack = []
+            seen = {}
             cur = 0 if (nodes.shape[0] and active) else EMPTY
             while True:
                 if cur == EMPTY:
                     if not stack:
                         break
                     g, cur = stack.pop()
-                    if g < -t_last():
+                    if (g < -t_last()) if strict else (g <= -t_last()):
                         cur = EMPTY
                         continue
                 if cur & LEAF:
@@ -269,6 +274,9 @@ def walk_tree_all_hits(orc, nodes, recs, info, segs, rows, max_hits, spheres=Non
                 enter = np.fmax.reduce(np.fmin(t1, t2), axis=0)
                 exit_ = np.fmin.reduce(np.fmax(t1, t2), axis=0)
                 skip = (exit_ < enter) | (exit_ < tmin) | (enter > tmax) | (enter > t_last())
+                if not strict:
+                    skip |= (exit_ == tmin) | (enter == tmax) | (enter == t_last())
+                note_box_arithmetic(stats, seen, t1, t2, nd["child"] != EMPTY)
                 decided = prunes & ~nan
                 kids = []
                 for c in range(4):

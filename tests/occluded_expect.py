@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from query_accel_expect import EMPTY, LEAF, RHO, WELL_CONDITIONED, leaf_span, records_of_rows
+from query_accel_expect import EMPTY, LEAF, RHO, WELL_CONDITIONED, leaf_span, note_box_arithmetic, records_of_rows
 
 INF = np.float32(np.inf)
 
@@ -131,12 +131,13 @@ def with_interval(rays, tmin, tmax):
 
 # ---- the any-hit traversal, restated -------------------------------------------------------------------------------------
 
-def walk_tree_occluded(orc, nodes, recs, info, segs, rows, spheres=None, contract=None, rho=RHO):
+def walk_tree_occluded(orc, nodes, recs, info, segs, rows, spheres=None, contract=None, rho=RHO, strict=True, stats=None):
     """occluded_bvh_kernel in numpy: spheres, the always-tested list, then the tree with the fp32 box test of
     csrc/rt_occluded.hpp operation by operation -- a child is skipped when exit < enter, exit < tmin or enter > tmax, unless
     the ray has a non-finite component or a zero direction or the child's arithmetic holds a NaN -- and the oracle's
     HitTriangle on the leaves' triangles (absolute rows).  The order of the visits does not change an OR, so the children are
-    entered as stored.  Returns ((n,) bool, triangle tests made)."""
+    entered as stored.  Returns ((n,) bool, triangle tests made).  strict=False (for tests of the tests) also skips a child whose
+    exit EQUALS tmin or whose enter EQUALS tmax; stats: a dict that receives note_box_arithmetic's counters."""
     contract = orc.FMA if contract is None else contract
     L = orc.lib()
     fp = C.POINTER(C.c_float)
@@ -174,6 +175,7 @@ def walk_tree_occluded(orc, nodes, recs, info, segs, rows, spheres=None, contrac
             inv = f32(1.0) / d
             omax = np.abs(o).max()
             stack = [0] if nodes.shape[0] else []
+            seen = {}
             while stack and not done:
                 cur = stack.pop()
                 if cur & LEAF:
@@ -193,6 +195,9 @@ def walk_tree_occluded(orc, nodes, recs, info, segs, rows, spheres=None, contrac
                 enter = np.fmax.reduce(np.fmin(t1, t2), axis=0)
                 exit_ = np.fmin.reduce(np.fmax(t1, t2), axis=0)
                 skip = (exit_ < enter) | (exit_ < tmin) | (enter > tmax)
+                if not strict:
+                    skip |= (exit_ == tmin) | (enter == tmax)
+                note_box_arithmetic(stats, seen, t1, t2, nd["child"] != EMPTY)
                 decided = prunes & ~nan
                 for c in range(4):
                     ref = int(nd["child"][c])

@@ -132,9 +132,26 @@ def check_tree(nodes, recs, info, rows, edges=False):
 
 # ---- the traversal's box test, restated -----------------------------------------------------------------------------------
 
-def walk_tree(orc, nodes, recs, info, rays, rows, contract=None, nearest=False, rho=RHO):
+def note_box_arithmetic(stats, seen, t1, t2, present):
+    """Into the dict `stats` of a walk (if given): which branches of the box test this node's present children reach.  seen is
+    the ray's own {"nan": bool, "inf": bool}; stats counts rays ("nan_rays", "inf_rays") and child boxes ("nan_boxes",
+    "inf_boxes") whose t1, t2 hold a NaN (0 * inf: the ray runs inside a slab's plane) or an infinity (parallel, outside)."""
+    if stats is None or (np.isfinite(t1).all() and np.isfinite(t2).all()):
+        return
+    for key, bad in (("nan", np.isnan(t1) | np.isnan(t2)), ("inf", np.isinf(t1) | np.isinf(t2))):
+        boxes = int((bad.any(axis=0) & present).sum())
+        stats[key + "_boxes"] = stats.get(key + "_boxes", 0) + boxes
+        if boxes and not seen.get(key):
+            seen[key] = True
+            stats[key + "_rays"] = stats.get(key + "_rays", 0) + 1
+
+
+def walk_tree(orc, nodes, recs, info, rays, rows, contract=None, nearest=False, rho=RHO, tie_rule=True, strict=True, stats=None):
     """query_bvh_kernel in numpy: the fp32 box test of csrc/rt_bvh.hpp operation by operation, the order-free hit rule, the
-    oracle's HitTriangle on the leaves' triangles (absolute rows).  Returns (HIT_DTYPE array, triangle tests made)."""
+    oracle's HitTriangle on the leaves' triangles (absolute rows).  Returns (HIT_DTYPE array, triangle tests made).
+    Switches that break one rule each, for tests of the tests: tie_rule=False drops "equal t: the lower upload index wins" (the
+    first visited keeps a tie); strict=False prunes and drops a child whose goodness EQUALS the best t.  stats: a dict that
+    receives note_box_arithmetic's counters."""
     contract = orc.FMA if contract is None else contract
     L = orc.lib()
     fp = C.POINTER(C.c_float)
@@ -163,17 +180,19 @@ def walk_tree(orc, nodes, recs, info, rays, rows, contract=None, nearest=False, 
                     return
                 tj = f32(t.value)
                 better = (tj > 0 and tj < state["t"]) if nearest else (state["t"] < tj)
-                if better or (tj == state["t"] and j < state["i"]):
+                if better or (tie_rule and tj == state["t"] and j < state["i"]):
                     state.update(t=tj, i=int(j), u=f32(u.value), v=f32(v.value))
 
             stack = []
+            seen = {}
             cur = 0 if nodes.shape[0] else EMPTY
             while True:
                 if cur == EMPTY:
                     if not stack:
                         break
                     g, cur = stack.pop()
-                    if g < (-state["t"] if nearest else state["t"]):
+                    lim = -state["t"] if nearest else state["t"]
+                    if (g < lim) if strict else (g <= lim):
                         cur = EMPTY
                         continue
                 if cur & LEAF:
@@ -193,7 +212,8 @@ def walk_tree(orc, nodes, recs, info, rays, rows, contract=None, nearest=False, 
                 exit_ = np.fmin.reduce(np.fmax(t1, t2), axis=0)
                 good = -enter if nearest else exit_
                 lim = -state["t"] if nearest else state["t"]
-                skip = (exit_ < enter) | (good < lim) | (nearest & (exit_ <= 0))
+                skip = (exit_ < enter) | ((good < lim) if strict else (good <= lim)) | (nearest & (exit_ <= 0))
+                note_box_arithmetic(stats, seen, t1, t2, nd["child"] != EMPTY)
                 decided = finite & ~nan
                 kids = []
                 for c in range(4):
