@@ -6,6 +6,7 @@
 // 307-314); LastError() tells what went wrong.  Methods below the marker are additive.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -149,6 +150,20 @@ public:
     uint64_t o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (mImpl) (void)rt_tracer_query_accel_info(mImpl, o);
     return QueryAccel{o[0] == RT_QUERY_BVH, o[1] != 0, o[2], o[3], o[4], o[5], o[6], o[7]};
+  }
+  // What an upload does to that tree (rt_tracer_set_query_accel_update): false = the next query builds a new one on the host
+  // (default); true = an upload of the same number of triangles keeps the topology and the next query refits the boxes on the
+  // device.  Same contracts either way; QueryAccelUpdateInfo().cost against costBuilt tells how far the tree has degraded.
+  bool SetQueryAccelUpdate(bool refit) { return mImpl && rt_tracer_set_query_accel_update(mImpl, refit ? RT_ACCEL_REFIT : RT_ACCEL_REBUILD) == RT_OK; }
+  bool RebuildQueryAccel() { return mImpl && rt_tracer_query_accel_rebuild(mImpl) == RT_OK; }
+  struct QueryAccelUpdate { bool refit; uint64_t refits, fallbacks, refitMicroseconds; double cost, costBuilt; };
+  QueryAccelUpdate QueryAccelUpdateInfo() const {
+    uint64_t o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (mImpl) (void)rt_tracer_query_accel_update_info(mImpl, o);
+    QueryAccelUpdate u{o[0] == RT_ACCEL_REFIT, o[1], o[2], o[3], 0.0, 0.0};
+    std::memcpy(&u.cost, &o[4], sizeof(double));
+    std::memcpy(&u.costBuilt, &o[5], sizeof(double));
+    return u;
   }
   std::string LastError() const { return mImpl ? rt_tracer_last_error(mImpl) : rt_last_error(); }
   rt_tracer* Handle() const { return mImpl; }

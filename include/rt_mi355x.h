@@ -286,6 +286,32 @@ int  rt_tracer_set_query_accel(rt_tracer* t, uint32_t mode);
  * time in us, device bytes of the tree}; the last six are 0 while no valid tree exists. */
 int  rt_tracer_query_accel_info(rt_tracer* t, uint64_t out[8]);
 
+/* What an upload does to the tree of RT_QUERY_BVH.  RT_ACCEL_REBUILD (default) is the behaviour described above.  Under
+ * RT_ACCEL_REFIT the next RT_QUERY_BVH query REFITS instead of building when a tree has been built (for any earlier upload),
+ * its record count equals the scene's triangle count, and rt_tracer_query_accel_rebuild has not been called since: the tree keeps
+ * its topology, every record slot takes the 36 bytes of the triangle with its upload index, and every box is recomputed on the
+ * device from the leaves up -- about ten small launches instead of a read-back, a host build and an upload.  The upload layout may
+ * differ between the two uploads (only the records matter); several uploads without a query in between are fine (the refit reads
+ * the current records only).  The first tree, a changed triangle count and an explicit rebuild build as before; UploadSpheres
+ * touches nothing.
+ * Contract: a refitted tree is a valid bounding tree of the new records, so every RT_QUERY_BVH contract above and below holds word
+ * for word, rho and rt_dbg_query_accel_slack included.  Only speed depends on how far the geometry moved: the tree's COST -- the sum
+ * over all nodes and their present children of half_area(child box), in double, divided by the half area of the union of the
+ * root's child boxes; 0 without nodes or when that union has no area -- is reported so that a caller can notice the degradation
+ * and call rt_tracer_query_accel_rebuild.  Nothing rebuilds by itself.
+ * Partition rule: a refit never moves a triangle between the leaves and the always-tested list.  A triangle is FINITE when its
+ * nine record floats and its outward-rounded box are finite.  If a leaf's triangle became non-finite or an always-tested one
+ * finite, the refit is abandoned and the tree is built on the host instead; out[2] counts these.
+ * A multi-device handle forwards all three calls to its first band. */
+#define RT_ACCEL_REBUILD 0u   /* default: an upload invalidates the tree, the next RT_QUERY_BVH query rebuilds it on the host */
+#define RT_ACCEL_REFIT   1u   /* an upload of the same number of triangles keeps the tree's topology; the next query refits its boxes on the device */
+int  rt_tracer_set_query_accel_update(rt_tracer* t, uint32_t policy);   /* other values: RT_ERR_INVALID */
+/* Drops the tree now: the next RT_QUERY_BVH query builds afresh, whatever the policy. */
+int  rt_tracer_query_accel_rebuild(rt_tracer* t);
+/* out = {policy, refits since the last build, refits that fell back to a build (over the tracer's life), device time of the last
+ * refit in us, tree cost now, tree cost at the last build (both doubles, bit-cast; 0 while no valid tree exists), 0, 0} */
+int  rt_tracer_query_accel_update_info(rt_tracer* t, uint64_t out[8]);
+
 /* Visibility (shadow rays, line of sight, ambient occlusion): is ray i blocked within its own t interval?
  *   segs      n x 8 floats: origin xyz, direction xyz (used as given, nothing normalised), tmin, tmax.
  *   occluded  occluded[i] = 1 when some primitive of the tracer's scene is hit by ray i with tmin <= t <= tmax, else 0.
@@ -467,6 +493,19 @@ int rt_dbg_classify(rt_tracer* t, uint32_t level, uint32_t forms, uint32_t slack
  *                      are in no box and which every ray tests. */
 int rt_dbg_bvh_build(const rt_float4* rows, size_t count, int edges_layout, void* nodes, size_t node_capacity_bytes,
                      void* leaf_records, size_t leaf_capacity_bytes, uint64_t info[8]);
+/* rtb::refit on its own, the reference of the device refit; needs no device.  nodes (node_bytes = nodes * 128), leaf_records
+ * (record_bytes = count / 3 * 48) and info are arrays rt_dbg_bvh_build (or this call) wrote for a scene of as many triangles; rows
+ * are the new scene.  In place: the records take the new triangles by upload index, every box and cmax is recomputed, child[] and
+ * info stay.  RT_ERR_STATE when the partition rule fails (nothing is written); RT_ERR_INVALID for arrays that are no such tree. */
+int rt_dbg_bvh_refit(const rt_float4* rows, size_t count, int edges_layout, void* nodes, size_t node_bytes, void* leaf_records,
+                     size_t record_bytes, uint64_t info[8]);
+/* rtb::tree_cost of a node array in rt_dbg_bvh_build's layout: the cost rt_tracer_query_accel_update_info reports, computed on
+ * the host.  0 for no nodes (or a NULL array). */
+double rt_dbg_bvh_tree_cost(const void* nodes, size_t node_bytes);
+/* The tracer's current device tree as the queries walk it, in rt_dbg_bvh_build's layouts and with its info.  With both
+ * capacities 0 only info is written.  RT_ERR_STATE while no valid tree exists. */
+int rt_dbg_query_tree_read(rt_tracer* t, void* nodes, size_t node_capacity_bytes, void* records, size_t record_capacity_bytes,
+                           uint64_t info[8]);
 /* Multiplies the box test's inflation rho for this tracer's following queries in RT_QUERY_BVH mode (1000 = the product; 300,
  * 100, 30, 10, 0 exist so that the margin can be measured in the shipped library, tools/bvh_margin.py). */
 int rt_dbg_query_accel_slack(rt_tracer* t, uint32_t slack_milli);

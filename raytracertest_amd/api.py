@@ -52,6 +52,8 @@ ABI_SYMBOLS = [
     "rt_tracer_occluded", "rt_tracer_occluded_device",
     "rt_tracer_intersect_all", "rt_tracer_intersect_all_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
+    "rt_tracer_set_query_accel_update", "rt_tracer_query_accel_rebuild", "rt_tracer_query_accel_update_info",
+    "rt_dbg_bvh_refit", "rt_dbg_query_tree_read", "rt_dbg_bvh_tree_cost",
 ]
 
 
@@ -62,6 +64,7 @@ class RtError(RuntimeError):
 PRIM_NONE = -1
 RT_MAX_HITS = 16         # rt_tracer_intersect_all: the longest row
 QUERY_SCAN, QUERY_BVH = 0, 1
+ACCEL_REBUILD, ACCEL_REFIT = 0, 1        # rt_tracer_set_query_accel_update: what an upload does to the tree of QUERY_BVH
 # the arrays of rt_dbg_bvh_build (include/rt_mi355x.h): a 4-wide node and a leaf record
 BVH_NODE_DTYPE = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("child", np.uint32, 4), ("cmax", np.float32, 4)])
 BVH_RECORD_DTYPE = np.dtype([("e2", np.float32, 3), ("e1", np.float32, 3), ("v0", np.float32, 3), ("index", np.uint32), ("pad", np.uint32, 2)])
@@ -82,9 +85,36 @@ def bvh_build(rows, edges=False):
     if L.rt_dbg_bvh_build(r.ctypes.data, r.shape[0], int(bool(edges)), nodes.ctypes.data, max(nodes.nbytes, 1), recs.ctypes.data,
                           max(recs.nbytes, 1), info) != 0:
         raise RtError("rt_dbg_bvh_build: " + L.rt_last_error().decode())
+    return nodes, recs, _tree_info(info)
+
+
+def _tree_info(info):
     d = dict(zip(_ACCEL_KEYS, (int(x) for x in info)))
     d["depth_bound"] = d.pop("mode")
-    return nodes, recs, d
+    return d
+
+
+def bvh_refit(rows, nodes, recs, info, edges=False):
+    """rt_dbg_bvh_refit: the tree (nodes, recs, info) of bvh_build -- or of an earlier refit -- refitted on the host to the
+    upload rows (3N, 4) of as many triangles -> (nodes, records, info) as new arrays.  RtError when a triangle changed between
+    finite and non-finite (the partition rule: such a scene has to be built)."""
+    L = load_library()
+    r = np.ascontiguousarray(rows, np.float32).reshape(-1, 4)
+    nodes = np.ascontiguousarray(nodes, BVH_NODE_DTYPE).copy()
+    recs = np.ascontiguousarray(recs, BVH_RECORD_DTYPE).copy()
+    raw = (C.c_uint64 * 8)(info["depth_bound"], 1, *(int(info[k]) for k in _ACCEL_KEYS[2:]))
+    rc = L.rt_dbg_bvh_refit(r.ctypes.data, r.shape[0], int(bool(edges)), nodes.ctypes.data, nodes.nbytes, recs.ctypes.data, recs.nbytes, raw)
+    if rc != 0:
+        raise RtError("rt_dbg_bvh_refit: %s (code %d)" % (L.rt_last_error().decode(), rc))
+    return nodes, recs, dict(info)
+
+
+def tree_cost(nodes):
+    """rt_dbg_bvh_tree_cost (rtb::tree_cost on the host): the half areas of all present children's boxes over the half area of
+    the union of the root's child boxes, in double; 0 without nodes or without such an area."""
+    L = load_library()
+    nodes = np.ascontiguousarray(nodes, BVH_NODE_DTYPE)
+    return float(L.rt_dbg_bvh_tree_cost(nodes.ctypes.data, nodes.nbytes)) if nodes.shape[0] else 0.0
 # rt_hit: one ray query's answer (include/rt_mi355x.h)
 HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("prim", np.int32)])
 
@@ -244,6 +274,13 @@ def load_library():
         L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_dbg_query_accel_slack.argtypes = [vp, C.c_uint32]
         L.rt_dbg_bvh_build.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint64)]
+        L.rt_tracer_set_query_accel_update.argtypes = [vp, C.c_uint32]
+        L.rt_tracer_query_accel_rebuild.argtypes = [vp]
+        L.rt_tracer_query_accel_update_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_dbg_bvh_refit.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint64)]
+        L.rt_dbg_query_tree_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint64)]
+        L.rt_dbg_bvh_tree_cost.argtypes = [vp, C.c_size_t]
+        L.rt_dbg_bvh_tree_cost.restype = C.c_double
         _lib = L
         return _lib
 
@@ -720,6 +757,35 @@ class RayTracer:
         out = (C.c_uint64 * 8)()
         self._check(self._lib.rt_tracer_query_accel_info(self._h, out))
         return dict(zip(_ACCEL_KEYS, (int(x) for x in out)))
+
+    def SetQueryAccelUpdate(self, policy):
+        """What an upload does to the tree of QUERY_BVH: ACCEL_REBUILD (0, the default: the next query builds a new one on the
+        host) or ACCEL_REFIT (1: an upload of the same number of triangles keeps the tree's topology and the next query refits
+        its boxes on the device).  The answers obey the same contracts either way."""
+        self._check(self._lib.rt_tracer_set_query_accel_update(self._h, int(policy)))
+
+    def RebuildQueryAccel(self):
+        """Drops the tree: the next QUERY_BVH query builds afresh, whatever the policy."""
+        self._check(self._lib.rt_tracer_query_accel_rebuild(self._h))
+
+    def QueryAccelUpdateInfo(self):
+        """rt_tracer_query_accel_update_info as a dict: policy, refits (since the last build), fallbacks (refits that became
+        builds), refit_us (device time of the last refit), cost and cost_built (floats: the tree's cost now and at its build)."""
+        out = (C.c_uint64 * 8)()
+        self._check(self._lib.rt_tracer_query_accel_update_info(self._h, out))
+        cost = np.array([out[4], out[5]], np.uint64).view(np.float64)
+        return {"policy": int(out[0]), "refits": int(out[1]), "fallbacks": int(out[2]), "refit_us": int(out[3]),
+                "cost": float(cost[0]), "cost_built": float(cost[1])}
+
+    def query_tree(self):
+        """rt_dbg_query_tree_read: the device tree the queries walk now -> (nodes, records, info) as bvh_build returns them."""
+        info = (C.c_uint64 * 8)()
+        self._check(self._lib.rt_dbg_query_tree_read(self._h, None, 0, None, 0, info))
+        nodes = np.zeros(int(info[2]), BVH_NODE_DTYPE)
+        recs = np.zeros((int(info[7]) - nodes.nbytes) // BVH_RECORD_DTYPE.itemsize, BVH_RECORD_DTYPE)
+        self._check(self._lib.rt_dbg_query_tree_read(self._h, nodes.ctypes.data, max(nodes.nbytes, 1), recs.ctypes.data,
+                                                     max(recs.nbytes, 1), info))
+        return nodes, recs, _tree_info(info)
 
     def DebugQueryAccelSlack(self, slack_milli):
         self._check(self._lib.rt_dbg_query_accel_slack(self._h, int(slack_milli)))

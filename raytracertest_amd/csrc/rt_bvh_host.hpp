@@ -16,6 +16,9 @@
 //     child: kBvhEmpty, or an inner node's index (< 2^31), or kBvhLeaf | (count - 1) << 28 | first record (count 1..4);
 //     cmax: the largest |coordinate| of the child's box (the box test's scale); an empty child has lo = +inf, hi = -inf.
 //   record, 48 bytes: float e2[3], e1[3], v0[3]; uint32 upload index; 2 x uint32 zero
+//
+// Refit: a re-uploaded scene of the same size keeps the tree's topology; refit() copies the new records
+// into their slots and recomputes every box bottom-up.  It is the reference of the kernels of rt_refit.hpp.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -50,6 +53,9 @@ struct Tree {
   std::vector<Record> records;      // the leaves' records, then the always-tested list (ascending upload index)
   uint32_t leaves = 0, depth = 0, always = 0;
   uint64_t build_us = 0;
+  // the node indices grouped by level (root first): level l (0-based) is level_nodes[level_begin[l] .. level_begin[l + 1]),
+  // depth levels in all (at most kBvhMaxDepth) -- a refit walks them deepest first
+  std::vector<uint32_t> level_nodes, level_begin;
   size_t bytes() const { return nodes.size() * sizeof(Node) + records.size() * sizeof(Record); }
 };
 
@@ -69,6 +75,22 @@ struct Box {
 };
 inline float round_down(double x) { float f = static_cast<float>(x); if (double(f) > x) f = std::nextafter(f, -INFINITY); return f; }
 inline float round_up(double x) { float f = static_cast<float>(x); if (double(f) < x) f = std::nextafter(f, INFINITY); return f; }
+
+// A triangle's box from its record r (e2 xyz, e1 xyz, v0 xyz): the corners v0, v0 + e1, v0 + e2 in double, rounded outward;
+// centre[a] = the box's middle before rounding.  False -- the triangle belongs to the always-tested list -- when a float of
+// the record or of the rounded box is not finite (box and centre are then incomplete).
+inline bool tri_box(const float* r, Box& box, double* centre) {
+  bool finite = true;
+  for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(r[k]);
+  for (int a = 0; a < 3 && finite; ++a) {
+    const double v0 = r[6 + a], c1 = v0 + double(r[3 + a]), c2 = v0 + double(r[a]);
+    const double lo = std::min(v0, std::min(c1, c2)), hi = std::max(v0, std::max(c1, c2));
+    box.lo[a] = round_down(lo); box.hi[a] = round_up(hi);
+    if (centre) centre[a] = 0.5 * (lo + hi);
+    finite = std::isfinite(box.lo[a]) && std::isfinite(box.hi[a]);
+  }
+  return finite;
+}
 
 struct Prim { Box box; double c[3]; uint32_t index; };
 struct BinNode { Box box; uint32_t left, right, first, count; };   // leaf: left == kBvhEmpty
@@ -157,19 +179,9 @@ inline Tree build(const float* rec, size_t n_tris) {
   std::vector<uint32_t> always;
   prims.reserve(n_tris);
   for (size_t i = 0; i < n_tris; ++i) {
-    const float* r = rec + 9u * i;
-    bool finite = true;
-    for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(r[k]);
     Prim p;
     p.index = static_cast<uint32_t>(i);
-    for (int a = 0; a < 3 && finite; ++a) {
-      const double v0 = r[6 + a], c1 = v0 + double(r[3 + a]), c2 = v0 + double(r[a]);
-      const double lo = std::min(v0, std::min(c1, c2)), hi = std::max(v0, std::max(c1, c2));
-      p.box.lo[a] = round_down(lo); p.box.hi[a] = round_up(hi);
-      p.c[a] = 0.5 * (lo + hi);
-      finite = std::isfinite(p.box.lo[a]) && std::isfinite(p.box.hi[a]);
-    }
-    if (finite) prims.push_back(p); else always.push_back(p.index);
+    if (tri_box(rec + 9u * i, p.box, p.c)) prims.push_back(p); else always.push_back(p.index);
   }
   Builder b{prims, {}};
   if (!prims.empty()) (void)b.build(0, prims.size(), 0u);
@@ -190,11 +202,14 @@ inline Tree build(const float* rec, size_t n_tris) {
     auto ref_of_leaf = [&](const BinNode& n) { tree.leaves++; return kBvhLeaf | (n.count - 1u) << 28 | n.first; };
     struct Todo { uint32_t bin, node, level; };
     std::vector<Todo> todo;
+    std::vector<uint32_t> level_of;                                  // per node, 0-based
     tree.nodes.push_back({});
     todo.push_back({0u, 0u, 1u});
     while (!todo.empty()) {
       const Todo t = todo.back(); todo.pop_back();
       tree.depth = std::max(tree.depth, t.level);
+      if (level_of.size() < tree.nodes.size()) level_of.resize(tree.nodes.size());
+      level_of[t.node] = t.level - 1u;
       uint32_t kids[4]; int nk = 0;
       const BinNode& root = b.bin[t.bin];
       if (root.left == kBvhEmpty) kids[nk++] = t.bin;              // a scene of at most 4 triangles: one leaf under the root
@@ -224,6 +239,12 @@ inline Tree build(const float* rec, size_t n_tris) {
       for (int i = ni - 1; i >= 0; --i) todo.push_back({kids[inner[i]], nd.child[inner[i]], t.level + 1u});
       tree.nodes[t.node] = nd;
     }
+    tree.level_begin.assign(tree.depth + 1u, 0u);                    // a counting sort of the nodes by level
+    for (uint32_t l : level_of) tree.level_begin[l + 1u]++;
+    for (uint32_t l = 0; l < tree.depth; ++l) tree.level_begin[l + 1u] += tree.level_begin[l];
+    tree.level_nodes.resize(tree.nodes.size());
+    std::vector<uint32_t> at(tree.level_begin.begin(), tree.level_begin.end() - 1);
+    for (uint32_t i = 0; i < level_of.size(); ++i) tree.level_nodes[at[level_of[i]]++] = i;
   }
   tree.build_us = static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
   return tree;
@@ -251,6 +272,67 @@ inline std::vector<float> records_of_device(const float* tri_a, const float* tri
     rec[9u * i + 8u] = tri_b[i];
   }
   return rec;
+}
+
+// A child's box as a node holds it
+inline detail::Box child_box(const Node& nd, int k) {
+  detail::Box b;
+  for (int a = 0; a < 3; ++a) { b.lo[a] = nd.lo[a][k]; b.hi[a] = nd.hi[a][k]; }
+  return b;
+}
+
+// The tree's cost: the half areas of all present children's boxes, summed in double, over the half area of
+// the union of the root's child boxes.  0 without nodes, and 0 when that union has no area (a scene on one line).
+inline double tree_cost(const Node* nodes, size_t n_nodes) {
+  if (n_nodes == 0u) return 0.0;
+  double sum = 0.0;
+  for (size_t i = 0; i < n_nodes; ++i)
+    for (int k = 0; k < 4; ++k)
+      if (nodes[i].child[k] != kBvhEmpty) sum += child_box(nodes[i], k).half_area();
+  detail::Box root; root.clear();
+  for (int k = 0; k < 4; ++k) root.grow(child_box(nodes[0], k));
+  const double area = root.half_area();
+  return area > 0.0 ? sum / area : 0.0;
+}
+inline double tree_cost(const std::vector<Node>& nodes) { return tree_cost(nodes.data(), nodes.size()); }
+
+// Refit: the tree keeps its topology and takes the records of `rec` (9 floats per triangle, by upload index; as many
+// triangles as the tree has records).  Every slot's 36 bytes are rewritten; a leaf child's box becomes the union of its
+// triangles' boxes, each computed as build() computes it; an inner child's box the union of the referenced node's four child
+// boxes; cmax follows.  Children come behind their parents in the node array, so one pass from the back sees every node after
+// its children.  Partition rule: a slot of the leaves must hold a finite triangle (detail::tri_box) and a slot of the
+// always-tested list a non-finite one; otherwise nothing is written and the result is false -- the tree has to be built.
+// The arrays must be a tree of build(): every reference in range (rt_dbg_bvh_refit checks that for its caller's arrays).
+inline bool refit(Node* nodes, size_t n_nodes, Record* records, size_t n_leaf_records, size_t n_always, const float* rec) {
+  using namespace detail;
+  Box box;
+  for (size_t s = 0; s < n_leaf_records + n_always; ++s)
+    if (tri_box(rec + 9u * size_t(records[s].index), box, nullptr) != (s < n_leaf_records)) return false;
+  for (size_t s = 0; s < n_leaf_records + n_always; ++s) memcpy(records[s].e2, rec + 9u * size_t(records[s].index), 9u * sizeof(float));
+  for (size_t i = n_nodes; i-- > 0u;) {
+    Node& nd = nodes[i];
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t ref = nd.child[k];
+      if (ref == kBvhEmpty) continue;
+      Box b; b.clear();
+      if (ref & kBvhLeaf) {
+        const uint32_t first = ref & 0x0FFFFFFFu, count = ((ref >> 28) & 3u) + 1u;
+        for (uint32_t j = first; j < first + count; ++j) { (void)tri_box(records[j].e2, box, nullptr); b.grow(box); }
+      } else {
+        for (int c = 0; c < 4; ++c) b.grow(child_box(nodes[ref], c));
+      }
+      float m = 0.0f;
+      for (int a = 0; a < 3; ++a) {
+        nd.lo[a][k] = b.lo[a]; nd.hi[a][k] = b.hi[a];
+        m = std::max(m, std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a])));
+      }
+      nd.cmax[k] = m;
+    }
+  }
+  return true;
+}
+inline bool refit(std::vector<Node>& nodes, std::vector<Record>& records, size_t n_leaf_records, size_t n_always, const float* rec) {
+  return refit(nodes.data(), nodes.size(), records.data(), n_leaf_records, n_always, rec);
 }
 
 }  // namespace rtb

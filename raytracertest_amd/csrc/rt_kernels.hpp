@@ -172,6 +172,14 @@ uint32_t allhits_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_allhits_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint32_t max_hits,
                               float4* hits, uint32_t* counts, hipStream_t st);
 
+// Refit of that tree on the device (rt_refit.hpp): the records of the current scene into their slots (flag: set to 1 when a
+// slot's triangle changed between finite and non-finite), the boxes of one level's nodes (deepest level first), the tree's cost.
+hipError_t launch_refit_gather(const float4* tri_a, const float* tri_b, uint32_t n_tris, float4* records, uint32_t n_leaf_records,
+                               uint32_t n_records, uint32_t* flag, hipStream_t st);
+hipError_t launch_refit_level(float4* nodes, uint32_t n_nodes, const float4* records, uint32_t n_leaf_records, const uint32_t* level_nodes,
+                              uint32_t count, hipStream_t st);
+hipError_t launch_refit_cost(const float4* nodes, uint32_t n_nodes, double* out, hipStream_t st);
+
 hipError_t launch_dbg_hit_triangle(bool fma, uint32_t n, const float* rays, const float* tris, int eps_mode,
                                    int* hit, float* tuv, float* normal, float* point, hipStream_t st);
 bool trace_can_fuse(TracePath path, bool filter);   // launches with TraceParams::iters > 1 are available

@@ -43,16 +43,51 @@ inline hipStream_t query_stream(rt_tracer* t) {
   return t->stream_q;
 }
 
+// RT_ACCEL_REFIT: the tree of an earlier upload with as many records as the scene has triangles takes the new records and
+// new boxes on the device (rt_refit.hpp), all on the query stream: the gather, one launch per level from the deepest up,
+// the cost, between two events; one 16-byte copy of {flag, cost} and the synchronisation the build has too.  False: a
+// triangle changed between finite and non-finite (the partition rule, rt_bvh_host.hpp) -- the caller builds.
+inline bool refit_query_tree(rt_tracer* t, hipStream_t st) {
+  const uint32_t n_nodes = static_cast<uint32_t>(t->bvh_info[0]), n_always = static_cast<uint32_t>(t->bvh_info[3]);
+  const uint32_t n_leaf = t->bvh_leaf_records, depth = static_cast<uint32_t>(t->bvh_info[2]);
+  t->d_refit_out.ensure(2u);
+  t->h_refit_out.ensure(2u);
+  if (!t->refit_begin) { t->refit_begin = Event::timing(); t->refit_end = Event::timing(); }
+  HIP_CHECK(hipMemsetAsync(t->d_refit_out.get(), 0, 2u * sizeof(uint64_t), st));
+  HIP_CHECK(hipEventRecord(t->refit_begin, st));
+  HIP_CHECK(rtk::launch_refit_gather(t->d_tri.get(), t->d_tri_b.get(), t->n_tris, t->d_bvh_records.get(), n_leaf, n_leaf + n_always,
+                                     reinterpret_cast<uint32_t*>(t->d_refit_out.get()), st));
+  for (uint32_t l = depth; l-- > 0u;)
+    HIP_CHECK(rtk::launch_refit_level(t->d_bvh_nodes.get(), n_nodes, t->d_bvh_records.get(), n_leaf, t->d_bvh_levels.get() + t->bvh_level_begin[l],
+                                      t->bvh_level_begin[l + 1u] - t->bvh_level_begin[l], st));
+  HIP_CHECK(rtk::launch_refit_cost(t->d_bvh_nodes.get(), n_nodes, reinterpret_cast<double*>(t->d_refit_out.get() + 1), st));
+  HIP_CHECK(hipEventRecord(t->refit_end, st));
+  HIP_CHECK(hipMemcpyAsync(t->h_refit_out.get(), t->d_refit_out.get(), 2u * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  if (static_cast<uint32_t>(t->h_refit_out.get()[0]) != 0u) { t->refit_fallbacks++; return false; }
+  float ms = 0.0f;
+  HIP_CHECK(hipEventElapsedTime(&ms, t->refit_begin, t->refit_end));
+  t->refit_us = static_cast<uint64_t>(ms * 1000.0f + 0.5f);
+  memcpy(&t->bvh_cost, t->h_refit_out.get() + 1, sizeof(double));
+  t->refits++;
+  t->bvh_scene = t->scene_generation;
+  return true;
+}
+
 // RT_QUERY_BVH: the tree of the current scene, built on the host from the records the kernel intersects (read back from the
 // device: for either upload layout they are what prep_triangles_kernel stored) and uploaded, all on the query stream -- the
 // upload that made the records has returned, so the build waits for no Trace.  Queries in flight may still read the old
-// tree: they are waited for before its buffers are rewritten.
+// tree: they are waited for before its buffers are rewritten.  Under RT_ACCEL_REFIT a tree of the same record count is
+// refitted instead (refit_query_tree).
 inline void ensure_query_tree(rt_tracer* t) {
   if (t->bvh_valid()) return;
   const hipStream_t st = query_stream(t);
   t->wait_queries();
   const size_t n = t->n_tris;
   if (n > rtb::kBvhMaxTris) throw HipFail{fmt("RT_QUERY_BVH: %zu triangles (at most %zu)", n, rtb::kBvhMaxTris)};
+  if (t->accel_update == RT_ACCEL_REFIT && t->bvh_built && n != 0u && size_t(t->bvh_leaf_records) + t->bvh_info[3] == n &&
+      refit_query_tree(t, st)) return;
+  t->bvh_built = false;                                                  // (a failure below leaves no tree to refit)
   std::vector<float> a(n * 8u), b(n);
   if (n != 0u) {
     HIP_CHECK(hipMemcpyAsync(a.data(), t->d_tri.get(), n * 8u * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -63,12 +98,18 @@ inline void ensure_query_tree(rt_tracer* t) {
   const rtb::Tree tree = rtb::build(rec.data(), n);
   t->d_bvh_nodes.ensure(std::max<size_t>(tree.nodes.size(), 1u) * 8u);
   t->d_bvh_records.ensure(std::max<size_t>(tree.records.size(), 1u) * 3u);
+  t->d_bvh_levels.ensure(std::max<size_t>(tree.level_nodes.size(), 1u));
   if (!tree.nodes.empty()) HIP_CHECK(hipMemcpyAsync(t->d_bvh_nodes.get(), tree.nodes.data(), tree.nodes.size() * sizeof(rtb::Node), hipMemcpyHostToDevice, st));
   if (!tree.records.empty()) HIP_CHECK(hipMemcpyAsync(t->d_bvh_records.get(), tree.records.data(), tree.records.size() * sizeof(rtb::Record), hipMemcpyHostToDevice, st));
+  if (!tree.level_nodes.empty()) HIP_CHECK(hipMemcpyAsync(t->d_bvh_levels.get(), tree.level_nodes.data(), tree.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   HIP_CHECK(hipStreamSynchronize(st));                                   // (the host vectors go away; a caller's stream may run the query)
   t->bvh_info[0] = tree.nodes.size(); t->bvh_info[1] = tree.leaves; t->bvh_info[2] = tree.depth; t->bvh_info[3] = tree.always;
   t->bvh_info[4] = tree.build_us; t->bvh_info[5] = tree.bytes();
   t->bvh_leaf_records = static_cast<uint32_t>(tree.records.size() - tree.always);
+  t->bvh_level_begin = tree.level_begin;
+  if (t->bvh_level_begin.empty()) t->bvh_level_begin.push_back(0u);
+  t->bvh_cost = t->bvh_cost_built = rtb::tree_cost(tree.nodes);
+  t->refits = 0;
   t->bvh_scene = t->scene_generation;
   t->bvh_built = true;
 }
@@ -177,6 +218,47 @@ int rt_tracer_query_accel_info(rt_tracer* t, uint64_t out[8]) {
   return RT_OK;
 }
 
+int rt_tracer_set_query_accel_update(rt_tracer* t, uint32_t policy) {
+  if (!t) return RT_ERR_INVALID;
+  if (policy != RT_ACCEL_REBUILD && policy != RT_ACCEL_REFIT) { t->set_error(fmt("rt_tracer_set_query_accel_update: unknown policy %u", policy)); return RT_ERR_INVALID; }
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_set_query_accel_update(t->mg->bands[0], policy);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  t->accel_update = policy;
+  return RT_OK;
+}
+
+int rt_tracer_query_accel_rebuild(rt_tracer* t) {
+  if (!t) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_query_accel_rebuild(t->mg->bands[0]);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  t->bvh_built = false;                                                  // (the buffers stay; queries in flight may still walk them)
+  return RT_OK;
+}
+
+int rt_tracer_query_accel_update_info(rt_tracer* t, uint64_t out[8]) {
+  if (!t || !out) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_query_accel_update_info(t->mg->bands[0], out);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  const bool valid = t->bvh_valid();
+  const double cost = valid ? t->bvh_cost : 0.0, built = valid ? t->bvh_cost_built : 0.0;
+  out[0] = t->accel_update; out[1] = t->refits; out[2] = t->refit_fallbacks; out[3] = t->refit_us;
+  memcpy(&out[4], &cost, sizeof(double)); memcpy(&out[5], &built, sizeof(double));
+  out[6] = out[7] = 0u;
+  return RT_OK;
+}
+
 int rt_dbg_query_accel_slack(rt_tracer* t, uint32_t slack_milli) {
   if (!t) return RT_ERR_INVALID;
   std::lock_guard<std::mutex> lk(t->api_mu);
@@ -200,6 +282,70 @@ int rt_dbg_bvh_build(const rt_float4* rows, size_t count, int edges_layout, void
       throw HipFail{fmt("rt_dbg_bvh_build: the tree needs %zu + %zu bytes", nb, rb)};
     if (nb) memcpy(nodes, tree.nodes.data(), nb);
     if (rb) memcpy(leaf_records, tree.records.data(), rb);
+  });
+}
+
+// what rt_dbg_bvh_refit may follow in its caller's arrays: every reference in range, children behind their parents
+static bool tree_refs_ok(const rtb::Node* nodes, size_t n_nodes, const rtb::Record* recs, size_t n_leaf, size_t n) {
+  for (size_t s = 0; s < n; ++s) if (recs[s].index >= n) return false;
+  for (size_t i = 0; i < n_nodes; ++i)
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t ref = nodes[i].child[k];
+      if (ref == rtb::kBvhEmpty) continue;
+      if (ref & rtb::kBvhLeaf) { if (size_t(ref & 0x0FFFFFFFu) + ((ref >> 28) & 3u) + 1u > n_leaf) return false; }
+      else if (ref >= n_nodes || ref <= i) return false;
+    }
+  return true;
+}
+
+int rt_dbg_bvh_refit(const rt_float4* rows, size_t count, int edges_layout, void* nodes, size_t node_bytes, void* leaf_records,
+                     size_t record_bytes, uint64_t info[8]) {
+  if (!rows || !info || !leaf_records || count < 3u || count % 3u != 0u || count / 3u > rtb::kBvhMaxTris) return RT_ERR_INVALID;
+  const size_t n = count / 3u, n_nodes = node_bytes / sizeof(rtb::Node);
+  if (node_bytes % sizeof(rtb::Node) != 0u || record_bytes != n * sizeof(rtb::Record) || (n_nodes != 0u && !nodes)) return RT_ERR_INVALID;
+  const size_t n_always = static_cast<size_t>(info[5]);
+  if (n_always > n || info[2] != n_nodes) return RT_ERR_INVALID;
+  rtb::Node* nd = static_cast<rtb::Node*>(nodes);
+  rtb::Record* rc = static_cast<rtb::Record*>(leaf_records);
+  if (!tree_refs_ok(nd, n_nodes, rc, n - n_always, n)) return RT_ERR_INVALID;
+  bool ok = true;
+  const int rcode = guarded(nullptr, [&] {
+    const std::vector<float> rec = rtb::records_of_rows(&rows[0].x, n, edges_layout != 0);
+    ok = rtb::refit(nd, n_nodes, rc, n - n_always, n_always, rec.data());
+  });
+  if (rcode != RT_OK) return rcode;
+  if (!ok) { set_global_error("rt_dbg_bvh_refit: a triangle changed between finite and non-finite; the tree has to be built"); return RT_ERR_STATE; }
+  return RT_OK;
+}
+
+double rt_dbg_bvh_tree_cost(const void* nodes, size_t node_bytes) {
+  if (!nodes || node_bytes % sizeof(rtb::Node) != 0u) return 0.0;
+  return rtb::tree_cost(static_cast<const rtb::Node*>(nodes), node_bytes / sizeof(rtb::Node));
+}
+
+int rt_dbg_query_tree_read(rt_tracer* t, void* nodes, size_t node_capacity_bytes, void* records, size_t record_capacity_bytes,
+                           uint64_t info[8]) {
+  if (!t || !info) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_dbg_query_tree_read(t->mg->bands[0], nodes, node_capacity_bytes, records, record_capacity_bytes, info);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  if (!t->bvh_valid()) { t->set_error("rt_dbg_query_tree_read: no valid tree (the next RT_QUERY_BVH query makes one)"); return RT_ERR_STATE; }
+  return guarded(t, [&] {
+    const size_t nb = t->bvh_info[0] * sizeof(rtb::Node), rb = (size_t(t->bvh_leaf_records) + t->bvh_info[3]) * sizeof(rtb::Record);
+    info[0] = rtb::kBvhMaxDepth; info[1] = 1u;
+    for (int i = 0; i < 6; ++i) info[2 + i] = t->bvh_info[i];
+    if (node_capacity_bytes == 0u && record_capacity_bytes == 0u) return;  // sizes only
+    if (!nodes || !records || node_capacity_bytes < nb || record_capacity_bytes < rb)
+      throw HipFail{fmt("rt_dbg_query_tree_read: the tree needs %zu + %zu bytes", nb, rb)};
+    t->use_device();
+    const hipStream_t st = query_stream(t);
+    t->wait_queries();
+    if (nb) HIP_CHECK(hipMemcpyAsync(nodes, t->d_bvh_nodes.get(), nb, hipMemcpyDeviceToHost, st));
+    if (rb) HIP_CHECK(hipMemcpyAsync(records, t->d_bvh_records.get(), rb, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 

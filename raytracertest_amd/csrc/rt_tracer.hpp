@@ -593,6 +593,17 @@ struct rt_tracer {
   uint64_t bvh_info[6] = {0, 0, 0, 0, 0, 0};          // nodes, leaves, depth, always-tested, build us, device bytes
   uint32_t bvh_leaf_records = 0;
   bool bvh_valid() const { return bvh_built && bvh_scene == scene_generation; }
+  // RT_ACCEL_REFIT (rt_refit.hpp): what the next query in RT_QUERY_BVH mode does with a tree of an earlier
+  // upload.  bvh_built stays set across uploads -- the device tree keeps its topology, and its record count decides whether
+  // a refit may replace the build; rt_tracer_query_accel_rebuild clears it.
+  uint32_t accel_update = RT_ACCEL_REBUILD;
+  rtr::DevArray<uint32_t> d_bvh_levels;               // the node indices grouped by level, root first (rtb::Tree::level_nodes)
+  std::vector<uint32_t> bvh_level_begin;              // depth + 1 offsets into it
+  rtr::DevArray<uint64_t> d_refit_out;                // {class-change flag, the cost as a double}
+  rtr::PinnedArray<uint64_t> h_refit_out;
+  rtr::Event refit_begin, refit_end;
+  uint64_t refits = 0, refit_fallbacks = 0, refit_us = 0;   // since the last build; over the tracer's life; the last refit's
+  double bvh_cost = 0.0, bvh_cost_built = 0.0;
 
   // camera + callbacks (guarded by state_mu; snapshotted per launch like the by-value kernel argument)
   std::mutex state_mu;
