@@ -129,6 +129,21 @@ public:
     counts.resize(n);
     return rt_tracer_intersect_all(mImpl, segs.data(), n, maxHits, hits.data(), counts.data()) == RT_OK;
   }
+  // Point query (rt_mi355x.h, rt_tracer_closest_point): pts holds 4 floats per point -- x, y, z and the SQUARED search radius
+  // (+inf = unbounded); hits[i].t = the squared distance to the nearest surface point, u, v its barycentrics (the point is
+  // v0 + u*e1 + v*e2 of triangle prim), prim = RT_PRIM_NONE when nothing lies within the radius.  A vector whose size is no
+  // multiple of 4: false, hits untouched.
+  bool ClosestPoint(const std::vector<float>& pts, std::vector<rt_hit>& hits) {
+    if (!mImpl || pts.size() % 4 != 0) return false;
+    hits.resize(pts.size() / 4);
+    return rt_tracer_closest_point(mImpl, pts.data(), hits.size(), hits.data()) == RT_OK;
+  }
+  // The same, returning the hits: empty when the vector was rejected or the call failed (LastError()).
+  std::vector<rt_hit> ClosestPoint(const std::vector<float>& pts) {
+    std::vector<rt_hit> hits;
+    if (!ClosestPoint(pts, hits)) hits.clear();
+    return hits;
+  }
   // The pinhole ray of a full-image pixel; `ray` (origin, direction) when asked for: the hit point is o + t * d.
   bool Pick(const math::uvec2& pixel, rt_hit& hit) { return Pick(pixel, hit, nullptr); }
   bool Pick(const math::uvec2& pixel, rt_hit& hit, math::vec3 ray[2]) {

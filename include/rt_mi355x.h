@@ -372,6 +372,58 @@ int  rt_tracer_intersect_all(rt_tracer* t, const float* segs, size_t n, uint32_t
 int  rt_tracer_intersect_all_device(rt_tracer* t, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts,
                                     void* stream);
 
+/* ---- point queries --------------------------------------------------------------------------
+ * The nearest surface point of the tracer's scene to a point, and how far away it is (proximity and collision tests, snapping a
+ * camera target to the geometry, distance-field sampling, "which triangle did I click next to").
+ *   pts         n x 4 floats: x, y, z, d2max -- the SQUARED search radius of that point; +inf = unbounded.
+ *   out         out[i] = rt_hit with t = the squared distance, u, v = the nearest point's barycentrics, prim as in the ray queries
+ *               (a triangle index in [0, n_tris); n_tris + i for sphere i).  The nearest point is v0 + u*e1 + v*e2 of the
+ *               triangle's record, for the caller to form (a sphere: centre + radius * (p - centre) / |p - centre|).
+ *   candidates  every triangle through the record the renderer intersects (v0, e1, e2); for edge-format scenes
+ *               (rt_tracer_upload_scene_edges) these are the uploaded rows.  Every sphere through its surface.
+ *   triangle    Ericson's closest point on a triangle restated on the record.  There is no reference arithmetic to be faithful
+ *               to, so it is the same in RT_MATH_FMA and RT_MATH_STRICT: every operation is one separately rounded fp32 operation,
+ *               division is correctly rounded, dot products are (x*x' + y*y') + z*z'.
+ *                 With ap = p - v0:  a = e1.e1, b = e1.e2, c = e2.e2, d1 = e1.ap, d2 = e2.ap,
+ *                                    d3 = d1 - a, d4 = d2 - b, d5 = d1 - b, d6 = d2 - c;
+ *                 vc = d1*d4 - d3*d2,  vb = d5*d2 - d1*d6,  va = d3*d6 - d5*d4.
+ *                 The first of these regions that holds gives (u, v):
+ *                   1. d1 <= 0 && d2 <= 0                       (0, 0)
+ *                   2. d3 >= 0 && d4 <= d3                      (1, 0)
+ *                   3. vc <= 0 && d1 >= 0 && d3 <= 0            (d1 / (d1 - d3), 0)
+ *                   4. d6 >= 0 && d5 <= d6                      (0, 1)
+ *                   5. vb <= 0 && d2 >= 0 && d6 <= 0            (0, d2 / (d2 - d6))
+ *                   6. va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0  w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), (1 - w, w)
+ *                   7. otherwise                                den = 1 / ((va + vb) + vc), (vb * den, vc * den)
+ *                 Then r = (ap - u*e1) - v*e2 per component, and t = r.r.
+ *   sphere      w = p - centre, s = |sqrt(w.w) - radius| with the correctly rounded sqrt, t = s*s, u = v = 0, prim = n_tris + i.
+ *   accepted    a candidate is accepted when t <= d2max in plain fp32.  A NaN t is never accepted; a NaN or negative d2max
+ *               accepts nothing.
+ *   winner      the accepted candidate with the smallest (t, prim): equal t (==) goes to the lowest prim.  The rule names no
+ *               visiting order and does not depend on RT_FLAG_NEAREST_HIT.
+ *   no winner   {0, 0, 0, RT_PRIM_NONE}.
+ * No scene: every answer is that; spheres alone can win; n = 0 is a no-op; a NULL array with n > 0 is RT_ERR_INVALID.
+ * Scheduling is that of the ray queries: never cancels or joins a running Trace, serialised with the other calls, on the query
+ * stream or the caller's, waited for by uploads and destroy; a multi-device handle answers from its first band, a band tracer
+ * locally.
+ * RT_QUERY_SCAN (default): every point tests every candidate.  RT_QUERY_BVH: the ray queries' tree (built, or under
+ * RT_ACCEL_REFIT refitted, by the first query after an upload), walked nearest box first; bit for bit the scan's answer for
+ * every point whose three coordinates are finite.  There is no conditioning clause: a distance, unlike a ray against a plane it
+ * grazes, is well conditioned; regions 1-7 yield u, v in [0, 1] by the signs they test and region 7 divides by a sum of three
+ * positives, so a computed closest point never leaves its triangle's box by more than rounding, which the box test's allowance
+ * rho_c covers (rt_dbg_query_accel_slack scales it as it scales rho).  A point with a non-finite coordinate takes no pruning
+ * decision; triangles with a non-finite record stay in the always-tested list and go through the same rule.
+ * Accuracy, as measured (K = 64, four times the largest value seen): with scale = max|p| + the largest |vertex
+ * coordinate| and eps = 2^-24, sqrt(t) >= D - K*eps*scale for D the true distance to the nearest triangle -- the reported
+ * distance is never below the true one by more than rounding -- and sqrt(t) <= D_ws + K*eps*scale for D_ws the true distance to
+ * the nearest WELL-SHAPED triangle (smallest corner-angle sine >= 2^-6): within rounding of the true one whenever the truly
+ * nearest triangle is well shaped. */
+/* Host arrays: pts n*4, out n.  Returns with the answers in host memory. */
+int  rt_tracer_closest_point(rt_tracer* t, const float* pts, size_t n, rt_hit* out);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  pts and out must be 16-byte aligned; otherwise RT_ERR_INVALID. */
+int  rt_tracer_closest_point_device(rt_tracer* t, const float* pts, size_t n, rt_hit* out, void* stream);
+
 /* ---- one frame sharded over several GPUs --------------------------------------
  * The reference builds ONE rt::RayTracer pinned to device 0 (OpenGLView/MainFrame.cpp:44-45,
  * OpenGLView/GLCanvas.cpp:259-260).  Pixels are independent and a pixel's RNG stream is keyed by its

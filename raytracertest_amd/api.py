@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "rt_tracer_intersect", "rt_tracer_intersect_device", "rt_tracer_pick", "rt_tracer_focus_at",
     "rt_tracer_occluded", "rt_tracer_occluded_device",
     "rt_tracer_intersect_all", "rt_tracer_intersect_all_device",
+    "rt_tracer_closest_point", "rt_tracer_closest_point_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
     "rt_tracer_set_query_accel_update", "rt_tracer_query_accel_rebuild", "rt_tracer_query_accel_update_info",
     "rt_dbg_bvh_refit", "rt_dbg_query_tree_read", "rt_dbg_bvh_tree_cost",
@@ -270,6 +271,8 @@ def load_library():
         L.rt_tracer_occluded_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.rt_tracer_intersect_all.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp]
         L.rt_tracer_intersect_all_device.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
+        L.rt_tracer_closest_point.argtypes = [vp, vp, C.c_size_t, vp]
+        L.rt_tracer_closest_point_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.rt_tracer_set_query_accel.argtypes = [vp, C.c_uint32]
         L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_dbg_query_accel_slack.argtypes = [vp, C.c_uint32]
@@ -333,6 +336,7 @@ class RayTracer:
         self._h = C.c_void_p()
         self._cbs = {}
         self._retired = []
+        self._scene_rows, self._scene_edges, self._sphere_rows = None, False, None   # host copies, for ClosestPositions
         size = np.array(imageSize, np.uint32)
         opt = Options()
         opt.struct_size = C.sizeof(Options)
@@ -391,6 +395,7 @@ class RayTracer:
         if rc == 1:
             return False
         self._check(rc)
+        self._scene_rows, self._scene_edges = a.copy(), False
         return True
 
     def UploadSceneEdges(self, hostData):
@@ -400,6 +405,7 @@ class RayTracer:
         if rc == 1:
             return False
         self._check(rc)
+        self._scene_rows, self._scene_edges = a.copy(), True
         return True
 
     def SetUpdateCallback(self, callback):
@@ -420,6 +426,7 @@ class RayTracer:
     def UploadSpheres(self, spheres):
         a = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
         self._check(self._lib.rt_tracer_upload_spheres(self._h, a.ctypes.data, a.shape[0]))
+        self._sphere_rows = a.copy()
 
     def TraceEnqueue(self, iterationCount, samplesPerIteration):
         self._check(self._lib.rt_tracer_trace_enqueue(self._h, iterationCount, samplesPerIteration))
@@ -733,6 +740,83 @@ class RayTracer:
         self._check(self._lib.rt_tracer_intersect_all_device(self._h, segs.data_ptr(), segs.shape[0], k, hits.data_ptr(),
                                                              counts.data_ptr(), C.c_void_p(stream)))
         return hits, counts
+
+    # ---- point queries (rt_tracer_closest_point / _device) -----------------------------------------------------------
+    def ClosestPoint(self, points, max_distance=np.inf):
+        """The nearest surface point of the scene to each point.  points: (n, 3) float32 x, y, z, searched within max_distance
+        (squared on the host in fp32; a negative one keeps its sign and accepts nothing), or (n, 4) with the SQUARED search radius
+        of each point in column 3 (+inf = unbounded), as rt_tracer_closest_point takes them.  The answer's t is the squared
+        distance, u, v the nearest point's barycentrics (ClosestPositions forms the point), prim the triangle, n_tris + sphere
+        index, or PRIM_NONE when nothing lies within the radius.  Independent of the tracer's arithmetic mode and hit rule.  A
+        numpy array -> structured array HIT_DTYPE, on return.  A contiguous torch float32 tensor on the tracer's device -> (n, 4)
+        float32 tensor {t, u, v, prim bits}, enqueued on torch.cuda.current_stream() without a host synchronisation."""
+        if type(points).__module__.startswith("torch"):
+            return self._closest_point_tensor(points, max_distance)
+        p = np.asarray(points, np.float32)
+        if p.ndim == 0 or p.shape[-1] not in (3, 4):
+            raise ValueError("ClosestPoint: expected (n, 3) or (n, 4) float32 points, got shape %s" % (p.shape,))
+        if p.shape[-1] == 3:
+            q = np.empty(p.shape[:-1] + (4,), np.float32)
+            q[..., :3], q[..., 3] = p, self._d2max(max_distance)
+            p = q
+        p = np.ascontiguousarray(p).reshape(-1, 4)
+        hits = np.zeros(p.shape[0], HIT_DTYPE)
+        self._check(self._lib.rt_tracer_closest_point(self._h, p.ctypes.data, p.shape[0], hits.ctypes.data))
+        return hits
+
+    @staticmethod
+    def _d2max(max_distance):
+        with np.errstate(over="ignore"):
+            d = np.float32(max_distance)
+            return np.copysign(d * d, d)
+
+    def _closest_point_tensor(self, points, max_distance=np.inf):
+        import torch
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
+            raise ValueError("ClosestPoint: expected an (n, 3) or (n, 4) float32 tensor")
+        dev = self.Bands()[0]["device"]
+        if points.device.type != "cuda" or points.device.index != dev:
+            raise ValueError("ClosestPoint: the points are on %s, the tracer on cuda:%d" % (points.device, dev))
+        if points.shape[1] == 3:
+            q = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+            q[:, :3] = points
+            q[:, 3] = float(self._d2max(max_distance))
+            points = q
+        elif not points.is_contiguous():
+            raise ValueError("ClosestPoint: expected a contiguous (n, 4) float32 tensor")
+        hits = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+        stream = torch.cuda.current_stream(points.device).cuda_stream
+        self._check(self._lib.rt_tracer_closest_point_device(self._h, points.data_ptr(), points.shape[0], hits.data_ptr(),
+                                                             C.c_void_p(stream)))
+        return hits
+
+    def ClosestPositions(self, points, hits):
+        """The nearest points themselves, (n, 3) float32: v0 + u*e1 + v*e2 of the winning triangle's record (fp32, from this
+        object's host copy of the last uploaded scene), centre + radius * (p - centre) / |p - centre| for a sphere, NaN where
+        hits["prim"] is PRIM_NONE.  points, hits: what ClosestPoint took and returned (numpy)."""
+        p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, np.shape(points)[-1])[:, :3])
+        h = np.asarray(hits).reshape(-1)
+        if h.dtype != HIT_DTYPE or h.shape[0] != p.shape[0]:
+            raise ValueError("ClosestPositions: expected the points and the HIT_DTYPE answers of one ClosestPoint call")
+        n_tris = 0 if self._scene_rows is None else self._scene_rows.shape[0] // 3
+        out = np.full((p.shape[0], 3), np.nan, np.float32)
+        prim = h["prim"].astype(np.int64)
+        tri = (prim >= 0) & (prim < n_tris)
+        if tri.any():
+            r = self._scene_rows.reshape(-1, 3, 4)[prim[tri], :, :3]
+            v0 = r[:, 0]
+            e1, e2 = (r[:, 1], r[:, 2]) if self._scene_edges else (r[:, 1] - v0, r[:, 2] - v0)
+            out[tri] = (v0 + h["u"][tri, None] * e1) + h["v"][tri, None] * e2
+        sph = prim >= n_tris
+        if sph.any():
+            n_sph = 0 if self._sphere_rows is None else self._sphere_rows.shape[0]
+            if (prim[sph] - n_tris >= n_sph).any():
+                raise ValueError("ClosestPositions: a prim is beyond the scene this object uploaded")
+            s = self._sphere_rows[prim[sph] - n_tris]
+            w = p[sph] - s[:, :3]
+            with np.errstate(all="ignore"):
+                out[sph] = s[:, :3] + w * (s[:, 3] / np.sqrt((w * w).sum(axis=1, dtype=np.float32)))[:, None]
+        return out
 
     def Visible(self, a, b, tmin=0.0, tmax=1.0):
         """Line of sight between the points a[i] and b[i] ((n, 3) each): ~Occluded of the rays o = a, d = b - a (fp32, on the

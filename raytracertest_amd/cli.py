@@ -1,6 +1,6 @@
 """Headless front end: `python -m raytracertest_amd.cli`.  The reference's command line
 (OpenGLView/App.cpp:62-184: -w -h -s -i -u -cx -cy -cz -cxa -cya -f -l -a, integer values,
-defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --focus; the image is saved
+defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --focus; the image is saved
 in the reference's BMP format (Common/Bitmap.h).  Same options as tools/rt_cli.cpp."""
 import argparse
 import math
@@ -39,7 +39,9 @@ def build_parser():
     p.add_argument("--pick", type=_xy, default=None, metavar="X,Y", help="print `pick x y prim t u v` for the pixel's pinhole ray")
     p.add_argument("--hits", type=_xyk, default=None, metavar="X,Y[,K]",
                    help="print one line `prim t u v` per hit of the pixel's pinhole ray, in order, over all t (at most K, default 8)")
-    p.add_argument("--accel", action="store_true", help="--pick / --hits / --focus through the scene's BVH instead of the scan")
+    p.add_argument("--closest", type=_xyzr, default=None, metavar="X,Y,Z[,R]",
+                   help="print `closest prim distance x y z`: the nearest surface point to the point X,Y,Z (within the distance R)")
+    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --focus through the scene's BVH instead of the scan")
     p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
                    help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
     return p
@@ -55,6 +57,13 @@ def _xyk(s):
     if len(v) not in (2, 3):
         raise ValueError(s)
     return v[0], v[1], v[2] if len(v) == 3 else 8
+
+
+def _xyzr(s):
+    v = [float(x) for x in s.split(",")]
+    if len(v) not in (3, 4):
+        raise ValueError(s)
+    return v[0], v[1], v[2], v[3] if len(v) == 4 else math.inf
 
 
 def load_scene(name):
@@ -105,6 +114,14 @@ def main(argv=None):
             sys.exit("--hits: %s" % e)
         for h in hits[0, :counts[0]]:
             print("%d %.9g %.9g %.9g" % (h["prim"], h["t"], h["u"], h["v"]))
+    if a.closest is not None:
+        pt = np.float32([a.closest[:3]])
+        h = g.ClosestPoint(pt, a.closest[3])
+        q = g.ClosestPositions(pt, h)[0]
+        if h["prim"][0] < 0:
+            print("closest -1")
+        else:
+            print("closest %d %.9g %.9g %.9g %.9g" % (h["prim"][0], np.sqrt(h["t"][0]), q[0], q[1], q[2]))
     if a.focus is not None:
         try:
             f = g.FocusAt(*a.focus)

@@ -9,6 +9,7 @@
 //   query_bvh_kernel   <- the same answer through a bounding volume hierarchy (rt_bvh.hpp)
 //   occluded_*kernel   <- any hit within a caller's t interval (rt_occluded.hpp)
 //   allhits_*kernel    <- the first k hits within a caller's t interval, in order (rt_allhits.hpp)
+//   closest_*kernel    <- the nearest surface point to a caller's point (rt_closest.hpp)
 //   refit_*kernel      <- the tree's boxes recomputed for a re-uploaded scene of the same size (rt_refit.hpp)
 //   dbg_* kernels      <- single-function harnesses used by the parity tests
 #include <stdlib.h>
@@ -18,6 +19,7 @@
 #include "rt_bvh.hpp"
 #include "rt_occluded.hpp"
 #include "rt_allhits.hpp"
+#include "rt_closest.hpp"
 #include "rt_refit.hpp"
 
 namespace rtk {

@@ -172,6 +172,16 @@ uint32_t allhits_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_allhits_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint32_t max_hits,
                               float4* hits, uint32_t* counts, hipStream_t st);
 
+// The point query (rt_closest.hpp): n points {x, y, z, d2max}, 16-byte aligned; hits[i] = {squared distance, u, v, bits of the
+// int32 primitive} of the nearest candidate with t <= d2max, smallest (t, prim), or {0, 0, 0, -1}.  One arithmetic for both
+// math modes; one point per lane in both forms.  rho_c: RT_CLOSEST_RHO x the tracer's slack.
+#define RT_CLOSEST_RHO 3.814697265625e-06f      // 2^-18: DESIGN.md 4.3f derives it
+uint32_t closest_lds_bytes(uint32_t n_tris);
+hipError_t launch_closest(const TraceParams& p, uint32_t n, const float* pts, float4* hits, hipStream_t st);
+uint32_t closest_bvh_lds_bytes(uint32_t stack_cap);
+hipError_t launch_closest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, float4* hits,
+                              hipStream_t st);
+
 // Refit of that tree on the device (rt_refit.hpp): the records of the current scene into their slots (flag: set to 1 when a
 // slot's triangle changed between finite and non-finite), the boxes of one level's nodes (deepest level first), the tree's cost.
 hipError_t launch_refit_gather(const float4* tri_a, const float* tri_b, uint32_t n_tris, float4* records, uint32_t n_leaf_records,

@@ -1,5 +1,6 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
-// rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_intersect_all*).  Included by rt_tracer.hip.
+// rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_intersect_all*) and the point query (rt_tracer_closest_point*).  Included
+// by rt_tracer.hip.
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
 // calls by api_mu, reads only the scene and a snapshot of the camera (params(), under state_mu), and runs on a stream of its
@@ -176,6 +177,25 @@ inline void enqueue_intersect_all(rt_tracer* t, size_t n, const float* segs, uin
     HIP_CHECK(rtk::launch_allhits_bvh(p, b, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st));
   } else {
     HIP_CHECK(rtk::launch_allhits(p, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st));
+  }
+  HIP_CHECK(hipEventRecord(t->query_done, st));
+}
+
+// points -> one record per point on `st`, with enqueue_query's event discipline.  One arithmetic for both math modes and no hit
+// rule: p.flags stays 0.  The tree is the ray queries' (ensure_query_tree, so RT_ACCEL_REFIT applies); rho_c takes their slack.
+inline void enqueue_closest(rt_tracer* t, size_t n, const float* pts, float4* hits, hipStream_t st) {
+  rtk::TraceParams p = t->params(1);
+  p.flags = 0u;
+  const bool bvh = t->query_accel == RT_QUERY_BVH;
+  if (bvh) ensure_query_tree(t);
+  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
+  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
+  if (bvh) {
+    const rtk::BvhParams b = query_bvh_params(t);
+    const float rho_c = RT_CLOSEST_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f);
+    HIP_CHECK(rtk::launch_closest_bvh(p, b, rho_c, static_cast<uint32_t>(n), pts, hits, st));
+  } else {
+    HIP_CHECK(rtk::launch_closest(p, static_cast<uint32_t>(n), pts, hits, st));
   }
   HIP_CHECK(hipEventRecord(t->query_done, st));
 }
@@ -476,6 +496,48 @@ int rt_tracer_intersect_all_device(rt_tracer* t, const float* segs, size_t n, ui
     if (n == 0u) return;
     t->use_device();
     enqueue_intersect_all(t, n, segs, max_hits, reinterpret_cast<float4*>(hits), counts, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_closest_point(rt_tracer* t, const float* pts, size_t n, rt_hit* out) {
+  if (!t) return RT_ERR_INVALID;
+  if (!query_args_ok(t, n, pts, out)) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_closest_point(t->mg->bands[0], pts, n, out);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    const hipStream_t st = query_stream(t);
+    t->d_q_points.ensure(n);
+    t->d_q_hits.ensure(n);
+    HIP_CHECK(hipMemcpyAsync(t->d_q_points.get(), pts, n * 4u * sizeof(float), hipMemcpyHostToDevice, st));
+    enqueue_closest(t, n, reinterpret_cast<const float*>(t->d_q_points.get()), t->d_q_hits.get(), st);
+    HIP_CHECK(hipMemcpyAsync(out, t->d_q_hits.get(), n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_closest_point_device(rt_tracer* t, const float* pts, size_t n, rt_hit* out, void* stream) {
+  if (!t) return RT_ERR_INVALID;
+  if (!query_args_ok(t, n, pts, out)) return RT_ERR_INVALID;
+  if (n != 0u && (reinterpret_cast<uintptr_t>(pts) % 16u != 0u || reinterpret_cast<uintptr_t>(out) % 16u != 0u)) {
+    t->set_error("rt_tracer_closest_point_device: pts and out must be 16-byte aligned");
+    return RT_ERR_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_closest_point_device(t->mg->bands[0], pts, n, out, stream);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_closest(t, n, pts, reinterpret_cast<float4*>(out), static_cast<hipStream_t>(stream));
   });
 }
 

@@ -5,7 +5,10 @@ of a 512x288 frame, on C4's scene and on 200 000 random triangles -- repeated wi
 slack_milli / 1000 = 1, 0.3, 0.1, 0.03, 0.01 and 0 (rt_dbg_query_accel_slack).  Reports per slack how many rays with a
 well-conditioned scan winner get another answer, the largest slack at which one does, and the ratio allowance / reach.
 At slack 0 the boxes are bare: differences there are expected (wrong answers, not faults).
-Usage: bvh_margin.py [--out FILE.json] [--rays LOG2]"""
+--closest: the same sweep for the point query, whose allowance rho_c the same slack scales: ClosestPoint, scan
+against BVH, on 2^LOG2 points of tests/closest_expect.points_for and on the lattice points, C4's scene and the lattice scene;
+there is no conditioning clause, so every differing row counts.  Reports the smallest slack at which BVH still equals scan.
+Usage: bvh_margin.py [--closest] [--out FILE.json] [--rays LOG2]"""
 import argparse
 import json
 import os
@@ -20,13 +23,55 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 SLACKS = (1000, 300, 100, 30, 10, 0)
 
 
+def closest_margin(R, scenes, log2_points):
+    import closest_expect as ce
+    import lattice_cases as lc
+    res = {"version": R.api.load_library().rt_version().decode(), "rho_c": 2.0 ** -18, "derived_budget": 19 * 2.0 ** -24,
+           "slacks": list(SLACKS), "scenes": {}}
+    smallest_equal = {}
+    for name, rows in (("c4_10k", scenes.random_triangles(10000, 12345)), ("lattice_rooms", lc.rooms())):
+        g = R.RayTracer((64, 48), (0, 0, 0), (0.0, 0.0), 70.0, 3.0, 0.05, seed=1)
+        assert g.UploadScene(rows)
+        pts = ce.points_for(rows, 1 << log2_points, seed=81, spread=4.0)
+        if name == "lattice_rooms":
+            pts = np.concatenate([ce.lattice_points(), pts])
+        scan = g.ClosestPoint(pts)
+        batches = {"unbounded": ce.with_radius(pts, np.inf), "half": ce.with_radius(pts, np.float32(np.median(scan["t"])))}
+        scan = {k: g.ClosestPoint(p) for k, p in batches.items()}
+        g.SetQueryAcceleration(True)
+        out, equal = {}, []
+        for slack in SLACKS:
+            g.DebugQueryAccelSlack(slack)
+            per = {}
+            for k, p in batches.items():
+                got = g.ClosestPoint(p)
+                differ = (got.view(np.uint32).reshape(-1, 4) != scan[k].view(np.uint32).reshape(-1, 4)).any(axis=1)
+                per[k] = {"points": int(p.shape[0]), "differ": int(differ.sum())}
+            out[str(slack)] = per
+            if all(v["differ"] == 0 for v in per.values()):
+                equal.append(slack)
+        smallest_equal[name] = min(equal) if equal else None
+        res["scenes"][name] = out
+        g.close()
+    res["smallest_slack_milli_at_which_bvh_equals_scan"] = smallest_equal
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rays", type=int, default=18)
+    ap.add_argument("--closest", action="store_true")
     a = ap.parse_args()
     import raytracertest_amd as R
     from raytracertest_amd import scenes
+    if a.closest:
+        txt = json.dumps(closest_margin(R, scenes, a.rays), indent=1)
+        print(txt)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(txt + "\n")
+        return
     from query_accel_expect import WELL_CONDITIONED, conditioning, populations
 
     W, H = 512, 288

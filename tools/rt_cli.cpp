@@ -27,7 +27,8 @@ struct Args {
   uint64_t seed = 0; bool have_seed = false;
   std::string scene = "demo3", scene_file, out = "image0.bmp";
   bool quiet = false, edges = false, smooth = false, nearest = false;
-  bool pick = false, focus = false, accel = false, hits = false;
+  bool pick = false, focus = false, accel = false, hits = false, closest = false;
+  float closest_p[4] = {0, 0, 0, INFINITY};        // x, y, z, search distance
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0}, hits_xy[2] = {0, 0}, hits_k = 8;
 };
 
@@ -53,6 +54,20 @@ bool parse_xyk(const char* s, uint32_t xy[2], uint32_t& k) {
   if (end == v.c_str() + c2 + 1 || *end != 0) return false;
   k = static_cast<uint32_t>(kk);
   return parse_xy(v.substr(0, c2).c_str(), xy);
+}
+
+// "X,Y,Z" or "X,Y,Z,R": a point and an optional search distance
+bool parse_xyzr(const char* s, float out[4]) {
+  int n = 0;
+  for (const char* q = s;; ++n) {
+    char* end = nullptr;
+    const float f = std::strtof(q, &end);
+    if (end == q || n == 4) return false;
+    out[n] = f;
+    if (*end == 0) return n >= 2;
+    if (*end != ',') return false;
+    q = end + 1;
+  }
 }
 
 std::vector<float4> demo3() {                   // MainFrame.cpp:230-232
@@ -82,8 +97,10 @@ void usage() {
             "       [--pick X,Y]  (prints `pick x y prim t u v` for the pixel's pinhole ray)\n"
             "       [--hits X,Y[,K]] (prints one line `prim t u v` per hit of the pixel's pinhole ray, in order, over all t;\n"
             "                      at most K, default 8)\n"
+            "       [--closest X,Y,Z[,R]] (prints `closest prim distance x y z`: the nearest surface point to the point X,Y,Z,\n"
+            "                      within the distance R when given; `closest -1` when there is none)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
-            "       [--accel]     (--pick / --hits / --focus through the scene's BVH instead of the scan)");
+            "       [--accel]     (--pick / --hits / --closest / --focus through the scene's BVH instead of the scan)");
 }
 
 }  // namespace
@@ -128,6 +145,10 @@ int main(int argc, char** argv) {
     else if (k == "--hits") {
       if (!parse_xyk(next("--hits"), a.hits_xy, a.hits_k)) { std::fprintf(stderr, "--hits wants X,Y[,K]\n"); return 2; }
       a.hits = true;
+    }
+    else if (k == "--closest") {
+      if (!parse_xyzr(next("--closest"), a.closest_p)) { std::fprintf(stderr, "--closest wants X,Y,Z[,R]\n"); return 2; }
+      a.closest = true;
     }
     else if (k == "-o") a.out = next("-o");
     else if (k == "-q") a.quiet = true;
@@ -183,6 +204,29 @@ int main(int argc, char** argv) {
     }
     for (uint32_t j = 0; j < counts[0]; ++j)
       std::printf("%d %.9g %.9g %.9g\n", hits[j].prim, static_cast<double>(hits[j].t), static_cast<double>(hits[j].u), static_cast<double>(hits[j].v));
+  }
+  if (a.closest) {
+    const float r = a.closest_p[3];
+    const std::vector<float> pts = {a.closest_p[0], a.closest_p[1], a.closest_p[2], std::copysign(r * r, r)};
+    std::vector<rt_hit> hits;
+    if (!tracer.ClosestPoint(pts, hits)) {
+      std::fprintf(stderr, "rt_cli: --closest: %s\n", tracer.LastError().c_str());
+      return 1;
+    }
+    const rt_hit& h = hits[0];
+    if (h.prim < 0 || static_cast<size_t>(h.prim) >= scene.size() / 3) {
+      std::printf("closest -1\n");
+    } else {                                                    // v0 + u*e1 + v*e2 of the record the library intersects
+      const float4 r0 = scene[3 * h.prim], r1 = scene[3 * h.prim + 1], r2 = scene[3 * h.prim + 2];
+      const float v0[3] = {r0.x, r0.y, r0.z}, b[3] = {r1.x, r1.y, r1.z}, c[3] = {r2.x, r2.y, r2.z};
+      float q[3];
+      for (int i = 0; i < 3; ++i) {
+        const float e1 = a.edges ? b[i] : b[i] - v0[i], e2 = a.edges ? c[i] : c[i] - v0[i];
+        q[i] = (v0[i] + h.u * e1) + h.v * e2;
+      }
+      std::printf("closest %d %.9g %.9g %.9g %.9g\n", h.prim, static_cast<double>(std::sqrt(h.t)), static_cast<double>(q[0]),
+                  static_cast<double>(q[1]), static_cast<double>(q[2]));
+    }
   }
   if (a.focus) {
     float focal = 0.0f;
