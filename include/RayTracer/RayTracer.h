@@ -144,6 +144,27 @@ public:
     if (!ClosestPoint(pts, hits)) hits.clear();
     return hits;
   }
+  // The k nearest primitives (rt_mi355x.h, rt_tracer_closest_all): the same points; row i of hits (maxHits records) holds the
+  // point's counts[i] <= maxHits nearest primitives within its radius in ascending (t, prim) order, then records {0, 0, 0,
+  // RT_PRIM_NONE}; record 0 is ClosestPoint's answer.  counts[i] == maxHits: there may be more -- call again with after[i] =
+  // the row's last record.  after: empty (no cursor) or one record per point.  1 <= maxHits <= RT_MAX_HITS.  A point vector
+  // whose size is no multiple of 4, or an after of another length: false, the outputs untouched.
+  bool ClosestAll(const std::vector<float>& pts, uint32_t maxHits, std::vector<rt_hit>& hits, std::vector<uint32_t>& counts,
+                  const std::vector<rt_hit>& after = std::vector<rt_hit>()) {
+    if (!mImpl || pts.size() % 4 != 0 || maxHits == 0 || maxHits > RT_MAX_HITS) return false;
+    const size_t n = pts.size() / 4;
+    if (!after.empty() && after.size() != n) return false;
+    hits.resize(n * maxHits);
+    counts.resize(n);
+    return rt_tracer_closest_all(mImpl, pts.data(), after.empty() ? nullptr : after.data(), n, maxHits, hits.data(), counts.data()) == RT_OK;
+  }
+  // The same, returning the rows (n * maxHits records): empty when the arguments were rejected or the call failed.
+  std::vector<rt_hit> ClosestAll(const std::vector<float>& pts, uint32_t maxHits) {
+    std::vector<rt_hit> hits;
+    std::vector<uint32_t> counts;
+    if (!ClosestAll(pts, maxHits, hits, counts)) hits.clear();
+    return hits;
+  }
   // The pinhole ray of a full-image pixel; `ray` (origin, direction) when asked for: the hit point is o + t * d.
   bool Pick(const math::uvec2& pixel, rt_hit& hit) { return Pick(pixel, hit, nullptr); }
   bool Pick(const math::uvec2& pixel, rt_hit& hit, math::vec3 ray[2]) {

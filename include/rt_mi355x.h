@@ -424,6 +424,42 @@ int  rt_tracer_closest_point(rt_tracer* t, const float* pts, size_t n, rt_hit* o
  * synchronisation.  pts and out must be 16-byte aligned; otherwise RT_ERR_INVALID. */
 int  rt_tracer_closest_point_device(rt_tracer* t, const float* pts, size_t n, rt_hit* out, void* stream);
 
+/* The k nearest primitives to a point, in order (collision broad phase: every triangle a sphere touches; contact sets at edges
+ * and corners; blending the nearest few surfaces; "what else is near where I clicked"), with a cursor that enumerates ALL
+ * primitives within the radius however many there are.
+ *   pts         n x 4 floats, exactly as rt_tracer_closest_point takes them: x, y, z, d2max (the SQUARED search radius).
+ *   max_hits    1 .. RT_MAX_HITS; otherwise RT_ERR_INVALID.
+ *   candidates, arithmetic and acceptance are rt_tracer_closest_point's word for word: one arithmetic for both math modes; a
+ *               candidate is accepted when t <= d2max in plain fp32; a NaN t is never accepted; a NaN or negative d2max accepts
+ *               nothing.
+ *   after       optional (NULL: none): n records, the cursor of a continuation.  Where after[i].prim != RT_PRIM_NONE a candidate
+ *               of point i is additionally accepted only if it sorts strictly behind (after[i].t, after[i].prim): t > after.t,
+ *               or t == after.t && prim > after.prim with prim compared as int32.  A NaN after.t accepts nothing.  u and v of
+ *               the cursor are ignored.
+ *   order       ascending t; equal t (==) by ascending prim.  The rule names no visiting order.
+ *   hits        n * max_hits records.  Row i (hits + i * max_hits) holds counts[i] <= max_hits records in that order, then
+ *               records {0, 0, 0, RT_PRIM_NONE}.
+ *   counts      counts[i] = records stored for point i.  counts[i] == max_hits means there MAY be more.  To continue, call again
+ *               with after[i] = the row's last stored record: nothing is repeated and nothing is lost, coincident surfaces
+ *               included.
+ *   bits        t, u and v of a stored record are exactly what the triangle rule (or the sphere rule) of rt_tracer_closest_point
+ *               gives for that (point, primitive).  So with after == NULL record 0 of every row equals rt_tracer_closest_point's
+ *               answer bit for bit, for every max_hits.
+ * No scene: every count is 0; spheres alone can answer; n = 0 is a no-op; NULL pts, hits or counts with n > 0 is RT_ERR_INVALID.
+ * Scheduling is rt_tracer_closest_point's; a multi-device handle answers from its first band, a band tracer locally.
+ * RT_QUERY_SCAN (default): every point tests every candidate.  RT_QUERY_BVH: rt_tracer_closest_point's walk, pruning against
+ * min(d2max, the t of the list's last entry once the list is full) instead of against one best; bit for bit the scan's answer,
+ * counts included, for every point whose three coordinates are finite.  There is no conditioning clause.  A child is skipped
+ * only when its lower bound lies strictly above that bound, so it holds no record that could enter the list; the cursor takes
+ * no pruning decision. */
+/* Host arrays: pts n*4, after n or NULL, hits n*max_hits, counts n.  Returns with the results in host memory. */
+int  rt_tracer_closest_all(rt_tracer* t, const float* pts, const rt_hit* after, size_t n, uint32_t max_hits, rt_hit* hits,
+                           uint32_t* counts);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  pts, after (where given) and hits must be 16-byte aligned; otherwise RT_ERR_INVALID. */
+int  rt_tracer_closest_all_device(rt_tracer* t, const float* pts, const rt_hit* after, size_t n, uint32_t max_hits, rt_hit* hits,
+                                  uint32_t* counts, void* stream);
+
 /* ---- one frame sharded over several GPUs --------------------------------------
  * The reference builds ONE rt::RayTracer pinned to device 0 (OpenGLView/MainFrame.cpp:44-45,
  * OpenGLView/GLCanvas.cpp:259-260).  Pixels are independent and a pixel's RNG stream is keyed by its

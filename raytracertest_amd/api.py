@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "rt_tracer_occluded", "rt_tracer_occluded_device",
     "rt_tracer_intersect_all", "rt_tracer_intersect_all_device",
     "rt_tracer_closest_point", "rt_tracer_closest_point_device",
+    "rt_tracer_closest_all", "rt_tracer_closest_all_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
     "rt_tracer_set_query_accel_update", "rt_tracer_query_accel_rebuild", "rt_tracer_query_accel_update_info",
     "rt_dbg_bvh_refit", "rt_dbg_query_tree_read", "rt_dbg_bvh_tree_cost",
@@ -273,6 +274,8 @@ def load_library():
         L.rt_tracer_intersect_all_device.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
         L.rt_tracer_closest_point.argtypes = [vp, vp, C.c_size_t, vp]
         L.rt_tracer_closest_point_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.rt_tracer_closest_all.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
+        L.rt_tracer_closest_all_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
         L.rt_tracer_set_query_accel.argtypes = [vp, C.c_uint32]
         L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_dbg_query_accel_slack.argtypes = [vp, C.c_uint32]
@@ -789,6 +792,107 @@ class RayTracer:
         self._check(self._lib.rt_tracer_closest_point_device(self._h, points.data_ptr(), points.shape[0], hits.data_ptr(),
                                                              C.c_void_p(stream)))
         return hits
+
+    # ---- the k nearest primitives (rt_tracer_closest_all / _device) ------------------------------------------------------
+    def ClosestAll(self, points, max_hits=RT_MAX_HITS, max_distance=np.inf, after=None):
+        """The max_hits nearest primitives of the scene to each point, in order.  points and max_distance as ClosestPoint takes
+        them; 1 <= max_hits <= RT_MAX_HITS.  Row i holds the point's counts[i] <= max_hits nearest accepted primitives in
+        ascending t (equal t by ascending prim), then records {0, 0, 0, PRIM_NONE}; record 0 is ClosestPoint's answer.
+        counts[i] == max_hits means there may be more: call again with after[i] = the row's last record (ClosestWithin does).
+        after: the cursor, one record per point -- only candidates that sort strictly behind (after.t, after.prim) are
+        accepted; a record with prim PRIM_NONE is no cursor.  A numpy array -> (hits (n, max_hits) HIT_DTYPE, counts (n,)
+        uint32), on return; after is then a HIT_DTYPE (n,) array.  A torch float32 tensor on the tracer's device -> ((n,
+        max_hits, 4) float32 {t, u, v, prim bits}, (n,) int32), enqueued on torch.cuda.current_stream() without a host
+        synchronisation; after is then a contiguous (n, 4) float32 tensor."""
+        if type(points).__module__.startswith("torch"):
+            return self._closest_all_tensor(points, max_hits, max_distance, after)
+        p = np.asarray(points, np.float32)
+        if p.ndim == 0 or p.shape[-1] not in (3, 4):
+            raise ValueError("ClosestAll: expected (n, 3) or (n, 4) float32 points, got shape %s" % (p.shape,))
+        k = self._nearest_max_hits(max_hits)
+        if p.shape[-1] == 3:
+            q = np.empty(p.shape[:-1] + (4,), np.float32)
+            q[..., :3], q[..., 3] = p, self._d2max(max_distance)
+            p = q
+        p = np.ascontiguousarray(p).reshape(-1, 4)
+        a = None
+        if after is not None:
+            a = np.ascontiguousarray(np.asarray(after).reshape(-1))
+            if a.dtype != HIT_DTYPE or a.shape[0] != p.shape[0]:
+                raise ValueError("ClosestAll: after must be a HIT_DTYPE array with one record per point")
+        hits = np.zeros((p.shape[0], k), HIT_DTYPE)
+        counts = np.zeros(p.shape[0], np.uint32)
+        self._check(self._lib.rt_tracer_closest_all(self._h, p.ctypes.data, None if a is None else a.ctypes.data, p.shape[0], k,
+                                                    hits.ctypes.data, counts.ctypes.data))
+        return hits, counts
+
+    @staticmethod
+    def _nearest_max_hits(max_hits):
+        k = int(max_hits)
+        if k != max_hits or not 1 <= k <= RT_MAX_HITS:
+            raise ValueError("ClosestAll: max_hits = %r (1 to %d)" % (max_hits, RT_MAX_HITS))
+        return k
+
+    def _closest_all_tensor(self, points, max_hits=RT_MAX_HITS, max_distance=np.inf, after=None):
+        import torch
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
+            raise ValueError("ClosestAll: expected an (n, 3) or (n, 4) float32 tensor")
+        k = self._nearest_max_hits(max_hits)
+        dev = self.Bands()[0]["device"]
+        if points.device.type != "cuda" or points.device.index != dev:
+            raise ValueError("ClosestAll: the points are on %s, the tracer on cuda:%d" % (points.device, dev))
+        if points.shape[1] == 3:
+            q = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+            q[:, :3] = points
+            q[:, 3] = float(self._d2max(max_distance))
+            points = q
+        elif not points.is_contiguous():
+            raise ValueError("ClosestAll: expected a contiguous (n, 4) float32 tensor")
+        if after is not None:
+            if (not type(after).__module__.startswith("torch") or after.dtype != torch.float32 or after.dim() != 2 or
+                    tuple(after.shape) != (points.shape[0], 4) or not after.is_contiguous() or after.device != points.device):
+                raise ValueError("ClosestAll: after must be a contiguous (n, 4) float32 tensor on the points' device")
+        hits = torch.empty((points.shape[0], k, 4), dtype=torch.float32, device=points.device)
+        counts = torch.empty((points.shape[0],), dtype=torch.int32, device=points.device)
+        stream = torch.cuda.current_stream(points.device).cuda_stream
+        self._check(self._lib.rt_tracer_closest_all_device(self._h, points.data_ptr(), None if after is None else after.data_ptr(),
+                                                           points.shape[0], k, hits.data_ptr(), counts.data_ptr(),
+                                                           C.c_void_p(stream)))
+        return hits, counts
+
+    def ClosestWithin(self, points, max_distance, max_hits=RT_MAX_HITS):
+        """Every primitive within max_distance of each point (the sphere-overlap query), numpy only: ClosestAll repeated with
+        the cursor until every count is below max_hits.  points: (n, 3) with max_distance, or (n, 4) with the squared radius of
+        each point in column 3 (max_distance is then not used).  Returns (hits, offsets): the accepted primitives of all
+        points, flat, HIT_DTYPE, each point's in ascending (t, prim) order; point i's are hits[offsets[i]:offsets[i + 1]],
+        offsets (n + 1,) int64."""
+        p = np.asarray(points, np.float32)
+        if p.ndim == 0 or p.shape[-1] not in (3, 4):
+            raise ValueError("ClosestWithin: expected (n, 3) or (n, 4) float32 points, got shape %s" % (p.shape,))
+        k = self._nearest_max_hits(max_hits)
+        if p.shape[-1] == 3:
+            q = np.empty(p.shape[:-1] + (4,), np.float32)
+            q[..., :3], q[..., 3] = p, self._d2max(max_distance)
+            p = q
+        p = np.ascontiguousarray(p).reshape(-1, 4)
+        n = p.shape[0]
+        live = np.arange(n)                                                # the points that may have more
+        after = None
+        parts, owners = [], []
+        while live.size:
+            hits, counts = self.ClosestAll(p[live], k, after=after)
+            keep = np.arange(k)[None, :] < counts[:, None]
+            parts.append(hits[keep])
+            owners.append(np.repeat(live, counts))
+            more = counts == k
+            after = np.ascontiguousarray(hits[more, k - 1])
+            live = live[more]
+        owner = np.concatenate(owners) if owners else np.zeros(0, np.int64)
+        flat = np.concatenate(parts) if parts else np.zeros(0, HIT_DTYPE)
+        order = np.argsort(owner, kind="stable")                           # rounds are in order within a point already
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(np.bincount(owner, minlength=n), out=offsets[1:])
+        return flat[order], offsets
 
     def ClosestPositions(self, points, hits):
         """The nearest points themselves, (n, 3) float32: v0 + u*e1 + v*e2 of the winning triangle's record (fp32, from this

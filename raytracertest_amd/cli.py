@@ -1,6 +1,6 @@
 """Headless front end: `python -m raytracertest_amd.cli`.  The reference's command line
 (OpenGLView/App.cpp:62-184: -w -h -s -i -u -cx -cy -cz -cxa -cya -f -l -a, integer values,
-defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --focus; the image is saved
+defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --nearest X,Y,Z / --focus; the image is saved
 in the reference's BMP format (Common/Bitmap.h).  Same options as tools/rt_cli.cpp."""
 import argparse
 import math
@@ -31,7 +31,10 @@ def build_parser():
     p.add_argument("--scene", default="demo3", help="demo3 | cornell32 | rand10k | sphere1 | uvsphere | <file.f4> (raw float32 x,y,z,w)")
     p.add_argument("--edges", action="store_true", help="the scene file holds (v0, e0, e1) rows with packed vertex normals in .w")
     p.add_argument("--smooth", action="store_true", help="shade with the interpolated vertex normals (edge-format scenes)")
-    p.add_argument("--nearest", action="store_true", help="keep the nearest hit with t > 0 instead of the reference's farthest")
+    p.add_argument("--nearest", action=_Nearest, nargs="?", default=False, metavar="X,Y,Z[,R[,K]]",
+                   help="alone: keep the nearest hit with t > 0 instead of the reference's farthest.  With a value: print one line "
+                        "`prim distance u v` per primitive near the point X,Y,Z, nearest first (within the distance R; at most K, "
+                        "default 8)")
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("-o", default="image0.bmp", dest="out")
     p.add_argument("-q", action="store_true", dest="quiet")
@@ -41,7 +44,7 @@ def build_parser():
                    help="print one line `prim t u v` per hit of the pixel's pinhole ray, in order, over all t (at most K, default 8)")
     p.add_argument("--closest", type=_xyzr, default=None, metavar="X,Y,Z[,R]",
                    help="print `closest prim distance x y z`: the nearest surface point to the point X,Y,Z (within the distance R)")
-    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --focus through the scene's BVH instead of the scan")
+    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan")
     p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
                    help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
     return p
@@ -66,6 +69,30 @@ def _xyzr(s):
     return v[0], v[1], v[2], v[3] if len(v) == 4 else math.inf
 
 
+def _xyzrk(s):
+    v = s.split(",")
+    if len(v) not in (3, 4, 5):
+        raise ValueError(s)
+    k = int(v[4]) if len(v) == 5 else 8
+    if k < 0:
+        raise ValueError(s)
+    f = [float(x) for x in v[:4]]
+    return f[0], f[1], f[2], f[3] if len(f) == 4 else math.inf, k
+
+
+class _Nearest(argparse.Action):
+    """--nearest alone is the hit rule (a flag, as it always was); --nearest X,Y,Z[,R[,K]] is the k-nearest point query."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        if values is None:
+            namespace.nearest = True
+            return
+        try:
+            namespace.nearest_query = _xyzrk(values)
+        except ValueError:
+            parser.error("--nearest wants X,Y,Z[,R[,K]]")
+
+
 def load_scene(name):
     from . import scenes
     z = np.zeros((0, 4), np.float32)
@@ -85,6 +112,7 @@ def load_scene(name):
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    knn = getattr(a, "nearest_query", None)
     from . import RayTracer
     from .bitmap import write_bmp
     rad = np.float32(0.01745329251994329576923690768489)
@@ -122,6 +150,13 @@ def main(argv=None):
             print("closest -1")
         else:
             print("closest %d %.9g %.9g %.9g %.9g" % (h["prim"][0], np.sqrt(h["t"][0]), q[0], q[1], q[2]))
+    if knn is not None:
+        try:
+            hits, counts = g.ClosestAll(np.float32([knn[:3]]), knn[4], knn[3])
+        except Exception as e:
+            sys.exit("--nearest: %s" % e)
+        for h in hits[0, :counts[0]]:
+            print("%d %.9g %.9g %.9g" % (h["prim"], np.sqrt(h["t"]), h["u"], h["v"]))
     if a.focus is not None:
         try:
             f = g.FocusAt(*a.focus)

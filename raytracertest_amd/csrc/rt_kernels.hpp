@@ -182,6 +182,16 @@ uint32_t closest_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_closest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, float4* hits,
                               hipStream_t st);
 
+// The k-nearest point query (rt_nearest.hpp): the same points; after (or nullptr) n cursor records, 16-byte aligned; row i of
+// hits (max_hits records) holds the point's counts[i] <= max_hits nearest accepted candidates behind its cursor in ascending
+// (t, prim) order, then records {0, 0, 0, -1}.  1 <= max_hits <= 16; one point per lane in both forms.
+uint32_t nearest_lds_bytes(uint32_t n_tris);
+hipError_t launch_nearest(const TraceParams& p, uint32_t n, const float* pts, const float4* after, uint32_t max_hits, float4* hits,
+                          uint32_t* counts, hipStream_t st);
+uint32_t nearest_bvh_lds_bytes(uint32_t stack_cap);
+hipError_t launch_nearest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, const float4* after,
+                              uint32_t max_hits, float4* hits, uint32_t* counts, hipStream_t st);
+
 // Refit of that tree on the device (rt_refit.hpp): the records of the current scene into their slots (flag: set to 1 when a
 // slot's triangle changed between finite and non-finite), the boxes of one level's nodes (deepest level first), the tree's cost.
 hipError_t launch_refit_gather(const float4* tri_a, const float* tri_b, uint32_t n_tris, float4* records, uint32_t n_leaf_records,

@@ -1,6 +1,6 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
-// rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_intersect_all*) and the point query (rt_tracer_closest_point*).  Included
-// by rt_tracer.hip.
+// rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_intersect_all*) and the point queries (rt_tracer_closest_point*,
+// rt_tracer_closest_all*).  Included by rt_tracer.hip.
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
 // calls by api_mu, reads only the scene and a snapshot of the camera (params(), under state_mu), and runs on a stream of its
@@ -196,6 +196,26 @@ inline void enqueue_closest(rt_tracer* t, size_t n, const float* pts, float4* hi
     HIP_CHECK(rtk::launch_closest_bvh(p, b, rho_c, static_cast<uint32_t>(n), pts, hits, st));
   } else {
     HIP_CHECK(rtk::launch_closest(p, static_cast<uint32_t>(n), pts, hits, st));
+  }
+  HIP_CHECK(hipEventRecord(t->query_done, st));
+}
+
+// points (and their cursors, or nullptr) -> rows of max_hits records and one count per point on `st`, under enqueue_closest's
+// event discipline, tree and rho_c.
+inline void enqueue_closest_all(rt_tracer* t, size_t n, const float* pts, const float4* after, uint32_t max_hits, float4* hits,
+                                uint32_t* counts, hipStream_t st) {
+  rtk::TraceParams p = t->params(1);
+  p.flags = 0u;
+  const bool bvh = t->query_accel == RT_QUERY_BVH;
+  if (bvh) ensure_query_tree(t);
+  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
+  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
+  if (bvh) {
+    const rtk::BvhParams b = query_bvh_params(t);
+    const float rho_c = RT_CLOSEST_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f);
+    HIP_CHECK(rtk::launch_nearest_bvh(p, b, rho_c, static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st));
+  } else {
+    HIP_CHECK(rtk::launch_nearest(p, static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st));
   }
   HIP_CHECK(hipEventRecord(t->query_done, st));
 }
@@ -538,6 +558,57 @@ int rt_tracer_closest_point_device(rt_tracer* t, const float* pts, size_t n, rt_
     if (n == 0u) return;
     t->use_device();
     enqueue_closest(t, n, pts, reinterpret_cast<float4*>(out), static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_closest_all(rt_tracer* t, const float* pts, const rt_hit* after, size_t n, uint32_t max_hits, rt_hit* hits,
+                          uint32_t* counts) {
+  if (!t) return RT_ERR_INVALID;
+  if (!intersect_all_args_ok(t, "rt_tracer_closest_all", n, pts, max_hits, hits, counts)) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_closest_all(t->mg->bands[0], pts, after, n, max_hits, hits, counts);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    const hipStream_t st = query_stream(t);
+    t->d_q_points.ensure(n);
+    if (after) t->d_q_after.ensure(n);
+    t->d_q_all_hits.ensure(n * max_hits);
+    t->d_q_all_counts.ensure(n);
+    HIP_CHECK(hipMemcpyAsync(t->d_q_points.get(), pts, n * 4u * sizeof(float), hipMemcpyHostToDevice, st));
+    if (after) HIP_CHECK(hipMemcpyAsync(t->d_q_after.get(), after, n * sizeof(rt_hit), hipMemcpyHostToDevice, st));
+    enqueue_closest_all(t, n, reinterpret_cast<const float*>(t->d_q_points.get()), after ? t->d_q_after.get() : nullptr, max_hits,
+                        t->d_q_all_hits.get(), t->d_q_all_counts.get(), st);
+    HIP_CHECK(hipMemcpyAsync(hits, t->d_q_all_hits.get(), n * max_hits * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(counts, t->d_q_all_counts.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_closest_all_device(rt_tracer* t, const float* pts, const rt_hit* after, size_t n, uint32_t max_hits, rt_hit* hits,
+                                 uint32_t* counts, void* stream) {
+  if (!t) return RT_ERR_INVALID;
+  if (!intersect_all_args_ok(t, "rt_tracer_closest_all_device", n, pts, max_hits, hits, counts)) return RT_ERR_INVALID;
+  if (n != 0u && (reinterpret_cast<uintptr_t>(pts) % 16u != 0u || reinterpret_cast<uintptr_t>(after) % 16u != 0u ||
+                  reinterpret_cast<uintptr_t>(hits) % 16u != 0u || reinterpret_cast<uintptr_t>(counts) % 4u != 0u)) {
+    t->set_error("rt_tracer_closest_all_device: pts, after and hits must be 16-byte aligned, counts 4-byte aligned");
+    return RT_ERR_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_closest_all_device(t->mg->bands[0], pts, after, n, max_hits, hits, counts, stream);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_closest_all(t, n, pts, reinterpret_cast<const float4*>(after), max_hits, reinterpret_cast<float4*>(hits), counts,
+                        static_cast<hipStream_t>(stream));
   });
 }
 

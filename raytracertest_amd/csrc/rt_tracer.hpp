@@ -582,6 +582,7 @@ struct rt_tracer {
   rtr::DevArray<float4> d_q_all_hits; // rt_tracer_intersect_all: n x max_hits records and n counts out
   rtr::DevArray<uint32_t> d_q_all_counts;
   rtr::DevArray<float4> d_q_points;   // rt_tracer_closest_point: n x {x, y, z, d2max} in, n records (d_q_hits) out
+  rtr::DevArray<float4> d_q_after;    // rt_tracer_closest_all: n cursor records in (rows and counts: d_q_all_hits, d_q_all_counts)
   rtr::Event query_done;
   void wait_queries() { if (query_done) HIP_CHECK(hipEventSynchronize(query_done)); }
   // RT_QUERY_BVH (rt_bvh_host.hpp, rt_bvh.hpp): the tree of the scene of generation bvh_scene, built by the first query in

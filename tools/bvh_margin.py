@@ -8,7 +8,9 @@ At slack 0 the boxes are bare: differences there are expected (wrong answers, no
 --closest: the same sweep for the point query, whose allowance rho_c the same slack scales: ClosestPoint, scan
 against BVH, on 2^LOG2 points of tests/closest_expect.points_for and on the lattice points, C4's scene and the lattice scene;
 there is no conditioning clause, so every differing row counts.  Reports the smallest slack at which BVH still equals scan.
-Usage: bvh_margin.py [--closest] [--out FILE.json] [--rays LOG2]"""
+--nearest: the --closest sweep for the k-nearest query, which prunes with the same allowance against the
+list's last entry: ClosestAll with max_hits 4 and 16, rows and counts, scan against BVH, same points and scenes.
+Usage: bvh_margin.py [--closest | --nearest] [--out FILE.json] [--rays LOG2]"""
 import argparse
 import json
 import os
@@ -57,16 +59,52 @@ def closest_margin(R, scenes, log2_points):
     return res
 
 
+def nearest_margin(R, scenes, log2_points):
+    import closest_expect as ce
+    import lattice_cases as lc
+    res = {"version": R.api.load_library().rt_version().decode(), "rho_c": 2.0 ** -18, "derived_budget": 19 * 2.0 ** -24,
+           "slacks": list(SLACKS), "max_hits": [4, 16], "scenes": {}}
+    smallest_equal = {}
+    for name, rows in (("c4_10k", scenes.random_triangles(10000, 12345)), ("lattice_rooms", lc.rooms())):
+        g = R.RayTracer((64, 48), (0, 0, 0), (0.0, 0.0), 70.0, 3.0, 0.05, seed=1)
+        assert g.UploadScene(rows)
+        pts = ce.points_for(rows, 1 << log2_points, seed=81, spread=4.0)
+        if name == "lattice_rooms":
+            pts = np.concatenate([ce.lattice_points(), pts])
+        median = np.float32(np.median(g.ClosestPoint(pts)["t"]))
+        batches = {"unbounded": ce.with_radius(pts, np.inf), "median": ce.with_radius(pts, median)}
+        scan = {(k, m): g.ClosestAll(p, m) for k, p in batches.items() for m in (4, 16)}
+        g.SetQueryAcceleration(True)
+        out, equal = {}, []
+        for slack in SLACKS:
+            g.DebugQueryAccelSlack(slack)
+            per = {}
+            for (k, m), (hits, counts) in scan.items():
+                got, got_counts = g.ClosestAll(batches[k], m)
+                differ = (got.view(np.uint32).reshape(-1, 4 * m) != hits.view(np.uint32).reshape(-1, 4 * m)).any(axis=1)
+                per["%s_%d" % (k, m)] = {"points": int(hits.shape[0]), "rows_differ": int(differ.sum()),
+                                         "counts_differ": int((got_counts != counts).sum())}
+            out[str(slack)] = per
+            if all(v["rows_differ"] == 0 and v["counts_differ"] == 0 for v in per.values()):
+                equal.append(slack)
+        smallest_equal[name] = min(equal) if equal else None
+        res["scenes"][name] = out
+        g.close()
+    res["smallest_slack_milli_at_which_bvh_equals_scan"] = smallest_equal
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rays", type=int, default=18)
     ap.add_argument("--closest", action="store_true")
+    ap.add_argument("--nearest", action="store_true")
     a = ap.parse_args()
     import raytracertest_amd as R
     from raytracertest_amd import scenes
-    if a.closest:
-        txt = json.dumps(closest_margin(R, scenes, a.rays), indent=1)
+    if a.closest or a.nearest:
+        txt = json.dumps((nearest_margin if a.nearest else closest_margin)(R, scenes, a.rays), indent=1)
         print(txt)
         if a.out:
             with open(a.out, "w") as f:

@@ -27,8 +27,10 @@ struct Args {
   uint64_t seed = 0; bool have_seed = false;
   std::string scene = "demo3", scene_file, out = "image0.bmp";
   bool quiet = false, edges = false, smooth = false, nearest = false;
-  bool pick = false, focus = false, accel = false, hits = false, closest = false;
+  bool pick = false, focus = false, accel = false, hits = false, closest = false, knn = false;
   float closest_p[4] = {0, 0, 0, INFINITY};        // x, y, z, search distance
+  float knn_p[4] = {0, 0, 0, INFINITY};            // --nearest X,Y,Z[,R[,K]]: x, y, z, search distance
+  uint32_t knn_k = 8;
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0}, hits_xy[2] = {0, 0}, hits_k = 8;
 };
 
@@ -70,6 +72,25 @@ bool parse_xyzr(const char* s, float out[4]) {
   }
 }
 
+// "X,Y,Z", "X,Y,Z,R" or "X,Y,Z,R,K": a point, an optional search distance and an optional record count
+bool parse_xyzrk(const char* s, float out[4], uint32_t& k) {
+  const std::string v = s;
+  size_t commas = 0, last = std::string::npos;
+  for (size_t i = 0; i < v.size(); ++i) if (v[i] == ',') { ++commas; last = i; }
+  if (commas < 4) return parse_xyzr(s, out);
+  char* end = nullptr;
+  const unsigned long kk = std::strtoul(v.c_str() + last + 1, &end, 10);
+  if (commas != 4 || end == v.c_str() + last + 1 || *end != 0 || v[last + 1] == '-') return false;
+  k = static_cast<uint32_t>(kk);
+  return parse_xyzr(v.substr(0, last).c_str(), out);               // (three commas left: four numbers or a failure)
+}
+
+// what follows --nearest is the point of a k-nearest query (a number), not the next option
+bool looks_like_number(const char* s) {
+  if (*s == '+' || *s == '-') ++s;
+  return (*s >= '0' && *s <= '9') || (*s == '.' && s[1] >= '0' && s[1] <= '9');
+}
+
 std::vector<float4> demo3() {                   // MainFrame.cpp:230-232
   return {make_float4(0, 0, 10, 1), make_float4(0, 1, 10, 0), make_float4(1, 0, 10, 0),
           make_float4(1, 0, 10, 0), make_float4(0, 1, 10, 1), make_float4(1, 1, 10, 0),
@@ -94,13 +115,15 @@ void usage() {
             "       [--focal F] [--aperture A] [--fov F]                                  (float forms)\n"
             "       [--scene demo3|<file.f4>] [--seed N] [-o out.bmp] [-q]\n"
             "       [--edges] (file holds (v0,e0,e1) rows, packed vertex normals in .w)  [--smooth] [--nearest]\n"
+            "       [--nearest X,Y,Z[,R[,K]]] (with a value: prints one line `prim distance u v` per primitive near the point\n"
+            "                      X,Y,Z, nearest first, within the distance R when given; at most K, default 8)\n"
             "       [--pick X,Y]  (prints `pick x y prim t u v` for the pixel's pinhole ray)\n"
             "       [--hits X,Y[,K]] (prints one line `prim t u v` per hit of the pixel's pinhole ray, in order, over all t;\n"
             "                      at most K, default 8)\n"
             "       [--closest X,Y,Z[,R]] (prints `closest prim distance x y z`: the nearest surface point to the point X,Y,Z,\n"
             "                      within the distance R when given; `closest -1` when there is none)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
-            "       [--accel]     (--pick / --hits / --closest / --focus through the scene's BVH instead of the scan)");
+            "       [--accel]     (--pick / --hits / --closest / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan)");
 }
 
 }  // namespace
@@ -135,6 +158,10 @@ int main(int argc, char** argv) {
     else if (k == "--seed") { a.seed = std::strtoull(next("--seed"), nullptr, 10); a.have_seed = true; }
     else if (k == "--edges") a.edges = true;
     else if (k == "--smooth") a.smooth = true;
+    else if (k == "--nearest" && i + 1 < argc && looks_like_number(argv[i + 1])) {
+      if (!parse_xyzrk(next("--nearest"), a.knn_p, a.knn_k)) { std::fprintf(stderr, "--nearest wants X,Y,Z[,R[,K]]\n"); return 2; }
+      a.knn = true;
+    }
     else if (k == "--nearest") a.nearest = true;
     else if (k == "--accel") a.accel = true;
     else if (k == "--pick" || k == "--focus") {
@@ -227,6 +254,19 @@ int main(int argc, char** argv) {
       std::printf("closest %d %.9g %.9g %.9g %.9g\n", h.prim, static_cast<double>(std::sqrt(h.t)), static_cast<double>(q[0]),
                   static_cast<double>(q[1]), static_cast<double>(q[2]));
     }
+  }
+  if (a.knn) {
+    const float r = a.knn_p[3];
+    const std::vector<float> pts = {a.knn_p[0], a.knn_p[1], a.knn_p[2], std::copysign(r * r, r)};
+    std::vector<rt_hit> hits;
+    std::vector<uint32_t> counts;
+    if (!tracer.ClosestAll(pts, a.knn_k, hits, counts)) {
+      std::fprintf(stderr, "rt_cli: --nearest: %s\n", a.knn_k == 0 || a.knn_k > RT_MAX_HITS ? "K out of range" : tracer.LastError().c_str());
+      return 1;
+    }
+    for (uint32_t j = 0; j < counts[0]; ++j)
+      std::printf("%d %.9g %.9g %.9g\n", hits[j].prim, static_cast<double>(std::sqrt(hits[j].t)), static_cast<double>(hits[j].u),
+                  static_cast<double>(hits[j].v));
   }
   if (a.focus) {
     float focal = 0.0f;
