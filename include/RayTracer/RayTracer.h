@@ -165,6 +165,34 @@ public:
     if (!ClosestAll(pts, maxHits, hits, counts)) hits.clear();
     return hits;
   }
+  // Signed point query (rt_mi355x.h, rt_tracer_signed_distance): the same points; hits is ClosestPoint's answer bit for bit,
+  // sides[i].s > 0 in front of the nearest surface (outside a closed, outward-wound mesh), < 0 behind it, 0 on it or undecided;
+  // sides[i].feature names the face, vertex or edge that holds the nearest point (RT_FEATURE_SPHERE for a sphere,
+  // RT_FEATURE_NONE with s = 0 when nothing lies within the radius).  The signed distance is copysign(sqrt(hits[i].t),
+  // sides[i].s).  A vector whose size is no multiple of 4: false, the outputs untouched.
+  bool SignedDistance(const std::vector<float>& pts, std::vector<rt_hit>& hits, std::vector<rt_side>& sides) {
+    if (!mImpl || pts.size() % 4 != 0) return false;
+    hits.resize(pts.size() / 4);
+    sides.resize(pts.size() / 4);
+    return rt_tracer_signed_distance(mImpl, pts.data(), hits.size(), hits.data(), sides.data()) == RT_OK;
+  }
+  // The same, returning the sides: empty when the vector was rejected or the call failed (LastError()).
+  std::vector<rt_side> SignedDistance(const std::vector<float>& pts) {
+    std::vector<rt_hit> hits;
+    std::vector<rt_side> sides;
+    if (!SignedDistance(pts, hits, sides)) sides.clear();
+    return sides;
+  }
+  // The sides of records the caller has: hits holds perPoint records per point (1 for ClosestPoint's answers, maxHits for
+  // ClosestAll's rows; unfilled records come back as {0, RT_FEATURE_NONE}).  Sizes that do not fit: false, sides untouched.
+  bool ClosestSides(const std::vector<float>& pts, const std::vector<rt_hit>& hits, std::vector<rt_side>& sides) {
+    if (!mImpl || pts.size() % 4 != 0) return false;
+    const size_t n = pts.size() / 4;
+    if (n == 0) { if (!hits.empty()) return false; sides.clear(); return true; }
+    if (hits.size() % n != 0 || hits.size() / n == 0 || hits.size() / n > RT_MAX_HITS) return false;
+    sides.resize(hits.size());
+    return rt_tracer_closest_sides(mImpl, pts.data(), hits.data(), n, static_cast<uint32_t>(hits.size() / n), sides.data()) == RT_OK;
+  }
   // The pinhole ray of a full-image pixel; `ray` (origin, direction) when asked for: the hit point is o + t * d.
   bool Pick(const math::uvec2& pixel, rt_hit& hit) { return Pick(pixel, hit, nullptr); }
   bool Pick(const math::uvec2& pixel, rt_hit& hit, math::vec3 ray[2]) {

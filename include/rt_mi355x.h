@@ -460,6 +460,67 @@ int  rt_tracer_closest_all(rt_tracer* t, const float* pts, const rt_hit* after, 
 int  rt_tracer_closest_all_device(rt_tracer* t, const float* pts, const rt_hit* after, size_t n, uint32_t max_hits, rt_hit* hits,
                                   uint32_t* counts, void* stream);
 
+/* ---- signed point queries ------------------------------------------------------------------------
+ * Which side of the nearest surface a point lies on (is it inside the mesh, how far has a contact penetrated, which side of a
+ * wall is the camera on, sampling a signed distance field).  The hit half of the answer IS rt_tracer_closest_point's answer; the
+ * side half is a post-pass over those records (one kernel, one lane per record), so the searches are the point queries' own.
+ *   pts         n x 4 floats, exactly as rt_tracer_closest_point takes them: x, y, z, d2max (the SQUARED search radius).
+ *   hits        hits[i] is bit for bit rt_tracer_closest_point's out[i] in the current query mode.
+ *   sides       sides[i] = rt_side {s, feature} of hits[i]:
+ *     triangle  the triangle rule of rt_tracer_closest_point is evaluated again on the record of hits[i].prim -- the same
+ *               operations on the same operands, so the same region and the same residual r = (ap - u*e1) - v*e2 per component.
+ *               feature = the part of the triangle that holds the nearest point: RT_FEATURE_FACE 0 (region 7); 1, 2, 3 the
+ *               vertices A = v0, B = v0 + e1, C = v0 + e2 (regions 1, 2, 4); 4, 5, 6 the edges AB, AC, BC (regions 3, 5, 6).
+ *               N = the fp32 unit normal of that feature in the scene's feature table (below), and
+ *                 s = (r.x*N.x + r.y*N.y) + r.z*N.z
+ *               every operation one separately rounded fp32 operation, the same in RT_MATH_FMA and RT_MATH_STRICT.
+ *     sphere    feature = RT_FEATURE_SPHERE 7, w = p - centre, s = sqrt(w.w) - radius with the correctly rounded sqrt (the
+ *               operands of the point query's sphere rule, without the absolute value).
+ *     none      hits[i].prim == RT_PRIM_NONE (or any prim outside the scene): {0, RT_FEATURE_NONE}.
+ *   reading s   s > 0: the front side of the surface (outside, for a closed mesh wound outward); s < 0: the back side; s == 0:
+ *               on the surface, or undecided (a degenerate feature has the zero normal).  No epsilon is applied.  The signed
+ *               distance is copysign(sqrt(hits[i].t), s), for the caller to form.
+ *   feature table   seven unit normals per triangle in the order above (7 x 16 bytes, .w = 0): the angle-weighted pseudonormals of
+ *               Baerentzen & Aanaes, whose dot product with p - c has the right sign at faces, edges and vertices alike (a face
+ *               normal alone gives the wrong sign at a sharp convex vertex or a concave edge).  Computed in float64 from the
+ *               uploaded fp32 positions, each component rounded to fp32 at the end:
+ *                 face    (B - A) x (C - A), normalised.  A triangle whose cross product is zero or not finite contributes
+ *                         nothing anywhere and its own face entry is the zero vector.
+ *                 vertex  the sum over the incident contributing triangles, in ascending triangle index, of (the interior angle
+ *                         at the vertex, atan2(|a x b|, a . b) of its two edge vectors) * (the unit face normal), normalised.
+ *                 edge    the sum of the unit face normals of all contributing triangles that share the undirected edge, in
+ *                         ascending index, normalised (one triangle at a boundary edge, three or more at a non-manifold one).
+ *                 a zero sum gives the zero vector.
+ *               Vertices are welded by their exact fp32 bits, -0 taken as +0: the uploaded absolute vertex for
+ *               rt_tracer_upload_scene; fp32 v0, v0 + e0, v0 + e1 for rt_tracer_upload_scene_edges.  The tracer keeps one host
+ *               copy of the rows of its last upload for this.  The table is built on the host by the first signed query after
+ *               an upload and uploaded once; RT_ACCEL_REFIT does not refit it, it is rebuilt.
+ * No scene: every answer is {0, 0, 0, RT_PRIM_NONE} and {0, RT_FEATURE_NONE}; spheres alone can win; n = 0 is a no-op; a NULL
+ * array with n > 0 is RT_ERR_INVALID.
+ * Scheduling is that of the ray queries: never cancels or joins a running Trace, serialised with the other calls, on the query
+ * stream or the caller's, waited for by uploads and destroy; a multi-device handle answers from its first band, a band tracer
+ * locally.  RT_QUERY_SCAN and RT_QUERY_BVH decide how hits are found, exactly as for rt_tracer_closest_point; sides are a
+ * function of (point, record, table) and do not depend on the mode. */
+typedef struct rt_side { float s; int32_t feature; } rt_side;   /* 8 bytes */
+#define RT_FEATURE_NONE   (-1)
+#define RT_FEATURE_FACE   0
+#define RT_FEATURE_SPHERE 7
+/* Host arrays: pts n*4, hits n, sides n.  Returns with the answers in host memory. */
+int  rt_tracer_signed_distance(rt_tracer* t, const float* pts, size_t n, rt_hit* hits, rt_side* sides);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation once the scene's table exists.  pts and hits must be 16-byte aligned, sides 8-byte aligned; otherwise
+ * RT_ERR_INVALID. */
+int  rt_tracer_signed_distance_device(rt_tracer* t, const float* pts, size_t n, rt_hit* hits, rt_side* sides, void* stream);
+/* The sides of records the caller already has: hits holds n * per_point records, row i (hits + i * per_point) those of point i
+ * -- per_point = 1 for rt_tracer_closest_point's answers, max_hits for rt_tracer_closest_all's rows, whose unfilled records
+ * {0, 0, 0, RT_PRIM_NONE} come back as {0, RT_FEATURE_NONE}.  per_point outside 1 .. RT_MAX_HITS is RT_ERR_INVALID.  Only prim
+ * of a record is read; sides[j] is what rt_tracer_signed_distance defines for (point j / per_point, hits[j].prim).
+ * Host arrays: pts n*4, hits n*per_point, sides n*per_point. */
+int  rt_tracer_closest_sides(rt_tracer* t, const float* pts, const rt_hit* hits, size_t n, uint32_t per_point, rt_side* sides);
+/* Device pointers, as rt_tracer_signed_distance_device. */
+int  rt_tracer_closest_sides_device(rt_tracer* t, const float* pts, const rt_hit* hits, size_t n, uint32_t per_point, rt_side* sides,
+                                    void* stream);
+
 /* ---- one frame sharded over several GPUs --------------------------------------
  * The reference builds ONE rt::RayTracer pinned to device 0 (OpenGLView/MainFrame.cpp:44-45,
  * OpenGLView/GLCanvas.cpp:259-260).  Pixels are independent and a pixel's RNG stream is keyed by its
@@ -581,6 +642,10 @@ int rt_dbg_classify(rt_tracer* t, uint32_t level, uint32_t forms, uint32_t slack
  *                      are in no box and which every ray tests. */
 int rt_dbg_bvh_build(const rt_float4* rows, size_t count, int edges_layout, void* nodes, size_t node_capacity_bytes,
                      void* leaf_records, size_t leaf_capacity_bytes, uint64_t info[8]);
+/* The feature table of the signed point queries on its own; needs no device.  rows as rt_dbg_bvh_build takes them.  Writes
+ * count / 3 * 7 float4 (112 bytes per triangle) exactly as a tracer uploads them; info = {triangles, welded vertices, undirected
+ * edges, contributing triangles, build us, bytes, 0, 0}.  With capacity_bytes 0 only info is written. */
+int rt_dbg_feature_normals(const rt_float4* rows, size_t count, int edges_layout, void* out, size_t capacity_bytes, uint64_t info[8]);
 /* rtb::refit on its own, the reference of the device refit; needs no device.  nodes (node_bytes = nodes * 128), leaf_records
  * (record_bytes = count / 3 * 48) and info are arrays rt_dbg_bvh_build (or this call) wrote for a scene of as many triangles; rows
  * are the new scene.  In place: the records take the new triangles by upload index, every box and cmax is recomputed, child[] and

@@ -53,6 +53,8 @@ ABI_SYMBOLS = [
     "rt_tracer_intersect_all", "rt_tracer_intersect_all_device",
     "rt_tracer_closest_point", "rt_tracer_closest_point_device",
     "rt_tracer_closest_all", "rt_tracer_closest_all_device",
+    "rt_tracer_signed_distance", "rt_tracer_signed_distance_device",
+    "rt_tracer_closest_sides", "rt_tracer_closest_sides_device", "rt_dbg_feature_normals",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
     "rt_tracer_set_query_accel_update", "rt_tracer_query_accel_rebuild", "rt_tracer_query_accel_update_info",
     "rt_dbg_bvh_refit", "rt_dbg_query_tree_read", "rt_dbg_bvh_tree_cost",
@@ -119,6 +121,23 @@ def tree_cost(nodes):
     return float(L.rt_dbg_bvh_tree_cost(nodes.ctypes.data, nodes.nbytes)) if nodes.shape[0] else 0.0
 # rt_hit: one ray query's answer (include/rt_mi355x.h)
 HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("prim", np.int32)])
+# rt_side: the side half of a signed point query's answer
+SIDE_DTYPE = np.dtype([("s", np.float32), ("feature", np.int32)])
+FEATURE_NONE, FEATURE_FACE, FEATURE_SPHERE = -1, 0, 7
+_FEATURE_KEYS = ("triangles", "vertices", "edges", "contributing", "build_us", "bytes")
+
+
+def feature_normals(rows, edges=False, return_info=False):
+    """rt_dbg_feature_normals: the signed queries' feature table of upload rows (3N, 4), built on the host (no device needed)
+    -> (N, 7, 4) float32: per triangle the unit pseudonormals of the face, the vertices A, B, C and the edges AB, AC, BC
+    (.w = 0).  return_info: also the dict {triangles, vertices, edges, contributing, build_us, bytes}."""
+    L = load_library()
+    r = np.ascontiguousarray(rows, np.float32).reshape(-1, 4)
+    info = (C.c_uint64 * 8)()
+    out = np.zeros((r.shape[0] // 3, 7, 4), np.float32)
+    if L.rt_dbg_feature_normals(r.ctypes.data, r.shape[0], int(bool(edges)), out.ctypes.data, max(out.nbytes, 1), info) != 0:
+        raise RtError("rt_dbg_feature_normals: " + L.rt_last_error().decode())
+    return (out, dict(zip(_FEATURE_KEYS, (int(x) for x in info)))) if return_info else out
 
 
 class Options(C.Structure):
@@ -276,6 +295,11 @@ def load_library():
         L.rt_tracer_closest_point_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.rt_tracer_closest_all.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
         L.rt_tracer_closest_all_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
+        L.rt_tracer_signed_distance.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.rt_tracer_signed_distance_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+        L.rt_tracer_closest_sides.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
+        L.rt_tracer_closest_sides_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
+        L.rt_dbg_feature_normals.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
         L.rt_tracer_set_query_accel.argtypes = [vp, C.c_uint32]
         L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_dbg_query_accel_slack.argtypes = [vp, C.c_uint32]
@@ -893,6 +917,111 @@ class RayTracer:
         offsets = np.zeros(n + 1, np.int64)
         np.cumsum(np.bincount(owner, minlength=n), out=offsets[1:])
         return flat[order], offsets
+
+    # ---- signed point queries (rt_tracer_signed_distance / rt_tracer_closest_sides, and their _device forms) -------------
+    def SignedDistance(self, points, max_distance=np.inf):
+        """ClosestPoint and the side of the nearest surface each point lies on.  points and max_distance as ClosestPoint takes
+        them.  Returns (hits, sides): hits is ClosestPoint's answer bit for bit; sides["s"] > 0 in front of the surface
+        (outside a closed, outward-wound mesh), < 0 behind it, 0 on it or undecided; sides["feature"] is the part of the
+        triangle that holds the nearest point (0 the face, 1-3 the vertices A, B, C, 4-6 the edges AB, AC, BC, FEATURE_SPHERE,
+        or FEATURE_NONE with s = 0 where hits["prim"] is PRIM_NONE).  A numpy array -> (HIT_DTYPE (n,), SIDE_DTYPE (n,)), on
+        return.  A torch float32 tensor on the tracer's device -> ((n, 4) float32 {t, u, v, prim bits}, (n, 2) float32 {s,
+        feature bits}), enqueued on torch.cuda.current_stream() without a host synchronisation (the first signed query after
+        an upload builds the scene's table on the host first)."""
+        if type(points).__module__.startswith("torch"):
+            points = self._points_tensor("SignedDistance", points, max_distance)
+            import torch
+            hits = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+            sides = torch.empty((points.shape[0], 2), dtype=torch.float32, device=points.device)
+            stream = torch.cuda.current_stream(points.device).cuda_stream
+            self._check(self._lib.rt_tracer_signed_distance_device(self._h, points.data_ptr(), points.shape[0], hits.data_ptr(),
+                                                                   sides.data_ptr(), C.c_void_p(stream)))
+            return hits, sides
+        p = self._points_array("SignedDistance", points, max_distance)
+        hits = np.zeros(p.shape[0], HIT_DTYPE)
+        sides = np.zeros(p.shape[0], SIDE_DTYPE)
+        self._check(self._lib.rt_tracer_signed_distance(self._h, p.ctypes.data, p.shape[0], hits.ctypes.data, sides.ctypes.data))
+        return hits, sides
+
+    def ClosestSides(self, points, hits):
+        """The sides of records ClosestPoint or ClosestAll returned for these points: hits of shape (n,) or (n, max_hits)
+        HIT_DTYPE (torch: (n, 4) or (n, max_hits, 4) float32, contiguous) -> SIDE_DTYPE of the same shape (torch: (..., 2)
+        float32 {s, feature bits}).  Unfilled records of a ClosestAll row come back as {0, FEATURE_NONE}.  points: (n, 3) or
+        (n, 4); the radius column is not used."""
+        if type(points).__module__.startswith("torch"):
+            import torch
+            points = self._points_tensor("ClosestSides", points, np.inf)
+            n = points.shape[0]
+            if (not type(hits).__module__.startswith("torch") or hits.dtype != torch.float32 or hits.dim() not in (2, 3) or
+                    hits.shape[0] != n or hits.shape[-1] != 4 or not hits.is_contiguous() or hits.device != points.device):
+                raise ValueError("ClosestSides: hits must be a contiguous (n, 4) or (n, max_hits, 4) float32 tensor on the points' device")
+            k = 1 if hits.dim() == 2 else self._nearest_max_hits(hits.shape[1])
+            sides = torch.empty(tuple(hits.shape[:-1]) + (2,), dtype=torch.float32, device=points.device)
+            stream = torch.cuda.current_stream(points.device).cuda_stream
+            self._check(self._lib.rt_tracer_closest_sides_device(self._h, points.data_ptr(), hits.data_ptr(), n, k, sides.data_ptr(),
+                                                                 C.c_void_p(stream)))
+            return sides
+        p = self._points_array("ClosestSides", points, np.inf)
+        h = np.ascontiguousarray(hits)
+        if h.dtype != HIT_DTYPE or h.ndim not in (1, 2) or h.shape[0] != p.shape[0]:
+            raise ValueError("ClosestSides: expected the HIT_DTYPE answers (n,) or (n, max_hits) of these %d points" % p.shape[0])
+        k = 1 if h.ndim == 1 else self._nearest_max_hits(h.shape[1])
+        sides = np.zeros(h.shape, SIDE_DTYPE)
+        self._check(self._lib.rt_tracer_closest_sides(self._h, p.ctypes.data, h.ctypes.data, p.shape[0], k, sides.ctypes.data))
+        return sides
+
+    def Contains(self, points):
+        """(n,) bool: the point lies behind the nearest surface (SignedDistance's s < 0, unbounded radius) -- inside, for a
+        CLOSED mesh whose triangles are wound consistently outward; meaningless for anything else.  A point on the surface
+        (s == 0) is not contained.  numpy only."""
+        return self.SignedDistance(np.asarray(points, np.float32)[..., :3])[1]["s"] < 0
+
+    def SignedDistances(self, points):
+        """(n,) float32: copysign(sqrt(t), s) of SignedDistance with an unbounded radius, formed on the host -- negative
+        inside a closed, outward-wound mesh; NaN without a scene.  numpy only."""
+        hits, sides = self.SignedDistance(np.asarray(points, np.float32)[..., :3])
+        with np.errstate(invalid="ignore"):
+            d = np.copysign(np.sqrt(hits["t"]), sides["s"]).astype(np.float32)
+        d[hits["prim"] == PRIM_NONE] = np.nan
+        return d
+
+    def DistanceField(self, origin, spacing, shape):
+        """SignedDistances on a regular grid: sample (i, j, k) is at origin + spacing * (i, j, k) (float64 on the host, rounded
+        to fp32); spacing a scalar or one per axis -> float32 array of `shape` (three extents)."""
+        shape = tuple(int(x) for x in shape)
+        if len(shape) != 3 or min(shape) < 0:
+            raise ValueError("DistanceField: shape = %r (three extents)" % (shape,))
+        o = np.asarray(origin, np.float64).reshape(3)
+        sp = np.broadcast_to(np.asarray(spacing, np.float64), (3,))
+        axes = [o[a] + sp[a] * np.arange(shape[a]) for a in range(3)]
+        pts = np.stack(np.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
+        return self.SignedDistances(pts).reshape(shape)
+
+    def _points_array(self, who, points, max_distance):
+        p = np.asarray(points, np.float32)
+        if p.ndim == 0 or p.shape[-1] not in (3, 4):
+            raise ValueError("%s: expected (n, 3) or (n, 4) float32 points, got shape %s" % (who, p.shape))
+        if p.shape[-1] == 3:
+            q = np.empty(p.shape[:-1] + (4,), np.float32)
+            q[..., :3], q[..., 3] = p, self._d2max(max_distance)
+            p = q
+        return np.ascontiguousarray(p).reshape(-1, 4)
+
+    def _points_tensor(self, who, points, max_distance):
+        import torch
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
+            raise ValueError("%s: expected an (n, 3) or (n, 4) float32 tensor" % who)
+        dev = self.Bands()[0]["device"]
+        if points.device.type != "cuda" or points.device.index != dev:
+            raise ValueError("%s: the points are on %s, the tracer on cuda:%d" % (who, points.device, dev))
+        if points.shape[1] == 3:
+            q = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+            q[:, :3] = points
+            q[:, 3] = float(self._d2max(max_distance))
+            return q
+        if not points.is_contiguous():
+            raise ValueError("%s: expected a contiguous (n, 4) float32 tensor" % who)
+        return points
 
     def ClosestPositions(self, points, hits):
         """The nearest points themselves, (n, 3) float32: v0 + u*e1 + v*e2 of the winning triangle's record (fp32, from this

@@ -1,6 +1,6 @@
 """Headless front end: `python -m raytracertest_amd.cli`.  The reference's command line
 (OpenGLView/App.cpp:62-184: -w -h -s -i -u -cx -cy -cz -cxa -cya -f -l -a, integer values,
-defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --nearest X,Y,Z / --focus; the image is saved
+defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --signed / --nearest X,Y,Z / --focus; the image is saved
 in the reference's BMP format (Common/Bitmap.h).  Same options as tools/rt_cli.cpp."""
 import argparse
 import math
@@ -44,7 +44,11 @@ def build_parser():
                    help="print one line `prim t u v` per hit of the pixel's pinhole ray, in order, over all t (at most K, default 8)")
     p.add_argument("--closest", type=_xyzr, default=None, metavar="X,Y,Z[,R]",
                    help="print `closest prim distance x y z`: the nearest surface point to the point X,Y,Z (within the distance R)")
-    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan")
+    p.add_argument("--signed", type=_xyzr, default=None, metavar="X,Y,Z[,R]", dest="signed_query",
+                   help="print `signed prim distance x y z feature s signed_distance`: --closest's answer, the feature of the triangle "
+                        "that holds the nearest point (0 face, 1-3 vertices, 4-6 edges), the side s (> 0 in front of the surface, < 0 "
+                        "behind it) and the distance with that sign")
+    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --signed / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan")
     p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
                    help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
     return p
@@ -150,6 +154,16 @@ def main(argv=None):
             print("closest -1")
         else:
             print("closest %d %.9g %.9g %.9g %.9g" % (h["prim"][0], np.sqrt(h["t"][0]), q[0], q[1], q[2]))
+    if a.signed_query is not None:
+        pt = np.float32([a.signed_query[:3]])
+        h, sd = g.SignedDistance(pt, a.signed_query[3])
+        q = g.ClosestPositions(pt, h)[0]
+        if h["prim"][0] < 0:
+            print("signed -1")
+        else:
+            d = np.sqrt(h["t"][0])
+            print("signed %d %.9g %.9g %.9g %.9g %d %.9g %.9g" % (h["prim"][0], d, q[0], q[1], q[2], sd["feature"][0], sd["s"][0],
+                                                                 np.copysign(d, sd["s"][0])))
     if knn is not None:
         try:
             hits, counts = g.ClosestAll(np.float32([knn[:3]]), knn[4], knn[3])

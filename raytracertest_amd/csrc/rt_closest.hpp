@@ -29,8 +29,10 @@ namespace rtk {
 
 constexpr float kClosestDeflate = 0.999999523162841796875f;   // 1 - 2^-21
 
-// t = squared distance from p to the triangle (v0, e1, e2), (u, v) = the nearest point's barycentrics.
-__device__ __forceinline__ void closest_triangle(V3 p, V3 v0, V3 e1, V3 e2, float& t, float& u, float& v) {
+// t = squared distance from p to the triangle (v0, e1, e2), (u, v) = the nearest point's barycentrics; the residual r = p - c
+// it forms on the way and the feature of the triangle that holds c, in the order of rt_features_host.hpp's table: 0 the face
+// (region 7), 1, 2, 3 the vertices A, B, C (regions 1, 2, 4), 4, 5, 6 the edges AB, AC, BC (regions 3, 5, 6).
+__device__ __forceinline__ void closest_triangle_feature(V3 p, V3 v0, V3 e1, V3 e2, float& t, float& u, float& v, V3& r, int& feature) {
   using M = Math<false>;
   const V3 ap = rtd::sub(p, v0);
   const float a = M::dot(e1, e1), b = M::dot(e1, e2), c = M::dot(e2, e2);
@@ -55,8 +57,16 @@ __device__ __forceinline__ void closest_triangle(V3 p, V3 v0, V3 e1, V3 e2, floa
   else if (r5) { u = 0.0f; v = q; }
   else if (r6) { u = 1.0f - q; v = q; }
   else { u = vb * q; v = vc * q; }
-  const V3 r = {(ap.x - u * e1.x) - v * e2.x, (ap.y - u * e1.y) - v * e2.y, (ap.z - u * e1.z) - v * e2.z};
+  feature = r1 ? 1 : r2 ? 2 : r3 ? 4 : r4 ? 3 : r5 ? 5 : r6 ? 6 : 0;
+  r = {(ap.x - u * e1.x) - v * e2.x, (ap.y - u * e1.y) - v * e2.y, (ap.z - u * e1.z) - v * e2.z};
   t = M::dot(r, r);
+}
+
+// t, u and v alone: what the searches keep
+__device__ __forceinline__ void closest_triangle(V3 p, V3 v0, V3 e1, V3 e2, float& t, float& u, float& v) {
+  V3 r;
+  int feature;
+  closest_triangle_feature(p, v0, e1, e2, t, u, v, r, feature);
 }
 
 // one accepted candidate under the order-free winner rule (best starts at d2max with best_i = -1: t == d2max is accepted)

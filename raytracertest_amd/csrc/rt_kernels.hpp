@@ -192,6 +192,11 @@ uint32_t nearest_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_nearest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, const float4* after,
                               uint32_t max_hits, float4* hits, uint32_t* counts, hipStream_t st);
 
+// The side post-pass (rt_sides.hpp): n points, n * per_point records of them (hits, as the point queries wrote them), the feature
+// table (7 float4 per triangle, rt_features_host.hpp) -> n * per_point {s, feature} pairs of 8 bytes.
+hipError_t launch_sides(const TraceParams& p, const float4* table, uint32_t n, uint32_t per_point, const float* pts, const float4* hits,
+                        void* sides, hipStream_t st);
+
 // Refit of that tree on the device (rt_refit.hpp): the records of the current scene into their slots (flag: set to 1 when a
 // slot's triangle changed between finite and non-finite), the boxes of one level's nodes (deepest level first), the tree's cost.
 hipError_t launch_refit_gather(const float4* tri_a, const float* tri_b, uint32_t n_tris, float4* records, uint32_t n_leaf_records,

@@ -1,6 +1,6 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
 // rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_intersect_all*) and the point queries (rt_tracer_closest_point*,
-// rt_tracer_closest_all*).  Included by rt_tracer.hip.
+// rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*).  Included by rt_tracer.hip.
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
 // calls by api_mu, reads only the scene and a snapshot of the camera (params(), under state_mu), and runs on a stream of its
@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "rt_bvh_host.hpp"
+#include "rt_features_host.hpp"
 
 namespace rtr {
 
@@ -218,6 +219,51 @@ inline void enqueue_closest_all(rt_tracer* t, size_t n, const float* pts, const 
     HIP_CHECK(rtk::launch_nearest(p, static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st));
   }
   HIP_CHECK(hipEventRecord(t->query_done, st));
+}
+
+// The signed queries' feature table (rt_features_host.hpp) of the current scene: built on the host from the
+// tracer's copy of the rows of its last upload by the first signed query after that upload, keyed to scene_generation as
+// ensure_query_tree keys the tree, and uploaded once on the query stream.  Queries in flight may still read the old table: they
+// are waited for before its buffer is rewritten.  RT_ACCEL_REFIT does not apply: the table is rebuilt.
+inline void ensure_feature_table(rt_tracer* t) {
+  if (t->features_valid()) return;
+  const hipStream_t st = query_stream(t);
+  t->wait_queries();
+  t->features_built = false;
+  const size_t n = t->n_tris;
+  if (t->scene_rows.size() != n * 12u) throw HipFail{fmt("signed query: the host copy of the scene holds %zu floats, the scene %zu triangles", t->scene_rows.size(), n)};
+  const rtf::Table tab = rtf::build(t->scene_rows.data(), n, t->scene_rows_edges);
+  t->d_features.ensure(std::max<size_t>(n * rtf::kFeaturesPerTri, 1u));
+  if (n != 0u) {
+    HIP_CHECK(hipMemcpyAsync(t->d_features.get(), tab.normals.data(), tab.bytes(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));                                 // (the host vector goes away; a caller's stream may run the query)
+  }
+  t->features_info[0] = n; t->features_info[1] = tab.vertices; t->features_info[2] = tab.edges; t->features_info[3] = tab.contributing;
+  t->features_info[4] = tab.build_us; t->features_info[5] = tab.bytes();
+  t->features_scene = t->scene_generation;
+  t->features_built = true;
+}
+
+// points and n * per_point records of them -> as many rt_side on `st`, with enqueue_query's event discipline.  The table is
+// valid (ensure_feature_table, called before anything of this query was enqueued: it may wait for the queries in flight).
+inline void enqueue_sides(rt_tracer* t, size_t n, uint32_t per_point, const float* pts, const float4* hits, void* sides, hipStream_t st) {
+  rtk::TraceParams p = t->params(1);
+  p.flags = 0u;
+  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
+  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
+  HIP_CHECK(rtk::launch_sides(p, t->d_features.get(), static_cast<uint32_t>(n), per_point, pts, hits, sides, st));
+  HIP_CHECK(hipEventRecord(t->query_done, st));
+}
+
+inline bool sides_args_ok(rt_tracer* t, const char* who, size_t n, uint32_t per_point, const void* pts, const void* hits, const void* sides) {
+  if (per_point == 0u || per_point > RT_MAX_HITS) {
+    t->set_error(fmt("%s: per_point = %u (1 to %u)", who, per_point, RT_MAX_HITS));
+    return false;
+  }
+  if (n == 0u) return true;
+  if (!pts || !hits || !sides) { t->set_error("query: null array"); return false; }
+  if (n > kQueryMaxRays) { t->set_error(fmt("query: %zu rays (at most %zu)", n, kQueryMaxRays)); return false; }
+  return true;
 }
 
 inline bool query_args_ok(rt_tracer* t, size_t n, const void* a, const void* b) {
@@ -609,6 +655,116 @@ int rt_tracer_closest_all_device(rt_tracer* t, const float* pts, const rt_hit* a
     t->use_device();
     enqueue_closest_all(t, n, pts, reinterpret_cast<const float4*>(after), max_hits, reinterpret_cast<float4*>(hits), counts,
                         static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_signed_distance(rt_tracer* t, const float* pts, size_t n, rt_hit* hits, rt_side* sides) {
+  if (!t) return RT_ERR_INVALID;
+  if (!sides_args_ok(t, "rt_tracer_signed_distance", n, 1u, pts, hits, sides)) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_signed_distance(t->mg->bands[0], pts, n, hits, sides);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    const hipStream_t st = query_stream(t);
+    ensure_feature_table(t);
+    t->d_q_points.ensure(n);
+    t->d_q_hits.ensure(n);
+    t->d_q_sides.ensure(n);
+    HIP_CHECK(hipMemcpyAsync(t->d_q_points.get(), pts, n * 4u * sizeof(float), hipMemcpyHostToDevice, st));
+    enqueue_closest(t, n, reinterpret_cast<const float*>(t->d_q_points.get()), t->d_q_hits.get(), st);
+    enqueue_sides(t, n, 1u, reinterpret_cast<const float*>(t->d_q_points.get()), t->d_q_hits.get(), t->d_q_sides.get(), st);
+    HIP_CHECK(hipMemcpyAsync(hits, t->d_q_hits.get(), n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(sides, t->d_q_sides.get(), n * sizeof(rt_side), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_signed_distance_device(rt_tracer* t, const float* pts, size_t n, rt_hit* hits, rt_side* sides, void* stream) {
+  if (!t) return RT_ERR_INVALID;
+  if (!sides_args_ok(t, "rt_tracer_signed_distance_device", n, 1u, pts, hits, sides)) return RT_ERR_INVALID;
+  if (n != 0u && (reinterpret_cast<uintptr_t>(pts) % 16u != 0u || reinterpret_cast<uintptr_t>(hits) % 16u != 0u ||
+                  reinterpret_cast<uintptr_t>(sides) % 8u != 0u)) {
+    t->set_error("rt_tracer_signed_distance_device: pts and hits must be 16-byte aligned, sides 8-byte aligned");
+    return RT_ERR_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_signed_distance_device(t->mg->bands[0], pts, n, hits, sides, stream);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    ensure_feature_table(t);
+    enqueue_closest(t, n, pts, reinterpret_cast<float4*>(hits), static_cast<hipStream_t>(stream));
+    enqueue_sides(t, n, 1u, pts, reinterpret_cast<const float4*>(hits), sides, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_closest_sides(rt_tracer* t, const float* pts, const rt_hit* hits, size_t n, uint32_t per_point, rt_side* sides) {
+  if (!t) return RT_ERR_INVALID;
+  if (!sides_args_ok(t, "rt_tracer_closest_sides", n, per_point, pts, hits, sides)) return RT_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_closest_sides(t->mg->bands[0], pts, hits, n, per_point, sides);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    const hipStream_t st = query_stream(t);
+    ensure_feature_table(t);
+    t->d_q_points.ensure(n);
+    t->d_q_all_hits.ensure(n * per_point);
+    t->d_q_sides.ensure(n * per_point);
+    HIP_CHECK(hipMemcpyAsync(t->d_q_points.get(), pts, n * 4u * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(t->d_q_all_hits.get(), hits, n * per_point * sizeof(rt_hit), hipMemcpyHostToDevice, st));
+    enqueue_sides(t, n, per_point, reinterpret_cast<const float*>(t->d_q_points.get()), t->d_q_all_hits.get(), t->d_q_sides.get(), st);
+    HIP_CHECK(hipMemcpyAsync(sides, t->d_q_sides.get(), n * per_point * sizeof(rt_side), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_closest_sides_device(rt_tracer* t, const float* pts, const rt_hit* hits, size_t n, uint32_t per_point, rt_side* sides,
+                                   void* stream) {
+  if (!t) return RT_ERR_INVALID;
+  if (!sides_args_ok(t, "rt_tracer_closest_sides_device", n, per_point, pts, hits, sides)) return RT_ERR_INVALID;
+  if (n != 0u && (reinterpret_cast<uintptr_t>(pts) % 16u != 0u || reinterpret_cast<uintptr_t>(hits) % 16u != 0u ||
+                  reinterpret_cast<uintptr_t>(sides) % 8u != 0u)) {
+    t->set_error("rt_tracer_closest_sides_device: pts and hits must be 16-byte aligned, sides 8-byte aligned");
+    return RT_ERR_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (t->mg) {
+    const int rc = rt_tracer_closest_sides_device(t->mg->bands[0], pts, hits, n, per_point, sides, stream);
+    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
+    return rc;
+  }
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    ensure_feature_table(t);
+    enqueue_sides(t, n, per_point, pts, reinterpret_cast<const float4*>(hits), sides, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_dbg_feature_normals(const rt_float4* rows, size_t count, int edges_layout, void* out, size_t capacity_bytes, uint64_t info[8]) {
+  if (!rows || !info || count < 3u || count % 3u != 0u || count / 3u > rtb::kBvhMaxTris) return RT_ERR_INVALID;
+  return guarded(nullptr, [&] {
+    const size_t n = count / 3u;
+    const rtf::Table tab = rtf::build(&rows[0].x, n, edges_layout != 0);
+    info[0] = n; info[1] = tab.vertices; info[2] = tab.edges; info[3] = tab.contributing; info[4] = tab.build_us; info[5] = tab.bytes();
+    info[6] = info[7] = 0u;
+    if (capacity_bytes == 0u) return;                                    // sizes only
+    if (!out || capacity_bytes < tab.bytes()) throw HipFail{fmt("rt_dbg_feature_normals: the table needs %zu bytes", tab.bytes())};
+    memcpy(out, tab.normals.data(), tab.bytes());
   });
 }
 

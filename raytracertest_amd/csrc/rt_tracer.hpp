@@ -583,6 +583,7 @@ struct rt_tracer {
   rtr::DevArray<uint32_t> d_q_all_counts;
   rtr::DevArray<float4> d_q_points;   // rt_tracer_closest_point: n x {x, y, z, d2max} in, n records (d_q_hits) out
   rtr::DevArray<float4> d_q_after;    // rt_tracer_closest_all: n cursor records in (rows and counts: d_q_all_hits, d_q_all_counts)
+  rtr::DevArray<uint2> d_q_sides;     // rt_tracer_signed_distance, rt_tracer_closest_sides: one rt_side per record out
   rtr::Event query_done;
   void wait_queries() { if (query_done) HIP_CHECK(hipEventSynchronize(query_done)); }
   // RT_QUERY_BVH (rt_bvh_host.hpp, rt_bvh.hpp): the tree of the scene of generation bvh_scene, built by the first query in
@@ -595,6 +596,16 @@ struct rt_tracer {
   uint64_t bvh_info[6] = {0, 0, 0, 0, 0, 0};          // nodes, leaves, depth, always-tested, build us, device bytes
   uint32_t bvh_leaf_records = 0;
   bool bvh_valid() const { return bvh_built && bvh_scene == scene_generation; }
+  // The signed queries (rt_features_host.hpp, rt_sides.hpp): the host copy of the rows of the last upload, which
+  // the feature table is welded from, and the table of the scene of generation features_scene, built by the first signed query
+  // after an upload (rt_query_api.hpp, under api_mu).  The buffer is grow-only; a rebuild waits for the queries.
+  std::vector<float> scene_rows;                      // 12 floats per triangle, as uploaded
+  bool scene_rows_edges = false;
+  rtr::DevArray<float4> d_features;                   // 7 float4 per triangle
+  bool features_built = false;
+  uint32_t features_scene = 0;
+  uint64_t features_info[6] = {0, 0, 0, 0, 0, 0};     // triangles, welded vertices, edges, contributing triangles, build us, bytes
+  bool features_valid() const { return features_built && features_scene == scene_generation; }
   // RT_ACCEL_REFIT (rt_refit.hpp): what the next query in RT_QUERY_BVH mode does with a tree of an earlier
   // upload.  bvh_built stays set across uploads -- the device tree keeps its topology, and its record count decides whether
   // a refit may replace the build; rt_tracer_query_accel_rebuild clears it.

@@ -27,8 +27,9 @@ struct Args {
   uint64_t seed = 0; bool have_seed = false;
   std::string scene = "demo3", scene_file, out = "image0.bmp";
   bool quiet = false, edges = false, smooth = false, nearest = false;
-  bool pick = false, focus = false, accel = false, hits = false, closest = false, knn = false;
+  bool pick = false, focus = false, accel = false, hits = false, closest = false, knn = false, sgn = false;
   float closest_p[4] = {0, 0, 0, INFINITY};        // x, y, z, search distance
+  float signed_p[4] = {0, 0, 0, INFINITY};         // --signed: the same
   float knn_p[4] = {0, 0, 0, INFINITY};            // --nearest X,Y,Z[,R[,K]]: x, y, z, search distance
   uint32_t knn_k = 8;
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0}, hits_xy[2] = {0, 0}, hits_k = 8;
@@ -122,8 +123,11 @@ void usage() {
             "                      at most K, default 8)\n"
             "       [--closest X,Y,Z[,R]] (prints `closest prim distance x y z`: the nearest surface point to the point X,Y,Z,\n"
             "                      within the distance R when given; `closest -1` when there is none)\n"
+            "       [--signed X,Y,Z[,R]] (prints `signed prim distance x y z feature s signed_distance`: --closest's answer, the\n"
+            "                      feature of the triangle that holds the nearest point (0 face, 1-3 vertices, 4-6 edges), the side\n"
+            "                      s (> 0 in front of the surface, < 0 behind it) and the distance with that sign; `signed -1`)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
-            "       [--accel]     (--pick / --hits / --closest / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan)");
+            "       [--accel]     (--pick / --hits / --closest / --signed / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan)");
 }
 
 }  // namespace
@@ -176,6 +180,10 @@ int main(int argc, char** argv) {
     else if (k == "--closest") {
       if (!parse_xyzr(next("--closest"), a.closest_p)) { std::fprintf(stderr, "--closest wants X,Y,Z[,R]\n"); return 2; }
       a.closest = true;
+    }
+    else if (k == "--signed") {
+      if (!parse_xyzr(next("--signed"), a.signed_p)) { std::fprintf(stderr, "--signed wants X,Y,Z[,R]\n"); return 2; }
+      a.sgn = true;
     }
     else if (k == "-o") a.out = next("-o");
     else if (k == "-q") a.quiet = true;
@@ -253,6 +261,32 @@ int main(int argc, char** argv) {
       }
       std::printf("closest %d %.9g %.9g %.9g %.9g\n", h.prim, static_cast<double>(std::sqrt(h.t)), static_cast<double>(q[0]),
                   static_cast<double>(q[1]), static_cast<double>(q[2]));
+    }
+  }
+  if (a.sgn) {
+    const float r = a.signed_p[3];
+    const std::vector<float> pts = {a.signed_p[0], a.signed_p[1], a.signed_p[2], std::copysign(r * r, r)};
+    std::vector<rt_hit> hits;
+    std::vector<rt_side> sides;
+    if (!tracer.SignedDistance(pts, hits, sides)) {
+      std::fprintf(stderr, "rt_cli: --signed: %s\n", tracer.LastError().c_str());
+      return 1;
+    }
+    const rt_hit& h = hits[0];
+    if (h.prim < 0 || static_cast<size_t>(h.prim) >= scene.size() / 3) {
+      std::printf("signed -1\n");
+    } else {                                                    // --closest's line, then the side
+      const float4 r0 = scene[3 * h.prim], r1 = scene[3 * h.prim + 1], r2 = scene[3 * h.prim + 2];
+      const float v0[3] = {r0.x, r0.y, r0.z}, b[3] = {r1.x, r1.y, r1.z}, c[3] = {r2.x, r2.y, r2.z};
+      float q[3];
+      for (int i = 0; i < 3; ++i) {
+        const float e1 = a.edges ? b[i] : b[i] - v0[i], e2 = a.edges ? c[i] : c[i] - v0[i];
+        q[i] = (v0[i] + h.u * e1) + h.v * e2;
+      }
+      const float d = std::sqrt(h.t);
+      std::printf("signed %d %.9g %.9g %.9g %.9g %d %.9g %.9g\n", h.prim, static_cast<double>(d), static_cast<double>(q[0]),
+                  static_cast<double>(q[1]), static_cast<double>(q[2]), sides[0].feature, static_cast<double>(sides[0].s),
+                  static_cast<double>(std::copysign(d, sides[0].s)));
     }
   }
   if (a.knn) {
