@@ -673,14 +673,25 @@ class RayTracer:
         import torch
         if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6 or not rays.is_contiguous():
             raise ValueError("Intersect: expected a contiguous (n, 6) float32 tensor")
-        dev = self.Bands()[0]["device"]
-        if rays.device.type != "cuda" or rays.device.index != dev:
-            raise ValueError("Intersect: the rays are on %s, the tracer on cuda:%d" % (rays.device, dev))
+        stream = self._stream_of("Intersect", "rays", rays)
         hits = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
-        stream = torch.cuda.current_stream(rays.device).cuda_stream
-        self._check(self._lib.rt_tracer_intersect_device(self._h, rays.data_ptr(), rays.shape[0], hits.data_ptr(),
-                                                         C.c_void_p(stream)))
+        self._check(self._lib.rt_tracer_intersect_device(self._h, rays.data_ptr(), rays.shape[0], hits.data_ptr(), stream))
         return hits
+
+    def _stream_of(self, who, what, t):
+        """The tensor paths' device check (`what`: how the query calls its input) -> torch's current stream on that device."""
+        import torch
+        dev = self.Bands()[0]["device"]
+        if t.device.type != "cuda" or t.device.index != dev:
+            raise ValueError("%s: the %s are on %s, the tracer on cuda:%d" % (who, what, t.device, dev))
+        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    @staticmethod
+    def _max_hits(who, max_hits):
+        k = int(max_hits)
+        if k != max_hits or not 1 <= k <= RT_MAX_HITS:
+            raise ValueError("%s: max_hits = %r (1 to %d)" % (who, max_hits, RT_MAX_HITS))
+        return k
 
     def Pick(self, pixels, return_rays=False):
         """Pinhole rays of full-image (x, y) pixels (one pair or (n, 2)) against the scene: structured array HIT_DTYPE,
@@ -699,6 +710,20 @@ class RayTracer:
         self._check(self._lib.rt_tracer_focus_at(self._h, x, y, C.byref(f)))
         return np.float32(f.value)
 
+    @staticmethod
+    def _segs_array(who, segs):
+        s = np.asarray(segs, np.float32)
+        if s.ndim == 0 or s.shape[-1] != 8:                                # (an (n, 6) ray array is not silently reinterpreted)
+            raise ValueError("%s: expected (n, 8) float32 segments, got shape %s" % (who, s.shape))
+        return np.ascontiguousarray(s).reshape(-1, 8)
+
+    def _segs_tensor(self, who, segs, max_hits=1):
+        """-> (max_hits checked, stream): dtype and shape, then max_hits (IntersectAll's), then the device."""
+        import torch
+        if segs.dtype != torch.float32 or segs.dim() != 2 or segs.shape[1] != 8 or not segs.is_contiguous():
+            raise ValueError("%s: expected a contiguous (n, 8) float32 tensor" % who)
+        return self._max_hits(who, max_hits), self._stream_of(who, "segments", segs)
+
     def Occluded(self, segs):
         """Visibility: is each ray blocked within its own interval?  segs: (n, 8) float32 {origin, direction (used as given),
         tmin, tmax}; the answer is 1 when some primitive is hit with tmin <= t <= tmax (closed, fp32; NaN never occludes),
@@ -706,25 +731,16 @@ class RayTracer:
         tracer's device -> uint8 tensor, enqueued on torch.cuda.current_stream() without a host synchronisation."""
         if type(segs).__module__.startswith("torch"):
             return self._occluded_tensor(segs)
-        s = np.asarray(segs, np.float32)
-        if s.ndim == 0 or s.shape[-1] != 8:                                # (an (n, 6) ray array is not silently reinterpreted)
-            raise ValueError("Occluded: expected (n, 8) float32 segments, got shape %s" % (s.shape,))
-        s = np.ascontiguousarray(s).reshape(-1, 8)
+        s = self._segs_array("Occluded", segs)
         out = np.zeros(s.shape[0], np.uint8)
         self._check(self._lib.rt_tracer_occluded(self._h, s.ctypes.data, s.shape[0], out.ctypes.data))
         return out.view(np.bool_)
 
     def _occluded_tensor(self, segs):
         import torch
-        if segs.dtype != torch.float32 or segs.dim() != 2 or segs.shape[1] != 8 or not segs.is_contiguous():
-            raise ValueError("Occluded: expected a contiguous (n, 8) float32 tensor")
-        dev = self.Bands()[0]["device"]
-        if segs.device.type != "cuda" or segs.device.index != dev:
-            raise ValueError("Occluded: the segments are on %s, the tracer on cuda:%d" % (segs.device, dev))
+        _, stream = self._segs_tensor("Occluded", segs)
         out = torch.empty((segs.shape[0],), dtype=torch.uint8, device=segs.device)
-        stream = torch.cuda.current_stream(segs.device).cuda_stream
-        self._check(self._lib.rt_tracer_occluded_device(self._h, segs.data_ptr(), segs.shape[0], out.data_ptr(),
-                                                        C.c_void_p(stream)))
+        self._check(self._lib.rt_tracer_occluded_device(self._h, segs.data_ptr(), segs.shape[0], out.data_ptr(), stream))
         return out
 
     def IntersectAll(self, segs, max_hits=RT_MAX_HITS):
@@ -736,39 +752,58 @@ class RayTracer:
         float32 {t, u, v, prim bits}, (n,) int32), enqueued on torch.cuda.current_stream() without a host synchronisation."""
         if type(segs).__module__.startswith("torch"):
             return self._intersect_all_tensor(segs, max_hits)
-        s = np.asarray(segs, np.float32)
-        if s.ndim == 0 or s.shape[-1] != 8:                                # (an (n, 6) ray array is not silently reinterpreted)
-            raise ValueError("IntersectAll: expected (n, 8) float32 segments, got shape %s" % (s.shape,))
-        k = self._max_hits(max_hits)
-        s = np.ascontiguousarray(s).reshape(-1, 8)
+        s = self._segs_array("IntersectAll", segs)
+        k = self._max_hits("IntersectAll", max_hits)
         hits = np.zeros((s.shape[0], k), HIT_DTYPE)
         counts = np.zeros(s.shape[0], np.uint32)
         self._check(self._lib.rt_tracer_intersect_all(self._h, s.ctypes.data, s.shape[0], k, hits.ctypes.data, counts.ctypes.data))
         return hits, counts
 
-    @staticmethod
-    def _max_hits(max_hits):
-        k = int(max_hits)
-        if k != max_hits or not 1 <= k <= RT_MAX_HITS:
-            raise ValueError("IntersectAll: max_hits = %r (1 to %d)" % (max_hits, RT_MAX_HITS))
-        return k
-
     def _intersect_all_tensor(self, segs, max_hits=RT_MAX_HITS):
         import torch
-        if segs.dtype != torch.float32 or segs.dim() != 2 or segs.shape[1] != 8 or not segs.is_contiguous():
-            raise ValueError("IntersectAll: expected a contiguous (n, 8) float32 tensor")
-        k = self._max_hits(max_hits)
-        dev = self.Bands()[0]["device"]
-        if segs.device.type != "cuda" or segs.device.index != dev:
-            raise ValueError("IntersectAll: the segments are on %s, the tracer on cuda:%d" % (segs.device, dev))
+        k, stream = self._segs_tensor("IntersectAll", segs, max_hits)
         hits = torch.empty((segs.shape[0], k, 4), dtype=torch.float32, device=segs.device)
         counts = torch.empty((segs.shape[0],), dtype=torch.int32, device=segs.device)
-        stream = torch.cuda.current_stream(segs.device).cuda_stream
         self._check(self._lib.rt_tracer_intersect_all_device(self._h, segs.data_ptr(), segs.shape[0], k, hits.data_ptr(),
-                                                             counts.data_ptr(), C.c_void_p(stream)))
+                                                             counts.data_ptr(), stream))
         return hits, counts
 
     # ---- point queries (rt_tracer_closest_point / _device) -----------------------------------------------------------
+    @staticmethod
+    def _d2max(max_distance):
+        with np.errstate(over="ignore"):
+            d = np.float32(max_distance)
+            return np.copysign(d * d, d)
+
+    @staticmethod
+    def _points_array(who, points, max_distance):
+        """-> contiguous (n, 4) float32 {x, y, z, squared radius}: (n, 3) points get _d2max(max_distance) in column 3."""
+        p = np.asarray(points, np.float32)
+        if p.ndim == 0 or p.shape[-1] not in (3, 4):
+            raise ValueError("%s: expected (n, 3) or (n, 4) float32 points, got shape %s" % (who, p.shape))
+        if p.shape[-1] == 3:
+            q = np.empty(p.shape[:-1] + (4,), np.float32)
+            q[..., :3], q[..., 3] = p, RayTracer._d2max(max_distance)
+            p = q
+        return np.ascontiguousarray(p).reshape(-1, 4)
+
+    def _points_tensor(self, who, points, max_distance, max_hits=1):
+        """-> ((n, 4) points as _points_array forms them, max_hits checked, stream): dtype and shape, then max_hits (ClosestAll's),
+        then the device, then the contiguity of an (n, 4) tensor."""
+        import torch
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
+            raise ValueError("%s: expected an (n, 3) or (n, 4) float32 tensor" % who)
+        k = self._max_hits(who, max_hits)
+        stream = self._stream_of(who, "points", points)
+        if points.shape[1] == 3:
+            q = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+            q[:, :3] = points
+            q[:, 3] = float(self._d2max(max_distance))
+            points = q
+        elif not points.is_contiguous():
+            raise ValueError("%s: expected a contiguous (n, 4) float32 tensor" % who)
+        return points, k, stream
+
     def ClosestPoint(self, points, max_distance=np.inf):
         """The nearest surface point of the scene to each point.  points: (n, 3) float32 x, y, z, searched within max_distance
         (squared on the host in fp32; a negative one keeps its sign and accepts nothing), or (n, 4) with the SQUARED search radius
@@ -779,42 +814,16 @@ class RayTracer:
         float32 tensor {t, u, v, prim bits}, enqueued on torch.cuda.current_stream() without a host synchronisation."""
         if type(points).__module__.startswith("torch"):
             return self._closest_point_tensor(points, max_distance)
-        p = np.asarray(points, np.float32)
-        if p.ndim == 0 or p.shape[-1] not in (3, 4):
-            raise ValueError("ClosestPoint: expected (n, 3) or (n, 4) float32 points, got shape %s" % (p.shape,))
-        if p.shape[-1] == 3:
-            q = np.empty(p.shape[:-1] + (4,), np.float32)
-            q[..., :3], q[..., 3] = p, self._d2max(max_distance)
-            p = q
-        p = np.ascontiguousarray(p).reshape(-1, 4)
+        p = self._points_array("ClosestPoint", points, max_distance)
         hits = np.zeros(p.shape[0], HIT_DTYPE)
         self._check(self._lib.rt_tracer_closest_point(self._h, p.ctypes.data, p.shape[0], hits.ctypes.data))
         return hits
 
-    @staticmethod
-    def _d2max(max_distance):
-        with np.errstate(over="ignore"):
-            d = np.float32(max_distance)
-            return np.copysign(d * d, d)
-
     def _closest_point_tensor(self, points, max_distance=np.inf):
         import torch
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
-            raise ValueError("ClosestPoint: expected an (n, 3) or (n, 4) float32 tensor")
-        dev = self.Bands()[0]["device"]
-        if points.device.type != "cuda" or points.device.index != dev:
-            raise ValueError("ClosestPoint: the points are on %s, the tracer on cuda:%d" % (points.device, dev))
-        if points.shape[1] == 3:
-            q = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
-            q[:, :3] = points
-            q[:, 3] = float(self._d2max(max_distance))
-            points = q
-        elif not points.is_contiguous():
-            raise ValueError("ClosestPoint: expected a contiguous (n, 4) float32 tensor")
+        points, _, stream = self._points_tensor("ClosestPoint", points, max_distance)
         hits = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
-        stream = torch.cuda.current_stream(points.device).cuda_stream
-        self._check(self._lib.rt_tracer_closest_point_device(self._h, points.data_ptr(), points.shape[0], hits.data_ptr(),
-                                                             C.c_void_p(stream)))
+        self._check(self._lib.rt_tracer_closest_point_device(self._h, points.data_ptr(), points.shape[0], hits.data_ptr(), stream))
         return hits
 
     # ---- the k nearest primitives (rt_tracer_closest_all / _device) ------------------------------------------------------
@@ -830,15 +839,8 @@ class RayTracer:
         synchronisation; after is then a contiguous (n, 4) float32 tensor."""
         if type(points).__module__.startswith("torch"):
             return self._closest_all_tensor(points, max_hits, max_distance, after)
-        p = np.asarray(points, np.float32)
-        if p.ndim == 0 or p.shape[-1] not in (3, 4):
-            raise ValueError("ClosestAll: expected (n, 3) or (n, 4) float32 points, got shape %s" % (p.shape,))
-        k = self._nearest_max_hits(max_hits)
-        if p.shape[-1] == 3:
-            q = np.empty(p.shape[:-1] + (4,), np.float32)
-            q[..., :3], q[..., 3] = p, self._d2max(max_distance)
-            p = q
-        p = np.ascontiguousarray(p).reshape(-1, 4)
+        p = self._points_array("ClosestAll", points, max_distance)
+        k = self._max_hits("ClosestAll", max_hits)
         a = None
         if after is not None:
             a = np.ascontiguousarray(np.asarray(after).reshape(-1))
@@ -850,38 +852,17 @@ class RayTracer:
                                                     hits.ctypes.data, counts.ctypes.data))
         return hits, counts
 
-    @staticmethod
-    def _nearest_max_hits(max_hits):
-        k = int(max_hits)
-        if k != max_hits or not 1 <= k <= RT_MAX_HITS:
-            raise ValueError("ClosestAll: max_hits = %r (1 to %d)" % (max_hits, RT_MAX_HITS))
-        return k
-
     def _closest_all_tensor(self, points, max_hits=RT_MAX_HITS, max_distance=np.inf, after=None):
         import torch
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
-            raise ValueError("ClosestAll: expected an (n, 3) or (n, 4) float32 tensor")
-        k = self._nearest_max_hits(max_hits)
-        dev = self.Bands()[0]["device"]
-        if points.device.type != "cuda" or points.device.index != dev:
-            raise ValueError("ClosestAll: the points are on %s, the tracer on cuda:%d" % (points.device, dev))
-        if points.shape[1] == 3:
-            q = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
-            q[:, :3] = points
-            q[:, 3] = float(self._d2max(max_distance))
-            points = q
-        elif not points.is_contiguous():
-            raise ValueError("ClosestAll: expected a contiguous (n, 4) float32 tensor")
+        points, k, stream = self._points_tensor("ClosestAll", points, max_distance, max_hits)
         if after is not None:
             if (not type(after).__module__.startswith("torch") or after.dtype != torch.float32 or after.dim() != 2 or
                     tuple(after.shape) != (points.shape[0], 4) or not after.is_contiguous() or after.device != points.device):
                 raise ValueError("ClosestAll: after must be a contiguous (n, 4) float32 tensor on the points' device")
         hits = torch.empty((points.shape[0], k, 4), dtype=torch.float32, device=points.device)
         counts = torch.empty((points.shape[0],), dtype=torch.int32, device=points.device)
-        stream = torch.cuda.current_stream(points.device).cuda_stream
         self._check(self._lib.rt_tracer_closest_all_device(self._h, points.data_ptr(), None if after is None else after.data_ptr(),
-                                                           points.shape[0], k, hits.data_ptr(), counts.data_ptr(),
-                                                           C.c_void_p(stream)))
+                                                           points.shape[0], k, hits.data_ptr(), counts.data_ptr(), stream))
         return hits, counts
 
     def ClosestWithin(self, points, max_distance, max_hits=RT_MAX_HITS):
@@ -890,15 +871,8 @@ class RayTracer:
         each point in column 3 (max_distance is then not used).  Returns (hits, offsets): the accepted primitives of all
         points, flat, HIT_DTYPE, each point's in ascending (t, prim) order; point i's are hits[offsets[i]:offsets[i + 1]],
         offsets (n + 1,) int64."""
-        p = np.asarray(points, np.float32)
-        if p.ndim == 0 or p.shape[-1] not in (3, 4):
-            raise ValueError("ClosestWithin: expected (n, 3) or (n, 4) float32 points, got shape %s" % (p.shape,))
-        k = self._nearest_max_hits(max_hits)
-        if p.shape[-1] == 3:
-            q = np.empty(p.shape[:-1] + (4,), np.float32)
-            q[..., :3], q[..., 3] = p, self._d2max(max_distance)
-            p = q
-        p = np.ascontiguousarray(p).reshape(-1, 4)
+        p = self._points_array("ClosestWithin", points, max_distance)
+        k = self._max_hits("ClosestAll", max_hits)
         n = p.shape[0]
         live = np.arange(n)                                                # the points that may have more
         after = None
@@ -929,13 +903,12 @@ class RayTracer:
         feature bits}), enqueued on torch.cuda.current_stream() without a host synchronisation (the first signed query after
         an upload builds the scene's table on the host first)."""
         if type(points).__module__.startswith("torch"):
-            points = self._points_tensor("SignedDistance", points, max_distance)
             import torch
+            points, _, stream = self._points_tensor("SignedDistance", points, max_distance)
             hits = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
             sides = torch.empty((points.shape[0], 2), dtype=torch.float32, device=points.device)
-            stream = torch.cuda.current_stream(points.device).cuda_stream
             self._check(self._lib.rt_tracer_signed_distance_device(self._h, points.data_ptr(), points.shape[0], hits.data_ptr(),
-                                                                   sides.data_ptr(), C.c_void_p(stream)))
+                                                                   sides.data_ptr(), stream))
             return hits, sides
         p = self._points_array("SignedDistance", points, max_distance)
         hits = np.zeros(p.shape[0], HIT_DTYPE)
@@ -950,22 +923,20 @@ class RayTracer:
         (n, 4); the radius column is not used."""
         if type(points).__module__.startswith("torch"):
             import torch
-            points = self._points_tensor("ClosestSides", points, np.inf)
+            points, _, stream = self._points_tensor("ClosestSides", points, np.inf)
             n = points.shape[0]
             if (not type(hits).__module__.startswith("torch") or hits.dtype != torch.float32 or hits.dim() not in (2, 3) or
                     hits.shape[0] != n or hits.shape[-1] != 4 or not hits.is_contiguous() or hits.device != points.device):
                 raise ValueError("ClosestSides: hits must be a contiguous (n, 4) or (n, max_hits, 4) float32 tensor on the points' device")
-            k = 1 if hits.dim() == 2 else self._nearest_max_hits(hits.shape[1])
+            k = 1 if hits.dim() == 2 else self._max_hits("ClosestAll", hits.shape[1])
             sides = torch.empty(tuple(hits.shape[:-1]) + (2,), dtype=torch.float32, device=points.device)
-            stream = torch.cuda.current_stream(points.device).cuda_stream
-            self._check(self._lib.rt_tracer_closest_sides_device(self._h, points.data_ptr(), hits.data_ptr(), n, k, sides.data_ptr(),
-                                                                 C.c_void_p(stream)))
+            self._check(self._lib.rt_tracer_closest_sides_device(self._h, points.data_ptr(), hits.data_ptr(), n, k, sides.data_ptr(), stream))
             return sides
         p = self._points_array("ClosestSides", points, np.inf)
         h = np.ascontiguousarray(hits)
         if h.dtype != HIT_DTYPE or h.ndim not in (1, 2) or h.shape[0] != p.shape[0]:
             raise ValueError("ClosestSides: expected the HIT_DTYPE answers (n,) or (n, max_hits) of these %d points" % p.shape[0])
-        k = 1 if h.ndim == 1 else self._nearest_max_hits(h.shape[1])
+        k = 1 if h.ndim == 1 else self._max_hits("ClosestAll", h.shape[1])
         sides = np.zeros(h.shape, SIDE_DTYPE)
         self._check(self._lib.rt_tracer_closest_sides(self._h, p.ctypes.data, h.ctypes.data, p.shape[0], k, sides.ctypes.data))
         return sides
@@ -996,32 +967,6 @@ class RayTracer:
         axes = [o[a] + sp[a] * np.arange(shape[a]) for a in range(3)]
         pts = np.stack(np.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
         return self.SignedDistances(pts).reshape(shape)
-
-    def _points_array(self, who, points, max_distance):
-        p = np.asarray(points, np.float32)
-        if p.ndim == 0 or p.shape[-1] not in (3, 4):
-            raise ValueError("%s: expected (n, 3) or (n, 4) float32 points, got shape %s" % (who, p.shape))
-        if p.shape[-1] == 3:
-            q = np.empty(p.shape[:-1] + (4,), np.float32)
-            q[..., :3], q[..., 3] = p, self._d2max(max_distance)
-            p = q
-        return np.ascontiguousarray(p).reshape(-1, 4)
-
-    def _points_tensor(self, who, points, max_distance):
-        import torch
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
-            raise ValueError("%s: expected an (n, 3) or (n, 4) float32 tensor" % who)
-        dev = self.Bands()[0]["device"]
-        if points.device.type != "cuda" or points.device.index != dev:
-            raise ValueError("%s: the points are on %s, the tracer on cuda:%d" % (who, points.device, dev))
-        if points.shape[1] == 3:
-            q = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
-            q[:, :3] = points
-            q[:, 3] = float(self._d2max(max_distance))
-            return q
-        if not points.is_contiguous():
-            raise ValueError("%s: expected a contiguous (n, 4) float32 tensor" % who)
-        return points
 
     def ClosestPositions(self, points, hits):
         """The nearest points themselves, (n, 3) float32: v0 + u*e1 + v*e2 of the winning triangle's record (fp32, from this

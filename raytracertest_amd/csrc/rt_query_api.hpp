@@ -5,9 +5,12 @@
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
 // calls by api_mu, reads only the scene and a snapshot of the camera (params(), under state_mu), and runs on a stream of its
 // own (stream_q, created by the first query) or on the caller's.  query_done, recorded behind every query, is what the scene
-// uploads and destroy wait for before they touch the records a query may still read.
+// uploads and destroy wait for before they touch the records a query may still read: every launch goes through enqueue_launch,
+// the one place that waits for and records it.  Every entry point is query_call (or, with a check of its own, query_entry):
+// api_mu, a sharded handle forwarded to its first band, else the body under guarded().
 #pragma once
 #include <cmath>
+#include <initializer_list>
 
 #include "rt_bvh_host.hpp"
 #include "rt_features_host.hpp"
@@ -24,16 +27,64 @@ inline int query_k(const rt_tracer* t, size_t n) {
   return n >= 4u * kResidentLanes ? 4 : n >= 2u * kResidentLanes ? 2 : 1;
 }
 
-inline bool intersect_all_args_ok(rt_tracer* t, const char* who, size_t n, const float* segs, uint32_t max_hits, const rt_hit* hits,
-                                  const uint32_t* counts) {
-  if (max_hits == 0u || max_hits > RT_MAX_HITS) {
-    t->set_error(fmt("%s: max_hits = %u (1 to %u)", who, max_hits, RT_MAX_HITS));
-    return false;
-  }
+// The argument checks, made before the lock.  A batch of n != 0 needs every array and a count the kernels' 32-bit indices hold.
+inline bool query_args_ok(rt_tracer* t, size_t n, std::initializer_list<const void*> arrays) {
   if (n == 0u) return true;
-  if (!segs || !hits || !counts) { t->set_error("query: null array"); return false; }
+  for (const void* a : arrays)
+    if (!a) { t->set_error("query: null array"); return false; }
   if (n > kQueryMaxRays) { t->set_error(fmt("query: %zu rays (at most %zu)", n, kQueryMaxRays)); return false; }
   return true;
+}
+
+// records per ray or point (`what`: max_hits, per_point), checked whatever n is
+inline bool query_row_ok(rt_tracer* t, const char* who, const char* what, uint32_t k) {
+  if (k != 0u && k <= RT_MAX_HITS) return true;
+  t->set_error(fmt("%s: %s = %u (1 to %u)", who, what, k, RT_MAX_HITS));
+  return false;
+}
+
+// the device pointers of a _device entry point, each with the alignment its kernel's loads and stores need
+struct AlignedTo { const void* p; uintptr_t bytes; };
+inline bool query_aligned_ok(rt_tracer* t, size_t n, std::initializer_list<AlignedTo> ptrs, const char* message) {
+  if (n == 0u) return true;
+  for (const AlignedTo& a : ptrs)
+    if (reinterpret_cast<uintptr_t>(a.p) % a.bytes != 0u) { t->set_error(message); return false; }
+  return true;
+}
+
+// An entry point on a non-null handle: its API calls serialised, a sharded handle answered by its first band (whose error text
+// becomes the handle's), any other by rest().
+template <class Forward, class Rest>
+int query_entry(rt_tracer* t, Forward&& forward, Rest&& rest) {
+  std::lock_guard<std::mutex> lk(t->api_mu);
+  if (!t->mg) return rest();
+  rt_tracer* band = t->mg->bands[0];
+  const int rc = forward(band);
+  if (rc != RT_OK) t->set_error(band->last_error);
+  return rc;
+}
+
+template <class Forward, class Body>
+int query_call(rt_tracer* t, Forward&& forward, Body&& body) {
+  return query_entry(t, forward, [&] { return guarded(t, body); });
+}
+
+// The host-array entry points' staging buffers, grow-only: n elements of the caller's array into d on `st`, room for n
+// results in d, n results out of d into the caller's array on `st`.
+template <class T>
+T* staged_in(DevArray<T>& d, const void* src, size_t n, hipStream_t st) {
+  d.ensure(n);
+  HIP_CHECK(hipMemcpyAsync(d.get(), src, n * sizeof(T), hipMemcpyHostToDevice, st));
+  return d.get();
+}
+template <class T>
+T* room(DevArray<T>& d, size_t n) {
+  d.ensure(n);
+  return d.get();
+}
+template <class T>
+void staged_out(void* dst, const DevArray<T>& d, size_t n, hipStream_t st) {
+  HIP_CHECK(hipMemcpyAsync(dst, d.get(), n * sizeof(T), hipMemcpyDeviceToHost, st));
 }
 
 inline hipStream_t query_stream(rt_tracer* t) {
@@ -127,98 +178,71 @@ inline rtk::BvhParams query_bvh_params(const rt_tracer* t) {
   return b;
 }
 
-// rays (or pixels) -> hits on `st`, behind every earlier query: query_done then covers this one and all before it
+// One launch of a query on `st`, behind every earlier query: query_done then covers this one and all before it.  launch(p, b)
+// gets the launches' camera snapshot and scene with p.flags = flags, and the valid tree under RT_QUERY_BVH when the query
+// walks one (uses_tree), else b = nullptr: the scan.
+template <class Launch>
+void enqueue_launch(rt_tracer* t, hipStream_t st, uint32_t flags, bool uses_tree, Launch&& launch) {
+  rtk::TraceParams p = t->params(1);
+  p.flags = flags;
+  const bool bvh = uses_tree && t->query_accel == RT_QUERY_BVH;
+  if (bvh) ensure_query_tree(t);
+  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
+  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
+  if (bvh) {
+    const rtk::BvhParams b = query_bvh_params(t);
+    HIP_CHECK(launch(p, &b));
+  } else {
+    HIP_CHECK(launch(p, static_cast<const rtk::BvhParams*>(nullptr)));
+  }
+  HIP_CHECK(hipEventRecord(t->query_done, st));
+}
+
+// the point queries' slack on the box distance: rho_c takes the ray queries' (rt_dbg_query_accel_slack)
+inline float closest_rho(const rt_tracer* t) { return RT_CLOSEST_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f); }
+
+// rays (or pixels) -> hits, under the tracer's hit rule
 inline void enqueue_query(rt_tracer* t, size_t n, const float* rays, const uint32_t* pixels, float* rays_out, float4* hits,
                           hipStream_t st) {
-  rtk::TraceParams p = t->params(1);                                     // the launches' camera snapshot and scene
-  p.flags = t->nearest_hit ? rtk::TRACE_NEAREST_HIT : 0u;
-  const bool bvh = t->query_accel == RT_QUERY_BVH;
-  if (bvh) ensure_query_tree(t);
-  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
-  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
-  if (bvh) {
-    const rtk::BvhParams b = query_bvh_params(t);
-    HIP_CHECK(rtk::launch_query_bvh(p, b, t->fma, static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st));
-  } else {
-    HIP_CHECK(rtk::launch_query(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st));
-  }
-  HIP_CHECK(hipEventRecord(t->query_done, st));
+  enqueue_launch(t, st, t->nearest_hit ? rtk::TRACE_NEAREST_HIT : 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return b ? rtk::launch_query_bvh(p, *b, t->fma, static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st)
+             : rtk::launch_query(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st);
+  });
 }
 
-// segments -> one byte per ray on `st`, with enqueue_query's event discipline.  The hit rule plays no part (an OR over the
-// primitives), so p.flags stays 0.
+// segments -> one byte per ray.  The hit rule plays no part (an OR over the primitives), so the flags stay 0.
 inline void enqueue_occluded(rt_tracer* t, size_t n, const float* segs, uint8_t* occluded, hipStream_t st) {
-  rtk::TraceParams p = t->params(1);
-  p.flags = 0u;
-  const bool bvh = t->query_accel == RT_QUERY_BVH;
-  if (bvh) ensure_query_tree(t);
-  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
-  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
-  if (bvh) {
-    const rtk::BvhParams b = query_bvh_params(t);
-    HIP_CHECK(rtk::launch_occluded_bvh(p, b, t->fma, static_cast<uint32_t>(n), segs, occluded, st));
-  } else {
-    HIP_CHECK(rtk::launch_occluded(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), segs, occluded, st));
-  }
-  HIP_CHECK(hipEventRecord(t->query_done, st));
+  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return b ? rtk::launch_occluded_bvh(p, *b, t->fma, static_cast<uint32_t>(n), segs, occluded, st)
+             : rtk::launch_occluded(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), segs, occluded, st);
+  });
 }
 
-// segments -> rows of max_hits records and one count per ray on `st`, with enqueue_query's event discipline.  The order rule
-// names no hit rule, so p.flags stays 0.
+// segments -> rows of max_hits records and one count per ray.  The order rule names no hit rule, so the flags stay 0.
 inline void enqueue_intersect_all(rt_tracer* t, size_t n, const float* segs, uint32_t max_hits, float4* hits, uint32_t* counts,
                                   hipStream_t st) {
-  rtk::TraceParams p = t->params(1);
-  p.flags = 0u;
-  const bool bvh = t->query_accel == RT_QUERY_BVH;
-  if (bvh) ensure_query_tree(t);
-  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
-  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
-  if (bvh) {
-    const rtk::BvhParams b = query_bvh_params(t);
-    HIP_CHECK(rtk::launch_allhits_bvh(p, b, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st));
-  } else {
-    HIP_CHECK(rtk::launch_allhits(p, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st));
-  }
-  HIP_CHECK(hipEventRecord(t->query_done, st));
+  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return b ? rtk::launch_allhits_bvh(p, *b, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st)
+             : rtk::launch_allhits(p, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st);
+  });
 }
 
-// points -> one record per point on `st`, with enqueue_query's event discipline.  One arithmetic for both math modes and no hit
-// rule: p.flags stays 0.  The tree is the ray queries' (ensure_query_tree, so RT_ACCEL_REFIT applies); rho_c takes their slack.
+// points -> one record per point.  One arithmetic for both math modes and no hit rule: the flags stay 0.  The tree is the ray
+// queries' (ensure_query_tree, so RT_ACCEL_REFIT applies).
 inline void enqueue_closest(rt_tracer* t, size_t n, const float* pts, float4* hits, hipStream_t st) {
-  rtk::TraceParams p = t->params(1);
-  p.flags = 0u;
-  const bool bvh = t->query_accel == RT_QUERY_BVH;
-  if (bvh) ensure_query_tree(t);
-  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
-  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
-  if (bvh) {
-    const rtk::BvhParams b = query_bvh_params(t);
-    const float rho_c = RT_CLOSEST_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f);
-    HIP_CHECK(rtk::launch_closest_bvh(p, b, rho_c, static_cast<uint32_t>(n), pts, hits, st));
-  } else {
-    HIP_CHECK(rtk::launch_closest(p, static_cast<uint32_t>(n), pts, hits, st));
-  }
-  HIP_CHECK(hipEventRecord(t->query_done, st));
+  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return b ? rtk::launch_closest_bvh(p, *b, closest_rho(t), static_cast<uint32_t>(n), pts, hits, st)
+             : rtk::launch_closest(p, static_cast<uint32_t>(n), pts, hits, st);
+  });
 }
 
-// points (and their cursors, or nullptr) -> rows of max_hits records and one count per point on `st`, under enqueue_closest's
-// event discipline, tree and rho_c.
+// points (and their cursors, or nullptr) -> rows of max_hits records and one count per point, with enqueue_closest's tree and rho_c
 inline void enqueue_closest_all(rt_tracer* t, size_t n, const float* pts, const float4* after, uint32_t max_hits, float4* hits,
                                 uint32_t* counts, hipStream_t st) {
-  rtk::TraceParams p = t->params(1);
-  p.flags = 0u;
-  const bool bvh = t->query_accel == RT_QUERY_BVH;
-  if (bvh) ensure_query_tree(t);
-  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
-  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
-  if (bvh) {
-    const rtk::BvhParams b = query_bvh_params(t);
-    const float rho_c = RT_CLOSEST_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f);
-    HIP_CHECK(rtk::launch_nearest_bvh(p, b, rho_c, static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st));
-  } else {
-    HIP_CHECK(rtk::launch_nearest(p, static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st));
-  }
-  HIP_CHECK(hipEventRecord(t->query_done, st));
+  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return b ? rtk::launch_nearest_bvh(p, *b, closest_rho(t), static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st)
+             : rtk::launch_nearest(p, static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st);
+  });
 }
 
 // The signed queries' feature table (rt_features_host.hpp) of the current scene: built on the host from the
@@ -244,33 +268,12 @@ inline void ensure_feature_table(rt_tracer* t) {
   t->features_built = true;
 }
 
-// points and n * per_point records of them -> as many rt_side on `st`, with enqueue_query's event discipline.  The table is
-// valid (ensure_feature_table, called before anything of this query was enqueued: it may wait for the queries in flight).
+// points and n * per_point records of them -> as many rt_side; no tree.  The table is valid (ensure_feature_table, called
+// before anything of this query was enqueued: it may wait for the queries in flight).
 inline void enqueue_sides(rt_tracer* t, size_t n, uint32_t per_point, const float* pts, const float4* hits, void* sides, hipStream_t st) {
-  rtk::TraceParams p = t->params(1);
-  p.flags = 0u;
-  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
-  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
-  HIP_CHECK(rtk::launch_sides(p, t->d_features.get(), static_cast<uint32_t>(n), per_point, pts, hits, sides, st));
-  HIP_CHECK(hipEventRecord(t->query_done, st));
-}
-
-inline bool sides_args_ok(rt_tracer* t, const char* who, size_t n, uint32_t per_point, const void* pts, const void* hits, const void* sides) {
-  if (per_point == 0u || per_point > RT_MAX_HITS) {
-    t->set_error(fmt("%s: per_point = %u (1 to %u)", who, per_point, RT_MAX_HITS));
-    return false;
-  }
-  if (n == 0u) return true;
-  if (!pts || !hits || !sides) { t->set_error("query: null array"); return false; }
-  if (n > kQueryMaxRays) { t->set_error(fmt("query: %zu rays (at most %zu)", n, kQueryMaxRays)); return false; }
-  return true;
-}
-
-inline bool query_args_ok(rt_tracer* t, size_t n, const void* a, const void* b) {
-  if (n == 0u) return true;
-  if (!a || !b) { t->set_error("query: null array"); return false; }
-  if (n > kQueryMaxRays) { t->set_error(fmt("query: %zu rays (at most %zu)", n, kQueryMaxRays)); return false; }
-  return true;
+  enqueue_launch(t, st, 0u, false, [&](const rtk::TraceParams& p, const rtk::BvhParams*) {
+    return rtk::launch_sides(p, t->d_features.get(), static_cast<uint32_t>(n), per_point, pts, hits, sides, st);
+  });
 }
 
 }  // namespace rtr
@@ -280,77 +283,46 @@ extern "C" {
 int rt_tracer_set_query_accel(rt_tracer* t, uint32_t mode) {
   if (!t) return RT_ERR_INVALID;
   if (mode != RT_QUERY_SCAN && mode != RT_QUERY_BVH) { t->set_error(fmt("rt_tracer_set_query_accel: unknown mode %u", mode)); return RT_ERR_INVALID; }
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_set_query_accel(t->mg->bands[0], mode);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  t->query_accel = mode;
-  return RT_OK;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_set_query_accel(b, mode); }, [&] { t->query_accel = mode; });
 }
 
 int rt_tracer_query_accel_info(rt_tracer* t, uint64_t out[8]) {
   if (!t || !out) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_query_accel_info(t->mg->bands[0], out);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  const bool valid = t->bvh_valid();
-  out[0] = t->query_accel; out[1] = valid ? 1u : 0u;
-  for (int i = 0; i < 6; ++i) out[2 + i] = valid ? t->bvh_info[i] : 0u;
-  return RT_OK;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_query_accel_info(b, out); }, [&] {
+    const bool valid = t->bvh_valid();
+    out[0] = t->query_accel; out[1] = valid ? 1u : 0u;
+    for (int i = 0; i < 6; ++i) out[2 + i] = valid ? t->bvh_info[i] : 0u;
+  });
 }
 
 int rt_tracer_set_query_accel_update(rt_tracer* t, uint32_t policy) {
   if (!t) return RT_ERR_INVALID;
   if (policy != RT_ACCEL_REBUILD && policy != RT_ACCEL_REFIT) { t->set_error(fmt("rt_tracer_set_query_accel_update: unknown policy %u", policy)); return RT_ERR_INVALID; }
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_set_query_accel_update(t->mg->bands[0], policy);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  t->accel_update = policy;
-  return RT_OK;
+  // (checked before query_call takes api_mu, as every argument is)
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_set_query_accel_update(b, policy); }, [&] { t->accel_update = policy; });
 }
 
 int rt_tracer_query_accel_rebuild(rt_tracer* t) {
   if (!t) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_query_accel_rebuild(t->mg->bands[0]);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  t->bvh_built = false;                                                  // (the buffers stay; queries in flight may still walk them)
-  return RT_OK;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_query_accel_rebuild(b); }, [&] {
+    t->bvh_built = false;                                                // (the buffers stay; queries in flight may still walk them)
+  });
 }
 
 int rt_tracer_query_accel_update_info(rt_tracer* t, uint64_t out[8]) {
   if (!t || !out) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_query_accel_update_info(t->mg->bands[0], out);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  const bool valid = t->bvh_valid();
-  const double cost = valid ? t->bvh_cost : 0.0, built = valid ? t->bvh_cost_built : 0.0;
-  out[0] = t->accel_update; out[1] = t->refits; out[2] = t->refit_fallbacks; out[3] = t->refit_us;
-  memcpy(&out[4], &cost, sizeof(double)); memcpy(&out[5], &built, sizeof(double));
-  out[6] = out[7] = 0u;
-  return RT_OK;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_query_accel_update_info(b, out); }, [&] {
+    const bool valid = t->bvh_valid();
+    const double cost = valid ? t->bvh_cost : 0.0, built = valid ? t->bvh_cost_built : 0.0;
+    out[0] = t->accel_update; out[1] = t->refits; out[2] = t->refit_fallbacks; out[3] = t->refit_us;
+    memcpy(&out[4], &cost, sizeof(double)); memcpy(&out[5], &built, sizeof(double));
+    out[6] = out[7] = 0u;
+  });
 }
 
 int rt_dbg_query_accel_slack(rt_tracer* t, uint32_t slack_milli) {
   if (!t) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) return rt_dbg_query_accel_slack(t->mg->bands[0], slack_milli);
-  t->query_slack_milli = slack_milli;
-  return RT_OK;
+  return query_call(t, [&](rt_tracer* b) { return rt_dbg_query_accel_slack(b, slack_milli); }, [&] { t->query_slack_milli = slack_milli; });
 }
 
 int rt_dbg_bvh_build(const rt_float4* rows, size_t count, int edges_layout, void* nodes, size_t node_capacity_bytes,
@@ -412,65 +384,43 @@ double rt_dbg_bvh_tree_cost(const void* nodes, size_t node_bytes) {
 int rt_dbg_query_tree_read(rt_tracer* t, void* nodes, size_t node_capacity_bytes, void* records, size_t record_capacity_bytes,
                            uint64_t info[8]) {
   if (!t || !info) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_dbg_query_tree_read(t->mg->bands[0], nodes, node_capacity_bytes, records, record_capacity_bytes, info);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  if (!t->bvh_valid()) { t->set_error("rt_dbg_query_tree_read: no valid tree (the next RT_QUERY_BVH query makes one)"); return RT_ERR_STATE; }
-  return guarded(t, [&] {
-    const size_t nb = t->bvh_info[0] * sizeof(rtb::Node), rb = (size_t(t->bvh_leaf_records) + t->bvh_info[3]) * sizeof(rtb::Record);
-    info[0] = rtb::kBvhMaxDepth; info[1] = 1u;
-    for (int i = 0; i < 6; ++i) info[2 + i] = t->bvh_info[i];
-    if (node_capacity_bytes == 0u && record_capacity_bytes == 0u) return;  // sizes only
-    if (!nodes || !records || node_capacity_bytes < nb || record_capacity_bytes < rb)
-      throw HipFail{fmt("rt_dbg_query_tree_read: the tree needs %zu + %zu bytes", nb, rb)};
-    t->use_device();
-    const hipStream_t st = query_stream(t);
-    t->wait_queries();
-    if (nb) HIP_CHECK(hipMemcpyAsync(nodes, t->d_bvh_nodes.get(), nb, hipMemcpyDeviceToHost, st));
-    if (rb) HIP_CHECK(hipMemcpyAsync(records, t->d_bvh_records.get(), rb, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+  return query_entry(t, [&](rt_tracer* b) { return rt_dbg_query_tree_read(b, nodes, node_capacity_bytes, records, record_capacity_bytes, info); }, [&] {
+    if (!t->bvh_valid()) { t->set_error("rt_dbg_query_tree_read: no valid tree (the next RT_QUERY_BVH query makes one)"); return RT_ERR_STATE; }
+    return guarded(t, [&] {
+      const size_t nb = t->bvh_info[0] * sizeof(rtb::Node), rb = (size_t(t->bvh_leaf_records) + t->bvh_info[3]) * sizeof(rtb::Record);
+      info[0] = rtb::kBvhMaxDepth; info[1] = 1u;
+      for (int i = 0; i < 6; ++i) info[2 + i] = t->bvh_info[i];
+      if (node_capacity_bytes == 0u && record_capacity_bytes == 0u) return;  // sizes only
+      if (!nodes || !records || node_capacity_bytes < nb || record_capacity_bytes < rb)
+        throw HipFail{fmt("rt_dbg_query_tree_read: the tree needs %zu + %zu bytes", nb, rb)};
+      t->use_device();
+      const hipStream_t st = query_stream(t);
+      t->wait_queries();
+      if (nb) HIP_CHECK(hipMemcpyAsync(nodes, t->d_bvh_nodes.get(), nb, hipMemcpyDeviceToHost, st));
+      if (rb) HIP_CHECK(hipMemcpyAsync(records, t->d_bvh_records.get(), rb, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+    });
   });
 }
 
 int rt_tracer_intersect(rt_tracer* t, const float* rays, size_t n, rt_hit* hits) {
-  if (!t) return RT_ERR_INVALID;
-  if (!query_args_ok(t, n, rays, hits)) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_intersect(t->mg->bands[0], rays, n, hits);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  if (!t || !query_args_ok(t, n, {rays, hits})) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_intersect(b, rays, n, hits); }, [&] {
     if (n == 0u) return;
     t->use_device();
     const hipStream_t st = query_stream(t);
-    t->d_q_rays.ensure(n * 6u);
-    t->d_q_hits.ensure(n);
-    HIP_CHECK(hipMemcpyAsync(t->d_q_rays.get(), rays, n * 6u * sizeof(float), hipMemcpyHostToDevice, st));
-    enqueue_query(t, n, t->d_q_rays.get(), nullptr, nullptr, t->d_q_hits.get(), st);
-    HIP_CHECK(hipMemcpyAsync(hits, t->d_q_hits.get(), n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+    const float* d_rays = staged_in(t->d_q_rays, rays, n * 6u, st);
+    enqueue_query(t, n, d_rays, nullptr, nullptr, room(t->d_q_hits, n), st);
+    staged_out(hits, t->d_q_hits, n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 
 int rt_tracer_intersect_device(rt_tracer* t, const float* rays, size_t n, rt_hit* hits, void* stream) {
-  if (!t) return RT_ERR_INVALID;
-  if (!query_args_ok(t, n, rays, hits)) return RT_ERR_INVALID;
-  if (n != 0u && (reinterpret_cast<uintptr_t>(hits) % 16u != 0u || reinterpret_cast<uintptr_t>(rays) % 4u != 0u)) {
-    t->set_error("rt_tracer_intersect_device: hits must be 16-byte aligned, rays 4-byte aligned");
+  if (!t || !query_args_ok(t, n, {rays, hits}) ||
+      !query_aligned_ok(t, n, {{hits, 16u}, {rays, 4u}}, "rt_tracer_intersect_device: hits must be 16-byte aligned, rays 4-byte aligned"))
     return RT_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_intersect_device(t->mg->bands[0], rays, n, hits, stream);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_intersect_device(b, rays, n, hits, stream); }, [&] {
     if (n == 0u) return;
     t->use_device();
     enqueue_query(t, n, rays, nullptr, nullptr, reinterpret_cast<float4*>(hits), static_cast<hipStream_t>(stream));
@@ -478,41 +428,23 @@ int rt_tracer_intersect_device(rt_tracer* t, const float* rays, size_t n, rt_hit
 }
 
 int rt_tracer_occluded(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded) {
-  if (!t) return RT_ERR_INVALID;
-  if (!query_args_ok(t, n, segs, occluded)) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_occluded(t->mg->bands[0], segs, n, occluded);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  if (!t || !query_args_ok(t, n, {segs, occluded})) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_occluded(b, segs, n, occluded); }, [&] {
     if (n == 0u) return;
     t->use_device();
     const hipStream_t st = query_stream(t);
-    t->d_q_segs.ensure(n * 8u);
-    t->d_q_occluded.ensure(n);
-    HIP_CHECK(hipMemcpyAsync(t->d_q_segs.get(), segs, n * 8u * sizeof(float), hipMemcpyHostToDevice, st));
-    enqueue_occluded(t, n, t->d_q_segs.get(), t->d_q_occluded.get(), st);
-    HIP_CHECK(hipMemcpyAsync(occluded, t->d_q_occluded.get(), n, hipMemcpyDeviceToHost, st));
+    const float* d_segs = staged_in(t->d_q_segs, segs, n * 8u, st);
+    enqueue_occluded(t, n, d_segs, room(t->d_q_occluded, n), st);
+    staged_out(occluded, t->d_q_occluded, n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 
 int rt_tracer_occluded_device(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded, void* stream) {
-  if (!t) return RT_ERR_INVALID;
-  if (!query_args_ok(t, n, segs, occluded)) return RT_ERR_INVALID;
-  if (n != 0u && reinterpret_cast<uintptr_t>(segs) % 16u != 0u) {
-    t->set_error("rt_tracer_occluded_device: segs must be 16-byte aligned");
+  if (!t || !query_args_ok(t, n, {segs, occluded}) ||
+      !query_aligned_ok(t, n, {{segs, 16u}}, "rt_tracer_occluded_device: segs must be 16-byte aligned"))
     return RT_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_occluded_device(t->mg->bands[0], segs, n, occluded, stream);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_occluded_device(b, segs, n, occluded, stream); }, [&] {
     if (n == 0u) return;
     t->use_device();
     enqueue_occluded(t, n, segs, occluded, static_cast<hipStream_t>(stream));
@@ -520,45 +452,26 @@ int rt_tracer_occluded_device(rt_tracer* t, const float* segs, size_t n, uint8_t
 }
 
 int rt_tracer_intersect_all(rt_tracer* t, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts) {
-  if (!t) return RT_ERR_INVALID;
-  if (!intersect_all_args_ok(t, "rt_tracer_intersect_all", n, segs, max_hits, hits, counts)) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_intersect_all(t->mg->bands[0], segs, n, max_hits, hits, counts);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  if (!t || !query_row_ok(t, "rt_tracer_intersect_all", "max_hits", max_hits) || !query_args_ok(t, n, {segs, hits, counts})) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_intersect_all(b, segs, n, max_hits, hits, counts); }, [&] {
     if (n == 0u) return;
     t->use_device();
     const hipStream_t st = query_stream(t);
-    t->d_q_segs.ensure(n * 8u);
-    t->d_q_all_hits.ensure(n * max_hits);
-    t->d_q_all_counts.ensure(n);
-    HIP_CHECK(hipMemcpyAsync(t->d_q_segs.get(), segs, n * 8u * sizeof(float), hipMemcpyHostToDevice, st));
-    enqueue_intersect_all(t, n, t->d_q_segs.get(), max_hits, t->d_q_all_hits.get(), t->d_q_all_counts.get(), st);
-    HIP_CHECK(hipMemcpyAsync(hits, t->d_q_all_hits.get(), n * max_hits * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(counts, t->d_q_all_counts.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    const float* d_segs = staged_in(t->d_q_segs, segs, n * 8u, st);
+    enqueue_intersect_all(t, n, d_segs, max_hits, room(t->d_q_all_hits, n * max_hits), room(t->d_q_all_counts, n), st);
+    staged_out(hits, t->d_q_all_hits, n * max_hits, st);
+    staged_out(counts, t->d_q_all_counts, n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 
 int rt_tracer_intersect_all_device(rt_tracer* t, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts,
                                    void* stream) {
-  if (!t) return RT_ERR_INVALID;
-  if (!intersect_all_args_ok(t, "rt_tracer_intersect_all_device", n, segs, max_hits, hits, counts)) return RT_ERR_INVALID;
-  if (n != 0u && (reinterpret_cast<uintptr_t>(segs) % 16u != 0u || reinterpret_cast<uintptr_t>(hits) % 16u != 0u ||
-                  reinterpret_cast<uintptr_t>(counts) % 4u != 0u)) {
-    t->set_error("rt_tracer_intersect_all_device: segs and hits must be 16-byte aligned, counts 4-byte aligned");
+  if (!t || !query_row_ok(t, "rt_tracer_intersect_all_device", "max_hits", max_hits) || !query_args_ok(t, n, {segs, hits, counts}) ||
+      !query_aligned_ok(t, n, {{segs, 16u}, {hits, 16u}, {counts, 4u}},
+                        "rt_tracer_intersect_all_device: segs and hits must be 16-byte aligned, counts 4-byte aligned"))
     return RT_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_intersect_all_device(t->mg->bands[0], segs, n, max_hits, hits, counts, stream);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_intersect_all_device(b, segs, n, max_hits, hits, counts, stream); }, [&] {
     if (n == 0u) return;
     t->use_device();
     enqueue_intersect_all(t, n, segs, max_hits, reinterpret_cast<float4*>(hits), counts, static_cast<hipStream_t>(stream));
@@ -566,41 +479,23 @@ int rt_tracer_intersect_all_device(rt_tracer* t, const float* segs, size_t n, ui
 }
 
 int rt_tracer_closest_point(rt_tracer* t, const float* pts, size_t n, rt_hit* out) {
-  if (!t) return RT_ERR_INVALID;
-  if (!query_args_ok(t, n, pts, out)) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_closest_point(t->mg->bands[0], pts, n, out);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  if (!t || !query_args_ok(t, n, {pts, out})) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_point(b, pts, n, out); }, [&] {
     if (n == 0u) return;
     t->use_device();
     const hipStream_t st = query_stream(t);
-    t->d_q_points.ensure(n);
-    t->d_q_hits.ensure(n);
-    HIP_CHECK(hipMemcpyAsync(t->d_q_points.get(), pts, n * 4u * sizeof(float), hipMemcpyHostToDevice, st));
-    enqueue_closest(t, n, reinterpret_cast<const float*>(t->d_q_points.get()), t->d_q_hits.get(), st);
-    HIP_CHECK(hipMemcpyAsync(out, t->d_q_hits.get(), n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+    const float* d_pts = reinterpret_cast<const float*>(staged_in(t->d_q_points, pts, n, st));
+    enqueue_closest(t, n, d_pts, room(t->d_q_hits, n), st);
+    staged_out(out, t->d_q_hits, n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 
 int rt_tracer_closest_point_device(rt_tracer* t, const float* pts, size_t n, rt_hit* out, void* stream) {
-  if (!t) return RT_ERR_INVALID;
-  if (!query_args_ok(t, n, pts, out)) return RT_ERR_INVALID;
-  if (n != 0u && (reinterpret_cast<uintptr_t>(pts) % 16u != 0u || reinterpret_cast<uintptr_t>(out) % 16u != 0u)) {
-    t->set_error("rt_tracer_closest_point_device: pts and out must be 16-byte aligned");
+  if (!t || !query_args_ok(t, n, {pts, out}) ||
+      !query_aligned_ok(t, n, {{pts, 16u}, {out, 16u}}, "rt_tracer_closest_point_device: pts and out must be 16-byte aligned"))
     return RT_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_closest_point_device(t->mg->bands[0], pts, n, out, stream);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_point_device(b, pts, n, out, stream); }, [&] {
     if (n == 0u) return;
     t->use_device();
     enqueue_closest(t, n, pts, reinterpret_cast<float4*>(out), static_cast<hipStream_t>(stream));
@@ -609,48 +504,27 @@ int rt_tracer_closest_point_device(rt_tracer* t, const float* pts, size_t n, rt_
 
 int rt_tracer_closest_all(rt_tracer* t, const float* pts, const rt_hit* after, size_t n, uint32_t max_hits, rt_hit* hits,
                           uint32_t* counts) {
-  if (!t) return RT_ERR_INVALID;
-  if (!intersect_all_args_ok(t, "rt_tracer_closest_all", n, pts, max_hits, hits, counts)) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_closest_all(t->mg->bands[0], pts, after, n, max_hits, hits, counts);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  if (!t || !query_row_ok(t, "rt_tracer_closest_all", "max_hits", max_hits) || !query_args_ok(t, n, {pts, hits, counts})) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_all(b, pts, after, n, max_hits, hits, counts); }, [&] {
     if (n == 0u) return;
     t->use_device();
     const hipStream_t st = query_stream(t);
-    t->d_q_points.ensure(n);
-    if (after) t->d_q_after.ensure(n);
-    t->d_q_all_hits.ensure(n * max_hits);
-    t->d_q_all_counts.ensure(n);
-    HIP_CHECK(hipMemcpyAsync(t->d_q_points.get(), pts, n * 4u * sizeof(float), hipMemcpyHostToDevice, st));
-    if (after) HIP_CHECK(hipMemcpyAsync(t->d_q_after.get(), after, n * sizeof(rt_hit), hipMemcpyHostToDevice, st));
-    enqueue_closest_all(t, n, reinterpret_cast<const float*>(t->d_q_points.get()), after ? t->d_q_after.get() : nullptr, max_hits,
-                        t->d_q_all_hits.get(), t->d_q_all_counts.get(), st);
-    HIP_CHECK(hipMemcpyAsync(hits, t->d_q_all_hits.get(), n * max_hits * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(counts, t->d_q_all_counts.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    const float* d_pts = reinterpret_cast<const float*>(staged_in(t->d_q_points, pts, n, st));
+    const float4* d_after = after ? staged_in(t->d_q_after, after, n, st) : nullptr;
+    enqueue_closest_all(t, n, d_pts, d_after, max_hits, room(t->d_q_all_hits, n * max_hits), room(t->d_q_all_counts, n), st);
+    staged_out(hits, t->d_q_all_hits, n * max_hits, st);
+    staged_out(counts, t->d_q_all_counts, n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 
 int rt_tracer_closest_all_device(rt_tracer* t, const float* pts, const rt_hit* after, size_t n, uint32_t max_hits, rt_hit* hits,
                                  uint32_t* counts, void* stream) {
-  if (!t) return RT_ERR_INVALID;
-  if (!intersect_all_args_ok(t, "rt_tracer_closest_all_device", n, pts, max_hits, hits, counts)) return RT_ERR_INVALID;
-  if (n != 0u && (reinterpret_cast<uintptr_t>(pts) % 16u != 0u || reinterpret_cast<uintptr_t>(after) % 16u != 0u ||
-                  reinterpret_cast<uintptr_t>(hits) % 16u != 0u || reinterpret_cast<uintptr_t>(counts) % 4u != 0u)) {
-    t->set_error("rt_tracer_closest_all_device: pts, after and hits must be 16-byte aligned, counts 4-byte aligned");
+  if (!t || !query_row_ok(t, "rt_tracer_closest_all_device", "max_hits", max_hits) || !query_args_ok(t, n, {pts, hits, counts}) ||
+      !query_aligned_ok(t, n, {{pts, 16u}, {after, 16u}, {hits, 16u}, {counts, 4u}},
+                        "rt_tracer_closest_all_device: pts, after and hits must be 16-byte aligned, counts 4-byte aligned"))
     return RT_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_closest_all_device(t->mg->bands[0], pts, after, n, max_hits, hits, counts, stream);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_all_device(b, pts, after, n, max_hits, hits, counts, stream); }, [&] {
     if (n == 0u) return;
     t->use_device();
     enqueue_closest_all(t, n, pts, reinterpret_cast<const float4*>(after), max_hits, reinterpret_cast<float4*>(hits), counts,
@@ -659,46 +533,27 @@ int rt_tracer_closest_all_device(rt_tracer* t, const float* pts, const rt_hit* a
 }
 
 int rt_tracer_signed_distance(rt_tracer* t, const float* pts, size_t n, rt_hit* hits, rt_side* sides) {
-  if (!t) return RT_ERR_INVALID;
-  if (!sides_args_ok(t, "rt_tracer_signed_distance", n, 1u, pts, hits, sides)) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_signed_distance(t->mg->bands[0], pts, n, hits, sides);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  if (!t || !query_args_ok(t, n, {pts, hits, sides})) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_signed_distance(b, pts, n, hits, sides); }, [&] {
     if (n == 0u) return;
     t->use_device();
     const hipStream_t st = query_stream(t);
     ensure_feature_table(t);
-    t->d_q_points.ensure(n);
-    t->d_q_hits.ensure(n);
-    t->d_q_sides.ensure(n);
-    HIP_CHECK(hipMemcpyAsync(t->d_q_points.get(), pts, n * 4u * sizeof(float), hipMemcpyHostToDevice, st));
-    enqueue_closest(t, n, reinterpret_cast<const float*>(t->d_q_points.get()), t->d_q_hits.get(), st);
-    enqueue_sides(t, n, 1u, reinterpret_cast<const float*>(t->d_q_points.get()), t->d_q_hits.get(), t->d_q_sides.get(), st);
-    HIP_CHECK(hipMemcpyAsync(hits, t->d_q_hits.get(), n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(sides, t->d_q_sides.get(), n * sizeof(rt_side), hipMemcpyDeviceToHost, st));
+    const float* d_pts = reinterpret_cast<const float*>(staged_in(t->d_q_points, pts, n, st));
+    enqueue_closest(t, n, d_pts, room(t->d_q_hits, n), st);
+    enqueue_sides(t, n, 1u, d_pts, t->d_q_hits.get(), room(t->d_q_sides, n), st);
+    staged_out(hits, t->d_q_hits, n, st);
+    staged_out(sides, t->d_q_sides, n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 
 int rt_tracer_signed_distance_device(rt_tracer* t, const float* pts, size_t n, rt_hit* hits, rt_side* sides, void* stream) {
-  if (!t) return RT_ERR_INVALID;
-  if (!sides_args_ok(t, "rt_tracer_signed_distance_device", n, 1u, pts, hits, sides)) return RT_ERR_INVALID;
-  if (n != 0u && (reinterpret_cast<uintptr_t>(pts) % 16u != 0u || reinterpret_cast<uintptr_t>(hits) % 16u != 0u ||
-                  reinterpret_cast<uintptr_t>(sides) % 8u != 0u)) {
-    t->set_error("rt_tracer_signed_distance_device: pts and hits must be 16-byte aligned, sides 8-byte aligned");
+  if (!t || !query_args_ok(t, n, {pts, hits, sides}) ||
+      !query_aligned_ok(t, n, {{pts, 16u}, {hits, 16u}, {sides, 8u}},
+                        "rt_tracer_signed_distance_device: pts and hits must be 16-byte aligned, sides 8-byte aligned"))
     return RT_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_signed_distance_device(t->mg->bands[0], pts, n, hits, sides, stream);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_signed_distance_device(b, pts, n, hits, sides, stream); }, [&] {
     if (n == 0u) return;
     t->use_device();
     ensure_feature_table(t);
@@ -708,46 +563,27 @@ int rt_tracer_signed_distance_device(rt_tracer* t, const float* pts, size_t n, r
 }
 
 int rt_tracer_closest_sides(rt_tracer* t, const float* pts, const rt_hit* hits, size_t n, uint32_t per_point, rt_side* sides) {
-  if (!t) return RT_ERR_INVALID;
-  if (!sides_args_ok(t, "rt_tracer_closest_sides", n, per_point, pts, hits, sides)) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_closest_sides(t->mg->bands[0], pts, hits, n, per_point, sides);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  if (!t || !query_row_ok(t, "rt_tracer_closest_sides", "per_point", per_point) || !query_args_ok(t, n, {pts, hits, sides})) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_sides(b, pts, hits, n, per_point, sides); }, [&] {
     if (n == 0u) return;
     t->use_device();
     const hipStream_t st = query_stream(t);
     ensure_feature_table(t);
-    t->d_q_points.ensure(n);
-    t->d_q_all_hits.ensure(n * per_point);
-    t->d_q_sides.ensure(n * per_point);
-    HIP_CHECK(hipMemcpyAsync(t->d_q_points.get(), pts, n * 4u * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(t->d_q_all_hits.get(), hits, n * per_point * sizeof(rt_hit), hipMemcpyHostToDevice, st));
-    enqueue_sides(t, n, per_point, reinterpret_cast<const float*>(t->d_q_points.get()), t->d_q_all_hits.get(), t->d_q_sides.get(), st);
-    HIP_CHECK(hipMemcpyAsync(sides, t->d_q_sides.get(), n * per_point * sizeof(rt_side), hipMemcpyDeviceToHost, st));
+    const float* d_pts = reinterpret_cast<const float*>(staged_in(t->d_q_points, pts, n, st));
+    const float4* d_hits = staged_in(t->d_q_all_hits, hits, n * per_point, st);
+    enqueue_sides(t, n, per_point, d_pts, d_hits, room(t->d_q_sides, n * per_point), st);
+    staged_out(sides, t->d_q_sides, n * per_point, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 
 int rt_tracer_closest_sides_device(rt_tracer* t, const float* pts, const rt_hit* hits, size_t n, uint32_t per_point, rt_side* sides,
                                    void* stream) {
-  if (!t) return RT_ERR_INVALID;
-  if (!sides_args_ok(t, "rt_tracer_closest_sides_device", n, per_point, pts, hits, sides)) return RT_ERR_INVALID;
-  if (n != 0u && (reinterpret_cast<uintptr_t>(pts) % 16u != 0u || reinterpret_cast<uintptr_t>(hits) % 16u != 0u ||
-                  reinterpret_cast<uintptr_t>(sides) % 8u != 0u)) {
-    t->set_error("rt_tracer_closest_sides_device: pts and hits must be 16-byte aligned, sides 8-byte aligned");
+  if (!t || !query_row_ok(t, "rt_tracer_closest_sides_device", "per_point", per_point) || !query_args_ok(t, n, {pts, hits, sides}) ||
+      !query_aligned_ok(t, n, {{pts, 16u}, {hits, 16u}, {sides, 8u}},
+                        "rt_tracer_closest_sides_device: pts and hits must be 16-byte aligned, sides 8-byte aligned"))
     return RT_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
-    const int rc = rt_tracer_closest_sides_device(t->mg->bands[0], pts, hits, n, per_point, sides, stream);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  return guarded(t, [&] {
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_sides_device(b, pts, hits, n, per_point, sides, stream); }, [&] {
     if (n == 0u) return;
     t->use_device();
     ensure_feature_table(t);
@@ -769,33 +605,28 @@ int rt_dbg_feature_normals(const rt_float4* rows, size_t count, int edges_layout
 }
 
 int rt_tracer_pick(rt_tracer* t, const uint32_t* pixels, size_t n, rt_hit* hits, float* rays) {
-  if (!t) return RT_ERR_INVALID;
-  if (!query_args_ok(t, n, pixels, hits)) return RT_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(t->api_mu);
-  if (t->mg) {
+  if (!t || !query_args_ok(t, n, {pixels, hits})) return RT_ERR_INVALID;
+  const auto forward = [&](rt_tracer* b) {
     multi_push_camera(t);                                                // the camera of the whole frame
-    const int rc = rt_tracer_pick(t->mg->bands[0], pixels, n, hits, rays);
-    if (rc != RT_OK) t->set_error(t->mg->bands[0]->last_error);
-    return rc;
-  }
-  for (size_t i = 0; i < n; ++i) {                                       // full-image coordinates (a band may pick any row)
-    if (pixels[2u * i] >= t->W || pixels[2u * i + 1u] >= t->H) {
-      t->set_error(fmt("Pick: pixel (%u, %u) is outside the %u x %u image", pixels[2u * i], pixels[2u * i + 1u], t->W, t->H));
-      return RT_ERR_INVALID;
+    return rt_tracer_pick(b, pixels, n, hits, rays);
+  };
+  return query_entry(t, forward, [&] {
+    for (size_t i = 0; i < n; ++i) {                                     // full-image coordinates (a band may pick any row)
+      if (pixels[2u * i] >= t->W || pixels[2u * i + 1u] >= t->H) {
+        t->set_error(fmt("Pick: pixel (%u, %u) is outside the %u x %u image", pixels[2u * i], pixels[2u * i + 1u], t->W, t->H));
+        return RT_ERR_INVALID;
+      }
     }
-  }
-  return guarded(t, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
-    t->d_q_pixels.ensure(n * 2u);
-    t->d_q_hits.ensure(n);
-    if (rays) t->d_q_rays.ensure(n * 6u);
-    HIP_CHECK(hipMemcpyAsync(t->d_q_pixels.get(), pixels, n * 2u * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    enqueue_query(t, n, nullptr, t->d_q_pixels.get(), rays ? t->d_q_rays.get() : nullptr, t->d_q_hits.get(), st);
-    HIP_CHECK(hipMemcpyAsync(hits, t->d_q_hits.get(), n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
-    if (rays) HIP_CHECK(hipMemcpyAsync(rays, t->d_q_rays.get(), n * 6u * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    return guarded(t, [&] {
+      if (n == 0u) return;
+      t->use_device();
+      const hipStream_t st = query_stream(t);
+      const uint32_t* d_pixels = staged_in(t->d_q_pixels, pixels, n * 2u, st);
+      enqueue_query(t, n, nullptr, d_pixels, rays ? room(t->d_q_rays, n * 6u) : nullptr, room(t->d_q_hits, n), st);
+      staged_out(hits, t->d_q_hits, n, st);
+      if (rays) staged_out(rays, t->d_q_rays, n * 6u, st);
+      HIP_CHECK(hipStreamSynchronize(st));
+    });
   });
 }
 

@@ -5,6 +5,7 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 from query_expect import HIT_DTYPE
 
@@ -33,6 +34,13 @@ def test_python_class_has_intersect_all():
     from raytracertest_amd import api
     for m in ("IntersectAll", "_intersect_all_tensor"):
         assert callable(getattr(api.RayTracer, m))
+    k = api.RayTracer._max_hits
+    assert k("IntersectAll", 1) == 1 and k("IntersectAll", 16) == 16 and k("IntersectAll", 4.0) == 4
+    for bad in (0, 17, -1, 2.5):
+        with pytest.raises(ValueError, match="max_hits"):
+            k("IntersectAll", bad)
+    with pytest.raises(ValueError, match=r"^IntersectAll: max_hits = 0 \(1 to 16\)$"):
+        k("IntersectAll", 0)
 
 
 def test_header_compiles_as_c99_with_the_new_entries(tmp_path):

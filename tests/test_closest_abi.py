@@ -5,6 +5,7 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 from query_expect import HIT_DTYPE
 
@@ -35,6 +36,37 @@ def test_python_class_has_the_methods():
     d = api.RayTracer._d2max
     assert d(np.inf) == np.inf and d(3.0) == np.float32(9.0) and d(-2.0) == np.float32(-4.0) and np.isnan(d(np.nan))
     assert d(np.float32(1.1)) == np.float32(1.1) * np.float32(1.1)      # squared in fp32
+
+
+@pytest.mark.parametrize("max_distance", [np.inf, 2.0, -2.0, 1e30])    # (1e30 squared overflows fp32: +inf)
+def test_points_array_fills_the_radius_column_of_three_column_points(max_distance):
+    from raytracertest_amd import api
+    f, d2 = api.RayTracer._points_array, api.RayTracer._d2max(max_distance)
+    assert d2 == {np.inf: np.inf, 2.0: 4.0, -2.0: -4.0, 1e30: np.inf}[max_distance]
+    one = f("ClosestPoint", (1.0, 2.0, 3.0), max_distance)                # a single (3,) point
+    assert one.dtype == np.float32 and one.shape == (1, 4) and one.flags.c_contiguous
+    assert one.tobytes() == np.array([[1, 2, 3, d2]], np.float32).tobytes()
+    pts = np.arange(15, dtype=np.float32).reshape(5, 3)
+    got = f("ClosestAll", pts, max_distance)
+    assert got.dtype == np.float32 and got.shape == (5, 4) and got.flags.c_contiguous
+    assert np.array_equal(got[:, :3], pts) and got[:, 3].tobytes() == np.full(5, d2, np.float32).tobytes()
+
+
+def test_points_array_keeps_four_column_points_and_names_its_caller():
+    from raytracertest_amd import api
+    f = api.RayTracer._points_array
+    base = np.arange(40, dtype=np.float32).reshape(5, 8)
+    base[2, 3] = np.nan
+    view = base[:, :4]                                                    # not contiguous
+    got = f("SignedDistance", view, 2.0)                                  # the radius column is the caller's: max_distance plays no part
+    assert got.shape == (5, 4) and got.dtype == np.float32 and got.flags.c_contiguous
+    assert got.tobytes() == np.ascontiguousarray(view).tobytes()
+    assert f("ClosestPoint", np.zeros((0, 4), np.float32), np.inf).shape == (0, 4)
+    for who in ("ClosestPoint", "ClosestAll", "ClosestWithin", "SignedDistance", "ClosestSides"):
+        with pytest.raises(ValueError, match=r"^%s: expected \(n, 3\) or \(n, 4\) float32 points, got shape \(2, 5\)$" % who):
+            f(who, np.zeros((2, 5), np.float32), np.inf)
+        with pytest.raises(ValueError, match=r"^%s: expected .* got shape \(\)$" % who):
+            f(who, 1.0, np.inf)
 
 
 def test_header_compiles_as_c99_with_the_new_entries(tmp_path):

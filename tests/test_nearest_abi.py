@@ -39,11 +39,14 @@ def test_python_class_has_the_methods_and_checks_max_hits():
     from raytracertest_amd import api
     for m in ("ClosestAll", "_closest_all_tensor", "ClosestWithin"):
         assert callable(getattr(api.RayTracer, m))
-    k = api.RayTracer._nearest_max_hits
+    def k(max_hits):                                                   # ClosestAll, ClosestWithin and ClosestSides report as ClosestAll
+        return api.RayTracer._max_hits("ClosestAll", max_hits)
     assert k(1) == 1 and k(16) == 16 and k(4.0) == 4 and api.RT_MAX_HITS == 16
     for bad in (0, 17, -1, 2.5):
         with pytest.raises(ValueError, match="max_hits"):
             k(bad)
+    with pytest.raises(ValueError, match=r"^ClosestAll: max_hits = 17 \(1 to 16\)$"):
+        k(17)
 
 
 def test_header_compiles_as_c99_with_the_new_entries(tmp_path):

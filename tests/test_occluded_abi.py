@@ -4,6 +4,7 @@ import os
 import subprocess
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "raytracertest_amd", "lib")
@@ -27,6 +28,22 @@ def test_python_class_has_occluded_and_visible():
     from raytracertest_amd import api
     for m in ("Occluded", "Visible", "_occluded_tensor"):
         assert callable(getattr(api.RayTracer, m))
+
+
+@pytest.mark.parametrize("who", ["Occluded", "IntersectAll"])
+def test_segs_array_takes_eight_columns_and_does_not_reinterpret_six(who):
+    from raytracertest_amd import api
+    f = api.RayTracer._segs_array
+    segs = np.arange(40, dtype=np.float64).reshape(5, 8)
+    got = f(who, segs)
+    assert got.dtype == np.float32 and got.shape == (5, 8) and got.flags.c_contiguous and np.array_equal(got, segs.astype(np.float32))
+    assert f(who, segs[0]).shape == (1, 8) and f(who, np.zeros((0, 8), np.float32)).shape == (0, 8)
+    wide = np.arange(80, dtype=np.float32).reshape(5, 16)[:, :8]          # not contiguous
+    assert f(who, wide).flags.c_contiguous and f(who, wide).tobytes() == np.ascontiguousarray(wide).tobytes()
+    with pytest.raises(ValueError, match=r"^%s: expected \(n, 8\) float32 segments, got shape \(4, 6\)$" % who):
+        f(who, np.zeros((4, 6), np.float32))
+    with pytest.raises(ValueError, match=r"^%s: expected \(n, 8\) float32 segments, got shape \(\)$" % who):
+        f(who, 1.0)
 
 
 def test_header_compiles_as_c99_with_the_new_entries(tmp_path):
