@@ -5,6 +5,7 @@
 // -lrt_mi355x.  Nothing throws (the reference swallows every failure, RayTracerImpl.cu:42-45,
 // 307-314); LastError() tells what went wrong.  Methods below the marker are additive.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <mutex>
@@ -117,6 +118,35 @@ public:
   bool Occluded(const std::vector<float>& segs, std::vector<uint8_t>& occluded) {
     occluded.resize(segs.size() / 8);
     return mImpl && segs.size() % 8 == 0 && rt_tracer_occluded(mImpl, segs.data(), occluded.size(), occluded.data()) == RT_OK;
+  }
+  // Exposure (rt_mi355x.h, rt_tracer_exposure): points holds 8 floats per point -- origin, unit normal, tmin, tmax; dirs 4 floats
+  // per direction {x, y, z, -}, 1 .. RT_MAX_DIRS of them, in the frame of each point's normal (z along it) or, with world,
+  // used as given.  Bit j of masks[i] is set when direction j from point i is open: Occluded would answer 0 for that segment.
+  // A vector whose size does not fit, no direction or more than RT_MAX_DIRS: false, masks untouched.
+  bool Exposure(const std::vector<float>& points, const std::vector<float>& dirs, std::vector<uint64_t>& masks, bool world = false) {
+    if (!mImpl || points.size() % 8 != 0 || dirs.size() % 4 != 0 || dirs.empty() || dirs.size() / 4 > RT_MAX_DIRS) return false;
+    masks.resize(points.size() / 8);
+    return rt_tracer_exposure(mImpl, points.data(), masks.size(), dirs.data(), static_cast<uint32_t>(dirs.size() / 4),
+                              world ? RT_EXPOSURE_WORLD : RT_EXPOSURE_LOCAL, masks.data()) == RT_OK;
+  }
+  // The same, returning the masks: empty when the vectors were rejected or the call failed (LastError()).
+  std::vector<uint64_t> Exposure(const std::vector<float>& points, const std::vector<float>& dirs, bool world = false) {
+    std::vector<uint64_t> masks;
+    if (!Exposure(points, dirs, masks, world)) masks.clear();
+    return masks;
+  }
+  // A cosine-weighted Fibonacci set on the hemisphere z > 0 for Exposure's local frame, 4 floats {x, y, z, 0} per sample:
+  // sample k at r^2 = (k + 1/2) / samples, phi = (k + 1/2) * pi * (3 - sqrt(5)), in double, rounded to float once.
+  static std::vector<float> HemisphereDirections(uint32_t samples) {
+    std::vector<float> d(static_cast<size_t>(samples) * 4, 0.0f);
+    for (uint32_t k = 0; k < samples; ++k) {
+      const double h = static_cast<double>(k) + 0.5, r2 = h / static_cast<double>(samples);
+      const double phi = h * (3.141592653589793238462643383279502884 * (3.0 - std::sqrt(5.0))), r = std::sqrt(r2);
+      d[4 * k] = static_cast<float>(r * std::cos(phi));
+      d[4 * k + 1] = static_cast<float>(r * std::sin(phi));
+      d[4 * k + 2] = static_cast<float>(std::sqrt(1.0 - r2));
+    }
+    return d;
   }
   // All hits (rt_mi355x.h, rt_tracer_intersect_all): the same segments; row i of hits (maxHits records) holds the ray's first
   // counts[i] <= maxHits in-interval hits in ascending (t, prim) order, then records {0, 0, 0, RT_PRIM_NONE}.  counts[i] ==

@@ -338,6 +338,54 @@ int  rt_tracer_occluded(rt_tracer* t, const float* segs, size_t n, uint8_t* occl
  * synchronisation.  segs must be 16-byte aligned (a ray is two 16-byte loads); otherwise RT_ERR_INVALID. */
 int  rt_tracer_occluded_device(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded, void* stream);
 
+/* Exposure (ambient occlusion, sky-view factor, light-map visibility, several lights shadowed at once): a bundle of up to
+ * RT_MAX_DIRS rays from each point, in one fixed pattern, answered as one bit mask per point.  The rays are made on the device, in
+ * registers; the caller never materialises them.
+ *   points    n x 8 floats, laid out exactly like a segment of rt_tracer_occluded: origin xyz, NORMAL xyz in the direction slots,
+ *             tmin, tmax.  The normal is used as given: the caller supplies a unit normal, the library does not normalise and
+ *             does not check.
+ *   dirs      n_dirs x 4 floats {x, y, z, w}; w is ignored.  All points share the table.
+ *   n_dirs    1 .. RT_MAX_DIRS; otherwise RT_ERR_INVALID (whatever n is).
+ *   flags     RT_EXPOSURE_LOCAL (0): the directions live in the frame of each point's normal, z along the normal (below).
+ *             RT_EXPOSURE_WORLD (1): the directions are used as given; the normal slots are not read into any arithmetic, so NaNs
+ *             there change nothing (sky view, a set of sun positions, several lights).  Any other bit: RT_ERR_INVALID.
+ *   masks     n x uint64.  Bit j of masks[i] is set when direction j from point i is OPEN: rt_tracer_occluded would answer 0
+ *             for the segment {origin_i, d_ij, tmin_i, tmax_i}.  Bits j >= n_dirs are 0.
+ *   hit, interval, NaN   rt_tracer_occluded's, word for word: HitTriangle returns true in the tracer's arithmetic mode for the
+ *             record the renderer intersects, t is the value of Kernels.cuh:63, a sphere counts with the one t of its ray-sphere
+ *             test; the interval is closed and compared in plain fp32; a NaN t or a NaN bound never occludes and tmin > tmax
+ *             never occludes, so such a point has every bit j < n_dirs set.  Triangles are single-sided (the hit test culls back
+ *             faces, as for rt_tracer_occluded); spheres count.  The answer is an OR over the primitives and does not depend on
+ *             RT_FLAG_NEAREST_HIT.
+ *   frame     one arithmetic in both math modes, fp32, every operation rounded separately (nothing fused), the one division
+ *             correctly rounded: the branchless orthonormal basis of Duff et al. (JCGT 6(1), 2017).  With the normal
+ *             n = (x, y, z) and a table entry l:
+ *                 s = copysignf(1, z)           (z = -0 takes s = -1)
+ *                 a = -1 / (s + z)
+ *                 b = (x * y) * a
+ *                 T = (1 + s * ((x * x) * a),   s * b,               -(s * x))
+ *                 B = (b,                       s + (y * y) * a,     -y)
+ *                 d.c = ((l.x * T.c + l.y * B.c) + l.z * n.c)        for c = x, y, z, in this order
+ *             (T, B, n) is right-handed and orthonormal to rounding for a unit n.  A non-finite normal yields NaN directions:
+ *             they never occlude and take no pruning decision, exactly as rt_tracer_occluded treats such a ray.
+ * No scene: every bit j < n_dirs is set; spheres alone are enough to occlude; n = 0 is a no-op; a NULL array with n > 0 is
+ * RT_ERR_INVALID.  Scheduling is that of the other queries: never cancels or joins a running Trace, serialised with the other
+ * calls, on the query stream or the caller's, waited for by uploads and destroy; a multi-device handle answers from its first
+ * band, a band tracer locally.
+ * RT_QUERY_SCAN (default): exact.  RT_QUERY_BVH: every ray walks the tree as a ray of rt_tracer_occluded does (the same box test,
+ * rho, rt_dbg_query_accel_slack and RT_ACCEL_REFIT), so bit j is the complement of what rt_tracer_occluded answers for that
+ * segment in that mode, under the any-hit contract stated there. */
+#define RT_MAX_DIRS 64u
+#define RT_EXPOSURE_LOCAL 0u
+#define RT_EXPOSURE_WORLD 1u
+/* Host arrays: points n*8, dirs n_dirs*4, masks n.  Returns with the masks in host memory. */
+int  rt_tracer_exposure(rt_tracer* t, const float* points, size_t n, const float* dirs, uint32_t n_dirs, uint32_t flags,
+                        uint64_t* masks);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  points and dirs must be 16-byte aligned, masks 8-byte aligned; otherwise RT_ERR_INVALID. */
+int  rt_tracer_exposure_device(rt_tracer* t, const float* points, size_t n, const float* dirs, uint32_t n_dirs, uint32_t flags,
+                               uint64_t* masks, void* stream);
+
 /* All hits along a ray (seeing through surfaces, wall thickness, point-in-solid by the parity of the crossings, the nearest hit
  * in front of the origin under any hit rule): the first max_hits hits of ray i within its own t interval, in order.
  *   segs      n x 8 floats, exactly as rt_tracer_occluded takes them: origin, direction used as given, tmin, tmax.
@@ -646,6 +694,12 @@ int rt_dbg_bvh_build(const rt_float4* rows, size_t count, int edges_layout, void
  * count / 3 * 7 float4 (112 bytes per triangle) exactly as a tracer uploads them; info = {triangles, welded vertices, undirected
  * edges, contributing triangles, build us, bytes, 0, 0}.  With capacity_bytes 0 only info is written. */
 int rt_dbg_feature_normals(const rt_float4* rows, size_t count, int edges_layout, void* out, size_t capacity_bytes, uint64_t info[8]);
+/* The rays of rt_tracer_exposure on their own: segs_out receives the n * n_dirs segments {origin, d_ij, tmin_i, tmax_i} (8 floats
+ * each, point-major: segment i * n_dirs + j) that the query traces for these arguments, from the function its kernels call.  With
+ * a tracer a device kernel evaluates it (on the tracer's device, scheduled as a query; n * n_dirs < 2^31); with t == NULL the
+ * host does and no device is needed.  Host arrays; n_dirs and flags as rt_tracer_exposure checks them; n = 0 is a no-op. */
+int rt_dbg_exposure_rays(rt_tracer* t, const float* points, size_t n, const float* dirs, uint32_t n_dirs, uint32_t flags,
+                         float* segs_out);
 /* rtb::refit on its own, the reference of the device refit; needs no device.  nodes (node_bytes = nodes * 128), leaf_records
  * (record_bytes = count / 3 * 48) and info are arrays rt_dbg_bvh_build (or this call) wrote for a scene of as many triangles; rows
  * are the new scene.  In place: the records take the new triangles by upload index, every box and cmax is recomputed, child[] and

@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "rt_tracer_gather_only", "rt_tracer_group_info",
     "rt_tracer_intersect", "rt_tracer_intersect_device", "rt_tracer_pick", "rt_tracer_focus_at",
     "rt_tracer_occluded", "rt_tracer_occluded_device",
+    "rt_tracer_exposure", "rt_tracer_exposure_device", "rt_dbg_exposure_rays",
     "rt_tracer_intersect_all", "rt_tracer_intersect_all_device",
     "rt_tracer_closest_point", "rt_tracer_closest_point_device",
     "rt_tracer_closest_all", "rt_tracer_closest_all_device",
@@ -67,6 +68,8 @@ class RtError(RuntimeError):
 
 PRIM_NONE = -1
 RT_MAX_HITS = 16         # rt_tracer_intersect_all: the longest row
+RT_MAX_DIRS = 64         # rt_tracer_exposure: the longest direction table (one lane per direction)
+EXPOSURE_LOCAL, EXPOSURE_WORLD = 0, 1
 QUERY_SCAN, QUERY_BVH = 0, 1
 ACCEL_REBUILD, ACCEL_REFIT = 0, 1        # rt_tracer_set_query_accel_update: what an upload does to the tree of QUERY_BVH
 # the arrays of rt_dbg_bvh_build (include/rt_mi355x.h): a 4-wide node and a leaf record
@@ -138,6 +141,58 @@ def feature_normals(rows, edges=False, return_info=False):
     if L.rt_dbg_feature_normals(r.ctypes.data, r.shape[0], int(bool(edges)), out.ctypes.data, max(out.nbytes, 1), info) != 0:
         raise RtError("rt_dbg_feature_normals: " + L.rt_last_error().decode())
     return (out, dict(zip(_FEATURE_KEYS, (int(x) for x in info)))) if return_info else out
+
+
+def _dirs_array(who, directions):
+    """-> contiguous (k, 4) float32 {x, y, z, 0}, 1 <= k <= RT_MAX_DIRS, of (k, 3) or (k, 4) directions."""
+    d = np.asarray(directions, np.float32)
+    if d.ndim != 2 or d.shape[1] not in (3, 4):
+        raise ValueError("%s: expected (k, 3) or (k, 4) float32 directions, got shape %s" % (who, d.shape))
+    if not 1 <= d.shape[0] <= RT_MAX_DIRS:
+        raise ValueError("%s: %d directions (1 to %d)" % (who, d.shape[0], RT_MAX_DIRS))
+    out = np.zeros((d.shape[0], 4), np.float32)
+    out[:, :d.shape[1]] = d
+    return out
+
+
+def _exposure_points_array(who, points, tmin, tmax):
+    """-> contiguous (n, 8) float32 {origin, normal, tmin, tmax}: (n, 6) points get the scalar tmin / tmax in columns 6, 7."""
+    p = np.asarray(points, np.float32)
+    if p.ndim == 0 or p.shape[-1] not in (6, 8):
+        raise ValueError("%s: expected (n, 8) or (n, 6) float32 points, got shape %s" % (who, p.shape))
+    if p.shape[-1] == 8:
+        if tmin is not None or tmax is not None:
+            raise ValueError("%s: (n, 8) points carry their own tmin and tmax" % who)
+        return RayTracer._segs_array(who, p)
+    q = np.empty(p.shape[:-1] + (8,), np.float32)
+    q[..., :6], q[..., 6], q[..., 7] = p, np.float32(0.0 if tmin is None else tmin), np.float32(np.inf if tmax is None else tmax)
+    return np.ascontiguousarray(q).reshape(-1, 8)
+
+
+def hemisphere_directions(samples):
+    """A cosine-weighted Fibonacci set on the hemisphere z > 0, for Exposure's local frame: (samples, 3) float32 unit
+    vectors, sample k at r^2 = (k + 1/2) / samples, phi = (k + 1/2) * pi * (3 - sqrt(5)), (r cos phi, r sin phi, sqrt(1 - r^2)),
+    computed in float64 and rounded to fp32 once.  Equal weights estimate a cosine-weighted integral."""
+    n = int(samples)
+    if n != samples or n < 1:
+        raise ValueError("hemisphere_directions: samples = %r" % (samples,))
+    k = np.arange(n, dtype=np.float64) + 0.5
+    r2 = k / n
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    r = np.sqrt(r2)
+    return np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - r2)], axis=1).astype(np.float32)
+
+
+def exposure_rays(points, directions, world=False):
+    """rt_dbg_exposure_rays without a tracer: the (n, k, 8) float32 segments {origin, d_ij, tmin, tmax} Exposure traces for
+    (n, 8) points and (k, 3 | 4) directions, from the function its kernels call, evaluated on the host (no device needed)."""
+    L = load_library()
+    p = _exposure_points_array("exposure_rays", points, None, None)
+    d = _dirs_array("exposure_rays", directions)
+    out = np.zeros((p.shape[0], d.shape[0], 8), np.float32)
+    if L.rt_dbg_exposure_rays(None, p.ctypes.data, p.shape[0], d.ctypes.data, d.shape[0], int(bool(world)), out.ctypes.data) != 0:
+        raise RtError("rt_dbg_exposure_rays: " + L.rt_last_error().decode())
+    return out
 
 
 class Options(C.Structure):
@@ -289,6 +344,9 @@ def load_library():
         L.rt_tracer_focus_at.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
         L.rt_tracer_occluded.argtypes = [vp, vp, C.c_size_t, vp]
         L.rt_tracer_occluded_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.rt_tracer_exposure.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp]
+        L.rt_tracer_exposure_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp]
+        L.rt_dbg_exposure_rays.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp]
         L.rt_tracer_intersect_all.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp]
         L.rt_tracer_intersect_all_device.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
         L.rt_tracer_closest_point.argtypes = [vp, vp, C.c_size_t, vp]
@@ -741,6 +799,79 @@ class RayTracer:
         _, stream = self._segs_tensor("Occluded", segs)
         out = torch.empty((segs.shape[0],), dtype=torch.uint8, device=segs.device)
         self._check(self._lib.rt_tracer_occluded_device(self._h, segs.data_ptr(), segs.shape[0], out.data_ptr(), stream))
+        return out
+
+    def Exposure(self, points, directions, tmin=None, tmax=None, world=False):
+        """A bundle of rays per point as one bit mask (rt_tracer_exposure).  points: (n, 8) float32 {origin, unit normal, tmin,
+        tmax} laid out like Occluded's segments, or (n, 6) with the scalar tmin / tmax (default 0, +inf) filled in; directions:
+        (k, 3) or (k, 4), 1 <= k <= RT_MAX_DIRS, shared by all points -- in the frame of each point's normal (z along it), or
+        with world=True used as given (the normals are then not read).  Bit j of mask i is set when direction j from point i is
+        OPEN: Occluded would answer False for {origin_i, d_ij, tmin_i, tmax_i}; bits >= k are 0.  numpy arrays -> (n,) uint64,
+        on return.  Contiguous torch float32 tensors on the tracer's device -> (n,) int64 tensor holding the same bit patterns,
+        enqueued on torch.cuda.current_stream() without a host synchronisation when points AND directions are such tensors
+        (numpy directions beside torch points are uploaded first, a synchronous copy)."""
+        if type(points).__module__.startswith("torch"):
+            return self._exposure_tensor(points, directions, tmin, tmax, world)
+        p = _exposure_points_array("Exposure", points, tmin, tmax)
+        d = _dirs_array("Exposure", directions)
+        out = np.zeros(p.shape[0], np.uint64)
+        self._check(self._lib.rt_tracer_exposure(self._h, p.ctypes.data, p.shape[0], d.ctypes.data, d.shape[0], int(bool(world)),
+                                                 out.ctypes.data))
+        return out
+
+    def _exposure_tensor(self, points, directions, tmin, tmax, world):
+        import torch
+        if points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 6:
+            q = torch.empty((points.shape[0], 8), dtype=torch.float32, device=points.device)
+            q[:, :6], q[:, 6], q[:, 7] = points, float(0.0 if tmin is None else tmin), float(np.inf if tmax is None else tmax)
+            points = q
+        elif tmin is not None or tmax is not None:
+            raise ValueError("Exposure: (n, 8) points carry their own tmin and tmax")
+        _, stream = self._segs_tensor("Exposure", points)
+        d = directions
+        if not type(d).__module__.startswith("torch"):
+            d = torch.from_numpy(_dirs_array("Exposure", d)).to(points.device)
+        if d.dtype != torch.float32 or d.dim() != 2 or d.shape[1] not in (3, 4) or not 1 <= d.shape[0] <= RT_MAX_DIRS:
+            raise ValueError("Exposure: expected (k, 3) or (k, 4) float32 directions, 1 <= k <= %d" % RT_MAX_DIRS)
+        if d.device != points.device:
+            raise ValueError("Exposure: the directions are on %s, the points on %s" % (d.device, points.device))
+        if d.shape[1] == 3:
+            d4 = torch.zeros((d.shape[0], 4), dtype=torch.float32, device=d.device)
+            d4[:, :3] = d
+            d = d4
+        elif not d.is_contiguous():
+            raise ValueError("Exposure: expected contiguous (k, 4) float32 directions")
+        out = torch.empty((points.shape[0],), dtype=torch.int64, device=points.device)
+        self._check(self._lib.rt_tracer_exposure_device(self._h, points.data_ptr(), points.shape[0], d.data_ptr(), d.shape[0],
+                                                        int(bool(world)), out.data_ptr(), stream))
+        return out
+
+    def AmbientOcclusion(self, points, normals, samples=64, max_distance=np.inf, bias=1e-3):
+        """(n,) float32: the share of `samples` cosine-weighted hemisphere directions (hemisphere_directions) about each
+        normal that are open over [bias, max_distance] -- 1 = fully exposed.  points, normals: (n, 3) numpy arrays; the
+        normals are normalised in float64 on the host.  ceil(samples / RT_MAX_DIRS) calls of Exposure over slices of the set."""
+        p = np.asarray(points, np.float32).reshape(-1, 3)
+        nrm = np.asarray(normals, np.float64).reshape(-1, 3)
+        if p.shape != nrm.shape:
+            raise ValueError("AmbientOcclusion: %d points, %d normals" % (p.shape[0], nrm.shape[0]))
+        with np.errstate(all="ignore"):
+            nrm = nrm / np.sqrt((nrm * nrm).sum(axis=1))[:, None]
+        dirs = hemisphere_directions(samples)
+        pts = np.empty((p.shape[0], 8), np.float32)
+        pts[:, :3], pts[:, 3:6], pts[:, 6], pts[:, 7] = p, nrm, np.float32(bias), np.float32(max_distance)
+        count = np.zeros(p.shape[0], np.int64)
+        for k in range(0, dirs.shape[0], RT_MAX_DIRS):
+            masks = self.Exposure(pts, dirs[k:k + RT_MAX_DIRS])
+            count += np.unpackbits(masks.view(np.uint8).reshape(-1, 8), axis=1).sum(axis=1, dtype=np.int64)
+        return (count / np.float64(dirs.shape[0])).astype(np.float32)
+
+    def DebugExposureRays(self, points, directions, world=False):
+        """rt_dbg_exposure_rays on the tracer's device: exposure_rays' (n, k, 8) segments from the device function."""
+        p = _exposure_points_array("DebugExposureRays", points, None, None)
+        d = _dirs_array("DebugExposureRays", directions)
+        out = np.zeros((p.shape[0], d.shape[0], 8), np.float32)
+        self._check(self._lib.rt_dbg_exposure_rays(self._h, p.ctypes.data, p.shape[0], d.ctypes.data, d.shape[0], int(bool(world)),
+                                                   out.ctypes.data))
         return out
 
     def IntersectAll(self, segs, max_hits=RT_MAX_HITS):

@@ -1,6 +1,6 @@
 """Headless front end: `python -m raytracertest_amd.cli`.  The reference's command line
 (OpenGLView/App.cpp:62-184: -w -h -s -i -u -cx -cy -cz -cxa -cya -f -l -a, integer values,
-defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --signed / --nearest X,Y,Z / --focus; the image is saved
+defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --focus; the image is saved
 in the reference's BMP format (Common/Bitmap.h).  Same options as tools/rt_cli.cpp."""
 import argparse
 import math
@@ -48,7 +48,11 @@ def build_parser():
                    help="print `signed prim distance x y z feature s signed_distance`: --closest's answer, the feature of the triangle "
                         "that holds the nearest point (0 face, 1-3 vertices, 4-6 edges), the side s (> 0 in front of the surface, < 0 "
                         "behind it) and the distance with that sign")
-    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --signed / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan")
+    p.add_argument("--exposure", type=_exposure, default=None, metavar="X,Y,Z,NX,NY,NZ[,R[,K]]",
+                   help="print `exposure mask open K`: which of K (1 to 64, default 64) cosine-weighted hemisphere directions about "
+                        "the normal NX,NY,NZ (used as given) are open from the point X,Y,Z over [1e-3, R] -- the mask in hex, bit j "
+                        "= direction j, and their count")
+    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan")
     p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
                    help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
     return p
@@ -82,6 +86,17 @@ def _xyzrk(s):
         raise ValueError(s)
     f = [float(x) for x in v[:4]]
     return f[0], f[1], f[2], f[3] if len(f) == 4 else math.inf, k
+
+
+def _exposure(s):
+    v = s.split(",")
+    if len(v) not in (6, 7, 8):
+        raise ValueError(s)
+    k = int(v[7]) if len(v) == 8 else 64
+    if not 1 <= k <= 64:
+        raise ValueError(s)
+    f = [float(x) for x in v[:7]]
+    return tuple(f[:6]) + (f[6] if len(f) == 7 else math.inf, k)
 
 
 class _Nearest(argparse.Action):
@@ -164,6 +179,11 @@ def main(argv=None):
             d = np.sqrt(h["t"][0])
             print("signed %d %.9g %.9g %.9g %.9g %d %.9g %.9g" % (h["prim"][0], d, q[0], q[1], q[2], sd["feature"][0], sd["s"][0],
                                                                  np.copysign(d, sd["s"][0])))
+    if a.exposure is not None:
+        from .api import hemisphere_directions
+        pt = np.float32([a.exposure[:6] + (1e-3, a.exposure[6])])
+        mask = int(g.Exposure(pt, hemisphere_directions(a.exposure[7]))[0])
+        print("exposure %016x %d %d" % (mask, bin(mask).count("1"), a.exposure[7]))
     if knn is not None:
         try:
             hits, counts = g.ClosestAll(np.float32([knn[:3]]), knn[4], knn[3])

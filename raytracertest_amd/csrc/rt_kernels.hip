@@ -8,6 +8,7 @@
 //   query_kernel       <- Radiance's hit scan for caller rays / pixels (rt_query.hpp)
 //   query_bvh_kernel   <- the same answer through a bounding volume hierarchy (rt_bvh.hpp)
 //   occluded_*kernel   <- any hit within a caller's t interval (rt_occluded.hpp)
+//   exposure_*kernel   <- a bundle of rays per point as one bit mask (rt_exposure.hpp)
 //   allhits_*kernel    <- the first k hits within a caller's t interval, in order (rt_allhits.hpp)
 //   closest_*kernel    <- the nearest surface point to a caller's point (rt_closest.hpp)
 //   nearest_*kernel    <- a point's k nearest primitives in order, with a continuation cursor (rt_nearest.hpp)
@@ -20,6 +21,7 @@
 #include "rt_query.hpp"
 #include "rt_bvh.hpp"
 #include "rt_occluded.hpp"
+#include "rt_exposure.hpp"
 #include "rt_allhits.hpp"
 #include "rt_closest.hpp"
 #include "rt_nearest.hpp"

@@ -162,6 +162,21 @@ uint32_t occluded_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_occluded_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint8_t* occluded,
                                hipStream_t st);
 
+// The exposure query (rt_exposure.hpp): n points {origin xyz, normal xyz, tmin, tmax} and a table of n_dirs (1 .. 64) directions
+// {x, y, z, -}, both 16-byte aligned; bit j of masks[i] (8-byte aligned) = 1 when launch_occluded would answer 0 for the segment
+// {origin_i, d_ij, tmin_i, tmax_i}, d_ij = direction j in the frame of normal i (flags = 0) or as given (flags = 1); bits >= n_dirs
+// are 0.  One wave per point, one lane per direction, in both forms.  launch_exposure_rays / exposure_rays_host: the n * n_dirs
+// segments themselves, point-major, from the same function (debug).
+uint32_t exposure_lds_bytes(uint32_t n_tris);
+hipError_t launch_exposure(const TraceParams& p, bool fma, uint32_t n, const float* points, const float* dirs, uint32_t n_dirs,
+                           uint32_t flags, uint64_t* masks, hipStream_t st);
+uint32_t exposure_bvh_lds_bytes(uint32_t stack_cap);
+hipError_t launch_exposure_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* points, const float* dirs,
+                               uint32_t n_dirs, uint32_t flags, uint64_t* masks, hipStream_t st);
+hipError_t launch_exposure_rays(uint32_t n, const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags, float* segs,
+                                hipStream_t st);
+void exposure_rays_host(size_t n, const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags, float* segs);
+
 // The all-hits query (rt_allhits.hpp): the same segments; row i of hits (max_hits records {t, u, v, bits of the int32 primitive},
 // 16-byte aligned) holds the ray's first counts[i] <= max_hits in-interval hits in ascending (t, prim) order, then records
 // {0, 0, 0, -1}.  1 <= max_hits <= 16; one ray per lane in both forms.

@@ -1,5 +1,5 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
-// rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_intersect_all*) and the point queries (rt_tracer_closest_point*,
+// rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_exposure*, rt_tracer_intersect_all*) and the point queries (rt_tracer_closest_point*,
 // rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*).  Included by rt_tracer.hip.
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
@@ -216,6 +216,25 @@ inline void enqueue_occluded(rt_tracer* t, size_t n, const float* segs, uint8_t*
     return b ? rtk::launch_occluded_bvh(p, *b, t->fma, static_cast<uint32_t>(n), segs, occluded, st)
              : rtk::launch_occluded(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), segs, occluded, st);
   });
+}
+
+// points and a direction table -> one 64-bit mask per point (rt_exposure.hpp).  An OR per ray, as enqueue_occluded: the flags stay 0.
+inline void enqueue_exposure(rt_tracer* t, size_t n, const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags,
+                             uint64_t* masks, hipStream_t st) {
+  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return b ? rtk::launch_exposure_bvh(p, *b, t->fma, static_cast<uint32_t>(n), points, dirs, n_dirs, flags, masks, st)
+             : rtk::launch_exposure(p, t->fma, static_cast<uint32_t>(n), points, dirs, n_dirs, flags, masks, st);
+  });
+}
+
+// the direction count and the flags of the exposure entry points, checked whatever n is; t may be null (rt_dbg_exposure_rays)
+inline bool exposure_args_ok(rt_tracer* t, const char* who, uint32_t n_dirs, uint32_t flags) {
+  std::string msg;
+  if (n_dirs == 0u || n_dirs > RT_MAX_DIRS) msg = fmt("%s: n_dirs = %u (1 to %u)", who, n_dirs, RT_MAX_DIRS);
+  else if ((flags & ~RT_EXPOSURE_WORLD) != 0u) msg = fmt("%s: unknown flags 0x%x", who, flags);
+  else return true;
+  if (t) t->set_error(msg); else set_global_error(msg);
+  return false;
 }
 
 // segments -> rows of max_hits records and one count per ray.  The order rule names no hit rule, so the flags stay 0.
@@ -448,6 +467,56 @@ int rt_tracer_occluded_device(rt_tracer* t, const float* segs, size_t n, uint8_t
     if (n == 0u) return;
     t->use_device();
     enqueue_occluded(t, n, segs, occluded, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_exposure(rt_tracer* t, const float* points, size_t n, const float* dirs, uint32_t n_dirs, uint32_t flags, uint64_t* masks) {
+  if (!t || !exposure_args_ok(t, "rt_tracer_exposure", n_dirs, flags) || !query_args_ok(t, n, {points, dirs, masks})) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_exposure(b, points, n, dirs, n_dirs, flags, masks); }, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    const hipStream_t st = query_stream(t);
+    const float* d_points = staged_in(t->d_q_segs, points, n * 8u, st);
+    const float* d_dirs = reinterpret_cast<const float*>(staged_in(t->d_q_dirs, dirs, n_dirs, st));
+    enqueue_exposure(t, n, d_points, d_dirs, n_dirs, flags, room(t->d_q_masks, n), st);
+    staged_out(masks, t->d_q_masks, n, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_exposure_device(rt_tracer* t, const float* points, size_t n, const float* dirs, uint32_t n_dirs, uint32_t flags,
+                              uint64_t* masks, void* stream) {
+  if (!t || !exposure_args_ok(t, "rt_tracer_exposure_device", n_dirs, flags) || !query_args_ok(t, n, {points, dirs, masks}) ||
+      !query_aligned_ok(t, n, {{points, 16u}, {dirs, 16u}, {masks, 8u}},
+                        "rt_tracer_exposure_device: points and dirs must be 16-byte aligned, masks 8-byte aligned"))
+    return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_exposure_device(b, points, n, dirs, n_dirs, flags, masks, stream); }, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_exposure(t, n, points, dirs, n_dirs, flags, masks, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_dbg_exposure_rays(rt_tracer* t, const float* points, size_t n, const float* dirs, uint32_t n_dirs, uint32_t flags, float* segs_out) {
+  if (!exposure_args_ok(t, "rt_dbg_exposure_rays", n_dirs, flags)) return RT_ERR_INVALID;
+  if (!t) {                                                              // the host evaluates the kernels' function
+    if (n != 0u && (!points || !dirs || !segs_out)) { set_global_error("rt_dbg_exposure_rays: null array"); return RT_ERR_INVALID; }
+    return guarded(nullptr, [&] { rtk::exposure_rays_host(n, points, dirs, n_dirs, flags, segs_out); });
+  }
+  if (!query_args_ok(t, n, {points, dirs, segs_out})) return RT_ERR_INVALID;
+  if (n * static_cast<uint64_t>(n_dirs) >= 0x80000000ull) { t->set_error("rt_dbg_exposure_rays: n * n_dirs must be below 2^31"); return RT_ERR_INVALID; }
+  return query_call(t, [&](rt_tracer* b) { return rt_dbg_exposure_rays(b, points, n, dirs, n_dirs, flags, segs_out); }, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    const hipStream_t st = query_stream(t);
+    DevArray<float> d_out(n * n_dirs * 8u);
+    const float* d_points = staged_in(t->d_q_segs, points, n * 8u, st);
+    const float* d_dirs = reinterpret_cast<const float*>(staged_in(t->d_q_dirs, dirs, n_dirs, st));
+    enqueue_launch(t, st, 0u, false, [&](const rtk::TraceParams&, const rtk::BvhParams*) {
+      return rtk::launch_exposure_rays(static_cast<uint32_t>(n), d_points, d_dirs, n_dirs, flags, d_out.get(), st);
+    });
+    HIP_CHECK(hipMemcpyAsync(segs_out, d_out.get(), n * n_dirs * 8u * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 

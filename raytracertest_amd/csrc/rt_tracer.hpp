@@ -579,6 +579,8 @@ struct rt_tracer {
   rtr::DevArray<float4> d_q_hits;
   rtr::DevArray<float> d_q_segs;      // rt_tracer_occluded: n x 8 floats in, n bytes out
   rtr::DevArray<uint8_t> d_q_occluded;
+  rtr::DevArray<float4> d_q_dirs;     // rt_tracer_exposure: n_dirs directions in (the points: d_q_segs), n masks out
+  rtr::DevArray<uint64_t> d_q_masks;
   rtr::DevArray<float4> d_q_all_hits; // rt_tracer_intersect_all: n x max_hits records and n counts out
   rtr::DevArray<uint32_t> d_q_all_counts;
   rtr::DevArray<float4> d_q_points;   // rt_tracer_closest_point: n x {x, y, z, d2max} in, n records (d_q_hits) out

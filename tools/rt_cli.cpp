@@ -27,7 +27,9 @@ struct Args {
   uint64_t seed = 0; bool have_seed = false;
   std::string scene = "demo3", scene_file, out = "image0.bmp";
   bool quiet = false, edges = false, smooth = false, nearest = false;
-  bool pick = false, focus = false, accel = false, hits = false, closest = false, knn = false, sgn = false;
+  bool pick = false, focus = false, accel = false, hits = false, closest = false, knn = false, sgn = false, exposure = false;
+  float exposure_p[7] = {0, 0, 0, 0, 0, 1, INFINITY};   // --exposure: x, y, z, normal, far end of the interval
+  uint32_t exposure_k = 64;
   float closest_p[4] = {0, 0, 0, INFINITY};        // x, y, z, search distance
   float signed_p[4] = {0, 0, 0, INFINITY};         // --signed: the same
   float knn_p[4] = {0, 0, 0, INFINITY};            // --nearest X,Y,Z[,R[,K]]: x, y, z, search distance
@@ -86,6 +88,27 @@ bool parse_xyzrk(const char* s, float out[4], uint32_t& k) {
   return parse_xyzr(v.substr(0, last).c_str(), out);               // (three commas left: four numbers or a failure)
 }
 
+// "X,Y,Z,NX,NY,NZ", "...,R" or "...,R,K": a point, its normal, an optional far end of the interval and a direction count
+bool parse_exposure(const char* s, float out[7], uint32_t& k) {
+  int n = 0;
+  for (const char* q = s;; ++n) {
+    char* end = nullptr;
+    if (n == 7) {
+      if (*q == '-' || *q == '+') return false;
+      const unsigned long kk = std::strtoul(q, &end, 10);
+      if (end == q || *end != 0 || kk < 1 || kk > RT_MAX_DIRS) return false;
+      k = static_cast<uint32_t>(kk);
+      return true;
+    }
+    const float f = std::strtof(q, &end);
+    if (end == q) return false;
+    out[n] = f;
+    if (*end == 0) return n >= 5;
+    if (*end != ',') return false;
+    q = end + 1;
+  }
+}
+
 // what follows --nearest is the point of a k-nearest query (a number), not the next option
 bool looks_like_number(const char* s) {
   if (*s == '+' || *s == '-') ++s;
@@ -126,8 +149,11 @@ void usage() {
             "       [--signed X,Y,Z[,R]] (prints `signed prim distance x y z feature s signed_distance`: --closest's answer, the\n"
             "                      feature of the triangle that holds the nearest point (0 face, 1-3 vertices, 4-6 edges), the side\n"
             "                      s (> 0 in front of the surface, < 0 behind it) and the distance with that sign; `signed -1`)\n"
+            "       [--exposure X,Y,Z,NX,NY,NZ[,R[,K]]] (prints `exposure mask open K`: which of K (1 to 64, default 64) cosine-weighted\n"
+            "                      hemisphere directions about the normal NX,NY,NZ (used as given) are open from the point X,Y,Z over\n"
+            "                      [1e-3, R] -- the mask in hex, bit j = direction j, and their count)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
-            "       [--accel]     (--pick / --hits / --closest / --signed / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan)");
+            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan)");
 }
 
 }  // namespace
@@ -184,6 +210,10 @@ int main(int argc, char** argv) {
     else if (k == "--signed") {
       if (!parse_xyzr(next("--signed"), a.signed_p)) { std::fprintf(stderr, "--signed wants X,Y,Z[,R]\n"); return 2; }
       a.sgn = true;
+    }
+    else if (k == "--exposure") {
+      if (!parse_exposure(next("--exposure"), a.exposure_p, a.exposure_k)) { std::fprintf(stderr, "--exposure wants X,Y,Z,NX,NY,NZ[,R[,K]]\n"); return 2; }
+      a.exposure = true;
     }
     else if (k == "-o") a.out = next("-o");
     else if (k == "-q") a.quiet = true;
@@ -288,6 +318,18 @@ int main(int argc, char** argv) {
                   static_cast<double>(q[1]), static_cast<double>(q[2]), sides[0].feature, static_cast<double>(sides[0].s),
                   static_cast<double>(std::copysign(d, sides[0].s)));
     }
+  }
+  if (a.exposure) {
+    const float* e = a.exposure_p;
+    const std::vector<float> pts = {e[0], e[1], e[2], e[3], e[4], e[5], 1e-3f, e[6]};
+    std::vector<uint64_t> masks;
+    if (!tracer.Exposure(pts, rt::RayTracer::HemisphereDirections(a.exposure_k), masks)) {
+      std::fprintf(stderr, "rt_cli: --exposure: %s\n", tracer.LastError().c_str());
+      return 1;
+    }
+    int open = 0;
+    for (uint32_t j = 0; j < 64; ++j) open += static_cast<int>((masks[0] >> j) & 1u);
+    std::printf("exposure %016llx %d %u\n", static_cast<unsigned long long>(masks[0]), open, a.exposure_k);
   }
   if (a.knn) {
     const float r = a.knn_p[3];
