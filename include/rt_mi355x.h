@@ -278,7 +278,10 @@ int  rt_tracer_focus_at(rt_tracer* t, uint32_t x, uint32_t y, float* focal_lengt
  * noise, so that the scan may report a hit the line passes nowhere near; no finite padding of a box covers that.  For a ray
  * whose scan winner is not well conditioned the BVH mode may return another primitive that the exact test accepts, or none; it
  * never returns a primitive the exact test rejects.  Rays with a non-finite component, a zero direction, or for which the box
- * arithmetic yields a NaN take no pruning decision and get the scan's answer unconditionally. */
+ * arithmetic yields a NaN take no pruning decision and get the scan's answer unconditionally.  All of this is said of scenes
+ * whose hit arithmetic stays finite in fp32: its products are cubic in a record's size and distance from the origin, and beyond
+ * about 2^42 they overflow -- the exact test can then report t = +inf for a triangle behind the ray, which follows no geometry
+ * and which the tree does not reproduce. */
 #define RT_QUERY_SCAN 0u   /* default: every ray scans every triangle */
 #define RT_QUERY_BVH  1u
 int  rt_tracer_set_query_accel(rt_tracer* t, uint32_t mode);
@@ -309,7 +312,9 @@ int  rt_tracer_set_query_accel_update(rt_tracer* t, uint32_t policy);   /* other
 /* Drops the tree now: the next RT_QUERY_BVH query builds afresh, whatever the policy. */
 int  rt_tracer_query_accel_rebuild(rt_tracer* t);
 /* out = {policy, refits since the last build, refits that fell back to a build (over the tracer's life), device time of the last
- * refit in us, tree cost now, tree cost at the last build (both doubles, bit-cast; 0 while no valid tree exists), 0, 0} */
+ * refit in us, tree cost now, tree cost at the last build (both doubles, bit-cast; 0 while no valid tree exists), the stack
+ * entries per lane the walks of the valid tree run with (3 x its depth unless rt_dbg_query_stack_cap lowered it; 0 without a
+ * valid tree), 0} */
 int  rt_tracer_query_accel_update_info(rt_tracer* t, uint64_t out[8]);
 
 /* Visibility (shadow rays, line of sight, ambient occlusion): is ray i blocked within its own t interval?
@@ -716,6 +721,12 @@ int rt_dbg_query_tree_read(rt_tracer* t, void* nodes, size_t node_capacity_bytes
 /* Multiplies the box test's inflation rho for this tracer's following queries in RT_QUERY_BVH mode (1000 = the product; 300,
  * 100, 30, 10, 0 exist so that the margin can be measured in the shipped library, tools/bvh_margin.py). */
 int rt_dbg_query_accel_slack(rt_tracer* t, uint32_t slack_milli);
+/* Test-only: an upper limit on the entries per lane of the traversal stack of this tracer's following queries in RT_QUERY_BVH
+ * mode.  The walks run with min(3 x the tree's depth, cap) entries; UINT32_MAX (the default) is the product.  The limit can
+ * only lower the capacity -- the stack's LDS is sized from the lowered number, and 0 launches without any -- so that a lane
+ * whose walk wants one entry more takes the kernels' overflow path: its answer is recomputed from every leaf record and obeys
+ * the same contract.  It exists so that the tests can run that path, which a tree of the builder never takes on its own. */
+int rt_dbg_query_stack_cap(rt_tracer* t, uint32_t cap);
 /* states n*6 {d,v0..v4} advanced in place, out n*m uniforms in (0,1] */
 int rt_dbg_uniform(int device, uint32_t n, uint32_t m, uint32_t* states, float* out);
 /* thin-lens rays of the tracer's current camera for n (x, y) pixels with given RNG states */

@@ -58,7 +58,7 @@ ABI_SYMBOLS = [
     "rt_tracer_closest_sides", "rt_tracer_closest_sides_device", "rt_dbg_feature_normals",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
     "rt_tracer_set_query_accel_update", "rt_tracer_query_accel_rebuild", "rt_tracer_query_accel_update_info",
-    "rt_dbg_bvh_refit", "rt_dbg_query_tree_read", "rt_dbg_bvh_tree_cost",
+    "rt_dbg_bvh_refit", "rt_dbg_query_tree_read", "rt_dbg_bvh_tree_cost", "rt_dbg_query_stack_cap",
 ]
 
 
@@ -361,6 +361,7 @@ def load_library():
         L.rt_tracer_set_query_accel.argtypes = [vp, C.c_uint32]
         L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_dbg_query_accel_slack.argtypes = [vp, C.c_uint32]
+        L.rt_dbg_query_stack_cap.argtypes = [vp, C.c_uint32]
         L.rt_dbg_bvh_build.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint64)]
         L.rt_tracer_set_query_accel_update.argtypes = [vp, C.c_uint32]
         L.rt_tracer_query_accel_rebuild.argtypes = [vp]
@@ -1163,12 +1164,13 @@ class RayTracer:
 
     def QueryAccelUpdateInfo(self):
         """rt_tracer_query_accel_update_info as a dict: policy, refits (since the last build), fallbacks (refits that became
-        builds), refit_us (device time of the last refit), cost and cost_built (floats: the tree's cost now and at its build)."""
+        builds), refit_us (device time of the last refit), cost and cost_built (floats: the tree's cost now and at its build),
+        stack_entries (per lane, what the walks of the valid tree run with: 3 x depth unless DebugQueryStackCap lowered it)."""
         out = (C.c_uint64 * 8)()
         self._check(self._lib.rt_tracer_query_accel_update_info(self._h, out))
         cost = np.array([out[4], out[5]], np.uint64).view(np.float64)
         return {"policy": int(out[0]), "refits": int(out[1]), "fallbacks": int(out[2]), "refit_us": int(out[3]),
-                "cost": float(cost[0]), "cost_built": float(cost[1])}
+                "cost": float(cost[0]), "cost_built": float(cost[1]), "stack_entries": int(out[6])}
 
     def query_tree(self):
         """rt_dbg_query_tree_read: the device tree the queries walk now -> (nodes, records, info) as bvh_build returns them."""
@@ -1182,6 +1184,11 @@ class RayTracer:
 
     def DebugQueryAccelSlack(self, slack_milli):
         self._check(self._lib.rt_dbg_query_accel_slack(self._h, int(slack_milli)))
+
+    def DebugQueryStackCap(self, cap=None):
+        """rt_dbg_query_stack_cap (test-only): the following QUERY_BVH walks run with at most `cap` stack entries per lane --
+        a lane that wants more answers from every leaf record, under the same contract.  None restores the product."""
+        self._check(self._lib.rt_dbg_query_stack_cap(self._h, 0xFFFFFFFF if cap is None else int(cap)))
 
     def DebugGetRay(self, pixels, states):
         pix = np.ascontiguousarray(pixels, np.uint32).reshape(-1, 2)

@@ -106,6 +106,7 @@ inline uint32_t median_levels(size_t count) {
 struct Builder {
   std::vector<Prim>& prims;
   std::vector<BinNode> bin;
+  uint32_t max_binary_depth = kBvhMaxBinaryDepth;                // (a test's probe build raises it to see the SAH's own depth)
 
   uint32_t build(size_t first, size_t count, uint32_t level) {
     const uint32_t me = static_cast<uint32_t>(bin.size());
@@ -125,7 +126,7 @@ struct Builder {
     }
     int axis = 0;
     for (int a = 1; a < 3; ++a) if (chi[a] - clo[a] > chi[axis] - clo[axis]) axis = a;
-    const uint32_t room = kBvhMaxBinaryDepth - level - 1u;       // binary levels left below a child of this node
+    const uint32_t room = max_binary_depth - level - 1u;         // binary levels left below a child of this node
     size_t mid = 0;
     const double ext = chi[axis] - clo[axis];
     if (ext > 0.0 && std::isfinite(ext)) {                       // binned SAH

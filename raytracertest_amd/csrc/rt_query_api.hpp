@@ -173,7 +173,8 @@ inline rtk::BvhParams query_bvh_params(const rt_tracer* t) {
   b.nodes = t->d_bvh_nodes.get(); b.records = t->d_bvh_records.get();
   b.n_nodes = static_cast<uint32_t>(t->bvh_info[0]); b.n_leaf_records = t->bvh_leaf_records;
   b.n_always = static_cast<uint32_t>(t->bvh_info[3]);
-  b.stack_cap = rtb::stack_capacity(static_cast<uint32_t>(t->bvh_info[2]));
+  // (rt_dbg_query_stack_cap can only lower it: the kernels' sp < stack_cap keeps every store inside the LDS sized from it)
+  b.stack_cap = std::min(rtb::stack_capacity(static_cast<uint32_t>(t->bvh_info[2])), t->query_stack_cap);
   b.rho = RT_BVH_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f);
   return b;
 }
@@ -335,13 +336,19 @@ int rt_tracer_query_accel_update_info(rt_tracer* t, uint64_t out[8]) {
     const double cost = valid ? t->bvh_cost : 0.0, built = valid ? t->bvh_cost_built : 0.0;
     out[0] = t->accel_update; out[1] = t->refits; out[2] = t->refit_fallbacks; out[3] = t->refit_us;
     memcpy(&out[4], &cost, sizeof(double)); memcpy(&out[5], &built, sizeof(double));
-    out[6] = out[7] = 0u;
+    out[6] = valid ? rtr::query_bvh_params(t).stack_cap : 0u;             // what the walks run with (rt_dbg_query_stack_cap lowers it)
+    out[7] = 0u;
   });
 }
 
 int rt_dbg_query_accel_slack(rt_tracer* t, uint32_t slack_milli) {
   if (!t) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_dbg_query_accel_slack(b, slack_milli); }, [&] { t->query_slack_milli = slack_milli; });
+}
+
+int rt_dbg_query_stack_cap(rt_tracer* t, uint32_t cap) {
+  if (!t) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_dbg_query_stack_cap(b, cap); }, [&] { t->query_stack_cap = cap; });
 }
 
 int rt_dbg_bvh_build(const rt_float4* rows, size_t count, int edges_layout, void* nodes, size_t node_capacity_bytes,

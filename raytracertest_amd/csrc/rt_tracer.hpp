@@ -592,6 +592,7 @@ struct rt_tracer {
   // that mode after an upload (rt_query_api.hpp, under api_mu).  The buffers are grow-only; a rebuild waits for the queries.
   uint32_t query_accel = RT_QUERY_SCAN;
   uint32_t query_slack_milli = 1000u;                 // rt_dbg_query_accel_slack: multiplies the box test's rho
+  uint32_t query_stack_cap = UINT32_MAX;              // rt_dbg_query_stack_cap: an upper limit on the walks' stack entries per lane
   rtr::DevArray<float4> d_bvh_nodes, d_bvh_records;
   bool bvh_built = false;
   uint32_t bvh_scene = 0;                             // scene_generation the tree was built for

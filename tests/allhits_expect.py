@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from occluded_expect import conditioning_matrix
-from query_accel_expect import EMPTY, LEAF, RHO, WELL_CONDITIONED, leaf_span, note_box_arithmetic
+from query_accel_expect import EMPTY, LEAF, RHO, WELL_CONDITIONED, leaf_span, note_box_arithmetic, note_high_water
 from query_expect import HIT_DTYPE
 
 INF = np.float32(np.inf)
@@ -202,7 +202,7 @@ def walk_tree_all_hits(orc, nodes, recs, info, segs, rows, max_hits, spheres=Non
     with the oracle's HitTriangle on absolute rows.  Returns (hits, counts, triangle tests made).
     Switches that break one rule each, for tests of the tests: tie_rule=False keeps equal t in the order of arrival; strict=False
     also skips a child whose exit EQUALS tmin or whose enter EQUALS tmax or t_last, and drops a popped entry whose enter EQUALS
-    t_last.  stats: a dict that receives note_box_arithmetic's counters."""
+    t_last.  stats: a dict that receives note_box_arithmetic's counters and note_high_water's marks."""
     contract = orc.FMA if contract is None else contract
     L = orc.lib()
     fp = C.POINTER(C.c_float)
@@ -249,6 +249,7 @@ def walk_tree_all_hits(orc, nodes, recs, info, segs, rows, max_hits, spheres=Non
             omax = np.abs(o).max()
             stack = []
             seen = {}
+            mark = 0
             cur = 0 if (nodes.shape[0] and active) else EMPTY
             while True:
                 if cur == EMPTY:
@@ -289,6 +290,8 @@ def walk_tree_all_hits(orc, nodes, recs, info, segs, rows, max_hits, spheres=Non
                 for k in reversed(kids[1:]):
                     stack.append(k)
                 assert len(stack) <= cap
+                mark = max(mark, len(stack))
+            note_high_water(stats, mark)
             if active:
                 for j in index[n_leaf:]:
                     tests += 1

@@ -5,7 +5,7 @@ the traversal restated over a dumped tree; and the point populations of the test
 deterministic and needs no device."""
 import numpy as np
 
-from query_accel_expect import EMPTY, LEAF, leaf_span, records_of_rows
+from query_accel_expect import EMPTY, LEAF, leaf_span, note_high_water, records_of_rows
 from query_expect import HIT_DTYPE
 
 f32 = np.float32
@@ -295,12 +295,13 @@ def lattice_points(n=4):
 
 # ---- the traversal, restated ------------------------------------------------------------------------------------------------
 
-def walk_tree_closest(nodes, recs, info, pts, rows, edges=False, spheres=None, rho_c=RHO_C, tie_rule=True, strict=True):
+def walk_tree_closest(nodes, recs, info, pts, rows, edges=False, spheres=None, rho_c=RHO_C, tie_rule=True, strict=True, stats=None):
     """closest_bvh_kernel in numpy: the fp32 box test of csrc/rt_closest.hpp operation by operation over a dumped tree (nodes,
     recs, info of api.bvh_build / query_tree), the order-free winner rule, the triangle arithmetic of closest_triangle (looked
     up in table(): the same function on the same operands).  pts (n, 4).  Returns (HIT_DTYPE array, triangle tests made).
     Switches that break one rule each, for tests of the tests: strict=False skips a child at lb >= best and drops a popped
-    entry at lb >= best; tie_rule=False lets the first visited keep a tie."""
+    entry at lb >= best; tie_rule=False lets the first visited keep a tie.  stats: a dict that receives
+    query_accel_expect.note_high_water's marks."""
     pts = np.asarray(pts, f32).reshape(-1, 4)
     n_tris = recs.shape[0]
     tab = table(pts, rows, edges, spheres)
@@ -316,6 +317,7 @@ def walk_tree_closest(nodes, recs, info, pts, rows, edges=False, spheres=None, r
             p, d2max = pts[i, :3], pts[i, 3]
             if not d2max >= 0:                                           # a NaN or negative d2max accepts nothing
                 out[i] = (0, 0, 0, -1)
+                note_high_water(stats, 0)
                 continue
             state = {"t": d2max, "i": -1}
 
@@ -326,6 +328,7 @@ def walk_tree_closest(nodes, recs, info, pts, rows, edges=False, spheres=None, r
             finite = bool(np.isfinite(p).all())
             pmax = np.abs(p).max()
             stack = []
+            mark = 0
             cur = 0 if nodes.shape[0] else EMPTY
             while True:
                 if cur == EMPTY:
@@ -360,6 +363,8 @@ def walk_tree_closest(nodes, recs, info, pts, rows, edges=False, spheres=None, r
                 for k in reversed(kids[1:]):
                     stack.append(k)
                 assert len(stack) <= cap
+                mark = max(mark, len(stack))
+            note_high_water(stats, mark)
             for j in index[n_leaf:]:
                 tests += 1
                 keep(T[i, j], j)

@@ -5,7 +5,7 @@ helper, not a test.  Everything is deterministic and needs no device."""
 import numpy as np
 
 import closest_expect as ce
-from query_accel_expect import EMPTY, LEAF, leaf_span
+from query_accel_expect import EMPTY, LEAF, leaf_span, note_high_water
 from query_expect import HIT_DTYPE
 
 f32 = np.float32
@@ -141,12 +141,13 @@ def differing_rows(got, exp, got_counts=None, exp_counts=None):
 # ---- the traversal, restated ------------------------------------------------------------------------------------------------
 
 def walk_tree_nearest(nodes, recs, info, pts, rows, max_hits, after=None, edges=False, spheres=None, rho_c=ce.RHO_C, tie_rule=True,
-                      strict=True):
+                      strict=True, stats=None):
     """nearest_bvh_kernel in numpy: closest_expect.walk_tree_closest with the sorted list of max_hits (t, prim) pairs in place
     of (best, best_i) and  bound = min(d2max, t_last)  (t_last = +inf while the list is not full) in place of best; the cursor is
     applied before the insert and prunes nothing.  pts (n, 4).  Returns (hits (n, max_hits), counts, triangle tests made).
     Switches that break one rule each, for tests of the tests: strict=False skips a child at lb >= bound and drops a popped
-    entry at lb >= bound; tie_rule=False orders by t alone (the first visited keeps a tie, in the list and at the cut)."""
+    entry at lb >= bound; tie_rule=False orders by t alone (the first visited keeps a tie, in the list and at the cut).  stats: a dict that
+    receives query_accel_expect.note_high_water's marks."""
     pts = np.asarray(pts, f32).reshape(-1, 4)
     n_tris = recs.shape[0]
     tab = ce.table(pts, rows, edges, spheres)
@@ -165,6 +166,7 @@ def walk_tree_nearest(nodes, recs, info, pts, rows, max_hits, after=None, edges=
         for i in range(pts.shape[0]):
             p, d2max = pts[i, :3], pts[i, 3]
             if not d2max >= 0:                                           # a NaN or negative d2max accepts nothing
+                note_high_water(stats, 0)
                 continue
             has = cur_p is not None and cur_p[i] != -1
             lst = []                                                     # [(t, prim)] in order, at most max_hits
@@ -192,6 +194,7 @@ def walk_tree_nearest(nodes, recs, info, pts, rows, max_hits, after=None, edges=
             finite = bool(np.isfinite(p).all())
             pmax = np.abs(p).max()
             stack = []
+            mark = 0
             cur = 0 if nodes.shape[0] else EMPTY
             while True:
                 if cur == EMPTY:
@@ -227,6 +230,8 @@ def walk_tree_nearest(nodes, recs, info, pts, rows, max_hits, after=None, edges=
                 for k in reversed(kids[1:]):
                     stack.append(k)
                 assert len(stack) <= cap
+                mark = max(mark, len(stack))
+            note_high_water(stats, mark)
             for j in index[n_leaf:]:
                 tests += 1
                 keep(T[i, j], j)

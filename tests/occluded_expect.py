@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from query_accel_expect import EMPTY, LEAF, RHO, WELL_CONDITIONED, leaf_span, note_box_arithmetic, records_of_rows
+from query_accel_expect import EMPTY, LEAF, RHO, WELL_CONDITIONED, leaf_span, note_box_arithmetic, note_high_water, records_of_rows
 
 INF = np.float32(np.inf)
 
@@ -131,13 +131,18 @@ def with_interval(rays, tmin, tmax):
 
 # ---- the any-hit traversal, restated -------------------------------------------------------------------------------------
 
-def walk_tree_occluded(orc, nodes, recs, info, segs, rows, spheres=None, contract=None, rho=RHO, strict=True, stats=None):
+def walk_tree_occluded(orc, nodes, recs, info, segs, rows, spheres=None, contract=None, rho=RHO, strict=True, stats=None,
+                       kernel_order=False):
     """occluded_bvh_kernel in numpy: spheres, the always-tested list, then the tree with the fp32 box test of
     csrc/rt_occluded.hpp operation by operation -- a child is skipped when exit < enter, exit < tmin or enter > tmax, unless
     the ray has a non-finite component or a zero direction or the child's arithmetic holds a NaN -- and the oracle's
     HitTriangle on the leaves' triangles (absolute rows).  The order of the visits does not change an OR, so the children are
     entered as stored.  Returns ((n,) bool, triangle tests made).  strict=False (for tests of the tests) also skips a child whose
-    exit EQUALS tmin or whose enter EQUALS tmax; stats: a dict that receives note_box_arithmetic's counters."""
+    exit EQUALS tmin or whose enter EQUALS tmax; stats: a dict that receives note_box_arithmetic's counters and
+    note_high_water's marks -- the entries that WAIT: the kernel enters one of a node's children at once and stacks the others,
+    this walk stacks them all and pops one, so the child it pops next is not counted.  kernel_order: the children are entered
+    in the kernel's order -- the largest overlap of the child's span with the interval first, +inf where nothing is decided --
+    which is what the marks of a device lane follow; the answer is the same OR."""
     contract = orc.FMA if contract is None else contract
     L = orc.lib()
     fp = C.POINTER(C.c_float)
@@ -176,6 +181,7 @@ def walk_tree_occluded(orc, nodes, recs, info, segs, rows, spheres=None, contrac
             omax = np.abs(o).max()
             stack = [0] if nodes.shape[0] else []
             seen = {}
+            mark = 0
             while stack and not done:
                 cur = stack.pop()
                 if cur & LEAF:
@@ -199,10 +205,18 @@ def walk_tree_occluded(orc, nodes, recs, info, segs, rows, spheres=None, contrac
                     skip |= (exit_ == tmin) | (enter == tmax)
                 note_box_arithmetic(stats, seen, t1, t2, nd["child"] != EMPTY)
                 decided = prunes & ~nan
-                for c in range(4):
-                    ref = int(nd["child"][c])
-                    if ref != EMPTY and not (decided[c] and skip[c]):
-                        stack.append(ref)
+                below = len(stack)
+                kids = [c for c in range(4) if int(nd["child"][c]) != EMPTY and not (decided[c] and skip[c])]
+                if kernel_order:
+                    good = np.where(decided, np.fmax(np.fmin(exit_, tmax) - np.fmax(enter, tmin), -np.finfo(f32).max), INF)
+                    kids.sort(key=lambda c: -good[c])                    # (stable: equal overlaps stay in slot order)
+                    kids.reverse()                                       # the best on top
+                for c in kids:
+                    stack.append(int(nd["child"][c]))
                 assert len(stack) <= cap + 3
+                waiting = len(stack) - (1 if len(stack) > below else 0)
+                assert waiting <= cap
+                mark = max(mark, waiting)
+            note_high_water(stats, mark)
             out[i] = done
     return out, tests

@@ -146,12 +146,21 @@ def note_box_arithmetic(stats, seen, t1, t2, present):
             stats[key + "_rays"] = stats.get(key + "_rays", 0) + 1
 
 
+def note_high_water(stats, mark):
+    """Into the dict `stats` of a walk (if given): `mark`, the largest number of entries this ray's or point's stack held, is
+    appended to stats["high_water_per"] (one per ray or point, in order; 0 for one that never walks), and stats["high_water"]
+    is the largest of them.  A kernel lane whose capacity is below its mark takes the overflow path."""
+    if stats is not None:
+        stats.setdefault("high_water_per", []).append(int(mark))
+        stats["high_water"] = max(stats.get("high_water", 0), int(mark))
+
+
 def walk_tree(orc, nodes, recs, info, rays, rows, contract=None, nearest=False, rho=RHO, tie_rule=True, strict=True, stats=None):
     """query_bvh_kernel in numpy: the fp32 box test of csrc/rt_bvh.hpp operation by operation, the order-free hit rule, the
     oracle's HitTriangle on the leaves' triangles (absolute rows).  Returns (HIT_DTYPE array, triangle tests made).
     Switches that break one rule each, for tests of the tests: tie_rule=False drops "equal t: the lower upload index wins" (the
     first visited keeps a tie); strict=False prunes and drops a child whose goodness EQUALS the best t.  stats: a dict that
-    receives note_box_arithmetic's counters."""
+    receives note_box_arithmetic's counters and note_high_water's marks."""
     contract = orc.FMA if contract is None else contract
     L = orc.lib()
     fp = C.POINTER(C.c_float)
@@ -185,6 +194,7 @@ def walk_tree(orc, nodes, recs, info, rays, rows, contract=None, nearest=False, 
 
             stack = []
             seen = {}
+            mark = 0
             cur = 0 if nodes.shape[0] else EMPTY
             while True:
                 if cur == EMPTY:
@@ -226,6 +236,8 @@ def walk_tree(orc, nodes, recs, info, rays, rows, contract=None, nearest=False, 
                 for k in reversed(kids[1:]):
                     stack.append(k)
                 assert len(stack) <= cap
+                mark = max(mark, len(stack))
+            note_high_water(stats, mark)
             for j in index[n_leaf:]:
                 tests += 1
                 test(j)
