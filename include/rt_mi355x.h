@@ -741,6 +741,10 @@ void rt_dbg_rng_advance_host_n(uint32_t* states, uint32_t count, uint32_t n, int
 /* the draws a plain tracer owes to its certain-winner tiles: out = {owed draws, owing launches since the last settle,
  * settle kernels enqueued so far, device tables held} */
 int rt_dbg_owed_state(rt_tracer* t, uint64_t out[4]);
+/* the runtime calls the enqueue path of a plain tracer's trace launches has issued since the last call (reading clears them):
+ * out = {trace launches (steps) enqueued, kernel launches, event records, stream waits, list_ready events recorded as a call of
+ * their own, list_free events recorded as a call of their own, events a kernel launch carried as its stop event instead, 0} */
+int rt_dbg_enqueue_calls(rt_tracer* t, uint64_t out[8]);
 
 #ifdef __cplusplus
 }

@@ -245,4 +245,16 @@ int rt_dbg_owed_state(rt_tracer* t, uint64_t out[4]) {
   return RT_OK;
 }
 
+// out = {launches (steps) enqueued, kernel launches, event records, stream waits, list_ready records, list_free records,
+// events carried by a kernel as its stop event, 0} of the enqueue path since the last call; reading clears them
+int rt_dbg_enqueue_calls(rt_tracer* t, uint64_t out[8]) {
+  if (!t || t->mg || !out) return RT_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lk(t->order_mu);
+  const rtr::EnqueueCalls& c = t->calls;
+  out[0] = c.steps; out[1] = c.launches; out[2] = c.records; out[3] = c.waits; out[4] = c.ready_records; out[5] = c.free_records;
+  out[6] = c.stop_events; out[7] = 0;
+  t->calls = rtr::EnqueueCalls{};
+  return RT_OK;
+}
+
 }  // extern "C"

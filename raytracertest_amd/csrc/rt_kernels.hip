@@ -342,66 +342,99 @@ hipError_t launch_wave_lists(const TraceParams& p, bool fma, hipStream_t st) {
   return hipGetLastError();
 }
 
-// One launch of path P with K samples per pass.  Only the variants the host asks for exist, each a kernel of its own: every
+// The kernel of path P with K samples per pass.  Only the variants the host asks for exist, each a kernel of its own: every
 // path filtered or not and instrumented or not -- the forms paths filtered only, DenseLists never instrumented -- and the
 // filtered, un-instrumented kernels of every path but FullScan with fused iterations too (launch_trace checks the rest).
 template <bool FMA, int K, TracePath P>
-static void launch_trace_kernel(const TraceParams& p, bool filter, dim3 grid, size_t lds, hipStream_t st) {
+static const void* trace_symbol(bool filter, bool fused, bool stats) {
   constexpr bool FORMS = P == TracePath::ClassifyForms || P == TracePath::DenseLists;
   if constexpr (P != TracePath::FullScan) {
-    if (p.iters > 1u) { hipLaunchKernelGGL((trace_kernel<FMA, K, true, false, P, true>), grid, dim3(256), lds, st, p); return; }
+    if (fused) return reinterpret_cast<const void*>(&trace_kernel<FMA, K, true, false, P, true>);
   }
   if constexpr (!FORMS) {
     if (!filter) {
-      if (p.stats != nullptr) hipLaunchKernelGGL((trace_kernel<FMA, K, false, true, P>), grid, dim3(256), lds, st, p);
-      else hipLaunchKernelGGL((trace_kernel<FMA, K, false, false, P>), grid, dim3(256), lds, st, p);
-      return;
+      if (stats) return reinterpret_cast<const void*>(&trace_kernel<FMA, K, false, true, P>);
+      return reinterpret_cast<const void*>(&trace_kernel<FMA, K, false, false, P>);
     }
   }
   if constexpr (P != TracePath::DenseLists) {
-    if (p.stats != nullptr) { hipLaunchKernelGGL((trace_kernel<FMA, K, true, true, P>), grid, dim3(256), lds, st, p); return; }
+    if (stats) return reinterpret_cast<const void*>(&trace_kernel<FMA, K, true, true, P>);
   }
-  hipLaunchKernelGGL((trace_kernel<FMA, K, true, false, P>), grid, dim3(256), lds, st, p);
+  return reinterpret_cast<const void*>(&trace_kernel<FMA, K, true, false, P>);
 }
 
 static constexpr int variant(TracePath path, int K) { return static_cast<int>(path) * 8 + K; }
 
-hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, TracePath path, int K, hipStream_t st) {
+template <bool F>
+static const void* trace_symbol_of(TracePath path, int K, bool filter, bool fused, bool stats) {
+  using P = TracePath;
+  switch (variant(path, K)) {
+    case variant(P::FullScan, 1): return trace_symbol<F, 1, P::FullScan>(filter, fused, stats);
+    case variant(P::FullScan, 2): return trace_symbol<F, 2, P::FullScan>(filter, fused, stats);
+    case variant(P::FullScan, 4): return trace_symbol<F, 4, P::FullScan>(filter, fused, stats);
+    case variant(P::SmallLists, 1): return trace_symbol<F, 1, P::SmallLists>(filter, fused, stats);
+    case variant(P::SmallLists, 2): return trace_symbol<F, 2, P::SmallLists>(filter, fused, stats);
+    case variant(P::SmallLists, 4): return trace_symbol<F, 4, P::SmallLists>(filter, fused, stats);
+    case variant(P::Classify, 1): return trace_symbol<F, 1, P::Classify>(filter, fused, stats);
+    case variant(P::Classify, 2): return trace_symbol<F, 2, P::Classify>(filter, fused, stats);
+    case variant(P::Classify, 4): return trace_symbol<F, 4, P::Classify>(filter, fused, stats);
+    case variant(P::ClassifyForms, 1): return trace_symbol<F, 1, P::ClassifyForms>(filter, fused, stats);
+    case variant(P::ClassifyForms, 2): return trace_symbol<F, 2, P::ClassifyForms>(filter, fused, stats);
+    case variant(P::ClassifyForms, 4): return trace_symbol<F, 4, P::ClassifyForms>(filter, fused, stats);
+    case variant(P::DenseLists, 1): return trace_symbol<F, 1, P::DenseLists>(filter, fused, stats);
+    case variant(P::DenseLists, 2): return trace_symbol<F, 2, P::DenseLists>(filter, fused, stats);
+    case variant(P::DenseLists, 4): return trace_symbol<F, 4, P::DenseLists>(filter, fused, stats);
+  }
+  return nullptr;
+}
+
+// The descriptor in `slot` (a KernelTable entry, or a local one: resolved for this launch only), resolved from the kernel's
+// host symbol when the slot is empty.  Racing resolvers store the same value.
+template <class Symbol>
+static hipError_t resolve_kernel(std::atomic<hipFunction_t>& slot, Symbol&& symbol, hipFunction_t* f) {
+  *f = slot.load(std::memory_order_acquire);
+  if (*f != nullptr) return hipSuccess;
+  const void* const sym = symbol();
+  if (sym == nullptr) return hipErrorInvalidDeviceFunction;
+  const hipError_t e = hipGetFuncBySymbol(f, sym);
+  if (e == hipSuccess) slot.store(*f, std::memory_order_release);
+  return e;
+}
+
+// One launch of a kernel whose only argument is a TraceParams by value: the struct goes to the runtime as one buffer.
+// stop: an event that completes with this kernel (bound by the launch: no packet of its own behind it), or null.
+static hipError_t launch_with_params(hipFunction_t f, dim3 grid, size_t lds, hipStream_t st, const TraceParams& p, hipEvent_t stop) {
+  size_t size = sizeof(TraceParams);
+  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<TraceParams*>(&p), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+  if (stop != nullptr)     // (the ext launch takes the global size in work-items; flags 0: in order)
+    return hipExtModuleLaunchKernel(f, grid.x * 256u, grid.y, grid.z, 256u, 1u, 1u, lds, st, nullptr, extra, nullptr, stop, 0u);
+  return hipModuleLaunchKernel(f, grid.x, grid.y, grid.z, 256u, 1u, 1u, static_cast<unsigned int>(lds), st, nullptr, extra);
+}
+
+hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, TracePath path, int K, hipStream_t st, KernelTable* table,
+                        hipEvent_t stop) {
   // samples == 0 is a real launch, as in the reference (TraceKernel with sampleCount 0: counts += 0,
   // render += 0, RNG written back, Kernels.cuh:133-146): the fused clear / BGRA8 emit / list store of the
   // launch still have to happen
-  if (p.rows == 0 || p.W == 0) return hipSuccess;
+  if (p.rows == 0 || p.W == 0) return stop != nullptr ? hipEventRecord(stop, st) : hipSuccess;
   const bool forms = path == TracePath::ClassifyForms || path == TracePath::DenseLists;
   if ((forms && !filter) || (path == TracePath::SmallLists && p.n_tris > p.bin_list) ||
       (path == TracePath::DenseLists && (p.wave_lists == nullptr || p.stats != nullptr)) ||
       (p.iters > 1u && (!trace_can_fuse(path, filter) || p.stats != nullptr)) ||
       (p.row_il != 0u && (path != TracePath::SmallLists || p.stats != nullptr))) return hipErrorInvalidValue;
   const dim3 grid = trace_grid(p);                       // (row_il: every second block row, small-scene kernels only)
-  if (grid.y == 0u) return hipSuccess;
+  if (grid.y == 0u) return stop != nullptr ? hipEventRecord(stop, st) : hipSuccess;
   const size_t lds = trace_lds_bytes(p, path);
-  auto launch = [&](auto fma_c) {
-    constexpr bool F = decltype(fma_c)::value;
-    using P = TracePath;
-    switch (variant(path, K == 1 || K == 2 ? K : 4)) {
-      case variant(P::FullScan, 1): return launch_trace_kernel<F, 1, P::FullScan>(p, filter, grid, lds, st);
-      case variant(P::FullScan, 2): return launch_trace_kernel<F, 2, P::FullScan>(p, filter, grid, lds, st);
-      case variant(P::FullScan, 4): return launch_trace_kernel<F, 4, P::FullScan>(p, filter, grid, lds, st);
-      case variant(P::SmallLists, 1): return launch_trace_kernel<F, 1, P::SmallLists>(p, filter, grid, lds, st);
-      case variant(P::SmallLists, 2): return launch_trace_kernel<F, 2, P::SmallLists>(p, filter, grid, lds, st);
-      case variant(P::SmallLists, 4): return launch_trace_kernel<F, 4, P::SmallLists>(p, filter, grid, lds, st);
-      case variant(P::Classify, 1): return launch_trace_kernel<F, 1, P::Classify>(p, filter, grid, lds, st);
-      case variant(P::Classify, 2): return launch_trace_kernel<F, 2, P::Classify>(p, filter, grid, lds, st);
-      case variant(P::Classify, 4): return launch_trace_kernel<F, 4, P::Classify>(p, filter, grid, lds, st);
-      case variant(P::ClassifyForms, 1): return launch_trace_kernel<F, 1, P::ClassifyForms>(p, filter, grid, lds, st);
-      case variant(P::ClassifyForms, 2): return launch_trace_kernel<F, 2, P::ClassifyForms>(p, filter, grid, lds, st);
-      case variant(P::ClassifyForms, 4): return launch_trace_kernel<F, 4, P::ClassifyForms>(p, filter, grid, lds, st);
-      case variant(P::DenseLists, 1): return launch_trace_kernel<F, 1, P::DenseLists>(p, filter, grid, lds, st);
-      case variant(P::DenseLists, 2): return launch_trace_kernel<F, 2, P::DenseLists>(p, filter, grid, lds, st);
-      case variant(P::DenseLists, 4): return launch_trace_kernel<F, 4, P::DenseLists>(p, filter, grid, lds, st);
-    }
-  };
-  if (fma) launch(std::true_type{}); else launch(std::false_type{});
-  return hipGetLastError();
+  const int k = K == 1 || K == 2 ? K : 4;
+  const bool fused = p.iters > 1u, stats = p.stats != nullptr;
+  if (static_cast<uint32_t>(path) >= 5u) return hipErrorInvalidValue;
+  std::atomic<hipFunction_t> local{nullptr};
+  std::atomic<hipFunction_t>& slot = table != nullptr ? table->trace[fma][k >> 1][filter][static_cast<uint32_t>(path)][fused][stats] : local;
+  hipFunction_t f = nullptr;
+  const hipError_t e = resolve_kernel(slot, [&] { return fma ? trace_symbol_of<true>(path, k, filter, fused, stats)
+                                                            : trace_symbol_of<false>(path, k, filter, fused, stats); }, &f);
+  if (e != hipSuccess) return e;
+  return launch_with_params(f, grid, lds, st, p, stop);
 }
 
 // blocks of the default (fma, filtered) trace kernel the occupancy API admits per CU: the small scenes' at K = 1, 2,
@@ -503,31 +536,30 @@ hipError_t launch_sure_table(const float4* colors, uint32_t n_tris, uint32_t sam
   return hipGetLastError();
 }
 
-hipError_t launch_tile_lists(const TraceParams& p, bool fma, hipStream_t st) {
-  if (p.tile_lists == nullptr || p.rows == 0u || p.W == 0u) return hipSuccess;
-  if (p.tile_curv > 0.0f && p.n_tris <= 32u && p.n_tris != 0u) {   // two levels, two regions per wave
-    const dim3 grid(cdiv(cdiv(p.W, 32) * cdiv(cdiv(p.rows, 8), 2), 8u));
-    if (fma) hipLaunchKernelGGL((region_pair_lists_kernel<true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((region_pair_lists_kernel<false>), grid, dim3(256), 0, st, p);
-    return hipGetLastError();
-  }
-  if (p.tile_curv > 0.0f && p.n_tris <= 256u) {             // two levels: region -> tiles (its LDS candidate list holds 256)
-    const dim3 grid(cdiv(cdiv(p.W, 32) * cdiv(cdiv(p.rows, 8), 2), 4u));
-    if (fma) hipLaunchKernelGGL((region_lists_kernel<true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((region_lists_kernel<false>), grid, dim3(256), 0, st, p);
-    return hipGetLastError();
-  }
-  const uint32_t slots = cdiv(p.W, 32) * cdiv(p.rows, 8) * 4u;
-  if (p.n_tris <= 32u) {                                             // two tiles per wave
-    const dim3 grid(cdiv(slots, 8u));
-    if (fma) hipLaunchKernelGGL((tile_lists_kernel<true, 32>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((tile_lists_kernel<false, 32>), grid, dim3(256), 0, st, p);
-  } else {
-    const dim3 grid(cdiv(slots, 4u));
-    if (fma) hipLaunchKernelGGL((tile_lists_kernel<true, 64>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((tile_lists_kernel<false, 64>), grid, dim3(256), 0, st, p);
-  }
-  return hipGetLastError();
+hipError_t launch_tile_lists(const TraceParams& p, bool fma, hipStream_t st, KernelTable* table, hipEvent_t stop) {
+  if (p.tile_lists == nullptr || p.rows == 0u || p.W == 0u) return stop != nullptr ? hipEventRecord(stop, st) : hipSuccess;
+  // 0: two levels, two regions per wave; 1: two levels, region -> tiles (its LDS candidate list holds 256);
+  // 2: one level, two tiles per wave; 3: one level, a tile per wave
+  const uint32_t slots = cdiv(p.W, 32) * cdiv(p.rows, 8) * 4u, regions = cdiv(p.W, 32) * cdiv(cdiv(p.rows, 8), 2);
+  int kind;
+  dim3 grid;
+  if (p.tile_curv > 0.0f && p.n_tris <= 32u && p.n_tris != 0u) { kind = 0; grid = dim3(cdiv(regions, 8u)); }
+  else if (p.tile_curv > 0.0f && p.n_tris <= 256u) { kind = 1; grid = dim3(cdiv(regions, 4u)); }
+  else if (p.n_tris <= 32u) { kind = 2; grid = dim3(cdiv(slots, 8u)); }
+  else { kind = 3; grid = dim3(cdiv(slots, 4u)); }
+  std::atomic<hipFunction_t> local{nullptr};
+  std::atomic<hipFunction_t>& slot = table != nullptr ? table->lists[fma][kind] : local;
+  hipFunction_t f = nullptr;
+  const hipError_t e = resolve_kernel(slot, [&]() -> const void* {
+    switch (kind) {
+      case 0: return fma ? reinterpret_cast<const void*>(&region_pair_lists_kernel<true>) : reinterpret_cast<const void*>(&region_pair_lists_kernel<false>);
+      case 1: return fma ? reinterpret_cast<const void*>(&region_lists_kernel<true>) : reinterpret_cast<const void*>(&region_lists_kernel<false>);
+      case 2: return fma ? reinterpret_cast<const void*>(&tile_lists_kernel<true, 32>) : reinterpret_cast<const void*>(&tile_lists_kernel<false, 32>);
+      default: return fma ? reinterpret_cast<const void*>(&tile_lists_kernel<true, 64>) : reinterpret_cast<const void*>(&tile_lists_kernel<false, 64>);
+    }
+  }, &f);
+  if (e != hipSuccess) return e;
+  return launch_with_params(f, grid, 0, st, p, stop);
 }
 
 // every float in [2^-96, 2^96]: sqrt_midrange / rcp_midrange against the generic expansions

@@ -2,7 +2,9 @@
 // gfx950 kernels (rt_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
+#include <atomic>
 
 namespace rtk {
 
@@ -126,7 +128,18 @@ inline dim3 trace_grid(const TraceParams& p) {
   }
   return grid;
 }
-hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, TracePath path, int K, hipStream_t st);
+// Launch descriptors: the hipFunction_t of every trace and list-builder instantiation, resolved from the kernel's host symbol
+// the first time it is launched and kept -- a launch through the table skips the runtime's look-up of the host stub and the
+// template switch.  A descriptor belongs to a device: one table per tracer.
+struct KernelTable {
+  std::atomic<hipFunction_t> trace[2][3][2][5][2][2] = {};   // fma, K (1, 2, 4), filter, path, fused iterations, instrumented
+  std::atomic<hipFunction_t> lists[2][4] = {};               // fma, builder (launch_tile_lists)
+};
+// table: null resolves the kernel for this launch only.  stop: an event the launch binds to the kernel -- it completes when the
+// kernel does and serves hipStreamWaitEvent on other streams like an event recorded behind it, without a packet of its own
+// (where nothing is launched it is recorded instead); null: none.
+hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, TracePath path, int K, hipStream_t st, KernelTable* table = nullptr,
+                        hipEvent_t stop = nullptr);
 int trace_occupancy(int K, size_t lds);
 hipError_t launch_convert(const float4* render, uint32_t count, uint32_t* image, uint32_t npix, hipStream_t st);
 
@@ -236,7 +249,8 @@ hipError_t launch_publish_half_cost(uint32_t* half_cost, unsigned long long* hos
 // small scenes: the per-triangle table TraceParams::sure_table for launches of `samples` samples
 hipError_t launch_sure_table(const float4* colors, uint32_t n_tris, uint32_t samples, float4* out, hipStream_t st);
 // small scenes: the tiles' candidate lists + certain-winner verdicts of the (half-)launch `p` into p.tile_lists
-hipError_t launch_tile_lists(const TraceParams& p, bool fma, hipStream_t st);
+// (table, stop: as launch_trace takes them)
+hipError_t launch_tile_lists(const TraceParams& p, bool fma, hipStream_t st, KernelTable* table = nullptr, hipEvent_t stop = nullptr);
 hipError_t launch_dbg_check_midrange(unsigned long long* out, hipStream_t st);
 hipError_t launch_dbg_focal_boxes(bool fma, const TraceParams& p, float* boxes, float* focal, hipStream_t st);
 hipError_t launch_dbg_classify(bool fma, bool forms, uint32_t slack_milli, const TraceParams& p, uint32_t level, uint32_t n_regions,

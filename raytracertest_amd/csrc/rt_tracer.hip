@@ -203,7 +203,7 @@ int rt_tracer_create_ex(const uint32_t imageSize[2], const float cameraPosition[
     HIP_CHECK(hipDeviceSynchronize());                                    // (a null-stream memset is not ordered with the list stream)
     t->h_half_cost.ensure(1);
     *t->h_half_cost.get() = 0ull;
-    t->lists.create(t->stream, t->stream_b, t->stream_l);
+    t->lists.create(t->stream, t->stream_b, t->stream_l, &t->calls);
     t->handoff_event = Event(hipEventDisableTiming);
     t->join_event = Event(hipEventDisableTiming);
     t->fork_event = Event(hipEventDisableTiming);

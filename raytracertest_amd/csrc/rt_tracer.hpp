@@ -280,6 +280,13 @@ class RenderThread {
   bool quit_ = false;
 };
 
+// Runtime calls the enqueue path of the trace launches has issued since the last read (rt_dbg_enqueue_calls; guarded by
+// rt_tracer::order_mu): kernel launches, event records, stream waits -- of the records, those of a list_ready / a list_free
+// event as a call of their own -- the events kernels carried as stop events instead, and the launches (steps) enqueued.
+struct EnqueueCalls {
+  uint64_t steps = 0, launches = 0, records = 0, waits = 0, ready_records = 0, free_records = 0, stop_events = 0;
+};
+
 // What the stored candidate lists were built for: camera snapshot, lens, frame, list length (or macro geometry), scene and
 // arithmetic mode -- they do not depend on the samples.  rt_tracer::make_key zeroes the padding: keys compare bytewise.
 struct ListKey {
@@ -307,18 +314,27 @@ constexpr uint32_t kSettleStepMax = 96u;   // draws up to which rng_settle_kerne
 // half's trace kernel and stalled its own stream meanwhile, profiles/r03_lists_inline_timeline.txt).  Ordering: the trace
 // streams wait for list_ready[slot] (recorded on stream_l behind the build); a build into a slot waits until the slot's last
 // readers are done.  An event record is a packet the next kernel of its stream queues behind (two of them per step cost
-// 4 us of a 66 us C3 step), so the trace streams record a "free" event only every kFreeStride-th build -- it covers every
+// 4 us of a 66 us C3 step), so the trace streams mark a "free" event only every kFreeStride-th build -- it covers every
 // kernel enqueued before it -- and the ring is long enough that a build always finds such an event that is at least
-// kFreeStride builds old and still covers the readers of the slot it overwrites (build m: the oldest recorded at a build
+// kFreeStride builds old and still covers the readers of the slot it overwrites (build m: the oldest marked at a build
 // e >= m - kListRing + 1; then m - kListRing < e <= m - kFreeStride).
+// Neither event is a packet of its own where a kernel can carry it: list_ready is the stop event of the builder's launch,
+// and the free pair of build m (m a multiple of kFreeStride) is the stop event of the LAST kernel each trace stream got
+// before build m -- in the steady state the two half-frame trace kernels of launch m - 1.  The invariant: when build m is
+// enqueued, pair (m / kFreeStride) % kFreeEvents completes no earlier than every list-reading kernel enqueued on its stream
+// so far.  A kernel's stop event gives that exactly when no kernel follows it on the stream before build m; carry() hands
+// the event to a trace launch only under conditions that make it the last one (the launch built its own lists, so the next
+// launch that reads lists builds too or rebinds the event; no settle kernel follows), drop_carry() withdraws it when
+// something else is enqueued on a trace stream, and build_ahead() records the event where no kernel carries it for this
+// build (an unsplit launch leaves stream_b without a kernel: recorded).  The free_build_ check below stays.
 class TileListRing {
  public:
   static constexpr int kListRing = 8, kFreeEvents = 10;
   std::optional<ListKey> key;         // what the current lists were built for
 
-  // a = the primary trace stream, b = stream_b, l = stream_l
-  void create(hipStream_t a, hipStream_t b, hipStream_t l) {
-    a_ = a; b_ = b; l_ = l;
+  // a = the primary trace stream, b = stream_b, l = stream_l; calls: where the runtime calls are counted
+  void create(hipStream_t a, hipStream_t b, hipStream_t l, EnqueueCalls* calls) {
+    a_ = a; b_ = b; l_ = l; calls_ = calls;
     for (Event& e : list_ready_) e = Event(hipEventDisableTiming);
     for (int r = 0; r < kFreeEvents; ++r) { list_free_a_[r] = Event(hipEventDisableTiming); list_free_b_[r] = Event(hipEventDisableTiming); }
   }
@@ -350,8 +366,8 @@ class TileListRing {
     const uint64_t m = builds_;
     if (m > 0 && m % free_stride_ == 0) {                              // everything the trace streams hold now: the readers of every earlier build
       const int i = static_cast<int>((m / free_stride_) % kFreeEvents);
-      HIP_CHECK(hipEventRecord(list_free_a_[i], a_));
-      HIP_CHECK(hipEventRecord(list_free_b_[i], b_));
+      if (carried_[0] != m) { HIP_CHECK(hipEventRecord(list_free_a_[i], a_)); ++calls_->records; ++calls_->free_records; }
+      if (carried_[1] != m) { HIP_CHECK(hipEventRecord(list_free_b_[i], b_)); ++calls_->records; ++calls_->free_records; }
       free_build_[i] = m;
     }
     const int r = static_cast<int>(m % ring_n_);
@@ -362,19 +378,34 @@ class TileListRing {
       if (e != free_waited_) {                                         // (kFreeStride builds in a row need the same pair: stream_l has it behind it already)
         HIP_CHECK(hipStreamWaitEvent(l_, list_free_a_[i], 0));
         HIP_CHECK(hipStreamWaitEvent(l_, list_free_b_[i], 0));
+        calls_->waits += 2u;
         free_waited_ = e;
       }
     }
     cur_ = r;
     return m;
   }
-  void built() { HIP_CHECK(hipEventRecord(list_ready_[cur_], l_)); ++builds_; }
+  // the event the build kernel's launch takes as its stop event (launch_tile_lists): no record behind the kernel
+  hipEvent_t ready_event() const { return list_ready_[cur_]; }
+  void built() { ++builds_; }
   // trace stream `which` (0: a, 1: b) is about to run a trace kernel that reads the current lists
   void wait(hipStream_t st, int which) {
     if (waited_[which] == builds_) return;
     HIP_CHECK(hipStreamWaitEvent(st, list_ready_[cur_], 0));
+    ++calls_->waits;
     waited_[which] = builds_;
   }
+  // The stop event of the trace kernel about to be launched on stream `which`, or null.  last_before_next_build: the caller
+  // knows that no other kernel follows this one on the stream before the next build (see the type's comment).  Every
+  // launch passes here, so a launch that does not carry also withdraws what an earlier one on the stream carried.
+  hipEvent_t carry(int which, bool last_before_next_build) {
+    carried_[which] = 0;
+    if (!last_before_next_build || builds_ == 0 || builds_ % free_stride_ != 0) return nullptr;
+    carried_[which] = builds_;                                         // the next build's index
+    ++calls_->stop_events;
+    return (which == 0 ? list_free_a_ : list_free_b_)[(builds_ / free_stride_) % kFreeEvents];
+  }
+  void drop_carry() { carried_[0] = carried_[1] = 0; }                 // something else goes onto a trace stream
   // Points one (half-)launch at its slots of the current lists (null: `have` = false): a lower half starts behind the
   // upper half's block rows (the split row is a multiple of 8).
   void attach(rtk::TraceParams& p, uint32_t band_row0, bool have) const {
@@ -384,18 +415,21 @@ class TileListRing {
   void release() {                    // callers have synchronised every stream
     for (DevArray<uint32_t>& s : slots_) s.reset();
     words_ = 0; key.reset(); cur_ = 0; alloc_build_ = builds_;
+    drop_carry();
   }
   uint32_t* now() const { return slots_[cur_].get(); }
   size_t words() const { return words_; }
 
  private:
   hipStream_t a_ = nullptr, b_ = nullptr, l_ = nullptr;
+  EnqueueCalls* calls_ = nullptr;
   int ring_n_ = 8, free_stride_ = 4;
   DevArray<uint32_t> slots_[kListRing];
   size_t words_ = 0;                  // of each slot
   Event list_ready_[kListRing];
   Event list_free_a_[kFreeEvents], list_free_b_[kFreeEvents];
-  uint64_t free_build_[kFreeEvents] = {};   // the build index each pair was recorded at (0 = never)
+  uint64_t free_build_[kFreeEvents] = {};   // the build index each pair was marked for (0 = never)
+  uint64_t carried_[2] = {0, 0};            // per trace stream: the build index its last kernel carries the free event of (0 = none)
   uint64_t alloc_build_ = 0;          // builds before this one wrote buffers that no longer exist
   uint64_t free_waited_ = 0;          // the build index of the free-event pair stream_l waited for last
   int cur_ = 0;                       // slot of the current lists
@@ -459,9 +493,11 @@ struct rt_tracer {
     if (b_dirty) {
       HIP_CHECK(hipEventRecord(join_event, stream_b));
       HIP_CHECK(hipStreamWaitEvent(stream, join_event, 0));
+      ++calls.records; ++calls.waits;
       b_dirty = false;
     }
     a_dirty = true;
+    lists.drop_carry();                                                // (whatever the caller enqueues may read the lists)
     return stream;
   }
   void fork_b() {                     // stream_b waits for the non-launch work enqueued on the primary stream
@@ -469,9 +505,12 @@ struct rt_tracer {
     if (!a_dirty) return;
     HIP_CHECK(hipEventRecord(fork_event, stream));
     HIP_CHECK(hipStreamWaitEvent(stream_b, fork_event, 0));
+    ++calls.records; ++calls.waits;
     a_dirty = false;
   }
   void mark_b_dirty() { std::lock_guard<std::recursive_mutex> lk(order_mu); b_dirty = true; }
+  rtr::EnqueueCalls calls;            // guarded by order_mu
+  rtk::KernelTable kernels;           // launch descriptors of this tracer's device
   rtr::DevArray<float4> d_render;
   rtr::DevArray<uint32_t> d_counts, d_image, d_rng;
   // Two words of the per-pixel state are the same for every pixel of the band, so the tracer keeps them and the launches
@@ -531,6 +570,7 @@ struct rt_tracer {
     if (owed_draws == 0u) return;
     const uint32_t* const table = settle_table(owed_draws);
     HIP_CHECK(rtk::launch_rng_settle(owe_p, owed_draws, table, main_stream()));
+    ++calls.launches;
     owed_draws = 0u; owing_launches = 0u; ++settles_enqueued;
   }
   void drop_debt() {                           // the states are created anew
@@ -844,19 +884,25 @@ struct rt_tracer {
     if (owes) { owed_draws += 3u * p.samples * (p.iters > 1u ? p.iters : 1u); ++owing_launches; }   // once per launch, not per half
     const bool settle_now = owes && owing_launches >= owe_period();       // the periodic settle, behind this launch's kernels
     const uint32_t* const settle_tab = settle_now ? settle_table(owed_draws) : nullptr;
+    ++calls.steps;
+    // The list ring's free events ride on this launch's trace kernels when those are the last kernels their streams get
+    // before the next build (TileListRing): the launch built its lists -- then the next launch that reads lists builds too,
+    // or passes lists.carry() itself and withdraws the event -- and no settle kernel follows.
+    const bool last_before_build = build_lists && !settle_now;
     if (r0 == 0u) {
       (void)main_stream();                                               // a launch on one stream orders behind both
       if (build_lists) build_tile_lists_ahead(p);
       lists.attach(p, row0, have_lists);
-      if (timed) HIP_CHECK(hipEventRecord(e.a, stream));
+      if (timed) { HIP_CHECK(hipEventRecord(e.a, stream)); ++calls.records; }
       if (have_lists) lists.wait(stream, 0);
       attach_macro_lists(p, path, 0, stream, (flags & rtk::TRACE_ZERO_ACC) != 0u);   // part of the launch: timed with it
-      HIP_CHECK(rtk::launch_trace(p, fma, filter, path, K, stream));
-      if (timed) HIP_CHECK(hipEventRecord(e.b, stream));
+      HIP_CHECK(rtk::launch_trace(p, fma, filter, path, K, stream, &kernels, lists.carry(0, last_before_build)));
+      ++calls.launches;
+      if (timed) { HIP_CHECK(hipEventRecord(e.b, stream)); ++calls.records; }
       if (owes) owe_p = p;
-      if (settle_now) { HIP_CHECK(rtk::launch_rng_settle(p, owed_draws, settle_tab, stream)); ++settles_enqueued; }
+      if (settle_now) { HIP_CHECK(rtk::launch_rng_settle(p, owed_draws, settle_tab, stream)); ++settles_enqueued; ++calls.launches; }
     } else {
-      fork_b();
+      if (a_dirty) fork_b();                                             // (order_mu is held: the steady state takes it once per launch)
       if (build_lists) build_tile_lists_ahead(p);
       // The two halves overlap best in ANTI-phase (one half's drain under the other's bulk); started together -- both
       // released by the same event, or from an idle device -- they can lock IN phase and stay there for a whole run
@@ -876,7 +922,7 @@ struct rt_tracer {
       rtk::TraceParams half[2] = {sub_band(p, 0u, r0), sub_band(p, r0, p.rows - r0)};
       if (interleave) { half[0] = p; half[1] = p; half[0].row_il = half[1].row_il = 1u; half[1].row_phase = 1u; }
       hipStream_t st[2] = {stream, stream_b};
-      if (timed) HIP_CHECK(hipEventRecord(e.a, stream));                 // the sampled duration is the upper half-frame kernel's
+      if (timed) { HIP_CHECK(hipEventRecord(e.a, stream)); ++calls.records; }   // the sampled duration is the upper half-frame kernel's
       for (int h = 0; h < 2; ++h) {
         lists.attach(half[h], row0, have_lists);
         if (have_lists) lists.wait(st[h], h);
@@ -884,19 +930,20 @@ struct rt_tracer {
           // half a kernel behind the upper half: by the clock when the tracer knows how long its half-frame kernels take
           // (0.45 of the last sampled one), else behind the upper half's end
           const uint32_t us = static_cast<uint32_t>(clock.last_half_ms() * 450.0f);
-          if (us >= 5u) HIP_CHECK(rtk::launch_delay(us, stream_b));
-          else HIP_CHECK(hipStreamWaitEvent(stream_b, stagger_event, 0));
+          if (us >= 5u) { HIP_CHECK(rtk::launch_delay(us, stream_b)); ++calls.launches; }
+          else { HIP_CHECK(hipStreamWaitEvent(stream_b, stagger_event, 0)); ++calls.waits; }
         }
         const rtk::TracePath half_path = trace_path(half[h]);
         attach_macro_lists(half[h], half_path, h, st[h], (flags & rtk::TRACE_ZERO_ACC) != 0u);
-        HIP_CHECK(rtk::launch_trace(half[h], fma, filter, half_path, K, st[h]));
-        if (h == 0 && stagger) HIP_CHECK(hipEventRecord(stagger_event, stream));
+        HIP_CHECK(rtk::launch_trace(half[h], fma, filter, half_path, K, st[h], &kernels, lists.carry(h, last_before_build)));
+        ++calls.launches;
+        if (h == 0 && stagger) { HIP_CHECK(hipEventRecord(stagger_event, stream)); ++calls.records; }
       }
-      if (timed) { HIP_CHECK(hipEventRecord(e.b, stream)); HIP_CHECK(hipEventRecord(e.c, stream_b)); }
+      if (timed) { HIP_CHECK(hipEventRecord(e.b, stream)); HIP_CHECK(hipEventRecord(e.c, stream_b)); calls.records += 2u; }
       if (owes) { owe_p = p; lists.attach(owe_p, row0, true); }          // (the band as one launch: settle() orders behind both streams)
       // each half's tiles on that half's own stream, with the geometry of its trace kernel: no join
-      if (settle_now) for (int h = 0; h < 2; ++h) { HIP_CHECK(rtk::launch_rng_settle(half[h], owed_draws, settle_tab, st[h])); ++settles_enqueued; }
-      mark_b_dirty();
+      if (settle_now) for (int h = 0; h < 2; ++h) { HIP_CHECK(rtk::launch_rng_settle(half[h], owed_draws, settle_tab, st[h])); ++settles_enqueued; ++calls.launches; }
+      b_dirty = true;
     }
     if (settle_now) { owed_draws = 0u; owing_launches = 0u; }
     uniform_lk.unlock();
@@ -1024,6 +1071,7 @@ struct rt_tracer {
         d_sure_table.ensure(p.n_tris);
       }
       HIP_CHECK(rtk::launch_sure_table(p.tri_color, p.n_tris, p.samples, d_sure_table.get(), st));
+      ++calls.launches;
       sure_table_samples = p.samples; sure_table_scene = scene_generation;
     }
     p.sure_table = d_sure_table.get();
@@ -1038,9 +1086,10 @@ struct rt_tracer {
     // (counted by every 32nd build only: the atomics and the publishing kernel cost 3.5 us per step when every build has
     //  them -- and nothing to decide when the mode is pinned)
     if (sr != 0u && d_half_cost.get() != nullptr && env.row_interleave < 0 && (m % 32u) == 0u) { q.half_cost = d_half_cost.get(); q.cost_split_brow = sr / 8u; }
-    HIP_CHECK(rtk::launch_tile_lists(q, fma, stream_l));
+    HIP_CHECK(rtk::launch_tile_lists(q, fma, stream_l, &kernels, lists.ready_event()));   // list_ready: the build kernel's stop event
+    ++calls.launches;
     lists.built();
-    if (q.half_cost != nullptr) HIP_CHECK(rtk::launch_publish_half_cost(d_half_cost.get(), h_half_cost.get(), stream_l));   // (behind list_ready: nobody waits for it)
+    if (q.half_cost != nullptr) { HIP_CHECK(rtk::launch_publish_half_cost(d_half_cost.get(), h_half_cost.get(), stream_l)); ++calls.launches; }   // (behind list_ready: nobody waits for it)
   }
 
   // One synchronous launch of `p` on the primary stream, its lists built in-stream into the current slot (the
@@ -1052,12 +1101,12 @@ struct rt_tracer {
     (void)prepare_tile_lists(p, path, true, have_lists);
     sync_list_stream();
     lists.attach(p, row0, have_lists);
-    if (have_lists) HIP_CHECK(rtk::launch_tile_lists(p, fma, main_stream()));
+    if (have_lists) HIP_CHECK(rtk::launch_tile_lists(p, fma, main_stream(), &kernels));
     attach_macro_lists(p, path, 0, main_stream());
     {
       std::lock_guard<std::recursive_mutex> lk(order_mu);
       take_uniform_state(p);
-      HIP_CHECK(rtk::launch_trace(p, fma, filter, path, pick_k(samples), main_stream()));
+      HIP_CHECK(rtk::launch_trace(p, fma, filter, path, pick_k(samples), main_stream(), &kernels));
     }
     HIP_CHECK(hipStreamSynchronize(main_stream()));
   }
