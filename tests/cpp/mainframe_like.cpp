@@ -1,6 +1,7 @@
 // Drives rt::RayTracer the way the reference's only caller does
 // (OpenGLView/MainFrame.cpp:45,108-126,219-256,293,311,438), headless.  Prints one line the
-// pytest side parses: update/finished counts, image size, an FNV-1a hash of the final image.
+// pytest side parses: update/finished counts, image size, an FNV-1a hash of the final image -- and a second
+// line with the same hash of every update image, in the order of the callbacks.
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -15,15 +16,19 @@ struct Frame {                       // stands in for MainFrame
   std::atomic<int> updates{0}, finished{0};
   std::size_t lastSize = 0;
   uint64_t hash = 0;
+  std::vector<uint64_t> updateHashes;            // written by the render thread, read after Wait()
   rt::RayTracer::uptr mRayTracer;
 
-  void TracerUpdateCallback(rt::ColorPtr deviceImageBuffer, const std::size_t size) {
-    (void)deviceImageBuffer; lastSize = size; ++updates;
-  }
-  void TracerFinishedCallback(rt::ColorPtr deviceImageBuffer, const std::size_t size) {
+  static uint64_t Fnv1a(rt::ColorPtr deviceImageBuffer, const std::size_t size) {
     uint64_t h = 1469598103934665603ull;
     for (std::size_t i = 0; i < size / sizeof(rt::Color); ++i) { h ^= deviceImageBuffer[i]; h *= 1099511628211ull; }
-    hash = h; lastSize = size; ++finished;
+    return h;
+  }
+  void TracerUpdateCallback(rt::ColorPtr deviceImageBuffer, const std::size_t size) {
+    updateHashes.push_back(Fnv1a(deviceImageBuffer, size)); lastSize = size; ++updates;
+  }
+  void TracerFinishedCallback(rt::ColorPtr deviceImageBuffer, const std::size_t size) {
+    hash = Fnv1a(deviceImageBuffer, size); lastSize = size; ++finished;
   }
 };
 
@@ -58,6 +63,9 @@ int main(int argc, char** argv) {
   f.mRayTracer->ReadSampleCounts(counts);
   std::printf("RESULT done=%d updates=%d finished=%d size=%zu hash=%llu count0=%u\n", done ? 1 : 0, f.updates.load(),
               f.finished.load(), f.lastSize, static_cast<unsigned long long>(f.hash), counts.empty() ? 0u : counts[0]);
+  std::printf("UPDATES");
+  for (const uint64_t h : f.updateHashes) std::printf(" %llu", static_cast<unsigned long long>(h));
+  std::printf("\n");
   f.mRayTracer->Resize(math::uvec2(16, 9));                  // MainFrame.cpp:293
   f.mRayTracer->Trace(2, 2, 0);
   f.mRayTracer->Stop();                                      // MainFrame.cpp:311

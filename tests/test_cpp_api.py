@@ -30,9 +30,10 @@ def test_cpp_api_compiles_and_fails_loudly_without_gpu(tmp_path):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("bands", [0, 8])
-def test_cpp_driver_matches_python_host_mirror(tmp_path, bands):
+def test_cpp_driver_matches_python_host_mirror(tmp_path, bands, orc):
     """bands = 8: the same caller through the device-list constructor (rt_tracer_create_multi): the frame in 8 row
-    bands, same callback cadence (ONE callback per update with the whole frame), same image."""
+    bands, same callback cadence (ONE callback per update with the whole frame), same image.  The nine update images
+    and the finished one are the oracle's at i = 10, 20, .. 90 and at the end (tests/progressive_cases.py), by their hashes."""
     import raytracertest_amd as R
     from raytracertest_amd import scenes
     exe = build_driver(tmp_path)
@@ -53,3 +54,21 @@ def test_cpp_driver_matches_python_host_mirror(tmp_path, bands):
         ref = ((ref ^ int(px)) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
     assert ref == h
     assert len(np.unique(g.Image())) > 4      # the rotated camera really sees the demo triangles
+    import progressive_cases as pc
+    exp = _expected_of_the_driver(orc)
+    u = re.search(r"^UPDATES((?: \d+)*)$", out.stdout, re.M)
+    assert u, out.stdout
+    assert [int(x) for x in u.group(1).split()] == [pc.fnv1a(img) for _, img in exp["updates"]]
+    assert [i for i, _ in exp["updates"]] == list(range(10, 100, 10))
+    assert h == pc.fnv1a(exp["final"]) and np.array_equal(g.Image(), exp["final"])
+
+
+_EXPECTED = []
+
+
+def _expected_of_the_driver(orc):
+    """the oracle's images of the driver's Trace(100, 1, 10), computed once for both parametrisations"""
+    import progressive_cases as pc
+    if not _EXPECTED:
+        _EXPECTED.append(pc.expected(orc, pc.CPP))
+    return _EXPECTED[0]
