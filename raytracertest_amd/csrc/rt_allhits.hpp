@@ -1,8 +1,7 @@
 // rt_allhits.hpp -- the all-hits query (rt_tracer_intersect_all*): the first max_hits hits of ray i within its own
-// closed t interval, in ascending (t, prim) order.  Included by rt_kernels.hip only, behind rt_occluded.hpp.  As there, nothing
-// is shared with the other query kernels beyond the renderer's device functions (hit_triangle_exact, hit_sphere, Math<FMA>):
-// the triangle stages and the box test are stated here a third time, because the existing query kernels keep their schedule
-// only while their text is theirs alone (rt_bvh.hpp, rt_occluded.hpp).
+// closed t interval, in ascending (t, prim) order.  Included by rt_kernels.hip only, behind rt_occluded.hpp.  The triangle stages
+// are stated here a third time, because the scan kernels keep their schedule only while their text is theirs alone (rt_bvh.hpp,
+// rt_occluded.hpp).
 //
 // A "hit" is rt_occluded.hpp's: the reference's HitTriangle returning true (Kernels.cuh:29-65) with the t of :63, a sphere with
 // the one t of hit_sphere; tmin <= t && t <= tmax in plain fp32 (a NaN t or bound, or tmin > tmax: no hit).  Order: ascending
@@ -22,13 +21,12 @@
 // -- at one ray per lane and without the early exits: nothing is ever finished.  Padding lanes and rays whose interval is empty
 // (a NaN bound, tmin > tmax) stay out of the ballots.
 //
-// allhits_bvh_kernel (RT_QUERY_BVH): occluded_bvh_kernel's walk -- one wave per block, lane = ray -- with query_bvh_kernel's
-// stack of 8-byte {-enter, reference} entries in LDS at entry * 64 + lane.  Same pad, same operations, same NaN rule in the box
-// test; a child is skipped when  exit < enter,  exit < tmin,  enter > tmax  or, once the list is full,  enter > t_last  (strictly:
-// a tie is visited, a lower prim may be waiting in it).  The nearest child (smallest enter) is entered first; a popped entry is
-// dropped when its enter has fallen strictly behind t_last meanwhile.  The always-tested list and the spheres are tested
-// unconditionally.  A ray with a non-finite component or a zero direction, or a child with a NaN in its box arithmetic, takes no
-// pruning decision.
+// allhits_bvh_kernel (RT_QUERY_BVH): one wave per block, lane = ray, the walk of rt_bvh_walk.hpp with 8-byte stack entries
+// {-enter, reference}.  A child is skipped when  exit < enter,  exit < tmin,  enter > tmax  or, once the list is full,
+// enter > t_last  (strictly: a tie is visited, a lower prim may be waiting in it).  The nearest child (smallest enter) is
+// entered first; a popped entry is dropped when its enter has fallen strictly behind t_last meanwhile.  The always-tested list
+// and the spheres are tested unconditionally.  A ray with a non-finite component or a zero direction, or a child with a NaN in
+// its box arithmetic, takes no pruning decision (occluded_prune).
 #pragma once
 #include "rt_occluded.hpp"
 
@@ -182,11 +180,11 @@ __global__ __launch_bounds__(256, 4) void allhits_kernel(const TraceParams p, ui
 template <bool FMA, int CAP>
 __device__ __forceinline__ void allhits_test_record(const float4* __restrict__ rec, V3 o, V3 d, float tmin, float tmax,
                                                     float (&lt)[CAP], int (&lp)[CAP]) {
-  const float4 A0 = rec[0], A1 = rec[1], B = rec[2];
+  const BvhRecord r = bvh_record(rec);
   float t = 0.0f, u = 0.0f, v = 0.0f;
   int stage;
-  if (!hit_triangle_exact<FMA>(o, d, {A1.z, A1.w, B.x}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, RT_EPS, t, u, v, stage)) return;
-  if (tmin <= t && t <= tmax) allhits_insert<CAP>(lt, lp, t, __float_as_int(B.y));
+  if (!hit_triangle_exact<FMA>(o, d, r.v0, r.e1, r.e2, RT_EPS, t, u, v, stage)) return;
+  if (tmin <= t && t <= tmax) allhits_insert<CAP>(lt, lp, t, r.idx);
 }
 
 template <bool FMA, int CAP>
@@ -205,67 +203,19 @@ __global__ __launch_bounds__(64) void allhits_bvh_kernel(const TraceParams p, co
   int lp[CAP];
   allhits_init<CAP>(lt, lp, max_hits);
 
-  uint2* const stack = reinterpret_cast<uint2*>(s_mem) + lane;     // entry e at stack[e * 64]
   const float inf = __builtin_inff();
-  const bool finite = fabsf(o.x) < inf && fabsf(o.y) < inf && fabsf(o.z) < inf && fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf;
-  const bool prunes = finite && !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f);
-  const V3 inv = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-  const float omax = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
-  uint32_t sp = 0u;
-  uint32_t cur = (b.n_nodes != 0u && active) ? 0u : kBvhEmpty;
-  bool overflow = false;
-  for (;;) {
-    if (cur == kBvhEmpty) {
-      if (sp == 0u) break;
-      --sp;
-      const uint2 e = stack[sp * 64u];
-      // -enter fell strictly behind -t_last meanwhile (an empty last slot has t = +inf: nothing is below -inf)
-      if (__uint_as_float(e.x) < -lt[CAP - 1]) continue;
-      cur = e.y;
-    }
-    if ((cur & kBvhLeaf) != 0u) {
-      const uint32_t first = cur & 0x0FFFFFFFu, count = ((cur >> 28) & 3u) + 1u;
-      for (uint32_t j = 0; j < count; ++j) allhits_test_record<FMA, CAP>(b.records + 3u * (first + j), o, d, tmin, tmax, lt, lp);
-      cur = kBvhEmpty;
-      continue;
-    }
-    const float4* const nd = b.nodes + 8u * static_cast<size_t>(cur);
-    const float4 lox = nd[0], loy = nd[1], loz = nd[2], hix = nd[3], hiy = nd[4], hiz = nd[5], refs = nd[6], cm = nd[7];
-    const float L[3][4] = {{lox.x, lox.y, lox.z, lox.w}, {loy.x, loy.y, loy.z, loy.w}, {loz.x, loz.y, loz.z, loz.w}};
-    const float Hh[3][4] = {{hix.x, hix.y, hix.z, hix.w}, {hiy.x, hiy.y, hiy.z, hiy.w}, {hiz.x, hiz.y, hiz.z, hiz.w}};
-    const float cmax[4] = {cm.x, cm.y, cm.z, cm.w};
-    uint32_t ref[4] = {__float_as_uint(refs.x), __float_as_uint(refs.y), __float_as_uint(refs.z), __float_as_uint(refs.w)};
-    float good[4];
-    const float t_last = lt[CAP - 1];                              // +inf while the list is not full: enter > +inf never holds
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float pad = b.rho * (omax + cmax[c]);
-      const float t1x = ((L[0][c] - pad) - o.x) * inv.x, t2x = ((Hh[0][c] + pad) - o.x) * inv.x;
-      const float t1y = ((L[1][c] - pad) - o.y) * inv.y, t2y = ((Hh[1][c] + pad) - o.y) * inv.y;
-      const float t1z = ((L[2][c] - pad) - o.z) * inv.z, t2z = ((Hh[2][c] + pad) - o.z) * inv.z;
-      const bool nan = __builtin_isunordered(t1x, t2x) || __builtin_isunordered(t1y, t2y) || __builtin_isunordered(t1z, t2z);
-      const float enter = fmaxf(fmaxf(fminf(t1x, t2x), fminf(t1y, t2y)), fminf(t1z, t2z));
-      const float exit = fminf(fminf(fmaxf(t1x, t2x), fmaxf(t1y, t2y)), fmaxf(t1z, t2z));
-      const bool skip = (exit < enter) || (exit < tmin) || (enter > tmax) || (enter > t_last);
-      const bool decided = prunes && !nan;
-      float g = decided ? fmaxf(-enter, -FLT_MAX) : inf;           // nearest first; an undecided child is never dropped
-      if (ref[c] == kBvhEmpty || (decided && skip)) { ref[c] = kBvhEmpty; g = -inf; }
-      good[c] = g;
-    }
-    // nearest first (a 5-exchange network); an empty reference carries -inf, a visited one at least -FLT_MAX
-#define RT_ALL_CSWAP(i, j)                                                                            \
-    if (good[i] < good[j]) { const float tg = good[i]; good[i] = good[j]; good[j] = tg;               \
-                             const uint32_t tr = ref[i]; ref[i] = ref[j]; ref[j] = tr; }
-    RT_ALL_CSWAP(0, 1) RT_ALL_CSWAP(2, 3) RT_ALL_CSWAP(0, 2) RT_ALL_CSWAP(1, 3) RT_ALL_CSWAP(1, 2)
-#undef RT_ALL_CSWAP
-    cur = ref[0];
-    auto push = [&](float g, uint32_t r) {
-      if (r == kBvhEmpty) return;
-      if (sp < b.stack_cap) { stack[sp * 64u] = make_uint2(__float_as_uint(g), r); ++sp; }
-      else overflow = true;                                        // (cannot happen: the capacity is 3 x the tree's depth)
-    };
-    push(good[3], ref[3]); push(good[2], ref[2]); push(good[1], ref[1]);   // the nearer of them on top
-  }
+  const OccludedPrune q = occluded_prune(o, d);
+  auto child = [&](const BvhNode& nd, int c) {
+    float enter, exit;
+    const bool nan = bvh_slab(nd, c, b.rho * (q.omax + nd.cmax[c]), o, q.inv, enter, exit);
+    // (t_last is +inf while the list is not full: enter > +inf never holds)
+    const bool skip = (exit < enter) || (exit < tmin) || (enter > tmax) || (enter > lt[CAP - 1]);
+    return !(q.prunes && !nan) ? inf : skip ? -inf : fmaxf(-enter, -FLT_MAX);   // nearest first
+  };
+  auto leaf = [&](const float4* rec) { allhits_test_record<FMA, CAP>(rec, o, d, tmin, tmax, lt, lp); return false; };
+  // -enter fell strictly behind -t_last meanwhile (an empty last slot has t = +inf: nothing is below -inf)
+  auto stale = [&](float key) { return key < -lt[CAP - 1]; };
+  const bool overflow = bvh_walk<64u, true>(b, s_mem, lane, active, child, leaf, stale);
   if (overflow) {                                                  // an entry was not kept: every leaf record, from an empty list
     allhits_init<CAP>(lt, lp, max_hits);
     for (uint32_t j = 0; j < b.n_leaf_records; ++j) allhits_test_record<FMA, CAP>(b.records + 3u * j, o, d, tmin, tmax, lt, lp);
@@ -280,10 +230,6 @@ __global__ __launch_bounds__(64) void allhits_bvh_kernel(const TraceParams p, co
 
 uint32_t allhits_lds_bytes(uint32_t n_tris) {
   return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
-}
-
-uint32_t allhits_bvh_lds_bytes(uint32_t stack_cap) {
-  return stack_cap * 64u * 8u;
 }
 
 hipError_t launch_allhits(const TraceParams& p, bool fma, uint32_t n, const float* segs, uint32_t max_hits, float4* hits,
@@ -303,8 +249,8 @@ hipError_t launch_allhits_bvh(const TraceParams& p, const BvhParams& b, bool fma
                               float4* hits, uint32_t* counts, hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (max_hits == 0u || max_hits > kAllHitsMax || segs == nullptr || hits == nullptr || counts == nullptr) return hipErrorInvalidValue;
-  const uint32_t lds = allhits_bvh_lds_bytes(b.stack_cap);
-  if (lds > 65536u) return hipErrorInvalidValue;                   // (3 x kBvhMaxDepth entries are 24 KiB)
+  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, true);
+  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
   const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
   const float4* const s4 = reinterpret_cast<const float4*>(segs);
   auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), lds, st, p, b, n, s4, max_hits, hits, counts); };

@@ -24,13 +24,14 @@
 // keeps the largest t, ties to the LOWEST upload index (nearest: the smallest t > 0, ties to the lowest index) -- the scan's
 // first-scanned-wins rule in a form that does not depend on the order of the visits.  The always-tested list (triangles with
 // a non-finite record) follows under the same rule.
+//
+// query_bvh_kernel keeps the walk in its own text -- the loop, the node unpack and the ordering network are A SECOND COPY of
+// rt_bvh_walk.hpp's bvh_walk, its box test of bvh_slab: change them together.  On the shared function this kernel measured slower than its
+// parent by more than the parent's own run-to-run spread, in every shape of the function that was tried.
 #pragma once
-#include "rt_query.hpp"
+#include "rt_bvh_walk.hpp"
 
 namespace rtk {
-
-constexpr uint32_t kBvhEmpty = 0xFFFFFFFFu;
-constexpr uint32_t kBvhLeaf = 0x80000000u;
 
 // One ray's result from its best triangle (dist, win; win < 0: none): the spheres, scanned after the triangles by the trace
 // kernel's rule (rt_trace.hpp), and the winner's u, v recomputed from its record (Kernels.cuh:50,57).
@@ -171,16 +172,12 @@ __global__ __launch_bounds__(64) void query_bvh_kernel(const TraceParams p, cons
   }
 }
 
-uint32_t query_bvh_lds_bytes(uint32_t stack_cap) {
-  return stack_cap * 64u * 8u;
-}
-
 hipError_t launch_query_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* rays, const uint32_t* pixels,
                             float* rays_out, float4* hits, hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (hits == nullptr || (rays == nullptr && pixels == nullptr)) return hipErrorInvalidValue;
-  const uint32_t lds = query_bvh_lds_bytes(b.stack_cap);
-  if (lds > 65536u) return hipErrorInvalidValue;                   // (3 x kBvhMaxDepth entries are 24 KiB)
+  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, true);
+  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
   const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
   if (fma) hipLaunchKernelGGL(query_bvh_kernel<true>, grid, dim3(64), lds, st, p, b, n, rays, pixels, rays_out, hits);
   else hipLaunchKernelGGL(query_bvh_kernel<false>, grid, dim3(64), lds, st, p, b, n, rays, pixels, rays_out, hits);

@@ -22,6 +22,10 @@
 // when lb > best STRICTLY (a tie may hide a lower index); the nearest child is entered first, the others wait on the stack and
 // are dropped at the pop when their lb has fallen strictly behind best.  best starts at d2max.  A point with a non-finite
 // coordinate, or a child whose lb is a NaN, takes no pruning decision.  The always-tested list and the spheres follow.
+//
+// closest_bvh_kernel keeps the walk in its own text -- the loop, the node unpack and the ordering network are A SECOND COPY of
+// rt_bvh_walk.hpp's bvh_walk: change them together.  On the shared function this kernel measured slower than its
+// parent by more than the parent's own run-to-run spread, in every shape of the function that was tried.
 #pragma once
 #include "rt_allhits.hpp"
 
@@ -227,10 +231,6 @@ uint32_t closest_lds_bytes(uint32_t n_tris) {
   return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
 }
 
-uint32_t closest_bvh_lds_bytes(uint32_t stack_cap) {
-  return stack_cap * 64u * 8u;
-}
-
 hipError_t launch_closest(const TraceParams& p, uint32_t n, const float* pts, float4* hits, hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (pts == nullptr || hits == nullptr) return hipErrorInvalidValue;
@@ -243,8 +243,8 @@ hipError_t launch_closest_bvh(const TraceParams& p, const BvhParams& b, float rh
                               hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (pts == nullptr || hits == nullptr) return hipErrorInvalidValue;
-  const uint32_t lds = closest_bvh_lds_bytes(b.stack_cap);
-  if (lds > 65536u) return hipErrorInvalidValue;                   // (3 x kBvhMaxDepth entries are 24 KiB)
+  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, true);
+  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
   const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
   hipLaunchKernelGGL(closest_bvh_kernel, grid, dim3(64), lds, st, p, b, rho_c, n, reinterpret_cast<const float4*>(pts), hits);
   return hipGetLastError();

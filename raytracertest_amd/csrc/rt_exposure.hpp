@@ -17,10 +17,9 @@
 // in ascending chunks of kQueryChunk records, a finished wave skips a chunk's loop but still stages, the block leaves through
 // __syncthreads_or.  No thread returns before the last barrier.
 //
-// exposure_bvh_kernel (RT_QUERY_BVH): every lane runs occluded_bvh_kernel's any-hit walk on its own ray -- the same box test,
-// pad, NaN rule and strict interval pruning, spheres and the always-tested list first, the overflow fallback -- with the
-// lane's stack in LDS at entry * 256 + tid.  The walk is stated a second time (as occluded_test_triangle restates
-// test_triangle): occluded_bvh_kernel keeps its code only while its text is its own.  A SECOND COPY: change both together.
+// exposure_bvh_kernel (RT_QUERY_BVH): every lane runs occluded_bvh_kernel's any-hit walk on its own ray -- occluded_child's
+// pruning, spheres and the always-tested list first, the overflow fallback -- with the lane's stack in LDS at entry * 256 + tid.
+// No lane returns before the ballot of exposure_store.
 #pragma once
 #include "rt_occluded.hpp"
 
@@ -134,64 +133,10 @@ __global__ __launch_bounds__(256) void exposure_bvh_kernel(const TraceParams p, 
   for (uint32_t j = 0; j < b.n_always && !done; ++j)
     done = occluded_test_record<FMA>(b.records + 3u * (b.n_leaf_records + j), o, d, tmin, tmax);
 
-  uint32_t* const stack = reinterpret_cast<uint32_t*>(s_mem) + threadIdx.x;   // entry e at stack[e * 256]
-  const float inf = __builtin_inff();
-  const bool finite = fabsf(o.x) < inf && fabsf(o.y) < inf && fabsf(o.z) < inf && fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf;
-  const bool prunes = finite && !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f);
-  const V3 inv = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-  const float omax = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
-  uint32_t sp = 0u;
-  uint32_t cur = (b.n_nodes != 0u && !done) ? 0u : kBvhEmpty;
-  bool overflow = false;
-  while (!done) {
-    if (cur == kBvhEmpty) {
-      if (sp == 0u) break;
-      --sp;
-      cur = stack[sp * 256u];
-    }
-    if ((cur & kBvhLeaf) != 0u) {
-      const uint32_t first = cur & 0x0FFFFFFFu, count = ((cur >> 28) & 3u) + 1u;
-      for (uint32_t j = 0; j < count && !done; ++j) done = occluded_test_record<FMA>(b.records + 3u * (first + j), o, d, tmin, tmax);
-      cur = kBvhEmpty;
-      continue;
-    }
-    const float4* const nd = b.nodes + 8u * static_cast<size_t>(cur);
-    const float4 lox = nd[0], loy = nd[1], loz = nd[2], hix = nd[3], hiy = nd[4], hiz = nd[5], refs = nd[6], cm = nd[7];
-    const float L[3][4] = {{lox.x, lox.y, lox.z, lox.w}, {loy.x, loy.y, loy.z, loy.w}, {loz.x, loz.y, loz.z, loz.w}};
-    const float Hh[3][4] = {{hix.x, hix.y, hix.z, hix.w}, {hiy.x, hiy.y, hiy.z, hiy.w}, {hiz.x, hiz.y, hiz.z, hiz.w}};
-    const float cmax[4] = {cm.x, cm.y, cm.z, cm.w};
-    uint32_t ref[4] = {__float_as_uint(refs.x), __float_as_uint(refs.y), __float_as_uint(refs.z), __float_as_uint(refs.w)};
-    float good[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float pad = b.rho * (omax + cmax[c]);
-      const float t1x = ((L[0][c] - pad) - o.x) * inv.x, t2x = ((Hh[0][c] + pad) - o.x) * inv.x;
-      const float t1y = ((L[1][c] - pad) - o.y) * inv.y, t2y = ((Hh[1][c] + pad) - o.y) * inv.y;
-      const float t1z = ((L[2][c] - pad) - o.z) * inv.z, t2z = ((Hh[2][c] + pad) - o.z) * inv.z;
-      const bool nan = __builtin_isunordered(t1x, t2x) || __builtin_isunordered(t1y, t2y) || __builtin_isunordered(t1z, t2z);
-      const float enter = fmaxf(fmaxf(fminf(t1x, t2x), fminf(t1y, t2y)), fminf(t1z, t2z));
-      const float exit = fminf(fminf(fmaxf(t1x, t2x), fmaxf(t1y, t2y)), fmaxf(t1z, t2z));
-      const bool skip = (exit < enter) || (exit < tmin) || (enter > tmax);
-      const bool decided = prunes && !nan;
-      // the overlap of the child's span with the interval (inf - inf: a NaN, which fmaxf drops)
-      float g = decided ? fmaxf(fminf(exit, tmax) - fmaxf(enter, tmin), -FLT_MAX) : inf;
-      if (ref[c] == kBvhEmpty || (decided && skip)) { ref[c] = kBvhEmpty; g = -inf; }
-      good[c] = g;
-    }
-    // largest overlap first (a 5-exchange network); an empty reference carries -inf, a visited one at least -FLT_MAX
-#define RT_EXP_CSWAP(i, j)                                                                            \
-    if (good[i] < good[j]) { const float tg = good[i]; good[i] = good[j]; good[j] = tg;               \
-                             const uint32_t tr = ref[i]; ref[i] = ref[j]; ref[j] = tr; }
-    RT_EXP_CSWAP(0, 1) RT_EXP_CSWAP(2, 3) RT_EXP_CSWAP(0, 2) RT_EXP_CSWAP(1, 3) RT_EXP_CSWAP(1, 2)
-#undef RT_EXP_CSWAP
-    cur = ref[0];
-    auto push = [&](uint32_t e) {
-      if (e == kBvhEmpty) return;
-      if (sp < b.stack_cap) { stack[sp * 256u] = e; ++sp; }
-      else overflow = true;                                        // (cannot happen: the capacity is 3 x the tree's depth)
-    };
-    push(ref[3]); push(ref[2]); push(ref[1]);                      // the better of them on top
-  }
+  const OccludedPrune q = occluded_prune(o, d);
+  const bool overflow = bvh_walk<256u, false>(
+      b, s_mem, threadIdx.x, !done, [&](const BvhNode& nd, int c) { return occluded_child(nd, c, b.rho, q, o, tmin, tmax); },
+      [&](const float4* rec) { return done = occluded_test_record<FMA>(rec, o, d, tmin, tmax); }, [](float) { return false; });
   if (overflow && !done) {                                         // an entry was not kept: every leaf record
     for (uint32_t j = 0; j < b.n_leaf_records && !done; ++j) done = occluded_test_record<FMA>(b.records + 3u * j, o, d, tmin, tmax);
   }
@@ -227,10 +172,6 @@ uint32_t exposure_lds_bytes(uint32_t n_tris) {
   return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
 }
 
-uint32_t exposure_bvh_lds_bytes(uint32_t stack_cap) {
-  return stack_cap * 256u * 4u;
-}
-
 // the launch functions' own guard (the entry points have checked the same rules with an error text: rt_query_api.hpp)
 static bool exposure_launch_ok(const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags, const void* out) {
   return points != nullptr && dirs != nullptr && out != nullptr && n_dirs != 0u && n_dirs <= kExposureMaxDirs && (flags & ~kExposureWorld) == 0u;
@@ -255,8 +196,8 @@ hipError_t launch_exposure_bvh(const TraceParams& p, const BvhParams& b, bool fm
                                uint32_t n_dirs, uint32_t flags, uint64_t* masks, hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (!exposure_launch_ok(points, dirs, n_dirs, flags, masks)) return hipErrorInvalidValue;
-  const uint32_t lds = exposure_bvh_lds_bytes(b.stack_cap);
-  if (lds > 65536u) return hipErrorInvalidValue;                   // (3 x kBvhMaxDepth entries are 48 KiB)
+  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 256u, false);
+  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
   const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 3u) / 4u));
   const float4* const p4 = reinterpret_cast<const float4*>(points);
   const float4* const d4 = reinterpret_cast<const float4*>(dirs);

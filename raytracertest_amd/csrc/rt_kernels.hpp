@@ -162,7 +162,8 @@ struct BvhParams {
   uint32_t stack_cap;       // entries per lane
   float rho;                // RT_BVH_RHO x the tracer's slack
 };
-uint32_t query_bvh_lds_bytes(uint32_t stack_cap);
+// the dynamic LDS of the walks' stacks (rt_bvh_walk.hpp): stride lanes per block, 8-byte keyed or 4-byte entries
+uint32_t bvh_stack_lds_bytes(uint32_t stack_cap, uint32_t stride, bool keyed);
 hipError_t launch_query_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* rays, const uint32_t* pixels,
                             float* rays_out, float4* hits, hipStream_t st);
 
@@ -171,7 +172,6 @@ hipError_t launch_query_bvh(const TraceParams& p, const BvhParams& b, bool fma, 
 // hit rule plays no part.  The scan with K in {1, 2, 4} rays per lane, or the any-hit walk of the tree, one ray per lane.
 uint32_t occluded_lds_bytes(uint32_t n_tris);
 hipError_t launch_occluded(const TraceParams& p, bool fma, int K, uint32_t n, const float* segs, uint8_t* occluded, hipStream_t st);
-uint32_t occluded_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_occluded_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint8_t* occluded,
                                hipStream_t st);
 
@@ -183,7 +183,6 @@ hipError_t launch_occluded_bvh(const TraceParams& p, const BvhParams& b, bool fm
 uint32_t exposure_lds_bytes(uint32_t n_tris);
 hipError_t launch_exposure(const TraceParams& p, bool fma, uint32_t n, const float* points, const float* dirs, uint32_t n_dirs,
                            uint32_t flags, uint64_t* masks, hipStream_t st);
-uint32_t exposure_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_exposure_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* points, const float* dirs,
                                uint32_t n_dirs, uint32_t flags, uint64_t* masks, hipStream_t st);
 hipError_t launch_exposure_rays(uint32_t n, const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags, float* segs,
@@ -196,7 +195,6 @@ void exposure_rays_host(size_t n, const float* points, const float* dirs, uint32
 uint32_t allhits_lds_bytes(uint32_t n_tris);
 hipError_t launch_allhits(const TraceParams& p, bool fma, uint32_t n, const float* segs, uint32_t max_hits, float4* hits,
                           uint32_t* counts, hipStream_t st);
-uint32_t allhits_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_allhits_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint32_t max_hits,
                               float4* hits, uint32_t* counts, hipStream_t st);
 
@@ -206,7 +204,6 @@ hipError_t launch_allhits_bvh(const TraceParams& p, const BvhParams& b, bool fma
 #define RT_CLOSEST_RHO 3.814697265625e-06f      // 2^-18: DESIGN.md 4.3f derives it
 uint32_t closest_lds_bytes(uint32_t n_tris);
 hipError_t launch_closest(const TraceParams& p, uint32_t n, const float* pts, float4* hits, hipStream_t st);
-uint32_t closest_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_closest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, float4* hits,
                               hipStream_t st);
 
@@ -216,7 +213,6 @@ hipError_t launch_closest_bvh(const TraceParams& p, const BvhParams& b, float rh
 uint32_t nearest_lds_bytes(uint32_t n_tris);
 hipError_t launch_nearest(const TraceParams& p, uint32_t n, const float* pts, const float4* after, uint32_t max_hits, float4* hits,
                           uint32_t* counts, hipStream_t st);
-uint32_t nearest_bvh_lds_bytes(uint32_t stack_cap);
 hipError_t launch_nearest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, const float4* after,
                               uint32_t max_hits, float4* hits, uint32_t* counts, hipStream_t st);
 

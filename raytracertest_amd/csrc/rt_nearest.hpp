@@ -20,6 +20,10 @@
 // lb > bound STRICTLY (a tie may hide a lower index that displaces the last slot); a popped entry is dropped when its lb has
 // fallen strictly behind bound.  The invariant: every record inside a skipped child computes t >= lb > bound, so it is either
 // not accepted (t > d2max) or sorts behind a full list's last entry, and the list only ever tightens.
+//
+// nearest_bvh_kernel keeps the walk in its own text -- the loop, the node unpack and the ordering network are A SECOND COPY of
+// rt_bvh_walk.hpp's bvh_walk: change them together.  On the shared function this kernel measured slower than its
+// parent by more than the parent's own run-to-run spread, in every shape of the function that was tried.
 #pragma once
 #include "rt_closest.hpp"
 
@@ -234,10 +238,6 @@ uint32_t nearest_lds_bytes(uint32_t n_tris) {
   return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
 }
 
-uint32_t nearest_bvh_lds_bytes(uint32_t stack_cap) {
-  return stack_cap * 64u * 8u;
-}
-
 hipError_t launch_nearest(const TraceParams& p, uint32_t n, const float* pts, const float4* after, uint32_t max_hits, float4* hits,
                           uint32_t* counts, hipStream_t st) {
   if (n == 0u) return hipSuccess;
@@ -254,8 +254,8 @@ hipError_t launch_nearest_bvh(const TraceParams& p, const BvhParams& b, float rh
                               uint32_t max_hits, float4* hits, uint32_t* counts, hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (max_hits == 0u || max_hits > kAllHitsMax || pts == nullptr || hits == nullptr || counts == nullptr) return hipErrorInvalidValue;
-  const uint32_t lds = nearest_bvh_lds_bytes(b.stack_cap);
-  if (lds > 65536u) return hipErrorInvalidValue;                   // (3 x kBvhMaxDepth entries are 24 KiB)
+  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, true);
+  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
   const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
   const float4* const p4 = reinterpret_cast<const float4*>(pts);
   auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), lds, st, p, b, rho_c, n, p4, after, max_hits, hits, counts); };

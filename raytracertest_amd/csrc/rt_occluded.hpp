@@ -1,8 +1,7 @@
 // rt_occluded.hpp -- the visibility query (rt_tracer_occluded*): is ray i blocked by ANY primitive of the
-// scene with tmin <= t <= tmax?  Included by rt_kernels.hip only, behind rt_bvh.hpp.  Nothing of rt_query.hpp or rt_bvh.hpp is
-// shared beyond the renderer's device functions (hit_triangle_exact, hit_sphere, Math<FMA>): the triangle stages and the box
-// test are stated here again, because query_kernel and query_bvh_kernel keep their schedule only while their text is theirs
-// alone (rt_bvh.hpp).
+// scene with tmin <= t <= tmax?  Included by rt_kernels.hip only, behind rt_bvh.hpp.  The triangle stages are stated here
+// again (occluded_test_triangle beside rt_trace.hpp's test_triangle), because query_kernel keeps its schedule only while its
+// text is its own (rt_bvh.hpp).
 //
 // A "hit" is the reference's HitTriangle returning true (Kernels.cuh:29-65) and its t is the value of :63, a sphere's the one t
 // of hit_sphere; the interval is closed and compared in plain fp32 (a NaN t or bound, or tmin > tmax, never occludes).  The
@@ -15,12 +14,12 @@
 // uniform, never under divergent control flow).  Rays are two 16-byte loads each, the answers one byte per ray (a wave's 64
 // lanes store 64 consecutive bytes).  Padding lanes (ray index >= n) start finished.
 //
-// occluded_bvh_kernel (RT_QUERY_BVH): query_bvh_kernel's walk -- one wave per block, lane = ray, the lane's stack in LDS at
-// entry * 64 + lane -- as an any-hit traversal.  The box test is that kernel's (same pad, same operations, same NaN rule); a
+// occluded_bvh_kernel (RT_QUERY_BVH): one wave per block, lane = ray, the walk of rt_bvh_walk.hpp as an any-hit traversal.  A
 // child is skipped when  exit < enter,  exit < tmin  or  enter > tmax  (strictly: a tie is visited).  There is no best t, so a
 // stack entry is the child's reference alone and no popped entry is judged again.  The child whose span overlaps [tmin, tmax]
 // most is entered first.  The always-tested list comes before the tree (it may end the walk before it starts); a ray with a
 // non-finite component or a zero direction, or a child with a NaN in its box arithmetic, takes no pruning decision.
+// occluded_prune and occluded_child are the ray's side of that rule; exposure_bvh_kernel (rt_exposure.hpp) walks with them too.
 #pragma once
 #include "rt_bvh.hpp"
 
@@ -151,11 +150,35 @@ __global__ __launch_bounds__(256, 4) void occluded_kernel(const TraceParams p, u
 // one record against one ray: the exact test, then the closed interval
 template <bool FMA>
 __device__ __forceinline__ bool occluded_test_record(const float4* __restrict__ rec, V3 o, V3 d, float tmin, float tmax) {
-  const float4 A0 = rec[0], A1 = rec[1], B = rec[2];
+  const BvhRecord r = bvh_record(rec);
   float t = 0.0f, u = 0.0f, v = 0.0f;
   int stage;
-  if (!hit_triangle_exact<FMA>(o, d, {A1.z, A1.w, B.x}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, RT_EPS, t, u, v, stage)) return false;
+  if (!hit_triangle_exact<FMA>(o, d, r.v0, r.e1, r.e2, RT_EPS, t, u, v, stage)) return false;
   return tmin <= t && t <= tmax;
+}
+
+// what the any-hit walk keeps of a ray besides the segment: whether it prunes at all, 1 / d, max|o|
+struct OccludedPrune {
+  bool prunes;
+  V3 inv;
+  float omax;
+};
+
+__device__ __forceinline__ OccludedPrune occluded_prune(V3 o, V3 d) {
+  const float inf = __builtin_inff();
+  const bool finite = fabsf(o.x) < inf && fabsf(o.y) < inf && fabsf(o.z) < inf && fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf;
+  return {finite && !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f), {1.0f / d.x, 1.0f / d.y, 1.0f / d.z},
+          fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z))};
+}
+
+// the goodness of child c (bvh_walk's convention): the overlap of the child's span with the interval
+__device__ __forceinline__ float occluded_child(const BvhNode& nd, int c, float rho, const OccludedPrune& q, V3 o, float tmin, float tmax) {
+  const float inf = __builtin_inff();
+  float enter, exit;
+  const bool nan = bvh_slab(nd, c, rho * (q.omax + nd.cmax[c]), o, q.inv, enter, exit);
+  const bool skip = (exit < enter) || (exit < tmin) || (enter > tmax);
+  // (inf - inf: a NaN, which fmaxf drops)
+  return !(q.prunes && !nan) ? inf : skip ? -inf : fmaxf(fminf(exit, tmax) - fmaxf(enter, tmin), -FLT_MAX);
 }
 
 template <bool FMA>
@@ -177,64 +200,10 @@ __global__ __launch_bounds__(64) void occluded_bvh_kernel(const TraceParams p, c
   for (uint32_t j = 0; j < b.n_always && !done; ++j)
     done = occluded_test_record<FMA>(b.records + 3u * (b.n_leaf_records + j), o, d, tmin, tmax);
 
-  uint32_t* const stack = reinterpret_cast<uint32_t*>(s_mem) + lane;   // entry e at stack[e * 64]
-  const float inf = __builtin_inff();
-  const bool finite = fabsf(o.x) < inf && fabsf(o.y) < inf && fabsf(o.z) < inf && fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf;
-  const bool prunes = finite && !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f);
-  const V3 inv = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-  const float omax = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
-  uint32_t sp = 0u;
-  uint32_t cur = (b.n_nodes != 0u && !done) ? 0u : kBvhEmpty;
-  bool overflow = false;
-  while (!done) {
-    if (cur == kBvhEmpty) {
-      if (sp == 0u) break;
-      --sp;
-      cur = stack[sp * 64u];
-    }
-    if ((cur & kBvhLeaf) != 0u) {
-      const uint32_t first = cur & 0x0FFFFFFFu, count = ((cur >> 28) & 3u) + 1u;
-      for (uint32_t j = 0; j < count && !done; ++j) done = occluded_test_record<FMA>(b.records + 3u * (first + j), o, d, tmin, tmax);
-      cur = kBvhEmpty;
-      continue;
-    }
-    const float4* const nd = b.nodes + 8u * static_cast<size_t>(cur);
-    const float4 lox = nd[0], loy = nd[1], loz = nd[2], hix = nd[3], hiy = nd[4], hiz = nd[5], refs = nd[6], cm = nd[7];
-    const float L[3][4] = {{lox.x, lox.y, lox.z, lox.w}, {loy.x, loy.y, loy.z, loy.w}, {loz.x, loz.y, loz.z, loz.w}};
-    const float Hh[3][4] = {{hix.x, hix.y, hix.z, hix.w}, {hiy.x, hiy.y, hiy.z, hiy.w}, {hiz.x, hiz.y, hiz.z, hiz.w}};
-    const float cmax[4] = {cm.x, cm.y, cm.z, cm.w};
-    uint32_t ref[4] = {__float_as_uint(refs.x), __float_as_uint(refs.y), __float_as_uint(refs.z), __float_as_uint(refs.w)};
-    float good[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float pad = b.rho * (omax + cmax[c]);
-      const float t1x = ((L[0][c] - pad) - o.x) * inv.x, t2x = ((Hh[0][c] + pad) - o.x) * inv.x;
-      const float t1y = ((L[1][c] - pad) - o.y) * inv.y, t2y = ((Hh[1][c] + pad) - o.y) * inv.y;
-      const float t1z = ((L[2][c] - pad) - o.z) * inv.z, t2z = ((Hh[2][c] + pad) - o.z) * inv.z;
-      const bool nan = __builtin_isunordered(t1x, t2x) || __builtin_isunordered(t1y, t2y) || __builtin_isunordered(t1z, t2z);
-      const float enter = fmaxf(fmaxf(fminf(t1x, t2x), fminf(t1y, t2y)), fminf(t1z, t2z));
-      const float exit = fminf(fminf(fmaxf(t1x, t2x), fmaxf(t1y, t2y)), fmaxf(t1z, t2z));
-      const bool skip = (exit < enter) || (exit < tmin) || (enter > tmax);
-      const bool decided = prunes && !nan;
-      // the overlap of the child's span with the interval (inf - inf: a NaN, which fmaxf drops)
-      float g = decided ? fmaxf(fminf(exit, tmax) - fmaxf(enter, tmin), -FLT_MAX) : inf;
-      if (ref[c] == kBvhEmpty || (decided && skip)) { ref[c] = kBvhEmpty; g = -inf; }
-      good[c] = g;
-    }
-    // largest overlap first (a 5-exchange network); an empty reference carries -inf, a visited one at least -FLT_MAX
-#define RT_OCC_CSWAP(i, j)                                                                            \
-    if (good[i] < good[j]) { const float tg = good[i]; good[i] = good[j]; good[j] = tg;               \
-                             const uint32_t tr = ref[i]; ref[i] = ref[j]; ref[j] = tr; }
-    RT_OCC_CSWAP(0, 1) RT_OCC_CSWAP(2, 3) RT_OCC_CSWAP(0, 2) RT_OCC_CSWAP(1, 3) RT_OCC_CSWAP(1, 2)
-#undef RT_OCC_CSWAP
-    cur = ref[0];
-    auto push = [&](uint32_t r) {
-      if (r == kBvhEmpty) return;
-      if (sp < b.stack_cap) { stack[sp * 64u] = r; ++sp; }
-      else overflow = true;                                        // (cannot happen: the capacity is 3 x the tree's depth)
-    };
-    push(ref[3]); push(ref[2]); push(ref[1]);                      // the better of them on top
-  }
+  const OccludedPrune q = occluded_prune(o, d);
+  const bool overflow = bvh_walk<64u, false>(
+      b, s_mem, lane, !done, [&](const BvhNode& nd, int c) { return occluded_child(nd, c, b.rho, q, o, tmin, tmax); },
+      [&](const float4* rec) { return done = occluded_test_record<FMA>(rec, o, d, tmin, tmax); }, [](float) { return false; });
   if (overflow && !done) {                                         // an entry was not kept: every leaf record
     for (uint32_t j = 0; j < b.n_leaf_records && !done; ++j) done = occluded_test_record<FMA>(b.records + 3u * j, o, d, tmin, tmax);
   }
@@ -243,10 +212,6 @@ __global__ __launch_bounds__(64) void occluded_bvh_kernel(const TraceParams p, c
 
 uint32_t occluded_lds_bytes(uint32_t n_tris) {
   return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
-}
-
-uint32_t occluded_bvh_lds_bytes(uint32_t stack_cap) {
-  return stack_cap * 64u * 4u;
 }
 
 hipError_t launch_occluded(const TraceParams& p, bool fma, int K, uint32_t n, const float* segs, uint8_t* occluded, hipStream_t st) {
@@ -268,8 +233,8 @@ hipError_t launch_occluded_bvh(const TraceParams& p, const BvhParams& b, bool fm
                                hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (segs == nullptr || occluded == nullptr) return hipErrorInvalidValue;
-  const uint32_t lds = occluded_bvh_lds_bytes(b.stack_cap);
-  if (lds > 65536u) return hipErrorInvalidValue;                   // (3 x kBvhMaxDepth entries are 12 KiB)
+  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, false);
+  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
   const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
   const float4* const s4 = reinterpret_cast<const float4*>(segs);
   if (fma) hipLaunchKernelGGL(occluded_bvh_kernel<true>, grid, dim3(64), lds, st, p, b, n, s4, occluded);
