@@ -97,7 +97,11 @@ typedef struct rt_options {
 
 /* RayTracer::RayTracer, RayTracer.h:17-22.  imageSize = {width, height} pixels, fov in
  * degrees, cameraAngles in radians.  cameraPosition is stored and ignored exactly like
- * the reference (ThinLensCamera.cuh:54-57,132-141: the camera sits at the world origin). */
+ * the reference (ThinLensCamera.cuh:54-57,132-141: the camera sits at the world origin).
+ * Sizes: a frame (imageSize, or imageSize[0] x full_height) holds at most 2^32 - 1 pixels -- a pixel's random subsequence
+ * x + y * width is a 32-bit word, Kernels.cuh:128 -- and ONE tracer at most 2^32 - 2^19 of them; a larger frame is rendered as
+ * several row bands (rt_options.full_height / row_begin).  rt_tracer_create_ex, rt_tracer_resize and rt_tracer_set_band refuse
+ * anything else with RT_ERR_INVALID before they allocate or release a buffer: the tracer stays as it was. */
 int  rt_tracer_create(const uint32_t imageSize[2], const float cameraPosition[3],
                       const float cameraAngles[2], float fov, float focalLength, float aperture,
                       rt_tracer** out);

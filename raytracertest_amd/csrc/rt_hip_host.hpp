@@ -21,6 +21,9 @@ inline std::string fmt(const char* f, ...) {
 }
 
 struct HipFail { std::string what; };
+// an argument the library refuses before it touches the device: RT_ERR_INVALID where HipFail is RT_ERR_HIP (guarded());
+// every other handler takes it for the HipFail it derives from and keeps its text
+struct BadArgument : HipFail { explicit BadArgument(std::string w) : HipFail{std::move(w)} {} };
 #define HIP_CHECK(expr)                                                                                     \
   do {                                                                                                      \
     hipError_t e_ = (expr);                                                                                 \

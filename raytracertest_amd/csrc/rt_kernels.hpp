@@ -109,6 +109,9 @@ enum class TracePath : uint32_t {
 
 // jump: J^(2^k), k < 32, 160 columns x 8 words; win: the 4-bit window tables of J^(2^m), m < 6 (rt_rng_host.hpp).
 // Writes planes 1..5 (v0..v4); the Weyl word seeded[0] is every pixel's and stays with the host (TraceParams::weyl).
+// npix <= kRngInitMaxPixels: the kernel's chunk loop (base += stride, i = base + lane) and the launcher's rounded-up block
+// count are 32-bit, and the margin of 2^19 holds the largest stride (512 blocks x 512 threads = 2^18) and that rounding.
+constexpr uint64_t kRngInitMaxPixels = (1ull << 32) - (1ull << 19);
 hipError_t launch_rng_init(uint32_t* rng, uint32_t npix, uint32_t p0, const uint32_t seeded[6],
                            const uint32_t* jump, const uint32_t* win, hipStream_t st);
 // Small scenes: advances v0..v4 of every pixel of the certain-winner tiles of the (half-)launch `p` (p.tile_lists, p.rng and

@@ -139,6 +139,7 @@ hipError_t launch_rng_init(uint32_t* rng, uint32_t npix, uint32_t p0, const uint
                            const uint32_t* jump, const uint32_t* win, hipStream_t st) {
   Rng s = {seeded[0], seeded[1], seeded[2], seeded[3], seeded[4], seeded[5]};
   if (npix == 0) return hipSuccess;
+  if (npix > kRngInitMaxPixels) return hipErrorInvalidValue;          // (rt_kernels.hpp; the tracer refuses such a band before it allocates)
   // two 512-thread blocks fit a CU's LDS (75 KiB of tables each, 8 waves per block: no register cap); small frames get one block per 512 pixels
   // a power of two, so that a wave's next chunk is ONE fixed jump J^(blocks * 512) away
   const uint32_t want = cdiv(npix, kRngInitThreads);

@@ -149,6 +149,9 @@ int rt_tracer_create_ex(const uint32_t imageSize[2], const float cameraPosition[
     opt.use_time_seed = 0;
     memcpy(&opt, options, n);
   }
+  // the geometry is judged before a device is asked for anything
+  const std::string refused = band_refusal(imageSize[0], opt.full_height ? opt.full_height : imageSize[1], imageSize[1]);
+  if (!refused.empty()) { set_global_error("rt_tracer_create: " + refused); return RT_ERR_INVALID; }
   int rc = require_device(opt.device);
   if (rc != RT_OK) return rc;
 
@@ -271,6 +274,8 @@ int rt_tracer_resize(rt_tracer* t, const uint32_t size[2]) {             // :94-
   return exclusive(t, [&] {
     if (t->mg) { multi_resize(t, size[0], size[1]); return; }
     if (t->grp) throw HipFail{"Resize: the tracer is a member of a multi-process group (leave and re-join with the new bands)"};
+    const std::string refused = band_refusal(size[0], t->band_mode ? t->H : size[1], size[1]);   // before the buffers go
+    if (!refused.empty()) throw BadArgument{refused};
     t->use_device();
     HIP_CHECK(hipStreamSynchronize(t->main_stream()));
     t->release_buffers();

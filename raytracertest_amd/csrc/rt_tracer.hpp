@@ -446,6 +446,18 @@ struct HalfLists {
   size_t wave_tiles = 0;
 };
 
+// What a tracer of `rows` rows of a w x h frame cannot be, as the text of the refusal; empty = acceptable.  Asked before
+// anything is allocated (rt_tracer_create_ex, rt_tracer_resize, rt_tracer::reshape): a pixel's subsequence x + y * W and
+// the band's pixel count are 32-bit words everywhere, and rng_init_kernel indexes a band only up to kRngInitMaxPixels.
+inline std::string band_refusal(uint32_t w, uint32_t h, uint32_t rows) {
+  if (static_cast<uint64_t>(w) * h > 0xFFFFFFFFull)
+    return "frames above 2^32 - 1 pixels are not supported (32-bit pixel index, Kernels.cuh:128)";
+  if (static_cast<uint64_t>(w) * rows > rtk::kRngInitMaxPixels)
+    return fmt("a tracer holds at most 2^32 - 2^19 = %llu pixels (%u x %u asked for): shard a larger frame into row bands "
+               "(rt_options.full_height / row_begin)", static_cast<unsigned long long>(rtk::kRngInitMaxPixels), w, rows);
+  return std::string();
+}
+
 struct Group;        // rt_multi.hpp: the tile gather of a frame sharded over several GPUs
 struct MultiState;   // rt_multi.hpp: the bands of a multi-device tracer
 
@@ -710,7 +722,8 @@ struct rt_tracer {
     uint32_t seeded[6];
     rth::seed_state(seed, seeded);
     const uint32_t p0 = row0 * W;                                        // subsequence of the band's first pixel
-    if (static_cast<uint64_t>(W) * H > 0xFFFFFFFFull) throw rtr::HipFail{"frames above 2^32 pixels are not supported (32-bit pixel index, Kernels.cuh:128)"};
+    const std::string refused = rtr::band_refusal(W, H, rows);           // (the entry points asked before they allocated)
+    if (!refused.empty()) throw rtr::BadArgument{refused};
     uint32_t* const tables = rtr::jump_device(device);
     std::lock_guard<std::recursive_mutex> lk(order_mu);
     HIP_CHECK(rtk::launch_rng_init(d_rng.get(), npix(), p0, seeded, tables, tables + rtr::kJumpWords, main_stream()));
@@ -735,6 +748,8 @@ struct rt_tracer {
 
   // multi-device Resize: new frame size AND new band of it (scene, camera and options stay)
   void reshape(uint32_t w, uint32_t h, uint32_t r0, uint32_t n) {
+    const std::string refused = rtr::band_refusal(w, h, n);              // before the buffers go: a refused tracer stays as it is
+    if (!refused.empty()) throw rtr::BadArgument{refused};
     HIP_CHECK(hipStreamSynchronize(main_stream()));
     sync_list_stream();
     release_buffers();
@@ -1316,6 +1331,8 @@ int guarded(rt_tracer* t, F&& f) {
   try {
     f();
     return RT_OK;
+  } catch (const BadArgument& e) {
+    return fail(e.what, RT_ERR_INVALID);
   } catch (const HipFail& e) {
     return fail(e.what, RT_ERR_HIP);
   } catch (const std::exception& e) {
