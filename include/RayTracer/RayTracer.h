@@ -195,6 +195,29 @@ public:
     if (!ClosestAll(pts, maxHits, hits, counts)) hits.clear();
     return hits;
   }
+  // Region query (rt_mi355x.h, rt_tracer_overlap): boxes holds 8 floats per box, lo.x lo.y lo.z _ hi.x hi.y hi.z _ (the pads are
+  // never read).  Row i of prims (maxHits ints) holds the min(counts[i], maxHits) lowest primitives that touch box i in
+  // ascending order, then RT_PRIM_NONE; counts[i] is their TOTAL behind the cursor, so counts[i] > maxHits means there are more
+  // -- call again with after[i] = the row's last prim.  after: empty (no cursor) or one int per box.  0 <= maxHits <=
+  // RT_MAX_HITS (0: counts only).  A box vector whose size is no multiple of 8, or an after of another length: false, the
+  // outputs untouched.
+  bool Overlap(const std::vector<float>& boxes, uint32_t maxHits, std::vector<int32_t>& prims, std::vector<uint32_t>& counts,
+               const std::vector<int32_t>& after = std::vector<int32_t>()) {
+    if (!mImpl || boxes.size() % 8 != 0 || maxHits > RT_MAX_HITS) return false;
+    const size_t n = boxes.size() / 8;
+    if (!after.empty() && after.size() != n) return false;
+    prims.resize(n * maxHits);
+    counts.resize(n);
+    return rt_tracer_overlap(mImpl, boxes.data(), after.empty() ? nullptr : after.data(), n, maxHits,
+                             maxHits != 0 ? prims.data() : nullptr, counts.data()) == RT_OK;
+  }
+  // The same, returning the counts: empty when the arguments were rejected or the call failed (LastError()).
+  std::vector<uint32_t> Overlap(const std::vector<float>& boxes, uint32_t maxHits = 0) {
+    std::vector<int32_t> prims;
+    std::vector<uint32_t> counts;
+    if (!Overlap(boxes, maxHits, prims, counts)) counts.clear();
+    return counts;
+  }
   // Signed point query (rt_mi355x.h, rt_tracer_signed_distance): the same points; hits is ClosestPoint's answer bit for bit,
   // sides[i].s > 0 in front of the nearest surface (outside a closed, outward-wound mesh), < 0 behind it, 0 on it or undecided;
   // sides[i].feature names the face, vertex or edge that holds the nearest point (RT_FEATURE_SPHERE for a sphere,

@@ -578,6 +578,79 @@ int  rt_tracer_closest_sides(rt_tracer* t, const float* pts, const rt_hit* hits,
 int  rt_tracer_closest_sides_device(rt_tracer* t, const float* pts, const rt_hit* hits, size_t n, uint32_t per_point, rt_side* sides,
                                     void* stream);
 
+/* ---- region queries ------------------------------------------------------------------------------
+ * Which primitives of the tracer's scene touch an axis-aligned box (surface voxelisation, the broad phase of box colliders,
+ * "select everything inside this volume", building a grid over the scene).
+ *   boxes       n x 8 floats: lo.x lo.y lo.z _ hi.x hi.y hi.z _ (two 16-byte loads, like a segment).  The two pad floats are
+ *               never read into any arithmetic: NaNs there change nothing.
+ *   max_hits    0 .. RT_MAX_HITS; above that RT_ERR_INVALID.  With 0 only the counts are produced and prims may be NULL.
+ *   after       optional (NULL: none): n cursors.  Where after[i] != RT_PRIM_NONE a primitive of box i is accepted only if
+ *               prim > after[i], compared as int32.
+ *   prims       n * max_hits int32.  Row i (prims + i * max_hits) holds the min(counts[i], max_hits) LOWEST accepted prims in
+ *               ascending order, then RT_PRIM_NONE.  Numbering as in the other queries: a triangle's upload index, n_tris + i
+ *               for sphere i.
+ *   counts      counts[i] = the TOTAL number of accepted primitives of box i behind its cursor, not capped.  counts[i] >
+ *               max_hits means exactly "there are more": call again with after[i] = the row's last prim; nothing repeats and
+ *               nothing is lost.  (The total is free: the order names the lowest prims, so every overlapping leaf is visited.)
+ *   triangle    one arithmetic in RT_MATH_FMA and RT_MATH_STRICT: every operation is one separately rounded fp32 operation, dot
+ *               products are (x*x' + y*y') + z*z', cross products (a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x, a.x*b.y - b.x*a.y);
+ *               min and max are IEEE minNum / maxNum (a NaN operand is dropped).  On the record the renderer intersects
+ *               (v0, e1, e2; for edge-format scenes the uploaded rows), with corners A = v0, B = fl(v0 + e1), C = fl(v0 + e2):
+ *                 1. Box step.  Per axis: tmin = min(min(A, B), C), tmax = max(max(A, B), C).  Accepted only if, on all three
+ *                    axes, lo <= hi, neither B nor C is a NaN (a NaN A makes both one), tmin <= hi and tmax >= lo.  Plain
+ *                    comparisons, closed: touching counts.  So a NaN anywhere in the box bounds or the record, or lo > hi on an
+ *                    axis, rejects.
+ *                 2. Plane step.  c = 0.5*lo + 0.5*hi,  h = 0.5*hi - 0.5*lo  per axis;  n = e1 x e2;  a = A - c;
+ *                    s = n.a,  r = h.|n|  (|n| per component).  Separated when |s| > r.
+ *                 3. The nine axes unit_k x f of Akenine-Moller's separating-axis test.  With a = A - c, b = B - c, c' = C - c:
+ *                      f = e1       on the corners P = a, Q = c'
+ *                      f = c' - b   on the corners P = a, Q = b
+ *                      f = a - c'   on the corners P = a, Q = b
+ *                    (the two corners whose projections differ in exact arithmetic) and for each f, with p(V) on V = P, Q:
+ *                      k = x:  p = f.y*V.z - f.z*V.y,  r = h.y*|f.z| + h.z*|f.y|
+ *                      k = y:  p = f.z*V.x - f.x*V.z,  r = h.x*|f.z| + h.z*|f.x|
+ *                      k = z:  p = f.x*V.y - f.y*V.x,  r = h.x*|f.y| + h.y*|f.x|
+ *                    Separated on an axis when  p(P) > r && p(Q) > r  or  p(P) < -r && p(Q) < -r.
+ *               A triangle is accepted when step 1 accepts and nothing in steps 2-3 is separated.  Steps 2-3 reject only when a
+ *               "separated" is TRUE, so a NaN there (products overflow for boxes near FLT_MAX: inf - inf) never rejects.  A
+ *               zero-area triangle gets what this arithmetic gives it (n = 0: the plane step never separates); it is not
+ *               special-cased.
+ *   sphere      a sphere is its surface, as in the point queries.  Centre s, radius r, per axis a = lo - s, b = s - hi:
+ *                 g = max(max(a, b), 0),  f = max(|a|, |b|);  d2min = (gx*gx + gy*gy) + gz*gz,  d2max = (fx*fx + fy*fy) + fz*fz.
+ *               Accepted when lo <= hi on every axis and d2min <= r*r && r*r <= d2max.  A box wholly inside the ball touches
+ *               nothing, just as a box inside a closed mesh touches no triangle.
+ *   infinite    bounds on the right side (lo = -inf and / or hi = +inf: a half space, a slab, all of space) are valid boxes: steps
+ *               2-3 then compute with inf and NaN and never separate, so exactly what step 1 accepts is accepted.  lo = +inf or
+ *               hi = -inf is lo > hi: nothing.
+ *   accuracy    as measured (tests/test_overlap_expect.py): against the 13-axis separating-axis test in float64
+ *               on the same fp32 corners, the largest disagreement margin seen is "none in 2 000 000 pairs" of random triangles
+ *               and boxes, and none in 2 000 000 pairs of the same inputs snapped to multiples of 1/4, where touching is exact.
+ * No scene: every count is 0; spheres alone can answer; n = 0 is a no-op; NULL boxes or counts with n > 0, or NULL prims with
+ * max_hits > 0, is RT_ERR_INVALID, and the outputs are then untouched.
+ * Scheduling is that of the other queries: never cancels or joins a running Trace, serialised with the other calls, on the query
+ * stream or the caller's, waited for by uploads and destroy; a multi-device handle answers from its first band, a band tracer
+ * locally.
+ * RT_QUERY_SCAN (default): every box tests every primitive.  RT_QUERY_BVH: the ray queries' tree (built, or under RT_ACCEL_REFIT
+ * refitted, by the first query after an upload).  A child is entered when its box and the query box overlap -- clo <= hi &&
+ * chi >= lo per axis, the same closed comparisons, NO inflation -- and the result is bit for bit the scan's rows and counts for
+ * every input whatsoever.  rt_dbg_query_accel_slack has no effect on this query.  Why scan and tree agree:
+ *   - a leaf record's tree box is the box of the corners v0, v0 + e1, v0 + e2 evaluated in double and rounded outward; the fp32
+ *     corners fl(v0 + e) lie between the exact sum rounded down and rounded up;
+ *   - so step 1's [tmin, tmax] lies inside the record's tree box, which lies inside every ancestor's child box: a child the
+ *     walk skips holds only triangles step 1 rejects;
+ *   - acceptance is a pure function of (box, record, cursor), and a walk visits every record at most once;
+ *   - triangles with a non-finite record sit in the always-tested list and go through the same rule; spheres are never in the
+ *     tree and are scanned after the triangles;
+ *   - a walk whose stack overflowed recomputes from every leaf record, restarting the list and the count. */
+/* Host arrays: boxes n*8, after n or NULL, prims n*max_hits (NULL allowed when max_hits = 0), counts n.  Returns with the
+ * results in host memory. */
+int  rt_tracer_overlap(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                       uint32_t* counts);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  boxes must be 16-byte aligned; otherwise RT_ERR_INVALID. */
+int  rt_tracer_overlap_device(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                              uint32_t* counts, void* stream);
+
 /* ---- one frame sharded over several GPUs --------------------------------------
  * The reference builds ONE rt::RayTracer pinned to device 0 (OpenGLView/MainFrame.cpp:44-45,
  * OpenGLView/GLCanvas.cpp:259-260).  Pixels are independent and a pixel's RNG stream is keyed by its

@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "rt_tracer_closest_all", "rt_tracer_closest_all_device",
     "rt_tracer_signed_distance", "rt_tracer_signed_distance_device",
     "rt_tracer_closest_sides", "rt_tracer_closest_sides_device", "rt_dbg_feature_normals",
+    "rt_tracer_overlap", "rt_tracer_overlap_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
     "rt_tracer_set_query_accel_update", "rt_tracer_query_accel_rebuild", "rt_tracer_query_accel_update_info",
     "rt_dbg_bvh_refit", "rt_dbg_query_tree_read", "rt_dbg_bvh_tree_cost", "rt_dbg_query_stack_cap",
@@ -359,6 +360,8 @@ def load_library():
         L.rt_tracer_signed_distance_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
         L.rt_tracer_closest_sides.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
         L.rt_tracer_closest_sides_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
+        L.rt_tracer_overlap.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
+        L.rt_tracer_overlap_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
         L.rt_dbg_feature_normals.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
         L.rt_tracer_set_query_accel.argtypes = [vp, C.c_uint32]
         L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -1036,6 +1039,131 @@ class RayTracer:
         offsets = np.zeros(n + 1, np.int64)
         np.cumsum(np.bincount(owner, minlength=n), out=offsets[1:])
         return flat[order], offsets
+
+    # ---- region queries (rt_tracer_overlap / _device) ------------------------------------------------------------------
+    @staticmethod
+    def _boxes_array(who, boxes):
+        """-> contiguous (n, 8) float32 {lo xyz, 0, hi xyz, 0}: from (n, 8) as it is (the pads are never read), from (n, 6)
+        {lo xyz, hi xyz}, or from a (lo, hi) pair of (n, 3) arrays."""
+        if isinstance(boxes, (tuple, list)) and len(boxes) == 2 and np.ndim(boxes[0]) >= 1 and np.shape(boxes[0])[-1] == 3:
+            lo, hi = (np.asarray(b, np.float32).reshape(-1, 3) for b in boxes)
+            if lo.shape != hi.shape:
+                raise ValueError("%s: %d lower corners, %d upper corners" % (who, lo.shape[0], hi.shape[0]))
+            b = np.concatenate([lo, hi], axis=1)
+        else:
+            b = np.asarray(boxes, np.float32)
+        if b.ndim == 0 or b.shape[-1] not in (6, 8):
+            raise ValueError("%s: expected (n, 6) or (n, 8) float32 boxes or a (lo, hi) pair, got shape %s" % (who, b.shape))
+        if b.shape[-1] == 6:
+            b = b.reshape(-1, 6)
+            q = np.zeros((b.shape[0], 8), np.float32)
+            q[:, 0:3], q[:, 4:7] = b[:, 0:3], b[:, 3:6]
+            b = q
+        return np.ascontiguousarray(b).reshape(-1, 8)
+
+    @staticmethod
+    def _overlap_hits(max_hits):
+        k = int(max_hits)
+        if k != max_hits or not 0 <= k <= RT_MAX_HITS:
+            raise ValueError("Overlap: max_hits = %r (0 to %d)" % (max_hits, RT_MAX_HITS))
+        return k
+
+    def Overlap(self, boxes, max_hits=RT_MAX_HITS, after=None):
+        """The primitives that touch each axis-aligned box (rt_tracer_overlap).  boxes: (n, 8) float32 {lo xyz, -, hi xyz, -},
+        (n, 6) {lo xyz, hi xyz}, or a (lo, hi) pair of (n, 3) arrays; closed boxes, touching counts; a NaN bound or lo > hi on
+        an axis touches nothing.  0 <= max_hits <= RT_MAX_HITS.  Returns (prims (n, max_hits) int32, counts (n,) uint32): row i
+        holds the min(counts[i], max_hits) lowest touching prims in ascending order, then PRIM_NONE; counts[i] is the TOTAL
+        behind the cursor, so counts[i] > max_hits means there are more (OverlapAll chains the cursor).  after: (n,) int32, only
+        prims above after[i] are accepted; PRIM_NONE is no cursor.  Independent of the tracer's arithmetic mode and hit rule; a
+        sphere is its surface.  numpy in, numpy out, on return.  A contiguous (n, 8) float32 torch tensor on the tracer's device
+        -> ((n, max_hits) int32, (n,) int32) tensors, enqueued on torch.cuda.current_stream() without a host synchronisation;
+        after is then a contiguous (n,) int32 tensor."""
+        if type(boxes).__module__.startswith("torch"):
+            return self._overlap_tensor(boxes, max_hits, after)
+        b = self._boxes_array("Overlap", boxes)
+        k = self._overlap_hits(max_hits)
+        a = None
+        if after is not None:
+            a = np.ascontiguousarray(after, np.int32).reshape(-1)
+            if a.shape[0] != b.shape[0]:
+                raise ValueError("Overlap: after must hold one int32 cursor per box")
+        prims = np.full((b.shape[0], k), PRIM_NONE, np.int32)
+        counts = np.zeros(b.shape[0], np.uint32)
+        self._check(self._lib.rt_tracer_overlap(self._h, b.ctypes.data, None if a is None else a.ctypes.data, b.shape[0], k,
+                                                prims.ctypes.data if k else None, counts.ctypes.data))
+        return prims, counts
+
+    def _overlap_tensor(self, boxes, max_hits=RT_MAX_HITS, after=None):
+        import torch
+        if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 8 or not boxes.is_contiguous():
+            raise ValueError("Overlap: expected a contiguous (n, 8) float32 tensor")
+        k = self._overlap_hits(max_hits)
+        stream = self._stream_of("Overlap", "boxes", boxes)
+        n = boxes.shape[0]
+        if after is not None:
+            if (not type(after).__module__.startswith("torch") or after.dtype != torch.int32 or tuple(after.shape) != (n,) or
+                    not after.is_contiguous() or after.device != boxes.device):
+                raise ValueError("Overlap: after must be a contiguous (n,) int32 tensor on the boxes' device")
+        prims = torch.empty((n, k), dtype=torch.int32, device=boxes.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=boxes.device)
+        self._check(self._lib.rt_tracer_overlap_device(self._h, boxes.data_ptr(), None if after is None else after.data_ptr(), n, k,
+                                                       prims.data_ptr() if k else None, counts.data_ptr(), stream))
+        return prims, counts
+
+    def OverlapAll(self, boxes, max_hits=RT_MAX_HITS):
+        """Every primitive that touches each box, numpy only: Overlap repeated with the cursor while a count exceeds max_hits
+        (1 <= max_hits <= RT_MAX_HITS is the row length of one round).  Returns (prims, offsets): the touching prims of all
+        boxes, flat, int32, each box's in ascending order; box i's are prims[offsets[i]:offsets[i + 1]], offsets (n + 1,)
+        int64."""
+        b = self._boxes_array("OverlapAll", boxes)
+        k = self._max_hits("OverlapAll", max_hits)
+        n = b.shape[0]
+        live = np.arange(n)                                                # the boxes that have more
+        after = None
+        parts, owners = [], []
+        while live.size:
+            prims, counts = self.Overlap(b[live], k, after=after)
+            stored = np.minimum(counts, k)
+            keep = np.arange(k)[None, :] < stored[:, None]
+            parts.append(prims[keep])
+            owners.append(np.repeat(live, stored))
+            more = counts > k
+            after = np.ascontiguousarray(prims[more, k - 1])
+            live = live[more]
+        owner = np.concatenate(owners) if owners else np.zeros(0, np.int64)
+        flat = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+        order = np.argsort(owner, kind="stable")                           # rounds are in order within a box already
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(np.bincount(owner, minlength=n), out=offsets[1:])
+        return flat[order], offsets
+
+    @staticmethod
+    def voxel_boxes(origin, spacing, shape):
+        """The (nx * ny * nz, 8) float32 boxes of Voxelize's grid, voxel (i, j, k) at row (i * ny + j) * nz + k.  All in fp32,
+        per axis:  lo = origin + spacing * float32(i),  hi = origin + spacing * float32(i + 1)  (one multiplication, one
+        addition, each rounded) -- so hi of voxel i and lo of voxel i + 1 are the same bits and neighbours share their face."""
+        o = np.asarray(origin, np.float32).reshape(3)
+        sp = np.broadcast_to(np.asarray(spacing, np.float32), (3,))
+        shape = tuple(int(v) for v in shape)
+        if len(shape) != 3 or min(shape) < 0:
+            raise ValueError("Voxelize: shape must be three non-negative counts")
+        edges = [(o[a] + sp[a] * np.arange(shape[a] + 1, dtype=np.float32)).astype(np.float32) for a in range(3)]
+        boxes = np.zeros(shape + (8,), np.float32)
+        for a in range(3):
+            sl = [None, None, None]
+            sl[a] = slice(None)
+            boxes[..., a] = edges[a][:-1][tuple(sl)]
+            boxes[..., 4 + a] = edges[a][1:][tuple(sl)]
+        return boxes.reshape(-1, 8)
+
+    def Voxelize(self, origin, spacing, shape):
+        """Surface voxelisation: a bool array of `shape` = (nx, ny, nz), True where the closed voxel touches a primitive (the
+        surface: a voxel wholly inside a closed mesh or a ball is False; DistanceField / Contains give the solid).  Voxel (i, j,
+        k) is the box voxel_boxes states, origin + spacing * (i, j, k) .. origin + spacing * (i + 1, j + 1, k + 1) in fp32;
+        spacing is a scalar or one value per axis.  One Overlap call with max_hits = 0: True when counts > 0."""
+        boxes = self.voxel_boxes(origin, spacing, shape)
+        _, counts = self.Overlap(boxes, 0)
+        return (counts > 0).reshape(tuple(int(v) for v in shape))
 
     # ---- signed point queries (rt_tracer_signed_distance / rt_tracer_closest_sides, and their _device forms) -------------
     def SignedDistance(self, points, max_distance=np.inf):

@@ -1,6 +1,6 @@
 """Headless front end: `python -m raytracertest_amd.cli`.  The reference's command line
 (OpenGLView/App.cpp:62-184: -w -h -s -i -u -cx -cy -cz -cxa -cya -f -l -a, integer values,
-defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --focus; the image is saved
+defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --focus; the image is saved
 in the reference's BMP format (Common/Bitmap.h).  Same options as tools/rt_cli.cpp."""
 import argparse
 import math
@@ -52,7 +52,10 @@ def build_parser():
                    help="print `exposure mask open K`: which of K (1 to 64, default 64) cosine-weighted hemisphere directions about "
                         "the normal NX,NY,NZ (used as given) are open from the point X,Y,Z over [1e-3, R] -- the mask in hex, bit j "
                         "= direction j, and their count")
-    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan")
+    p.add_argument("--overlap", type=_overlap, default=None, metavar="X0,Y0,Z0,X1,Y1,Z1[,K]",
+                   help="print `overlap count`, the number of primitives that touch the box with the corners X0,Y0,Z0 and X1,Y1,Z1, "
+                        "then one line `prim` for each of the K lowest (default 8)")
+    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --focus through the scene's BVH instead of the scan")
     p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
                    help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
     return p
@@ -97,6 +100,16 @@ def _exposure(s):
         raise ValueError(s)
     f = [float(x) for x in v[:7]]
     return tuple(f[:6]) + (f[6] if len(f) == 7 else math.inf, k)
+
+
+def _overlap(s):
+    v = s.split(",")
+    if len(v) not in (6, 7):
+        raise ValueError(s)
+    k = int(v[6]) if len(v) == 7 else 8
+    if k < 0:
+        raise ValueError(s)
+    return tuple(float(x) for x in v[:6]) + (k,)
 
 
 class _Nearest(argparse.Action):
@@ -191,6 +204,14 @@ def main(argv=None):
             sys.exit("--nearest: %s" % e)
         for h in hits[0, :counts[0]]:
             print("%d %.9g %.9g %.9g" % (h["prim"], np.sqrt(h["t"]), h["u"], h["v"]))
+    if a.overlap is not None:
+        try:
+            prims, counts = g.Overlap(np.float32([a.overlap[:6]]), a.overlap[6])
+        except Exception as e:
+            sys.exit("--overlap: %s" % e)
+        print("overlap %d" % counts[0])
+        for prim in prims[0, :min(int(counts[0]), a.overlap[6])]:
+            print("%d" % prim)
     if a.focus is not None:
         try:
             f = g.FocusAt(*a.focus)

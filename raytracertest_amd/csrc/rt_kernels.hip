@@ -12,6 +12,7 @@
 //   allhits_*kernel    <- the first k hits within a caller's t interval, in order (rt_allhits.hpp)
 //   closest_*kernel    <- the nearest surface point to a caller's point (rt_closest.hpp)
 //   nearest_*kernel    <- a point's k nearest primitives in order, with a continuation cursor (rt_nearest.hpp)
+//   overlap_*kernel    <- the primitives that touch a caller's box, lowest first, and how many (rt_overlap.hpp)
 //   sides_kernel       <- the side of the surface a point query's records lie on (rt_sides.hpp)
 //   refit_*kernel      <- the tree's boxes recomputed for a re-uploaded scene of the same size (rt_refit.hpp)
 //   dbg_* kernels      <- single-function harnesses used by the parity tests
@@ -25,6 +26,7 @@
 #include "rt_allhits.hpp"
 #include "rt_closest.hpp"
 #include "rt_nearest.hpp"
+#include "rt_overlap.hpp"
 #include "rt_sides.hpp"
 #include "rt_refit.hpp"
 

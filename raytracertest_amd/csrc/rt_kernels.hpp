@@ -219,6 +219,16 @@ hipError_t launch_nearest(const TraceParams& p, uint32_t n, const float* pts, co
 hipError_t launch_nearest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, const float4* after,
                               uint32_t max_hits, float4* hits, uint32_t* counts, hipStream_t st);
 
+// The region query (rt_overlap.hpp): n boxes {lo xyz, -, hi xyz, -}, 16-byte aligned; after (or nullptr) n int32 cursors; row i
+// of prims (max_hits int32) holds the min(counts[i], max_hits) lowest accepted prims behind the cursor in ascending order, then
+// -1; counts[i] is the total, not capped.  0 <= max_hits <= 16 (0: prims may be nullptr); one arithmetic for both math modes;
+// one box per lane in both forms.  The tree form reads neither b.rho nor a slack: its prune is exact.
+uint32_t overlap_lds_bytes(uint32_t n_tris);
+hipError_t launch_overlap(const TraceParams& p, uint32_t n, const float* boxes, const int* after, uint32_t max_hits, int* prims,
+                          uint32_t* counts, hipStream_t st);
+hipError_t launch_overlap_bvh(const TraceParams& p, const BvhParams& b, uint32_t n, const float* boxes, const int* after,
+                              uint32_t max_hits, int* prims, uint32_t* counts, hipStream_t st);
+
 // The side post-pass (rt_sides.hpp): n points, n * per_point records of them (hits, as the point queries wrote them), the feature
 // table (7 float4 per triangle, rt_features_host.hpp) -> n * per_point {s, feature} pairs of 8 bytes.
 hipError_t launch_sides(const TraceParams& p, const float4* table, uint32_t n, uint32_t per_point, const float* pts, const float4* hits,

@@ -1,6 +1,7 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
 // rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_exposure*, rt_tracer_intersect_all*) and the point queries (rt_tracer_closest_point*,
-// rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*).  Included by rt_tracer.hip.
+// rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*) and the region query (rt_tracer_overlap*).
+// Included by rt_tracer.hip.
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
 // calls by api_mu, reads only the scene and a snapshot of the camera (params(), under state_mu), and runs on a stream of its
@@ -263,6 +264,25 @@ inline void enqueue_closest_all(rt_tracer* t, size_t n, const float* pts, const 
     return b ? rtk::launch_nearest_bvh(p, *b, closest_rho(t), static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st)
              : rtk::launch_nearest(p, static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st);
   });
+}
+
+// boxes (and their cursors, or nullptr) -> rows of max_hits prims and one total per box (rt_overlap.hpp).  One arithmetic for both
+// math modes: the flags stay 0.  The tree is the ray queries' (ensure_query_tree, so RT_ACCEL_REFIT applies); no rho is passed.
+inline void enqueue_overlap(rt_tracer* t, size_t n, const float* boxes, const int32_t* after, uint32_t max_hits, int32_t* prims,
+                            uint32_t* counts, hipStream_t st) {
+  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return b ? rtk::launch_overlap_bvh(p, *b, static_cast<uint32_t>(n), boxes, after, max_hits, prims, counts, st)
+             : rtk::launch_overlap(p, static_cast<uint32_t>(n), boxes, after, max_hits, prims, counts, st);
+  });
+}
+
+// the arguments of the overlap entry points: max_hits checked whatever n is (0 is allowed: counts only), then the arrays
+inline bool overlap_args_ok(rt_tracer* t, const char* who, size_t n, const float* boxes, uint32_t max_hits, const int32_t* prims,
+                            const uint32_t* counts) {
+  if (max_hits > RT_MAX_HITS) { t->set_error(fmt("%s: max_hits = %u (0 to %u)", who, max_hits, RT_MAX_HITS)); return false; }
+  if (!query_args_ok(t, n, {boxes, counts})) return false;
+  if (n != 0u && max_hits != 0u && !prims) { t->set_error("query: null array"); return false; }
+  return true;
 }
 
 // The signed queries' feature table (rt_features_host.hpp) of the current scene: built on the host from the
@@ -664,6 +684,36 @@ int rt_tracer_closest_sides_device(rt_tracer* t, const float* pts, const rt_hit*
     t->use_device();
     ensure_feature_table(t);
     enqueue_sides(t, n, per_point, pts, reinterpret_cast<const float4*>(hits), sides, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_overlap(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                      uint32_t* counts) {
+  if (!t || !overlap_args_ok(t, "rt_tracer_overlap", n, boxes, max_hits, prims, counts)) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap(b, boxes, after, n, max_hits, prims, counts); }, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    const hipStream_t st = query_stream(t);
+    const float* d_boxes = staged_in(t->d_q_segs, boxes, n * 8u, st);
+    const int32_t* d_after = after ? staged_in(t->d_q_cursors, after, n, st) : nullptr;
+    int32_t* d_prims = max_hits != 0u ? room(t->d_q_prims, n * max_hits) : nullptr;
+    enqueue_overlap(t, n, d_boxes, d_after, max_hits, d_prims, room(t->d_q_all_counts, n), st);
+    if (max_hits != 0u) staged_out(prims, t->d_q_prims, n * max_hits, st);
+    staged_out(counts, t->d_q_all_counts, n, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_overlap_device(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                             uint32_t* counts, void* stream) {
+  if (!t || !overlap_args_ok(t, "rt_tracer_overlap_device", n, boxes, max_hits, prims, counts) ||
+      !query_aligned_ok(t, n, {{boxes, 16u}, {after, 4u}, {prims, 4u}, {counts, 4u}},
+                        "rt_tracer_overlap_device: boxes must be 16-byte aligned, after, prims and counts 4-byte aligned"))
+    return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap_device(b, boxes, after, n, max_hits, prims, counts, stream); }, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_overlap(t, n, boxes, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
   });
 }
 

@@ -638,6 +638,8 @@ struct rt_tracer {
   rtr::DevArray<float4> d_q_points;   // rt_tracer_closest_point: n x {x, y, z, d2max} in, n records (d_q_hits) out
   rtr::DevArray<float4> d_q_after;    // rt_tracer_closest_all: n cursor records in (rows and counts: d_q_all_hits, d_q_all_counts)
   rtr::DevArray<uint2> d_q_sides;     // rt_tracer_signed_distance, rt_tracer_closest_sides: one rt_side per record out
+  rtr::DevArray<int32_t> d_q_cursors; // rt_tracer_overlap: n x 8 floats (d_q_segs) and n cursors in, n x max_hits prims and n totals
+  rtr::DevArray<int32_t> d_q_prims;   // (d_q_all_counts) out
   rtr::Event query_done;
   void wait_queries() { if (query_done) HIP_CHECK(hipEventSynchronize(query_done)); }
   // RT_QUERY_BVH (rt_bvh_host.hpp, rt_bvh.hpp): the tree of the scene of generation bvh_scene, built by the first query in

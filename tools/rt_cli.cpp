@@ -27,13 +27,15 @@ struct Args {
   uint64_t seed = 0; bool have_seed = false;
   std::string scene = "demo3", scene_file, out = "image0.bmp";
   bool quiet = false, edges = false, smooth = false, nearest = false;
-  bool pick = false, focus = false, accel = false, hits = false, closest = false, knn = false, sgn = false, exposure = false;
+  bool pick = false, focus = false, accel = false, hits = false, closest = false, knn = false, sgn = false, exposure = false, overlap = false;
   float exposure_p[7] = {0, 0, 0, 0, 0, 1, INFINITY};   // --exposure: x, y, z, normal, far end of the interval
   uint32_t exposure_k = 64;
   float closest_p[4] = {0, 0, 0, INFINITY};        // x, y, z, search distance
   float signed_p[4] = {0, 0, 0, INFINITY};         // --signed: the same
   float knn_p[4] = {0, 0, 0, INFINITY};            // --nearest X,Y,Z[,R[,K]]: x, y, z, search distance
   uint32_t knn_k = 8;
+  float overlap_b[6] = {0, 0, 0, 0, 0, 0};         // --overlap X0,Y0,Z0,X1,Y1,Z1[,K]: lo, hi
+  uint32_t overlap_k = 8;
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0}, hits_xy[2] = {0, 0}, hits_k = 8;
 };
 
@@ -109,6 +111,27 @@ bool parse_exposure(const char* s, float out[7], uint32_t& k) {
   }
 }
 
+// "X0,Y0,Z0,X1,Y1,Z1" or "...,K": the two corners of a box and an optional row length (0 to RT_MAX_HITS is checked by the query)
+bool parse_overlap(const char* s, float out[6], uint32_t& k) {
+  int n = 0;
+  for (const char* q = s;; ++n) {
+    char* end = nullptr;
+    if (n == 6) {
+      if (*q == '-' || *q == '+') return false;
+      const unsigned long kk = std::strtoul(q, &end, 10);
+      if (end == q || *end != 0) return false;
+      k = static_cast<uint32_t>(kk);
+      return true;
+    }
+    const float f = std::strtof(q, &end);
+    if (end == q) return false;
+    out[n] = f;
+    if (*end == 0) return n == 5;
+    if (*end != ',') return false;
+    q = end + 1;
+  }
+}
+
 // what follows --nearest is the point of a k-nearest query (a number), not the next option
 bool looks_like_number(const char* s) {
   if (*s == '+' || *s == '-') ++s;
@@ -152,8 +175,10 @@ void usage() {
             "       [--exposure X,Y,Z,NX,NY,NZ[,R[,K]]] (prints `exposure mask open K`: which of K (1 to 64, default 64) cosine-weighted\n"
             "                      hemisphere directions about the normal NX,NY,NZ (used as given) are open from the point X,Y,Z over\n"
             "                      [1e-3, R] -- the mask in hex, bit j = direction j, and their count)\n"
+            "       [--overlap X0,Y0,Z0,X1,Y1,Z1[,K]] (prints `overlap count`, the number of primitives that touch the box with the\n"
+            "                      corners X0,Y0,Z0 and X1,Y1,Z1, then one line `prim` for each of the K lowest, default 8)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
-            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --focus through the scene's BVH instead of the scan)");
+            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --focus through the scene's BVH instead of the scan)");
 }
 
 }  // namespace
@@ -193,6 +218,10 @@ int main(int argc, char** argv) {
       a.knn = true;
     }
     else if (k == "--nearest") a.nearest = true;
+    else if (k == "--overlap") {
+      if (!parse_overlap(next("--overlap"), a.overlap_b, a.overlap_k)) { std::fprintf(stderr, "--overlap wants X0,Y0,Z0,X1,Y1,Z1[,K]\n"); return 2; }
+      a.overlap = true;
+    }
     else if (k == "--accel") a.accel = true;
     else if (k == "--pick" || k == "--focus") {
       const bool pk = k == "--pick";
@@ -343,6 +372,18 @@ int main(int argc, char** argv) {
     for (uint32_t j = 0; j < counts[0]; ++j)
       std::printf("%d %.9g %.9g %.9g\n", hits[j].prim, static_cast<double>(std::sqrt(hits[j].t)), static_cast<double>(hits[j].u),
                   static_cast<double>(hits[j].v));
+  }
+  if (a.overlap) {
+    const float* b = a.overlap_b;
+    const std::vector<float> boxes = {b[0], b[1], b[2], 0.0f, b[3], b[4], b[5], 0.0f};
+    std::vector<int32_t> prims;
+    std::vector<uint32_t> counts;
+    if (!tracer.Overlap(boxes, a.overlap_k, prims, counts)) {
+      std::fprintf(stderr, "rt_cli: --overlap: %s\n", a.overlap_k > RT_MAX_HITS ? "K out of range" : tracer.LastError().c_str());
+      return 1;
+    }
+    std::printf("overlap %u\n", counts[0]);
+    for (uint32_t j = 0; j < a.overlap_k && j < counts[0]; ++j) std::printf("%d\n", prims[j]);
   }
   if (a.focus) {
     float focal = 0.0f;
