@@ -228,35 +228,23 @@ __global__ __launch_bounds__(64) void allhits_bvh_kernel(const TraceParams p, co
   allhits_store<FMA, CAP>(p, o, d, lt, lp, max_hits, hits + i * max_hits, counts + i);
 }
 
-uint32_t allhits_lds_bytes(uint32_t n_tris) {
-  return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
-}
-
-hipError_t launch_allhits(const TraceParams& p, bool fma, uint32_t n, const float* segs, uint32_t max_hits, float4* hits,
-                          uint32_t* counts, hipStream_t st) {
+// CAP = 4 for max_hits 1 .. 4, else 16, in both forms
+hipError_t launch_allhits(const TraceParams& p, const BvhParams* b, bool fma, uint32_t n, const float* segs, uint32_t max_hits,
+                          float4* hits, uint32_t* counts, hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (max_hits == 0u || max_hits > kAllHitsMax || segs == nullptr || hits == nullptr || counts == nullptr) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 255u) / 256u));
-  const size_t lds = allhits_lds_bytes(p.n_tris);
   const float4* const s4 = reinterpret_cast<const float4*>(segs);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, n, s4, max_hits, hits, counts); };
-  if (fma) { if (max_hits <= 4u) go(allhits_kernel<true, 4>); else go(allhits_kernel<true, 16>); }
-  else { if (max_hits <= 4u) go(allhits_kernel<false, 4>); else go(allhits_kernel<false, 16>); }
-  return hipGetLastError();
-}
-
-hipError_t launch_allhits_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint32_t max_hits,
-                              float4* hits, uint32_t* counts, hipStream_t st) {
-  if (n == 0u) return hipSuccess;
-  if (max_hits == 0u || max_hits > kAllHitsMax || segs == nullptr || hits == nullptr || counts == nullptr) return hipErrorInvalidValue;
-  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, true);
-  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
-  const float4* const s4 = reinterpret_cast<const float4*>(segs);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), lds, st, p, b, n, s4, max_hits, hits, counts); };
-  if (fma) { if (max_hits <= 4u) go(allhits_bvh_kernel<true, 4>); else go(allhits_bvh_kernel<true, 16>); }
-  else { if (max_hits <= 4u) go(allhits_bvh_kernel<false, 4>); else go(allhits_bvh_kernel<false, 16>); }
-  return hipGetLastError();
+  const bool small = max_hits <= 4u;
+  if (b != nullptr) {                                              // one wave per block, lane = ray, keyed stack entries
+    const uint32_t lds = bvh_stack_lds_bytes(b->stack_cap, 64u, true);
+    if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
+    const auto walk = fma ? (small ? allhits_bvh_kernel<true, 4> : allhits_bvh_kernel<true, 16>)
+                          : (small ? allhits_bvh_kernel<false, 4> : allhits_bvh_kernel<false, 16>);
+    return launch_blocks(walk, n, 64u, 64u, lds, st, p, *b, n, s4, max_hits, hits, counts);
+  }
+  const auto scan = fma ? (small ? allhits_kernel<true, 4> : allhits_kernel<true, 16>)
+                        : (small ? allhits_kernel<false, 4> : allhits_kernel<false, 16>);
+  return launch_blocks(scan, n, 256u, 256u, query_chunk_lds_bytes(p.n_tris), st, p, n, s4, max_hits, hits, counts);
 }
 
 }  // namespace rtk

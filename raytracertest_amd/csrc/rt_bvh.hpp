@@ -172,16 +172,20 @@ __global__ __launch_bounds__(64) void query_bvh_kernel(const TraceParams p, cons
   }
 }
 
-hipError_t launch_query_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* rays, const uint32_t* pixels,
-                            float* rays_out, float4* hits, hipStream_t st) {
+// the ray query's one launch (rt_query.hpp's query_kernel is the scan: it is launched from here, where both kernels are seen)
+hipError_t launch_query(const TraceParams& p, const BvhParams* b, bool fma, int K, uint32_t n, const float* rays, const uint32_t* pixels,
+                        float* rays_out, float4* hits, hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (hits == nullptr || (rays == nullptr && pixels == nullptr)) return hipErrorInvalidValue;
-  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, true);
-  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
-  if (fma) hipLaunchKernelGGL(query_bvh_kernel<true>, grid, dim3(64), lds, st, p, b, n, rays, pixels, rays_out, hits);
-  else hipLaunchKernelGGL(query_bvh_kernel<false>, grid, dim3(64), lds, st, p, b, n, rays, pixels, rays_out, hits);
-  return hipGetLastError();
+  if (b != nullptr) {                                              // one wave per block, lane = ray, keyed stack entries
+    const uint32_t lds = bvh_stack_lds_bytes(b->stack_cap, 64u, true);
+    if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
+    return launch_blocks(fma ? query_bvh_kernel<true> : query_bvh_kernel<false>, n, 64u, 64u, lds, st, p, *b, n, rays, pixels, rays_out, hits);
+  }
+  if (K != 1 && K != 2 && K != 4) return hipErrorInvalidValue;
+  const auto kern = fma ? (K == 1 ? query_kernel<true, 1> : K == 2 ? query_kernel<true, 2> : query_kernel<true, 4>)
+                        : (K == 1 ? query_kernel<false, 1> : K == 2 ? query_kernel<false, 2> : query_kernel<false, 4>);
+  return launch_blocks(kern, n, 256u * K, 256u, query_lds_bytes(p.n_tris, K), st, p, n, rays, pixels, rays_out, hits);
 }
 
 }  // namespace rtk

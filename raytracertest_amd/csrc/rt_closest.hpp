@@ -227,27 +227,17 @@ __global__ __launch_bounds__(64) void closest_bvh_kernel(const TraceParams p, co
   hits[i] = closest_finish(p, pt, best, best_i);
 }
 
-uint32_t closest_lds_bytes(uint32_t n_tris) {
-  return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
-}
-
-hipError_t launch_closest(const TraceParams& p, uint32_t n, const float* pts, float4* hits, hipStream_t st) {
+hipError_t launch_closest(const TraceParams& p, const BvhParams* b, float rho_c, uint32_t n, const float* pts, float4* hits,
+                          hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (pts == nullptr || hits == nullptr) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 255u) / 256u));
-  hipLaunchKernelGGL(closest_kernel, grid, dim3(256), closest_lds_bytes(p.n_tris), st, p, n, reinterpret_cast<const float4*>(pts), hits);
-  return hipGetLastError();
-}
-
-hipError_t launch_closest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, float4* hits,
-                              hipStream_t st) {
-  if (n == 0u) return hipSuccess;
-  if (pts == nullptr || hits == nullptr) return hipErrorInvalidValue;
-  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, true);
-  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
-  hipLaunchKernelGGL(closest_bvh_kernel, grid, dim3(64), lds, st, p, b, rho_c, n, reinterpret_cast<const float4*>(pts), hits);
-  return hipGetLastError();
+  const float4* const p4 = reinterpret_cast<const float4*>(pts);
+  if (b != nullptr) {                                              // one wave per block, lane = point, keyed stack entries
+    const uint32_t lds = bvh_stack_lds_bytes(b->stack_cap, 64u, true);
+    if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
+    return launch_blocks(closest_bvh_kernel, n, 64u, 64u, lds, st, p, *b, rho_c, n, p4, hits);
+  }
+  return launch_blocks(closest_kernel, n, 256u, 256u, query_chunk_lds_bytes(p.n_tris), st, p, n, p4, hits);
 }
 
 }  // namespace rtk

@@ -168,43 +168,27 @@ void exposure_rays_host(size_t n, const float* points, const float* dirs, uint32
   }
 }
 
-uint32_t exposure_lds_bytes(uint32_t n_tris) {
-  return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
-}
-
 // the launch functions' own guard (the entry points have checked the same rules with an error text: rt_query_api.hpp)
 static bool exposure_launch_ok(const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags, const void* out) {
   return points != nullptr && dirs != nullptr && out != nullptr && n_dirs != 0u && n_dirs <= kExposureMaxDirs && (flags & ~kExposureWorld) == 0u;
 }
 
-hipError_t launch_exposure(const TraceParams& p, bool fma, uint32_t n, const float* points, const float* dirs, uint32_t n_dirs,
-                           uint32_t flags, uint64_t* masks, hipStream_t st) {
+// four points (waves) to a 256-thread block in both forms; the walk's stacks at stride 256, the reference alone
+hipError_t launch_exposure(const TraceParams& p, const BvhParams* b, bool fma, uint32_t n, const float* points, const float* dirs,
+                           uint32_t n_dirs, uint32_t flags, uint64_t* masks, hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (!exposure_launch_ok(points, dirs, n_dirs, flags, masks)) return hipErrorInvalidValue;
-  const uint32_t lds = exposure_lds_bytes(p.n_tris);
+  const float4* const p4 = reinterpret_cast<const float4*>(points);
+  const float4* const d4 = reinterpret_cast<const float4*>(dirs);
+  unsigned long long* const m = reinterpret_cast<unsigned long long*>(masks);
+  if (b != nullptr) {
+    const uint32_t lds = bvh_stack_lds_bytes(b->stack_cap, 256u, false);
+    if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
+    return launch_blocks(fma ? exposure_bvh_kernel<true> : exposure_bvh_kernel<false>, n, 4u, 256u, lds, st, p, *b, n, p4, d4, n_dirs, flags, m);
+  }
+  const uint32_t lds = query_chunk_lds_bytes(p.n_tris);
   if (lds > 65536u) return hipErrorInvalidValue;                   // (kQueryChunk records are 36 KiB)
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 3u) / 4u));
-  const float4* const p4 = reinterpret_cast<const float4*>(points);
-  const float4* const d4 = reinterpret_cast<const float4*>(dirs);
-  unsigned long long* const m = reinterpret_cast<unsigned long long*>(masks);
-  if (fma) hipLaunchKernelGGL(exposure_kernel<true>, grid, dim3(256), lds, st, p, n, p4, d4, n_dirs, flags, m);
-  else hipLaunchKernelGGL(exposure_kernel<false>, grid, dim3(256), lds, st, p, n, p4, d4, n_dirs, flags, m);
-  return hipGetLastError();
-}
-
-hipError_t launch_exposure_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* points, const float* dirs,
-                               uint32_t n_dirs, uint32_t flags, uint64_t* masks, hipStream_t st) {
-  if (n == 0u) return hipSuccess;
-  if (!exposure_launch_ok(points, dirs, n_dirs, flags, masks)) return hipErrorInvalidValue;
-  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 256u, false);
-  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 3u) / 4u));
-  const float4* const p4 = reinterpret_cast<const float4*>(points);
-  const float4* const d4 = reinterpret_cast<const float4*>(dirs);
-  unsigned long long* const m = reinterpret_cast<unsigned long long*>(masks);
-  if (fma) hipLaunchKernelGGL(exposure_bvh_kernel<true>, grid, dim3(256), lds, st, p, b, n, p4, d4, n_dirs, flags, m);
-  else hipLaunchKernelGGL(exposure_bvh_kernel<false>, grid, dim3(256), lds, st, p, b, n, p4, d4, n_dirs, flags, m);
-  return hipGetLastError();
+  return launch_blocks(fma ? exposure_kernel<true> : exposure_kernel<false>, n, 4u, 256u, lds, st, p, n, p4, d4, n_dirs, flags, m);
 }
 
 hipError_t launch_exposure_rays(uint32_t n, const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags, float* segs,

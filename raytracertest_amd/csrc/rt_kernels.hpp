@@ -146,16 +146,12 @@ hipError_t launch_trace(const TraceParams& p, bool fma, bool filter, TracePath p
 int trace_occupancy(int K, size_t lds);
 hipError_t launch_convert(const float4* render, uint32_t count, uint32_t* image, uint32_t npix, hipStream_t st);
 
-// Ray queries (rt_query.hpp): n rays {origin xyz, direction xyz} -- or, when `pixels` is not null, the pinhole rays of n
-// full-image (x, y) pairs, also written to rays_out when that is not null -- against p's scene under p.flags' hit rule; hits[i] =
-// {t, u, v, bits of the int32 primitive}.  K in {1, 2, 4} rays per lane.
-uint32_t query_lds_bytes(uint32_t n_tris, int K);
-hipError_t launch_query(const TraceParams& p, bool fma, int K, uint32_t n, const float* rays, const uint32_t* pixels,
-                        float* rays_out, float4* hits, hipStream_t st);
-
-// The same through the scene's bounding volume hierarchy (rt_bvh.hpp; the tree: rt_bvh_host.hpp), one ray per lane.
+// The queries below have one launch function each: b == nullptr is the scan of the staged triangles (256-thread blocks), otherwise
+// the walk of the tree *b (rt_bvh_walk.hpp; one element per lane).  An argument only one form reads is ignored by the other.  n == 0
+// launches nothing; a null array, a K or max_hits outside its range or a stack beyond 64 KiB of LDS is hipErrorInvalidValue.
 #define RT_BVH_RHO 0.00390625f      // 2^-8: DESIGN.md 4.3b derives it
 
+// the scene's bounding volume hierarchy as the walks take it (the tree: rt_bvh_host.hpp)
 struct BvhParams {
   const float4* nodes;      // 8 float4 per node
   const float4* records;    // 3 float4 per record: (e2.xyz, e1.x), (e1.yz, v0.xy), (v0.z, upload index, 0, 0)
@@ -167,27 +163,26 @@ struct BvhParams {
 };
 // the dynamic LDS of the walks' stacks (rt_bvh_walk.hpp): stride lanes per block, 8-byte keyed or 4-byte entries
 uint32_t bvh_stack_lds_bytes(uint32_t stack_cap, uint32_t stride, bool keyed);
-hipError_t launch_query_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* rays, const uint32_t* pixels,
-                            float* rays_out, float4* hits, hipStream_t st);
+
+// Ray queries (rt_query.hpp, rt_bvh.hpp): n rays {origin xyz, direction xyz} -- or, when `pixels` is not null, the pinhole rays of n
+// full-image (x, y) pairs, also written to rays_out when that is not null -- against p's scene under p.flags' hit rule; hits[i] =
+// {t, u, v, bits of the int32 primitive}.  The scan with K in {1, 2, 4} rays per lane, or the walk, one ray per lane (K not read).
+hipError_t launch_query(const TraceParams& p, const BvhParams* b, bool fma, int K, uint32_t n, const float* rays, const uint32_t* pixels,
+                        float* rays_out, float4* hits, hipStream_t st);
 
 // The visibility query (rt_occluded.hpp): n segments {origin xyz, direction xyz, tmin, tmax}, 16-byte aligned; occluded[i] = 1
 // when some primitive of p's scene is hit by ray i with tmin <= t <= tmax (closed, plain fp32 comparisons), else 0.  p.flags'
-// hit rule plays no part.  The scan with K in {1, 2, 4} rays per lane, or the any-hit walk of the tree, one ray per lane.
-uint32_t occluded_lds_bytes(uint32_t n_tris);
-hipError_t launch_occluded(const TraceParams& p, bool fma, int K, uint32_t n, const float* segs, uint8_t* occluded, hipStream_t st);
-hipError_t launch_occluded_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint8_t* occluded,
-                               hipStream_t st);
+// hit rule plays no part.  The scan with K in {1, 2, 4} rays per lane, or the any-hit walk, one ray per lane (K not read).
+hipError_t launch_occluded(const TraceParams& p, const BvhParams* b, bool fma, int K, uint32_t n, const float* segs, uint8_t* occluded,
+                           hipStream_t st);
 
 // The exposure query (rt_exposure.hpp): n points {origin xyz, normal xyz, tmin, tmax} and a table of n_dirs (1 .. 64) directions
 // {x, y, z, -}, both 16-byte aligned; bit j of masks[i] (8-byte aligned) = 1 when launch_occluded would answer 0 for the segment
 // {origin_i, d_ij, tmin_i, tmax_i}, d_ij = direction j in the frame of normal i (flags = 0) or as given (flags = 1); bits >= n_dirs
 // are 0.  One wave per point, one lane per direction, in both forms.  launch_exposure_rays / exposure_rays_host: the n * n_dirs
 // segments themselves, point-major, from the same function (debug).
-uint32_t exposure_lds_bytes(uint32_t n_tris);
-hipError_t launch_exposure(const TraceParams& p, bool fma, uint32_t n, const float* points, const float* dirs, uint32_t n_dirs,
-                           uint32_t flags, uint64_t* masks, hipStream_t st);
-hipError_t launch_exposure_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* points, const float* dirs,
-                               uint32_t n_dirs, uint32_t flags, uint64_t* masks, hipStream_t st);
+hipError_t launch_exposure(const TraceParams& p, const BvhParams* b, bool fma, uint32_t n, const float* points, const float* dirs,
+                           uint32_t n_dirs, uint32_t flags, uint64_t* masks, hipStream_t st);
 hipError_t launch_exposure_rays(uint32_t n, const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags, float* segs,
                                 hipStream_t st);
 void exposure_rays_host(size_t n, const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags, float* segs);
@@ -195,39 +190,28 @@ void exposure_rays_host(size_t n, const float* points, const float* dirs, uint32
 // The all-hits query (rt_allhits.hpp): the same segments; row i of hits (max_hits records {t, u, v, bits of the int32 primitive},
 // 16-byte aligned) holds the ray's first counts[i] <= max_hits in-interval hits in ascending (t, prim) order, then records
 // {0, 0, 0, -1}.  1 <= max_hits <= 16; one ray per lane in both forms.
-uint32_t allhits_lds_bytes(uint32_t n_tris);
-hipError_t launch_allhits(const TraceParams& p, bool fma, uint32_t n, const float* segs, uint32_t max_hits, float4* hits,
-                          uint32_t* counts, hipStream_t st);
-hipError_t launch_allhits_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint32_t max_hits,
-                              float4* hits, uint32_t* counts, hipStream_t st);
+hipError_t launch_allhits(const TraceParams& p, const BvhParams* b, bool fma, uint32_t n, const float* segs, uint32_t max_hits,
+                          float4* hits, uint32_t* counts, hipStream_t st);
 
 // The point query (rt_closest.hpp): n points {x, y, z, d2max}, 16-byte aligned; hits[i] = {squared distance, u, v, bits of the
 // int32 primitive} of the nearest candidate with t <= d2max, smallest (t, prim), or {0, 0, 0, -1}.  One arithmetic for both
-// math modes; one point per lane in both forms.  rho_c: RT_CLOSEST_RHO x the tracer's slack.
+// math modes; one point per lane in both forms.  rho_c: RT_CLOSEST_RHO x the tracer's slack (the walk's; the scan does not read it).
 #define RT_CLOSEST_RHO 3.814697265625e-06f      // 2^-18: DESIGN.md 4.3f derives it
-uint32_t closest_lds_bytes(uint32_t n_tris);
-hipError_t launch_closest(const TraceParams& p, uint32_t n, const float* pts, float4* hits, hipStream_t st);
-hipError_t launch_closest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, float4* hits,
-                              hipStream_t st);
+hipError_t launch_closest(const TraceParams& p, const BvhParams* b, float rho_c, uint32_t n, const float* pts, float4* hits,
+                          hipStream_t st);
 
-// The k-nearest point query (rt_nearest.hpp): the same points; after (or nullptr) n cursor records, 16-byte aligned; row i of
-// hits (max_hits records) holds the point's counts[i] <= max_hits nearest accepted candidates behind its cursor in ascending
+// The k-nearest point query (rt_nearest.hpp): the same points and rho_c; after (or nullptr) n cursor records, 16-byte aligned; row
+// i of hits (max_hits records) holds the point's counts[i] <= max_hits nearest accepted candidates behind its cursor in ascending
 // (t, prim) order, then records {0, 0, 0, -1}.  1 <= max_hits <= 16; one point per lane in both forms.
-uint32_t nearest_lds_bytes(uint32_t n_tris);
-hipError_t launch_nearest(const TraceParams& p, uint32_t n, const float* pts, const float4* after, uint32_t max_hits, float4* hits,
-                          uint32_t* counts, hipStream_t st);
-hipError_t launch_nearest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, const float4* after,
-                              uint32_t max_hits, float4* hits, uint32_t* counts, hipStream_t st);
+hipError_t launch_nearest(const TraceParams& p, const BvhParams* b, float rho_c, uint32_t n, const float* pts, const float4* after,
+                          uint32_t max_hits, float4* hits, uint32_t* counts, hipStream_t st);
 
 // The region query (rt_overlap.hpp): n boxes {lo xyz, -, hi xyz, -}, 16-byte aligned; after (or nullptr) n int32 cursors; row i
 // of prims (max_hits int32) holds the min(counts[i], max_hits) lowest accepted prims behind the cursor in ascending order, then
 // -1; counts[i] is the total, not capped.  0 <= max_hits <= 16 (0: prims may be nullptr); one arithmetic for both math modes;
-// one box per lane in both forms.  The tree form reads neither b.rho nor a slack: its prune is exact.
-uint32_t overlap_lds_bytes(uint32_t n_tris);
-hipError_t launch_overlap(const TraceParams& p, uint32_t n, const float* boxes, const int* after, uint32_t max_hits, int* prims,
-                          uint32_t* counts, hipStream_t st);
-hipError_t launch_overlap_bvh(const TraceParams& p, const BvhParams& b, uint32_t n, const float* boxes, const int* after,
-                              uint32_t max_hits, int* prims, uint32_t* counts, hipStream_t st);
+// one box per lane in both forms.  The tree form reads neither b->rho nor a slack: its prune is exact.
+hipError_t launch_overlap(const TraceParams& p, const BvhParams* b, uint32_t n, const float* boxes, const int* after, uint32_t max_hits,
+                          int* prims, uint32_t* counts, hipStream_t st);
 
 // The side post-pass (rt_sides.hpp): n points, n * per_point records of them (hits, as the point queries wrote them), the feature
 // table (7 float4 per triangle, rt_features_host.hpp) -> n * per_point {s, feature} pairs of 8 bytes.

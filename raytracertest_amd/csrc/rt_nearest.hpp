@@ -234,33 +234,20 @@ __global__ __launch_bounds__(64) void nearest_bvh_kernel(const TraceParams p, co
   nearest_store<CAP>(p, pt, lt, lp, max_hits, hits + i * max_hits, counts + i);
 }
 
-uint32_t nearest_lds_bytes(uint32_t n_tris) {
-  return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
-}
-
-hipError_t launch_nearest(const TraceParams& p, uint32_t n, const float* pts, const float4* after, uint32_t max_hits, float4* hits,
-                          uint32_t* counts, hipStream_t st) {
+// CAP = 4 for max_hits 1 .. 4, else 16, in both forms
+hipError_t launch_nearest(const TraceParams& p, const BvhParams* b, float rho_c, uint32_t n, const float* pts, const float4* after,
+                          uint32_t max_hits, float4* hits, uint32_t* counts, hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (max_hits == 0u || max_hits > kAllHitsMax || pts == nullptr || hits == nullptr || counts == nullptr) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 255u) / 256u));
-  const size_t lds = nearest_lds_bytes(p.n_tris);
   const float4* const p4 = reinterpret_cast<const float4*>(pts);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, n, p4, after, max_hits, hits, counts); };
-  if (max_hits <= 4u) go(nearest_kernel<4>); else go(nearest_kernel<16>);
-  return hipGetLastError();
-}
-
-hipError_t launch_nearest_bvh(const TraceParams& p, const BvhParams& b, float rho_c, uint32_t n, const float* pts, const float4* after,
-                              uint32_t max_hits, float4* hits, uint32_t* counts, hipStream_t st) {
-  if (n == 0u) return hipSuccess;
-  if (max_hits == 0u || max_hits > kAllHitsMax || pts == nullptr || hits == nullptr || counts == nullptr) return hipErrorInvalidValue;
-  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, true);
-  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
-  const float4* const p4 = reinterpret_cast<const float4*>(pts);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), lds, st, p, b, rho_c, n, p4, after, max_hits, hits, counts); };
-  if (max_hits <= 4u) go(nearest_bvh_kernel<4>); else go(nearest_bvh_kernel<16>);
-  return hipGetLastError();
+  if (b != nullptr) {                                              // one wave per block, lane = point, keyed stack entries
+    const uint32_t lds = bvh_stack_lds_bytes(b->stack_cap, 64u, true);
+    if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
+    return launch_blocks(max_hits <= 4u ? nearest_bvh_kernel<4> : nearest_bvh_kernel<16>, n, 64u, 64u, lds, st, p, *b, rho_c, n, p4, after,
+                         max_hits, hits, counts);
+  }
+  return launch_blocks(max_hits <= 4u ? nearest_kernel<4> : nearest_kernel<16>, n, 256u, 256u, query_chunk_lds_bytes(p.n_tris), st, p, n, p4,
+                       after, max_hits, hits, counts);
 }
 
 }  // namespace rtk

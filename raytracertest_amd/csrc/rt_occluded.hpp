@@ -210,36 +210,20 @@ __global__ __launch_bounds__(64) void occluded_bvh_kernel(const TraceParams p, c
   occluded[i] = done ? 1u : 0u;
 }
 
-uint32_t occluded_lds_bytes(uint32_t n_tris) {
-  return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
-}
-
-hipError_t launch_occluded(const TraceParams& p, bool fma, int K, uint32_t n, const float* segs, uint8_t* occluded, hipStream_t st) {
-  if (n == 0u) return hipSuccess;
-  if ((K != 1 && K != 2 && K != 4) || segs == nullptr || occluded == nullptr) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 256u * K - 1u) / (256u * K)));
-  const size_t lds = occluded_lds_bytes(p.n_tris);
-  const float4* const s4 = reinterpret_cast<const float4*>(segs);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, n, s4, occluded); };
-  if (fma) {
-    if (K == 1) go(occluded_kernel<true, 1>); else if (K == 2) go(occluded_kernel<true, 2>); else go(occluded_kernel<true, 4>);
-  } else {
-    if (K == 1) go(occluded_kernel<false, 1>); else if (K == 2) go(occluded_kernel<false, 2>); else go(occluded_kernel<false, 4>);
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_occluded_bvh(const TraceParams& p, const BvhParams& b, bool fma, uint32_t n, const float* segs, uint8_t* occluded,
-                               hipStream_t st) {
+hipError_t launch_occluded(const TraceParams& p, const BvhParams* b, bool fma, int K, uint32_t n, const float* segs, uint8_t* occluded,
+                           hipStream_t st) {
   if (n == 0u) return hipSuccess;
   if (segs == nullptr || occluded == nullptr) return hipErrorInvalidValue;
-  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, false);
-  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
   const float4* const s4 = reinterpret_cast<const float4*>(segs);
-  if (fma) hipLaunchKernelGGL(occluded_bvh_kernel<true>, grid, dim3(64), lds, st, p, b, n, s4, occluded);
-  else hipLaunchKernelGGL(occluded_bvh_kernel<false>, grid, dim3(64), lds, st, p, b, n, s4, occluded);
-  return hipGetLastError();
+  if (b != nullptr) {                                              // one wave per block, lane = ray, the reference alone on the stack
+    const uint32_t lds = bvh_stack_lds_bytes(b->stack_cap, 64u, false);
+    if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
+    return launch_blocks(fma ? occluded_bvh_kernel<true> : occluded_bvh_kernel<false>, n, 64u, 64u, lds, st, p, *b, n, s4, occluded);
+  }
+  if (K != 1 && K != 2 && K != 4) return hipErrorInvalidValue;
+  const auto kern = fma ? (K == 1 ? occluded_kernel<true, 1> : K == 2 ? occluded_kernel<true, 2> : occluded_kernel<true, 4>)
+                        : (K == 1 ? occluded_kernel<false, 1> : K == 2 ? occluded_kernel<false, 2> : occluded_kernel<false, 4>);
+  return launch_blocks(kern, n, 256u * K, 256u, query_chunk_lds_bytes(p.n_tris), st, p, n, s4, occluded);
 }
 
 }  // namespace rtk

@@ -257,37 +257,20 @@ __global__ __launch_bounds__(64) void overlap_bvh_kernel(const TraceParams p, co
   L.store_tree(max_hits, prims + i * max_hits, counts + i);
 }
 
-uint32_t overlap_lds_bytes(uint32_t n_tris) {
-  return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
-}
-
-static bool overlap_launch_ok(const float* boxes, uint32_t max_hits, const int* prims, const uint32_t* counts) {
-  return max_hits <= kAllHitsMax && boxes != nullptr && counts != nullptr && (prims != nullptr || max_hits == 0u);
-}
-
-hipError_t launch_overlap(const TraceParams& p, uint32_t n, const float* boxes, const int* after, uint32_t max_hits, int* prims,
-                          uint32_t* counts, hipStream_t st) {
+// CAP = 0 for max_hits 0, 4 for 1 .. 4, else 16, in both forms
+hipError_t launch_overlap(const TraceParams& p, const BvhParams* b, uint32_t n, const float* boxes, const int* after, uint32_t max_hits,
+                          int* prims, uint32_t* counts, hipStream_t st) {
   if (n == 0u) return hipSuccess;
-  if (!overlap_launch_ok(boxes, max_hits, prims, counts)) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 255u) / 256u));
-  const size_t lds = overlap_lds_bytes(p.n_tris);
+  if (max_hits > kAllHitsMax || boxes == nullptr || counts == nullptr || (prims == nullptr && max_hits != 0u)) return hipErrorInvalidValue;
   const float4* const b4 = reinterpret_cast<const float4*>(boxes);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, n, b4, after, max_hits, prims, counts); };
-  if (max_hits == 0u) go(overlap_kernel<0>); else if (max_hits <= 4u) go(overlap_kernel<4>); else go(overlap_kernel<16>);
-  return hipGetLastError();
-}
-
-hipError_t launch_overlap_bvh(const TraceParams& p, const BvhParams& b, uint32_t n, const float* boxes, const int* after,
-                              uint32_t max_hits, int* prims, uint32_t* counts, hipStream_t st) {
-  if (n == 0u) return hipSuccess;
-  if (!overlap_launch_ok(boxes, max_hits, prims, counts)) return hipErrorInvalidValue;
-  const uint32_t lds = bvh_stack_lds_bytes(b.stack_cap, 64u, false);
-  if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u));
-  const float4* const b4 = reinterpret_cast<const float4*>(boxes);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), lds, st, p, b, n, b4, after, max_hits, prims, counts); };
-  if (max_hits == 0u) go(overlap_bvh_kernel<0>); else if (max_hits <= 4u) go(overlap_bvh_kernel<4>); else go(overlap_bvh_kernel<16>);
-  return hipGetLastError();
+  if (b != nullptr) {                                              // one wave per block, lane = box, the reference alone on the stack
+    const uint32_t lds = bvh_stack_lds_bytes(b->stack_cap, 64u, false);
+    if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
+    const auto walk = max_hits == 0u ? overlap_bvh_kernel<0> : max_hits <= 4u ? overlap_bvh_kernel<4> : overlap_bvh_kernel<16>;
+    return launch_blocks(walk, n, 64u, 64u, lds, st, p, *b, n, b4, after, max_hits, prims, counts);
+  }
+  const auto scan = max_hits == 0u ? overlap_kernel<0> : max_hits <= 4u ? overlap_kernel<4> : overlap_kernel<16>;
+  return launch_blocks(scan, n, 256u, 256u, query_chunk_lds_bytes(p.n_tris), st, p, n, b4, after, max_hits, prims, counts);
 }
 
 }  // namespace rtk

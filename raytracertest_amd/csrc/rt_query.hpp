@@ -123,24 +123,28 @@ __global__ __launch_bounds__(256, 4) void query_kernel(const TraceParams p, uint
   }
 }
 
-uint32_t query_lds_bytes(uint32_t n_tris, int K) {
-  const uint32_t tris = (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
+// What the launch functions of the seven query headers share (host).  Each query has ONE launch function, launch_X(p, b, ...):
+// b == nullptr is the scan, otherwise the walk of *b; it guards its arguments, picks the instantiation and states the launch
+// geometry -- elements per block, threads per block, dynamic LDS -- in its call of launch_blocks.  launch_query is in rt_bvh.hpp.
+
+// the dynamic LDS of a scan kernel's staged chunk: min(n_tris, kQueryChunk) records of 36 bytes
+static uint32_t query_chunk_lds_bytes(uint32_t n_tris) {
+  return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
+}
+
+// query_kernel stages its block's rays (24 bytes each) through the same LDS first
+static uint32_t query_lds_bytes(uint32_t n_tris, int K) {
+  const uint32_t tris = query_chunk_lds_bytes(n_tris);
   const uint32_t rays = 256u * static_cast<uint32_t>(K) * 24u;
   return tris > rays ? tris : rays;
 }
 
-hipError_t launch_query(const TraceParams& p, bool fma, int K, uint32_t n, const float* rays, const uint32_t* pixels,
-                        float* rays_out, float4* hits, hipStream_t st) {
-  if (n == 0u) return hipSuccess;
-  if ((K != 1 && K != 2 && K != 4) || hits == nullptr || (rays == nullptr && pixels == nullptr)) return hipErrorInvalidValue;
-  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + 256u * K - 1u) / (256u * K)));
-  const size_t lds = query_lds_bytes(p.n_tris, K);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, n, rays, pixels, rays_out, hits); };
-  if (fma) {
-    if (K == 1) go(query_kernel<true, 1>); else if (K == 2) go(query_kernel<true, 2>); else go(query_kernel<true, 4>);
-  } else {
-    if (K == 1) go(query_kernel<false, 1>); else if (K == 2) go(query_kernel<false, 2>); else go(query_kernel<false, 4>);
-  }
+// kern(a...) over n > 0 elements, per_block of them to a block of `threads` threads (the grid rounded up in 64 bits)
+template <class... KA, class... A>
+hipError_t launch_blocks(void (*kern)(KA...), uint32_t n, uint32_t per_block, uint32_t threads, size_t lds, hipStream_t st,
+                         const A&... a) {
+  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + per_block - 1u) / per_block));
+  hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, a...);
   return hipGetLastError();
 }
 

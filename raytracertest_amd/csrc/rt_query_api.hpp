@@ -207,16 +207,14 @@ inline float closest_rho(const rt_tracer* t) { return RT_CLOSEST_RHO * (static_c
 inline void enqueue_query(rt_tracer* t, size_t n, const float* rays, const uint32_t* pixels, float* rays_out, float4* hits,
                           hipStream_t st) {
   enqueue_launch(t, st, t->nearest_hit ? rtk::TRACE_NEAREST_HIT : 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return b ? rtk::launch_query_bvh(p, *b, t->fma, static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st)
-             : rtk::launch_query(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st);
+    return rtk::launch_query(p, b, t->fma, query_k(t, n), static_cast<uint32_t>(n), rays, pixels, rays_out, hits, st);
   });
 }
 
 // segments -> one byte per ray.  The hit rule plays no part (an OR over the primitives), so the flags stay 0.
 inline void enqueue_occluded(rt_tracer* t, size_t n, const float* segs, uint8_t* occluded, hipStream_t st) {
   enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return b ? rtk::launch_occluded_bvh(p, *b, t->fma, static_cast<uint32_t>(n), segs, occluded, st)
-             : rtk::launch_occluded(p, t->fma, query_k(t, n), static_cast<uint32_t>(n), segs, occluded, st);
+    return rtk::launch_occluded(p, b, t->fma, query_k(t, n), static_cast<uint32_t>(n), segs, occluded, st);
   });
 }
 
@@ -224,8 +222,7 @@ inline void enqueue_occluded(rt_tracer* t, size_t n, const float* segs, uint8_t*
 inline void enqueue_exposure(rt_tracer* t, size_t n, const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags,
                              uint64_t* masks, hipStream_t st) {
   enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return b ? rtk::launch_exposure_bvh(p, *b, t->fma, static_cast<uint32_t>(n), points, dirs, n_dirs, flags, masks, st)
-             : rtk::launch_exposure(p, t->fma, static_cast<uint32_t>(n), points, dirs, n_dirs, flags, masks, st);
+    return rtk::launch_exposure(p, b, t->fma, static_cast<uint32_t>(n), points, dirs, n_dirs, flags, masks, st);
   });
 }
 
@@ -243,8 +240,7 @@ inline bool exposure_args_ok(rt_tracer* t, const char* who, uint32_t n_dirs, uin
 inline void enqueue_intersect_all(rt_tracer* t, size_t n, const float* segs, uint32_t max_hits, float4* hits, uint32_t* counts,
                                   hipStream_t st) {
   enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return b ? rtk::launch_allhits_bvh(p, *b, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st)
-             : rtk::launch_allhits(p, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st);
+    return rtk::launch_allhits(p, b, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st);
   });
 }
 
@@ -252,8 +248,7 @@ inline void enqueue_intersect_all(rt_tracer* t, size_t n, const float* segs, uin
 // queries' (ensure_query_tree, so RT_ACCEL_REFIT applies).
 inline void enqueue_closest(rt_tracer* t, size_t n, const float* pts, float4* hits, hipStream_t st) {
   enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return b ? rtk::launch_closest_bvh(p, *b, closest_rho(t), static_cast<uint32_t>(n), pts, hits, st)
-             : rtk::launch_closest(p, static_cast<uint32_t>(n), pts, hits, st);
+    return rtk::launch_closest(p, b, closest_rho(t), static_cast<uint32_t>(n), pts, hits, st);
   });
 }
 
@@ -261,8 +256,7 @@ inline void enqueue_closest(rt_tracer* t, size_t n, const float* pts, float4* hi
 inline void enqueue_closest_all(rt_tracer* t, size_t n, const float* pts, const float4* after, uint32_t max_hits, float4* hits,
                                 uint32_t* counts, hipStream_t st) {
   enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return b ? rtk::launch_nearest_bvh(p, *b, closest_rho(t), static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st)
-             : rtk::launch_nearest(p, static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st);
+    return rtk::launch_nearest(p, b, closest_rho(t), static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st);
   });
 }
 
@@ -271,8 +265,7 @@ inline void enqueue_closest_all(rt_tracer* t, size_t n, const float* pts, const 
 inline void enqueue_overlap(rt_tracer* t, size_t n, const float* boxes, const int32_t* after, uint32_t max_hits, int32_t* prims,
                             uint32_t* counts, hipStream_t st) {
   enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return b ? rtk::launch_overlap_bvh(p, *b, static_cast<uint32_t>(n), boxes, after, max_hits, prims, counts, st)
-             : rtk::launch_overlap(p, static_cast<uint32_t>(n), boxes, after, max_hits, prims, counts, st);
+    return rtk::launch_overlap(p, b, static_cast<uint32_t>(n), boxes, after, max_hits, prims, counts, st);
   });
 }
 
