@@ -241,7 +241,7 @@ void rt_dbg_rng_advance_host(uint32_t state[5], uint32_t n, int use_table) { rt_
 int rt_dbg_owed_state(rt_tracer* t, uint64_t out[4]) {
   if (!t || t->mg || !out) return RT_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lk(t->order_mu);
-  out[0] = t->owed_draws; out[1] = t->owing_launches; out[2] = t->settles_enqueued; out[3] = t->settle_tables.size();
+  out[0] = t->debt.owed_draws; out[1] = t->debt.owing_launches; out[2] = t->debt.settles_enqueued; out[3] = t->debt.settle_tables.size();
   return RT_OK;
 }
 

@@ -5,7 +5,7 @@
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
 // calls by api_mu, reads only the scene and a snapshot of the camera (params(), under state_mu), and runs on a stream of its
-// own (stream_q, created by the first query) or on the caller's.  query_done, recorded behind every query, is what the scene
+// own (QueryState::stream_q, created by the first query) or on the caller's.  QueryState::done, recorded behind every query, is what the scene
 // uploads and destroy wait for before they touch the records a query may still read: every launch goes through enqueue_launch,
 // the one place that waits for and records it.  Every entry point is query_call (or, with a check of its own, query_entry):
 // api_mu, a sharded handle forwarded to its first band, else the body under guarded().
@@ -70,61 +70,54 @@ int query_call(rt_tracer* t, Forward&& forward, Body&& body) {
   return query_entry(t, forward, [&] { return guarded(t, body); });
 }
 
-// The host-array entry points' staging buffers, grow-only: n elements of the caller's array into d on `st`, room for n
-// results in d, n results out of d into the caller's array on `st`.
+// The host-array entry points' staging buffers (QueryState::in, ::out), grow-only: n elements of T of the caller's array into
+// d on `st`, room for n results in d, n results out of d into the caller's array on `st`.
 template <class T>
-T* staged_in(DevArray<T>& d, const void* src, size_t n, hipStream_t st) {
-  d.ensure(n);
-  HIP_CHECK(hipMemcpyAsync(d.get(), src, n * sizeof(T), hipMemcpyHostToDevice, st));
-  return d.get();
+T* room(DevArray<unsigned char>& d, size_t n) {
+  d.ensure(n * sizeof(T));
+  return reinterpret_cast<T*>(d.get());
 }
 template <class T>
-T* room(DevArray<T>& d, size_t n) {
-  d.ensure(n);
-  return d.get();
+T* staged_in(DevArray<unsigned char>& d, const void* src, size_t n, hipStream_t st) {
+  HIP_CHECK(hipMemcpyAsync(room<T>(d, n), src, n * sizeof(T), hipMemcpyHostToDevice, st));
+  return reinterpret_cast<T*>(d.get());
 }
 template <class T>
-void staged_out(void* dst, const DevArray<T>& d, size_t n, hipStream_t st) {
+void staged_out(void* dst, const DevArray<unsigned char>& d, size_t n, hipStream_t st) {
   HIP_CHECK(hipMemcpyAsync(dst, d.get(), n * sizeof(T), hipMemcpyDeviceToHost, st));
 }
-
-inline hipStream_t query_stream(rt_tracer* t) {
-  if (!t->stream_q) {
-    int lo = 0, hi = 0;
-    if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo) t->stream_q = Stream(hipStreamNonBlocking, hi);
-    else t->stream_q = Stream(hipStreamNonBlocking);
-  }
-  return t->stream_q;
-}
+// what a host-array entry point starts with: the tracer's device current, the query stream made
+inline hipStream_t host_query_stream(rt_tracer* t) { t->use_device(); return t->queries.stream(); }
 
 // RT_ACCEL_REFIT: the tree of an earlier upload with as many records as the scene has triangles takes the new records and
 // new boxes on the device (rt_refit.hpp), all on the query stream: the gather, one launch per level from the deepest up,
 // the cost, between two events; one 16-byte copy of {flag, cost} and the synchronisation the build has too.  False: a
 // triangle changed between finite and non-finite (the partition rule, rt_bvh_host.hpp) -- the caller builds.
 inline bool refit_query_tree(rt_tracer* t, hipStream_t st) {
-  const uint32_t n_nodes = static_cast<uint32_t>(t->bvh_info[0]), n_always = static_cast<uint32_t>(t->bvh_info[3]);
-  const uint32_t n_leaf = t->bvh_leaf_records, depth = static_cast<uint32_t>(t->bvh_info[2]);
-  t->d_refit_out.ensure(2u);
-  t->h_refit_out.ensure(2u);
-  if (!t->refit_begin) { t->refit_begin = Event::timing(); t->refit_end = Event::timing(); }
-  HIP_CHECK(hipMemsetAsync(t->d_refit_out.get(), 0, 2u * sizeof(uint64_t), st));
-  HIP_CHECK(hipEventRecord(t->refit_begin, st));
-  HIP_CHECK(rtk::launch_refit_gather(t->d_tri.get(), t->d_tri_b.get(), t->n_tris, t->d_bvh_records.get(), n_leaf, n_leaf + n_always,
-                                     reinterpret_cast<uint32_t*>(t->d_refit_out.get()), st));
+  QueryState& q = t->queries;
+  const uint32_t n_nodes = static_cast<uint32_t>(q.bvh_info[0]), n_always = static_cast<uint32_t>(q.bvh_info[3]);
+  const uint32_t n_leaf = q.bvh_leaf_records, depth = static_cast<uint32_t>(q.bvh_info[2]);
+  q.d_refit_out.ensure(2u);
+  q.h_refit_out.ensure(2u);
+  if (!q.refit_begin) { q.refit_begin = Event::timing(); q.refit_end = Event::timing(); }
+  HIP_CHECK(hipMemsetAsync(q.d_refit_out.get(), 0, 2u * sizeof(uint64_t), st));
+  HIP_CHECK(hipEventRecord(q.refit_begin, st));
+  HIP_CHECK(rtk::launch_refit_gather(t->d_tri.get(), t->d_tri_b.get(), t->n_tris, q.d_bvh_records.get(), n_leaf, n_leaf + n_always,
+                                     reinterpret_cast<uint32_t*>(q.d_refit_out.get()), st));
   for (uint32_t l = depth; l-- > 0u;)
-    HIP_CHECK(rtk::launch_refit_level(t->d_bvh_nodes.get(), n_nodes, t->d_bvh_records.get(), n_leaf, t->d_bvh_levels.get() + t->bvh_level_begin[l],
-                                      t->bvh_level_begin[l + 1u] - t->bvh_level_begin[l], st));
-  HIP_CHECK(rtk::launch_refit_cost(t->d_bvh_nodes.get(), n_nodes, reinterpret_cast<double*>(t->d_refit_out.get() + 1), st));
-  HIP_CHECK(hipEventRecord(t->refit_end, st));
-  HIP_CHECK(hipMemcpyAsync(t->h_refit_out.get(), t->d_refit_out.get(), 2u * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(rtk::launch_refit_level(q.d_bvh_nodes.get(), n_nodes, q.d_bvh_records.get(), n_leaf, q.d_bvh_levels.get() + q.bvh_level_begin[l],
+                                      q.bvh_level_begin[l + 1u] - q.bvh_level_begin[l], st));
+  HIP_CHECK(rtk::launch_refit_cost(q.d_bvh_nodes.get(), n_nodes, reinterpret_cast<double*>(q.d_refit_out.get() + 1), st));
+  HIP_CHECK(hipEventRecord(q.refit_end, st));
+  HIP_CHECK(hipMemcpyAsync(q.h_refit_out.get(), q.d_refit_out.get(), 2u * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
-  if (static_cast<uint32_t>(t->h_refit_out.get()[0]) != 0u) { t->refit_fallbacks++; return false; }
+  if (static_cast<uint32_t>(q.h_refit_out.get()[0]) != 0u) { q.refit_fallbacks++; return false; }
   float ms = 0.0f;
-  HIP_CHECK(hipEventElapsedTime(&ms, t->refit_begin, t->refit_end));
-  t->refit_us = static_cast<uint64_t>(ms * 1000.0f + 0.5f);
-  memcpy(&t->bvh_cost, t->h_refit_out.get() + 1, sizeof(double));
-  t->refits++;
-  t->bvh_scene = t->scene_generation;
+  HIP_CHECK(hipEventElapsedTime(&ms, q.refit_begin, q.refit_end));
+  q.refit_us = static_cast<uint64_t>(ms * 1000.0f + 0.5f);
+  memcpy(&q.bvh_cost, q.h_refit_out.get() + 1, sizeof(double));
+  q.refits++;
+  q.bvh_scene = t->scene_generation;
   return true;
 }
 
@@ -134,14 +127,15 @@ inline bool refit_query_tree(rt_tracer* t, hipStream_t st) {
 // tree: they are waited for before its buffers are rewritten.  Under RT_ACCEL_REFIT a tree of the same record count is
 // refitted instead (refit_query_tree).
 inline void ensure_query_tree(rt_tracer* t) {
-  if (t->bvh_valid()) return;
-  const hipStream_t st = query_stream(t);
+  QueryState& q = t->queries;
+  if (q.bvh_valid(t->scene_generation)) return;
+  const hipStream_t st = q.stream();
   t->wait_queries();
   const size_t n = t->n_tris;
   if (n > rtb::kBvhMaxTris) throw HipFail{fmt("RT_QUERY_BVH: %zu triangles (at most %zu)", n, rtb::kBvhMaxTris)};
-  if (t->accel_update == RT_ACCEL_REFIT && t->bvh_built && n != 0u && size_t(t->bvh_leaf_records) + t->bvh_info[3] == n &&
+  if (q.accel_update == RT_ACCEL_REFIT && q.bvh_built && n != 0u && size_t(q.bvh_leaf_records) + q.bvh_info[3] == n &&
       refit_query_tree(t, st)) return;
-  t->bvh_built = false;                                                  // (a failure below leaves no tree to refit)
+  q.bvh_built = false;                                                  // (a failure below leaves no tree to refit)
   std::vector<float> a(n * 8u), b(n);
   if (n != 0u) {
     HIP_CHECK(hipMemcpyAsync(a.data(), t->d_tri.get(), n * 8u * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -150,58 +144,59 @@ inline void ensure_query_tree(rt_tracer* t) {
   }
   const std::vector<float> rec = rtb::records_of_device(a.data(), b.data(), n);
   const rtb::Tree tree = rtb::build(rec.data(), n);
-  t->d_bvh_nodes.ensure(std::max<size_t>(tree.nodes.size(), 1u) * 8u);
-  t->d_bvh_records.ensure(std::max<size_t>(tree.records.size(), 1u) * 3u);
-  t->d_bvh_levels.ensure(std::max<size_t>(tree.level_nodes.size(), 1u));
-  if (!tree.nodes.empty()) HIP_CHECK(hipMemcpyAsync(t->d_bvh_nodes.get(), tree.nodes.data(), tree.nodes.size() * sizeof(rtb::Node), hipMemcpyHostToDevice, st));
-  if (!tree.records.empty()) HIP_CHECK(hipMemcpyAsync(t->d_bvh_records.get(), tree.records.data(), tree.records.size() * sizeof(rtb::Record), hipMemcpyHostToDevice, st));
-  if (!tree.level_nodes.empty()) HIP_CHECK(hipMemcpyAsync(t->d_bvh_levels.get(), tree.level_nodes.data(), tree.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  q.d_bvh_nodes.ensure(std::max<size_t>(tree.nodes.size(), 1u) * 8u);
+  q.d_bvh_records.ensure(std::max<size_t>(tree.records.size(), 1u) * 3u);
+  q.d_bvh_levels.ensure(std::max<size_t>(tree.level_nodes.size(), 1u));
+  if (!tree.nodes.empty()) HIP_CHECK(hipMemcpyAsync(q.d_bvh_nodes.get(), tree.nodes.data(), tree.nodes.size() * sizeof(rtb::Node), hipMemcpyHostToDevice, st));
+  if (!tree.records.empty()) HIP_CHECK(hipMemcpyAsync(q.d_bvh_records.get(), tree.records.data(), tree.records.size() * sizeof(rtb::Record), hipMemcpyHostToDevice, st));
+  if (!tree.level_nodes.empty()) HIP_CHECK(hipMemcpyAsync(q.d_bvh_levels.get(), tree.level_nodes.data(), tree.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   HIP_CHECK(hipStreamSynchronize(st));                                   // (the host vectors go away; a caller's stream may run the query)
-  t->bvh_info[0] = tree.nodes.size(); t->bvh_info[1] = tree.leaves; t->bvh_info[2] = tree.depth; t->bvh_info[3] = tree.always;
-  t->bvh_info[4] = tree.build_us; t->bvh_info[5] = tree.bytes();
-  t->bvh_leaf_records = static_cast<uint32_t>(tree.records.size() - tree.always);
-  t->bvh_level_begin = tree.level_begin;
-  if (t->bvh_level_begin.empty()) t->bvh_level_begin.push_back(0u);
-  t->bvh_cost = t->bvh_cost_built = rtb::tree_cost(tree.nodes);
-  t->refits = 0;
-  t->bvh_scene = t->scene_generation;
-  t->bvh_built = true;
+  q.bvh_info[0] = tree.nodes.size(); q.bvh_info[1] = tree.leaves; q.bvh_info[2] = tree.depth; q.bvh_info[3] = tree.always;
+  q.bvh_info[4] = tree.build_us; q.bvh_info[5] = tree.bytes();
+  q.bvh_leaf_records = static_cast<uint32_t>(tree.records.size() - tree.always);
+  q.bvh_level_begin = tree.level_begin;
+  if (q.bvh_level_begin.empty()) q.bvh_level_begin.push_back(0u);
+  q.bvh_cost = q.bvh_cost_built = rtb::tree_cost(tree.nodes);
+  q.refits = 0;
+  q.bvh_scene = t->scene_generation;
+  q.bvh_built = true;
 }
 
 // the valid tree (ensure_query_tree) as the traversal kernels take it
 inline rtk::BvhParams query_bvh_params(const rt_tracer* t) {
+  const QueryState& q = t->queries;
   rtk::BvhParams b;
-  b.nodes = t->d_bvh_nodes.get(); b.records = t->d_bvh_records.get();
-  b.n_nodes = static_cast<uint32_t>(t->bvh_info[0]); b.n_leaf_records = t->bvh_leaf_records;
-  b.n_always = static_cast<uint32_t>(t->bvh_info[3]);
+  b.nodes = q.d_bvh_nodes.get(); b.records = q.d_bvh_records.get();
+  b.n_nodes = static_cast<uint32_t>(q.bvh_info[0]); b.n_leaf_records = q.bvh_leaf_records;
+  b.n_always = static_cast<uint32_t>(q.bvh_info[3]);
   // (rt_dbg_query_stack_cap can only lower it: the kernels' sp < stack_cap keeps every store inside the LDS sized from it)
-  b.stack_cap = std::min(rtb::stack_capacity(static_cast<uint32_t>(t->bvh_info[2])), t->query_stack_cap);
-  b.rho = RT_BVH_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f);
+  b.stack_cap = std::min(rtb::stack_capacity(static_cast<uint32_t>(q.bvh_info[2])), q.stack_cap);
+  b.rho = RT_BVH_RHO * (static_cast<float>(q.slack_milli) / 1000.0f);
   return b;
 }
 
-// One launch of a query on `st`, behind every earlier query: query_done then covers this one and all before it.  launch(p, b)
+// One launch of a query on `st`, behind every earlier query: QueryState::done then covers this one and all before it.  launch(p, b)
 // gets the launches' camera snapshot and scene with p.flags = flags, and the valid tree under RT_QUERY_BVH when the query
 // walks one (uses_tree), else b = nullptr: the scan.
 template <class Launch>
 void enqueue_launch(rt_tracer* t, hipStream_t st, uint32_t flags, bool uses_tree, Launch&& launch) {
   rtk::TraceParams p = t->params(1);
   p.flags = flags;
-  const bool bvh = uses_tree && t->query_accel == RT_QUERY_BVH;
+  const bool bvh = uses_tree && t->queries.accel == RT_QUERY_BVH;
   if (bvh) ensure_query_tree(t);
-  if (!t->query_done) t->query_done = Event(hipEventDisableTiming);
-  else HIP_CHECK(hipStreamWaitEvent(st, t->query_done, 0));
+  if (!t->queries.done) t->queries.done = Event(hipEventDisableTiming);
+  else HIP_CHECK(hipStreamWaitEvent(st, t->queries.done, 0));
   if (bvh) {
     const rtk::BvhParams b = query_bvh_params(t);
     HIP_CHECK(launch(p, &b));
   } else {
     HIP_CHECK(launch(p, static_cast<const rtk::BvhParams*>(nullptr)));
   }
-  HIP_CHECK(hipEventRecord(t->query_done, st));
+  HIP_CHECK(hipEventRecord(t->queries.done, st));
 }
 
 // the point queries' slack on the box distance: rho_c takes the ray queries' (rt_dbg_query_accel_slack)
-inline float closest_rho(const rt_tracer* t) { return RT_CLOSEST_RHO * (static_cast<float>(t->query_slack_milli) / 1000.0f); }
+inline float closest_rho(const rt_tracer* t) { return RT_CLOSEST_RHO * (static_cast<float>(t->queries.slack_milli) / 1000.0f); }
 
 // rays (or pixels) -> hits, under the tracer's hit rule
 inline void enqueue_query(rt_tracer* t, size_t n, const float* rays, const uint32_t* pixels, float* rays_out, float4* hits,
@@ -283,29 +278,30 @@ inline bool overlap_args_ok(rt_tracer* t, const char* who, size_t n, const float
 // ensure_query_tree keys the tree, and uploaded once on the query stream.  Queries in flight may still read the old table: they
 // are waited for before its buffer is rewritten.  RT_ACCEL_REFIT does not apply: the table is rebuilt.
 inline void ensure_feature_table(rt_tracer* t) {
-  if (t->features_valid()) return;
-  const hipStream_t st = query_stream(t);
+  QueryState& q = t->queries;
+  if (q.features_valid(t->scene_generation)) return;
+  const hipStream_t st = q.stream();
   t->wait_queries();
-  t->features_built = false;
+  q.features_built = false;
   const size_t n = t->n_tris;
-  if (t->scene_rows.size() != n * 12u) throw HipFail{fmt("signed query: the host copy of the scene holds %zu floats, the scene %zu triangles", t->scene_rows.size(), n)};
-  const rtf::Table tab = rtf::build(t->scene_rows.data(), n, t->scene_rows_edges);
-  t->d_features.ensure(std::max<size_t>(n * rtf::kFeaturesPerTri, 1u));
+  if (q.scene_rows.size() != n * 12u) throw HipFail{fmt("signed query: the host copy of the scene holds %zu floats, the scene %zu triangles", q.scene_rows.size(), n)};
+  const rtf::Table tab = rtf::build(q.scene_rows.data(), n, q.scene_rows_edges);
+  q.d_features.ensure(std::max<size_t>(n * rtf::kFeaturesPerTri, 1u));
   if (n != 0u) {
-    HIP_CHECK(hipMemcpyAsync(t->d_features.get(), tab.normals.data(), tab.bytes(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(q.d_features.get(), tab.normals.data(), tab.bytes(), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));                                 // (the host vector goes away; a caller's stream may run the query)
   }
-  t->features_info[0] = n; t->features_info[1] = tab.vertices; t->features_info[2] = tab.edges; t->features_info[3] = tab.contributing;
-  t->features_info[4] = tab.build_us; t->features_info[5] = tab.bytes();
-  t->features_scene = t->scene_generation;
-  t->features_built = true;
+  q.features_info[0] = n; q.features_info[1] = tab.vertices; q.features_info[2] = tab.edges; q.features_info[3] = tab.contributing;
+  q.features_info[4] = tab.build_us; q.features_info[5] = tab.bytes();
+  q.features_scene = t->scene_generation;
+  q.features_built = true;
 }
 
 // points and n * per_point records of them -> as many rt_side; no tree.  The table is valid (ensure_feature_table, called
 // before anything of this query was enqueued: it may wait for the queries in flight).
 inline void enqueue_sides(rt_tracer* t, size_t n, uint32_t per_point, const float* pts, const float4* hits, void* sides, hipStream_t st) {
   enqueue_launch(t, st, 0u, false, [&](const rtk::TraceParams& p, const rtk::BvhParams*) {
-    return rtk::launch_sides(p, t->d_features.get(), static_cast<uint32_t>(n), per_point, pts, hits, sides, st);
+    return rtk::launch_sides(p, t->queries.d_features.get(), static_cast<uint32_t>(n), per_point, pts, hits, sides, st);
   });
 }
 
@@ -316,15 +312,15 @@ extern "C" {
 int rt_tracer_set_query_accel(rt_tracer* t, uint32_t mode) {
   if (!t) return RT_ERR_INVALID;
   if (mode != RT_QUERY_SCAN && mode != RT_QUERY_BVH) { t->set_error(fmt("rt_tracer_set_query_accel: unknown mode %u", mode)); return RT_ERR_INVALID; }
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_set_query_accel(b, mode); }, [&] { t->query_accel = mode; });
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_set_query_accel(b, mode); }, [&] { t->queries.accel = mode; });
 }
 
 int rt_tracer_query_accel_info(rt_tracer* t, uint64_t out[8]) {
   if (!t || !out) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_query_accel_info(b, out); }, [&] {
-    const bool valid = t->bvh_valid();
-    out[0] = t->query_accel; out[1] = valid ? 1u : 0u;
-    for (int i = 0; i < 6; ++i) out[2 + i] = valid ? t->bvh_info[i] : 0u;
+    const bool valid = t->queries.bvh_valid(t->scene_generation);
+    out[0] = t->queries.accel; out[1] = valid ? 1u : 0u;
+    for (int i = 0; i < 6; ++i) out[2 + i] = valid ? t->queries.bvh_info[i] : 0u;
   });
 }
 
@@ -332,22 +328,22 @@ int rt_tracer_set_query_accel_update(rt_tracer* t, uint32_t policy) {
   if (!t) return RT_ERR_INVALID;
   if (policy != RT_ACCEL_REBUILD && policy != RT_ACCEL_REFIT) { t->set_error(fmt("rt_tracer_set_query_accel_update: unknown policy %u", policy)); return RT_ERR_INVALID; }
   // (checked before query_call takes api_mu, as every argument is)
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_set_query_accel_update(b, policy); }, [&] { t->accel_update = policy; });
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_set_query_accel_update(b, policy); }, [&] { t->queries.accel_update = policy; });
 }
 
 int rt_tracer_query_accel_rebuild(rt_tracer* t) {
   if (!t) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_query_accel_rebuild(b); }, [&] {
-    t->bvh_built = false;                                                // (the buffers stay; queries in flight may still walk them)
+    t->queries.bvh_built = false;                                                // (the buffers stay; queries in flight may still walk them)
   });
 }
 
 int rt_tracer_query_accel_update_info(rt_tracer* t, uint64_t out[8]) {
   if (!t || !out) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_query_accel_update_info(b, out); }, [&] {
-    const bool valid = t->bvh_valid();
-    const double cost = valid ? t->bvh_cost : 0.0, built = valid ? t->bvh_cost_built : 0.0;
-    out[0] = t->accel_update; out[1] = t->refits; out[2] = t->refit_fallbacks; out[3] = t->refit_us;
+    const bool valid = t->queries.bvh_valid(t->scene_generation);
+    const double cost = valid ? t->queries.bvh_cost : 0.0, built = valid ? t->queries.bvh_cost_built : 0.0;
+    out[0] = t->queries.accel_update; out[1] = t->queries.refits; out[2] = t->queries.refit_fallbacks; out[3] = t->queries.refit_us;
     memcpy(&out[4], &cost, sizeof(double)); memcpy(&out[5], &built, sizeof(double));
     out[6] = valid ? rtr::query_bvh_params(t).stack_cap : 0u;             // what the walks run with (rt_dbg_query_stack_cap lowers it)
     out[7] = 0u;
@@ -356,12 +352,12 @@ int rt_tracer_query_accel_update_info(rt_tracer* t, uint64_t out[8]) {
 
 int rt_dbg_query_accel_slack(rt_tracer* t, uint32_t slack_milli) {
   if (!t) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_dbg_query_accel_slack(b, slack_milli); }, [&] { t->query_slack_milli = slack_milli; });
+  return query_call(t, [&](rt_tracer* b) { return rt_dbg_query_accel_slack(b, slack_milli); }, [&] { t->queries.slack_milli = slack_milli; });
 }
 
 int rt_dbg_query_stack_cap(rt_tracer* t, uint32_t cap) {
   if (!t) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_dbg_query_stack_cap(b, cap); }, [&] { t->query_stack_cap = cap; });
+  return query_call(t, [&](rt_tracer* b) { return rt_dbg_query_stack_cap(b, cap); }, [&] { t->queries.stack_cap = cap; });
 }
 
 int rt_dbg_bvh_build(const rt_float4* rows, size_t count, int edges_layout, void* nodes, size_t node_capacity_bytes,
@@ -424,19 +420,18 @@ int rt_dbg_query_tree_read(rt_tracer* t, void* nodes, size_t node_capacity_bytes
                            uint64_t info[8]) {
   if (!t || !info) return RT_ERR_INVALID;
   return query_entry(t, [&](rt_tracer* b) { return rt_dbg_query_tree_read(b, nodes, node_capacity_bytes, records, record_capacity_bytes, info); }, [&] {
-    if (!t->bvh_valid()) { t->set_error("rt_dbg_query_tree_read: no valid tree (the next RT_QUERY_BVH query makes one)"); return RT_ERR_STATE; }
+    if (!t->queries.bvh_valid(t->scene_generation)) { t->set_error("rt_dbg_query_tree_read: no valid tree (the next RT_QUERY_BVH query makes one)"); return RT_ERR_STATE; }
     return guarded(t, [&] {
-      const size_t nb = t->bvh_info[0] * sizeof(rtb::Node), rb = (size_t(t->bvh_leaf_records) + t->bvh_info[3]) * sizeof(rtb::Record);
+      const size_t nb = t->queries.bvh_info[0] * sizeof(rtb::Node), rb = (size_t(t->queries.bvh_leaf_records) + t->queries.bvh_info[3]) * sizeof(rtb::Record);
       info[0] = rtb::kBvhMaxDepth; info[1] = 1u;
-      for (int i = 0; i < 6; ++i) info[2 + i] = t->bvh_info[i];
+      for (int i = 0; i < 6; ++i) info[2 + i] = t->queries.bvh_info[i];
       if (node_capacity_bytes == 0u && record_capacity_bytes == 0u) return;  // sizes only
       if (!nodes || !records || node_capacity_bytes < nb || record_capacity_bytes < rb)
         throw HipFail{fmt("rt_dbg_query_tree_read: the tree needs %zu + %zu bytes", nb, rb)};
-      t->use_device();
-      const hipStream_t st = query_stream(t);
+      const hipStream_t st = host_query_stream(t);
       t->wait_queries();
-      if (nb) HIP_CHECK(hipMemcpyAsync(nodes, t->d_bvh_nodes.get(), nb, hipMemcpyDeviceToHost, st));
-      if (rb) HIP_CHECK(hipMemcpyAsync(records, t->d_bvh_records.get(), rb, hipMemcpyDeviceToHost, st));
+      if (nb) HIP_CHECK(hipMemcpyAsync(nodes, t->queries.d_bvh_nodes.get(), nb, hipMemcpyDeviceToHost, st));
+      if (rb) HIP_CHECK(hipMemcpyAsync(records, t->queries.d_bvh_records.get(), rb, hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipStreamSynchronize(st));
     });
   });
@@ -446,11 +441,10 @@ int rt_tracer_intersect(rt_tracer* t, const float* rays, size_t n, rt_hit* hits)
   if (!t || !query_args_ok(t, n, {rays, hits})) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_intersect(b, rays, n, hits); }, [&] {
     if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
-    const float* d_rays = staged_in(t->d_q_rays, rays, n * 6u, st);
-    enqueue_query(t, n, d_rays, nullptr, nullptr, room(t->d_q_hits, n), st);
-    staged_out(hits, t->d_q_hits, n, st);
+    const hipStream_t st = host_query_stream(t);
+    const float* d_rays = staged_in<float>(t->queries.in[0], rays, n * 6u, st);
+    enqueue_query(t, n, d_rays, nullptr, nullptr, room<float4>(t->queries.out[0], n), st);
+    staged_out<float4>(hits, t->queries.out[0], n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
@@ -470,11 +464,10 @@ int rt_tracer_occluded(rt_tracer* t, const float* segs, size_t n, uint8_t* occlu
   if (!t || !query_args_ok(t, n, {segs, occluded})) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_occluded(b, segs, n, occluded); }, [&] {
     if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
-    const float* d_segs = staged_in(t->d_q_segs, segs, n * 8u, st);
-    enqueue_occluded(t, n, d_segs, room(t->d_q_occluded, n), st);
-    staged_out(occluded, t->d_q_occluded, n, st);
+    const hipStream_t st = host_query_stream(t);
+    const float* d_segs = staged_in<float>(t->queries.in[0], segs, n * 8u, st);
+    enqueue_occluded(t, n, d_segs, room<uint8_t>(t->queries.out[0], n), st);
+    staged_out<uint8_t>(occluded, t->queries.out[0], n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
@@ -494,12 +487,11 @@ int rt_tracer_exposure(rt_tracer* t, const float* points, size_t n, const float*
   if (!t || !exposure_args_ok(t, "rt_tracer_exposure", n_dirs, flags) || !query_args_ok(t, n, {points, dirs, masks})) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_exposure(b, points, n, dirs, n_dirs, flags, masks); }, [&] {
     if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
-    const float* d_points = staged_in(t->d_q_segs, points, n * 8u, st);
-    const float* d_dirs = reinterpret_cast<const float*>(staged_in(t->d_q_dirs, dirs, n_dirs, st));
-    enqueue_exposure(t, n, d_points, d_dirs, n_dirs, flags, room(t->d_q_masks, n), st);
-    staged_out(masks, t->d_q_masks, n, st);
+    const hipStream_t st = host_query_stream(t);
+    const float* d_points = staged_in<float>(t->queries.in[0], points, n * 8u, st);
+    const float* d_dirs = staged_in<float>(t->queries.in[1], dirs, n_dirs * 4u, st);
+    enqueue_exposure(t, n, d_points, d_dirs, n_dirs, flags, room<uint64_t>(t->queries.out[0], n), st);
+    staged_out<uint64_t>(masks, t->queries.out[0], n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
@@ -527,11 +519,10 @@ int rt_dbg_exposure_rays(rt_tracer* t, const float* points, size_t n, const floa
   if (n * static_cast<uint64_t>(n_dirs) >= 0x80000000ull) { t->set_error("rt_dbg_exposure_rays: n * n_dirs must be below 2^31"); return RT_ERR_INVALID; }
   return query_call(t, [&](rt_tracer* b) { return rt_dbg_exposure_rays(b, points, n, dirs, n_dirs, flags, segs_out); }, [&] {
     if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
+    const hipStream_t st = host_query_stream(t);
     DevArray<float> d_out(n * n_dirs * 8u);
-    const float* d_points = staged_in(t->d_q_segs, points, n * 8u, st);
-    const float* d_dirs = reinterpret_cast<const float*>(staged_in(t->d_q_dirs, dirs, n_dirs, st));
+    const float* d_points = staged_in<float>(t->queries.in[0], points, n * 8u, st);
+    const float* d_dirs = staged_in<float>(t->queries.in[1], dirs, n_dirs * 4u, st);
     enqueue_launch(t, st, 0u, false, [&](const rtk::TraceParams&, const rtk::BvhParams*) {
       return rtk::launch_exposure_rays(static_cast<uint32_t>(n), d_points, d_dirs, n_dirs, flags, d_out.get(), st);
     });
@@ -544,12 +535,11 @@ int rt_tracer_intersect_all(rt_tracer* t, const float* segs, size_t n, uint32_t 
   if (!t || !query_row_ok(t, "rt_tracer_intersect_all", "max_hits", max_hits) || !query_args_ok(t, n, {segs, hits, counts})) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_intersect_all(b, segs, n, max_hits, hits, counts); }, [&] {
     if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
-    const float* d_segs = staged_in(t->d_q_segs, segs, n * 8u, st);
-    enqueue_intersect_all(t, n, d_segs, max_hits, room(t->d_q_all_hits, n * max_hits), room(t->d_q_all_counts, n), st);
-    staged_out(hits, t->d_q_all_hits, n * max_hits, st);
-    staged_out(counts, t->d_q_all_counts, n, st);
+    const hipStream_t st = host_query_stream(t);
+    const float* d_segs = staged_in<float>(t->queries.in[0], segs, n * 8u, st);
+    enqueue_intersect_all(t, n, d_segs, max_hits, room<float4>(t->queries.out[0], n * max_hits), room<uint32_t>(t->queries.out[1], n), st);
+    staged_out<float4>(hits, t->queries.out[0], n * max_hits, st);
+    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
@@ -571,11 +561,10 @@ int rt_tracer_closest_point(rt_tracer* t, const float* pts, size_t n, rt_hit* ou
   if (!t || !query_args_ok(t, n, {pts, out})) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_point(b, pts, n, out); }, [&] {
     if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
-    const float* d_pts = reinterpret_cast<const float*>(staged_in(t->d_q_points, pts, n, st));
-    enqueue_closest(t, n, d_pts, room(t->d_q_hits, n), st);
-    staged_out(out, t->d_q_hits, n, st);
+    const hipStream_t st = host_query_stream(t);
+    const float* d_pts = staged_in<float>(t->queries.in[0], pts, n * 4u, st);
+    enqueue_closest(t, n, d_pts, room<float4>(t->queries.out[0], n), st);
+    staged_out<float4>(out, t->queries.out[0], n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
@@ -596,13 +585,12 @@ int rt_tracer_closest_all(rt_tracer* t, const float* pts, const rt_hit* after, s
   if (!t || !query_row_ok(t, "rt_tracer_closest_all", "max_hits", max_hits) || !query_args_ok(t, n, {pts, hits, counts})) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_all(b, pts, after, n, max_hits, hits, counts); }, [&] {
     if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
-    const float* d_pts = reinterpret_cast<const float*>(staged_in(t->d_q_points, pts, n, st));
-    const float4* d_after = after ? staged_in(t->d_q_after, after, n, st) : nullptr;
-    enqueue_closest_all(t, n, d_pts, d_after, max_hits, room(t->d_q_all_hits, n * max_hits), room(t->d_q_all_counts, n), st);
-    staged_out(hits, t->d_q_all_hits, n * max_hits, st);
-    staged_out(counts, t->d_q_all_counts, n, st);
+    const hipStream_t st = host_query_stream(t);
+    const float* d_pts = staged_in<float>(t->queries.in[0], pts, n * 4u, st);
+    const float4* d_after = after ? staged_in<float4>(t->queries.in[1], after, n, st) : nullptr;
+    enqueue_closest_all(t, n, d_pts, d_after, max_hits, room<float4>(t->queries.out[0], n * max_hits), room<uint32_t>(t->queries.out[1], n), st);
+    staged_out<float4>(hits, t->queries.out[0], n * max_hits, st);
+    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
@@ -625,14 +613,14 @@ int rt_tracer_signed_distance(rt_tracer* t, const float* pts, size_t n, rt_hit* 
   if (!t || !query_args_ok(t, n, {pts, hits, sides})) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_signed_distance(b, pts, n, hits, sides); }, [&] {
     if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
+    const hipStream_t st = host_query_stream(t);
     ensure_feature_table(t);
-    const float* d_pts = reinterpret_cast<const float*>(staged_in(t->d_q_points, pts, n, st));
-    enqueue_closest(t, n, d_pts, room(t->d_q_hits, n), st);
-    enqueue_sides(t, n, 1u, d_pts, t->d_q_hits.get(), room(t->d_q_sides, n), st);
-    staged_out(hits, t->d_q_hits, n, st);
-    staged_out(sides, t->d_q_sides, n, st);
+    const float* d_pts = staged_in<float>(t->queries.in[0], pts, n * 4u, st);
+    float4* const d_hits = room<float4>(t->queries.out[0], n);           // the closest kernel's output is the sides kernel's input
+    enqueue_closest(t, n, d_pts, d_hits, st);
+    enqueue_sides(t, n, 1u, d_pts, d_hits, room<uint2>(t->queries.out[1], n), st);
+    staged_out<float4>(hits, t->queries.out[0], n, st);
+    staged_out<uint2>(sides, t->queries.out[1], n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
@@ -655,13 +643,12 @@ int rt_tracer_closest_sides(rt_tracer* t, const float* pts, const rt_hit* hits, 
   if (!t || !query_row_ok(t, "rt_tracer_closest_sides", "per_point", per_point) || !query_args_ok(t, n, {pts, hits, sides})) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_sides(b, pts, hits, n, per_point, sides); }, [&] {
     if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
+    const hipStream_t st = host_query_stream(t);
     ensure_feature_table(t);
-    const float* d_pts = reinterpret_cast<const float*>(staged_in(t->d_q_points, pts, n, st));
-    const float4* d_hits = staged_in(t->d_q_all_hits, hits, n * per_point, st);
-    enqueue_sides(t, n, per_point, d_pts, d_hits, room(t->d_q_sides, n * per_point), st);
-    staged_out(sides, t->d_q_sides, n * per_point, st);
+    const float* d_pts = staged_in<float>(t->queries.in[0], pts, n * 4u, st);
+    const float4* d_hits = staged_in<float4>(t->queries.in[1], hits, n * per_point, st);
+    enqueue_sides(t, n, per_point, d_pts, d_hits, room<uint2>(t->queries.out[0], n * per_point), st);
+    staged_out<uint2>(sides, t->queries.out[0], n * per_point, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
@@ -685,14 +672,13 @@ int rt_tracer_overlap(rt_tracer* t, const float* boxes, const int32_t* after, si
   if (!t || !overlap_args_ok(t, "rt_tracer_overlap", n, boxes, max_hits, prims, counts)) return RT_ERR_INVALID;
   return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap(b, boxes, after, n, max_hits, prims, counts); }, [&] {
     if (n == 0u) return;
-    t->use_device();
-    const hipStream_t st = query_stream(t);
-    const float* d_boxes = staged_in(t->d_q_segs, boxes, n * 8u, st);
-    const int32_t* d_after = after ? staged_in(t->d_q_cursors, after, n, st) : nullptr;
-    int32_t* d_prims = max_hits != 0u ? room(t->d_q_prims, n * max_hits) : nullptr;
-    enqueue_overlap(t, n, d_boxes, d_after, max_hits, d_prims, room(t->d_q_all_counts, n), st);
-    if (max_hits != 0u) staged_out(prims, t->d_q_prims, n * max_hits, st);
-    staged_out(counts, t->d_q_all_counts, n, st);
+    const hipStream_t st = host_query_stream(t);
+    const float* d_boxes = staged_in<float>(t->queries.in[0], boxes, n * 8u, st);
+    const int32_t* d_after = after ? staged_in<int32_t>(t->queries.in[1], after, n, st) : nullptr;
+    int32_t* d_prims = max_hits != 0u ? room<int32_t>(t->queries.out[0], n * max_hits) : nullptr;
+    enqueue_overlap(t, n, d_boxes, d_after, max_hits, d_prims, room<uint32_t>(t->queries.out[1], n), st);
+    if (max_hits != 0u) staged_out<int32_t>(prims, t->queries.out[0], n * max_hits, st);
+    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
@@ -738,12 +724,11 @@ int rt_tracer_pick(rt_tracer* t, const uint32_t* pixels, size_t n, rt_hit* hits,
     }
     return guarded(t, [&] {
       if (n == 0u) return;
-      t->use_device();
-      const hipStream_t st = query_stream(t);
-      const uint32_t* d_pixels = staged_in(t->d_q_pixels, pixels, n * 2u, st);
-      enqueue_query(t, n, nullptr, d_pixels, rays ? room(t->d_q_rays, n * 6u) : nullptr, room(t->d_q_hits, n), st);
-      staged_out(hits, t->d_q_hits, n, st);
-      if (rays) staged_out(rays, t->d_q_rays, n * 6u, st);
+      const hipStream_t st = host_query_stream(t);
+      const uint32_t* d_pixels = staged_in<uint32_t>(t->queries.in[0], pixels, n * 2u, st);
+      enqueue_query(t, n, nullptr, d_pixels, rays ? room<float>(t->queries.out[1], n * 6u) : nullptr, room<float4>(t->queries.out[0], n), st);
+      staged_out<float4>(hits, t->queries.out[0], n, st);
+      if (rays) staged_out<float>(rays, t->queries.out[1], n * 6u, st);
       HIP_CHECK(hipStreamSynchronize(st));
     });
   });

@@ -332,7 +332,7 @@ static int upload_scene_impl(rt_tracer* t, const rt_float4* hostData, size_t cou
     t->wait_queries();                                                   // (and so may a query)
     t->d_tri.reset(); t->d_tri_b.reset(); t->d_tri_color.reset(); t->d_tri_n.reset();   // :128-137
     t->n_tris = 0;
-    t->scene_rows.clear();
+    t->queries.scene_rows.clear();
     const uint32_t n = static_cast<uint32_t>(count / 3);                 // :139
     DevArray<float4> verts(count);
     t->d_tri.ensure(static_cast<size_t>(n) * 2); t->d_tri_b.ensure(n); t->d_tri_color.ensure(n);
@@ -341,8 +341,8 @@ static int upload_scene_impl(rt_tracer* t, const rt_float4* hostData, size_t cou
     HIP_CHECK(rtk::launch_prep_triangles(t->fma, edges, verts.get(), n, t->d_tri.get(), t->d_tri_b.get(),
                                          t->d_tri_color.get(), t->d_tri_n.get(), t->main_stream()));
     HIP_CHECK(hipStreamSynchronize(t->main_stream()));
-    t->scene_rows.assign(&hostData[0].x, &hostData[0].x + count * 4u);    // what the signed queries weld their table from
-    t->scene_rows_edges = edges;
+    t->queries.scene_rows.assign(&hostData[0].x, &hostData[0].x + count * 4u);    // what the signed queries weld their table from
+    t->queries.scene_rows_edges = edges;
     t->n_tris = n;
     t->scene_generation++;
   });

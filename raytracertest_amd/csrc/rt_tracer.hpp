@@ -26,6 +26,7 @@
 #include "rt_device_math.hpp"
 #include "rt_hip_host.hpp"
 #include "rt_kernels.hpp"
+#include "rt_query_state.hpp"
 #include "rt_rng_host.hpp"
 
 namespace rtr {
@@ -308,6 +309,72 @@ struct OweKey {
 #endif
 constexpr uint32_t kSettleStepMax = 96u;   // draws up to which rng_settle_kernel steps (7 VALU per draw) instead of one table product (~300 VALU + 80 LDS reads)
 
+// Two words of the per-pixel state are the same for every pixel of the band, so the tracer keeps them and the launches
+// get them as scalars (TraceParams::weyl, ::count) instead of loading and storing them per pixel:
+//   weyl_now  -- the XORWOW Weyl word d: seeded[0] when the states are created (the subsequence jump acts on v0..v4
+//                only), + 362437 per draw, 3 draws per sample on every path (get_ray, or rng_discard for certain winners);
+//   count_now -- the samples accumulated since the accumulators were cleared.
+// Plane 0 of d_rng and d_counts hold them only after rt_tracer::materialise(), which every reader of the two buffers calls
+// first; *_plane is the word the plane was last filled with.  All guarded by rt_tracer::order_mu.
+struct UniformWords {
+  uint32_t weyl_now = 0, count_now = 0;
+  uint32_t weyl_plane = 0, count_plane = 0;
+  bool weyl_plane_ok = false, count_plane_ok = false;
+  // Once per launch of `p.samples` x `p.iters` samples (not per half of a split one), with order_mu held until the
+  // launch is enqueued: hands the launch the two words and advances them by what it will do to every pixel.
+  void take(rtk::TraceParams& p) {
+    if (p.flags & rtk::TRACE_ZERO_ACC) count_now = 0u;
+    p.weyl = weyl_now; p.count = count_now;
+    const uint32_t done = p.samples * (p.iters > 1u ? p.iters : 1u);
+    weyl_now += 362437u * 3u * done;
+    count_now += done;
+  }
+  bool weyl_plane_stale() const { return !(weyl_plane_ok && weyl_plane == weyl_now); }
+  bool count_plane_stale() const { return !(count_plane_ok && count_plane == count_now); }
+  void weyl_plane_filled() { weyl_plane = weyl_now; weyl_plane_ok = true; }
+  void count_plane_filled() { count_plane = count_now; count_plane_ok = true; }
+};
+
+// A third word of the same kind: owed_draws -- the xorshift steps the pixels of the certain-winner tiles are behind.  A
+// small-scene launch whose owe key equals that of the launch enqueued before it runs with TRACE_OWE_RNG: its
+// certain-winner waves neither load, advance nor store v0..v4, and the launch adds its 3 x samples x iterations here instead.
+// rt_tracer::settle() pays: one rng_settle_kernel over the tiles whose list header has the certain bit -- the same tiles in
+// every owing launch, their key being the same.  Who calls it: the first launch that may not owe or has another key (before it
+// replaces the lists), materialise(RT_BUF_RNG) -- every reader of the buffer --, the uploads, the instrumented launches,
+// and every period-th owing launch (on the streams of its halves, so that the debt stays one table product).
+// Where the states are created anew the debt is dropped.  All guarded by rt_tracer::order_mu.
+struct RngDebt {
+  uint32_t owed_draws = 0;
+  uint32_t owing_launches = 0;                 // since the last settle
+  uint64_t settles_enqueued = 0;               // settle kernels so far (rt_dbg_owed_state)
+  std::optional<OweKey> key;                   // of the launch enqueued last; none: the next launch does not owe
+  rtk::TraceParams owe_p;                      // the band-wide launch the debt is settled as: planes, lists, frame
+  std::map<uint32_t, DevArray<uint32_t>> settle_tables;   // window tables of T^n by n; steady state holds one, n = period x 3 x samples
+  uint32_t period;                             // owing launches between two periodic settles
+  explicit RngDebt(const Env& env) : period(env.owe_period > 0 ? static_cast<uint32_t>(env.owe_period) : static_cast<uint32_t>(RT_OWE_PERIOD)) {}
+  // whether a launch with owe key `k` (none: it may not owe) owes: its key is that of the launch before it
+  bool owes(const std::optional<OweKey>& k) const { return k && key && memcmp(&*k, &*key, sizeof(OweKey)) == 0; }
+  void add(const rtk::TraceParams& p) { owed_draws += 3u * p.samples * (p.iters > 1u ? p.iters : 1u); ++owing_launches; }   // once per launch, not per half
+  bool settle_due() const { return owing_launches >= period; }
+  // the device table of T^n, or null: n draws are stepped.  A new table is in device memory when this returns.
+  const uint32_t* table(uint32_t n, hipStream_t a, hipStream_t b) {
+    if (n <= kSettleStepMax) return nullptr;
+    auto it = settle_tables.find(n);
+    if (it != settle_tables.end()) return it->second.get();
+    if (settle_tables.size() >= 32u) {                                   // (earlier settles on the trace streams may still read theirs)
+      HIP_CHECK(hipStreamSynchronize(b));
+      HIP_CHECK(hipStreamSynchronize(a));
+      settle_tables.clear();
+    }
+    const std::vector<uint32_t> host = rth::build_window_table(rth::step_power(n));
+    DevArray<uint32_t> dev(host.size());
+    HIP_CHECK(hipMemcpy(dev.get(), host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return settle_tables.emplace(n, std::move(dev)).first->second.get();
+  }
+  void paid() { owed_draws = 0u; owing_launches = 0u; }
+  void dropped() { paid(); key.reset(); }      // the states are created anew
+};
+
 // The small scenes' tile lists live in a small ring of buffers and are built on a stream of their own (stream_l, high priority): a build is
 // enqueued when the launch that needs it is enqueued, so it runs UNDER the trace kernels of the previous launch instead of
 // in front of its own (measured in-stream: each half-frame build took 35-45 us competing for wave slots with the other
@@ -464,13 +531,15 @@ struct MultiState;   // rt_multi.hpp: the bands of a multi-device tracer
 }  // namespace rtr
 
 struct rt_tracer {
-  // A handle is one of: a plain tracer (one device, the whole frame or one row band), a band tracer that
-  // joined a multi-process group (grp != null), or a multi-device tracer (mg != null: the fields below then
-  // describe the whole frame and hold camera, callbacks, render thread and error text; the device buffers
-  // live in the band tracers mg owns).
+  // A handle is one of: a plain tracer (one device, the whole frame or one row band), a band tracer that joined a multi-process
+  // group (grp != null), or a multi-device tracer (mg != null: the fields below then describe the whole frame and hold camera,
+  // callbacks, render thread and error text; the device buffers live in the band tracers mg owns).
+  // Fields first, by subject, the functions behind them.  Members are destroyed in reverse order of declaration: the streams are
+  // declared before everything that is freed or recorded on them, the render thread behind everything its jobs use
+  // (rt_tracer_destroy calls quiesce() before any of it goes).
   rtr::Group* grp = nullptr;
   rtr::MultiState* mg = nullptr;
-  // configuration
+  // ---- configuration and options
   rtr::Env env;                     // the environment switches as they were at rt_tracer_create
   int device = 0;
   uint32_t W = 0, H = 0;            // full image
@@ -480,8 +549,25 @@ struct rt_tracer {
   bool fma = true, filter = true, bin = true, nearest_hit = false;
   bool smooth_normals = false;        // RT_FLAG_SMOOTH_NORMALS; takes effect for edge-format scenes
   uint32_t k_req = 0, chunk_req = 0, bin_list_req = 0;
-
-  // device state (declared first: the streams are destroyed last)
+  bool split_launches = true;         // RT_MI355X_NO_SPLIT=1 turns it off
+  bool macro = true;                  // RT_FLAG_NO_MACRO_BINS turns it off
+  bool pretest = true;                // RT_MI355X_NO_PRETEST=1 turns the per-sample forms off
+  bool sure_hit = true;               // RT_FLAG_NO_SURE_HIT: tiles of one certainly-hit triangle run the tests anyway
+  // Stored tile candidate lists (small scenes) survive from one Trace to the next while camera, lens, scene,
+  // frame and arithmetic mode are unchanged -- like any acceleration structure that is rebuilt only when its
+  // inputs change.  rt_tracer_set_list_reuse(t, 0) restricts the reuse to the launches of one Trace.
+  bool reuse_across_traces = true;
+  // the forms pay for themselves on dense scenes only (break-even ~3000 triangles at 1080p; C4: -13 %)
+  static constexpr uint32_t kPretestMinTris = 4096;
+  static constexpr uint32_t kMacroW = 128, kMacroH = 64, kMacroCapMax = 65536;
+  // Dense scenes: a level above the macro tiles (super tiles of kSuperF x kSuperF of them, super_bin_kernel) so that a macro
+  // tile tests its super tile's lists instead of the scene (rt_lists.hpp): C4 10.2 M -> ~1.5 M triangle tests per rebuild.
+#ifndef RT_SUPER_F
+#define RT_SUPER_F 4
+#endif
+  static constexpr uint32_t kSuperF = RT_SUPER_F, kSuperMinTris = 2048;
+  bool super_level = true;            // RT_FLAG_NO_SUPER_BINS turns it off
+  // ---- streams and ordering
   rtr::Stream stream;                 // primary stream: everything that is not the lower half of a split launch
   // Trace launches of tall frames are split into two half-frame kernels on two streams: consecutive
   // launches then overlap one half's drain (falling occupancy at the end of a kernel) with the other half's
@@ -489,17 +575,69 @@ struct rt_tracer {
   // because its half always uses the same stream.  main_stream() is the ordering point for everything else.
   rtr::Stream stream_b;
   rtr::Stream stream_l;               // the small scenes' list builds (highest priority; TileListRing)
-  rtr::Stream stream_q;               // ray queries (rt_query_api.hpp): created by the first query, highest priority
   rtr::Event join_event, fork_event;
   bool b_dirty = false;               // work on stream_b the primary stream has not waited for yet
   bool a_dirty = false;               // non-launch work on the primary stream that stream_b has not waited for yet
-  bool split_launches = true;         // RT_MI355X_NO_SPLIT=1 turns it off
-
   // The ordering state is shared by the render thread and by entry points that do not join it
   // (rt_tracer_sync, rt_tracer_read_buffer, the device copies): order_mu serialises the dirty flags and the
-  // re-recording of the two shared events -- and the uniform state words below with the launches that advance them
-  // (recursive: a launch is enqueued under it and asks for main_stream() / fork_b() on the way).
+  // re-recording of the two shared events -- and the uniform state words and the owed draws below with the launches that
+  // advance them (recursive: a launch is enqueued under it and asks for main_stream() / fork_b() on the way).
   std::recursive_mutex order_mu;
+  rtr::EnqueueCalls calls;            // guarded by order_mu
+  // ---- render buffers and scene
+  rtk::KernelTable kernels;           // launch descriptors of this tracer's device
+  rtr::DevArray<float4> d_render;
+  rtr::DevArray<uint32_t> d_counts, d_image, d_rng;
+  rtr::UniformWords words;            // the Weyl word and the sample count of every pixel (guarded by order_mu)
+  rtr::RngDebt debt{env};             // the draws the certain-winner tiles are behind (guarded by order_mu)
+  rtr::PinnedArray<uint32_t> h_image;       // handed to callbacks
+  rtr::PinnedArray<uint32_t> h_image_alt;   // second image: update i+1 is produced while the callback reads update i
+  uint32_t* image_mirror = nullptr; // rt_tracer_set_image_mirror: second target of emitting rt_tracer_launch* / trace_enqueue launches
+  rtr::Event handoff_event;
+  int handoff_next = 0;             // which of the two host images the next emitting launch of a Trace writes
+  rtr::DevArray<float4> d_tri;      // (e2.xyz,e1.x),(e1.yz,v0.xy) records
+  rtr::DevArray<float> d_tri_b;     // v0.z
+  rtr::DevArray<float4> d_tri_color;
+  rtr::DevArray<float4> d_tri_n;    // 3 unpacked vertex normals per triangle, edge-format scenes only
+  uint32_t n_tris = 0;
+  rtr::DevArray<float4> d_spheres;
+  uint32_t n_spheres = 0, scene_generation = 0;
+  // ---- lists
+  // Candidate lists + certain-winner verdicts of the small scenes' tiles (TracePath::SmallLists): built by tile_lists_kernel
+  // on stream_l into the next slot of a ring, ahead of the launch that needs them, and kept while camera snapshot, lens,
+  // scene, frame, list length and arithmetic mode are unchanged (lists.key; they do not depend on the samples).  The first
+  // launch of a Trace rebuilds them when lists are not kept across Traces (reuse_across_traces: bench.py's headline).
+  rtr::TileListRing lists;            // small scenes: the tile lists, built ahead on stream_l
+  rtr::Event stagger_event;
+  std::atomic<bool> stagger_next{true};   // the next split launch starts from an idle tracer: stagger its halves (enqueue_trace_launch)
+  // Which halves a split small-scene launch uses: the band's upper and lower rows (best when the two cost the same: C3 61.0
+  // against 62.2 us per step) or its even and odd block rows (the same cost whatever the picture: a tilted camera with 57 % /
+  // 22 % ray-generating tiles above / below the split 62.6 against 70.5 us).  The two-level list builder counts the
+  // ray-generating tiles per half and publishes the pair to pinned host memory behind every build; the enqueueing thread
+  // reads the latest pair (a few launches old: the picture does not jump) and switches with hysteresis -- a switch moves
+  // pixels from one stream to the other, so both streams are joined first (want_interleave()).
+  rtr::DevArray<uint32_t> d_half_cost;                // two device counters
+  rtr::PinnedArray<unsigned long long> h_half_cost;   // upper | lower << 32 of the latest finished build
+  bool rows_interleaved = false;
+  rtr::DevArray<float4> d_sure_table;                 // small scenes: what a certain-winner pixel accumulates (attach_sure_table())
+  uint32_t sure_table_samples = 0;
+  uint64_t sure_table_scene = ~0ull;
+  rtr::HalfLists half_lists[2];       // dense scenes: one per half of a split launch (attach_macro_lists())
+  // ---- queries (rt_query_api.hpp)
+  rtr::QueryState queries;
+  // ---- camera, callbacks and threads (camera + callbacks: guarded by state_mu; snapshotted per launch like the by-value kernel argument)
+  std::mutex state_mu;
+  rtr::Camera cam;
+  rt_callback_fn update_cb = nullptr; void* update_user = nullptr;
+  rt_callback_fn finished_cb = nullptr; void* finished_user = nullptr;
+  std::mutex api_mu;
+  rtr::RenderThread render;
+  std::atomic<bool> stopped{false}, completed{false};
+  rtr::LaunchClock clock;
+  std::mutex err_mu;
+  std::string last_error;
+  uint32_t last_k = 0, last_chunk = 0, last_lds = 0;
+
   hipStream_t main_stream() {         // primary stream, made to wait for everything enqueued on stream_b
     std::lock_guard<std::recursive_mutex> lk(order_mu);
     if (b_dirty) {
@@ -520,36 +658,7 @@ struct rt_tracer {
     ++calls.records; ++calls.waits;
     a_dirty = false;
   }
-  void mark_b_dirty() { std::lock_guard<std::recursive_mutex> lk(order_mu); b_dirty = true; }
-  rtr::EnqueueCalls calls;            // guarded by order_mu
-  rtk::KernelTable kernels;           // launch descriptors of this tracer's device
-  rtr::DevArray<float4> d_render;
-  rtr::DevArray<uint32_t> d_counts, d_image, d_rng;
-  // Two words of the per-pixel state are the same for every pixel of the band, so the tracer keeps them and the launches
-  // get them as scalars (TraceParams::weyl, ::count) instead of loading and storing them per pixel:
-  //   weyl_now  -- the XORWOW Weyl word d: seeded[0] when the states are created (the subsequence jump acts on v0..v4
-  //                only), + 362437 per draw, 3 draws per sample on every path (get_ray, or rng_discard for certain winners);
-  //   count_now -- the samples accumulated since the accumulators were cleared.
-  // Plane 0 of d_rng and d_counts hold them only after materialise(), which every reader of the two buffers calls first;
-  // *_plane is the word the plane was last filled with.  All guarded by order_mu.
-  uint32_t weyl_now = 0, count_now = 0;
-  uint32_t weyl_plane = 0, count_plane = 0;
-  bool weyl_plane_ok = false, count_plane_ok = false;
-  // A third word of the same kind: owed_draws -- the xorshift steps the pixels of the certain-winner tiles are behind.  A
-  // small-scene launch whose owe key equals that of the launch enqueued before it runs with TRACE_OWE_RNG: its
-  // certain-winner waves neither load, advance nor store v0..v4, and the launch adds its 3 x samples x iterations here instead.
-  // settle() pays: one rng_settle_kernel over the tiles whose list header has the certain bit -- the same tiles in every
-  // owing launch, their key being the same.  Who calls it: the first launch that may not owe or has another key (before it
-  // replaces the lists), materialise(RT_BUF_RNG) -- every reader of the buffer --, the uploads, the instrumented launches,
-  // and every owe_period()-th owing launch (on the streams of its halves, so that the debt stays one table product).
-  // Where the states are created anew the debt is dropped.  All guarded by order_mu.
-  uint32_t owed_draws = 0;
-  uint32_t owing_launches = 0;                 // since the last settle
-  uint64_t settles_enqueued = 0;               // settle kernels so far (rt_dbg_owed_state)
-  std::optional<rtr::OweKey> owe_key;          // of the launch enqueued last; none: the next launch does not owe
-  rtk::TraceParams owe_p;                      // the band-wide launch the debt is settled as: planes, lists, frame
-  std::map<uint32_t, rtr::DevArray<uint32_t>> settle_tables;   // window tables of T^n by n; steady state holds one, n = period x 3 x samples
-  uint32_t owe_period() const { return env.owe_period > 0 ? static_cast<uint32_t>(env.owe_period) : static_cast<uint32_t>(RT_OWE_PERIOD); }
+  void wait_queries() { queries.wait(); }
   // the owe key of the launch `p` on `path`, or none: such a launch may not owe
   std::optional<rtr::OweKey> owe_key_of(const rtk::TraceParams& p, rtk::TracePath path) const {
     const bool sure_ok = (p.flags & (rtk::TRACE_NEAREST_HIT | rtk::TRACE_NO_SURE_HIT)) == 0u && p.n_spheres == 0u && p.tri_n == nullptr;
@@ -561,137 +670,51 @@ struct rt_tracer {
     k.path = static_cast<uint32_t>(path);
     return k;
   }
-  // the device table of T^n, or null: n draws are stepped.  A new table is in device memory when this returns.
-  const uint32_t* settle_table(uint32_t n) {
-    if (n <= rtr::kSettleStepMax) return nullptr;
-    auto it = settle_tables.find(n);
-    if (it != settle_tables.end()) return it->second.get();
-    if (settle_tables.size() >= 32u) {                                   // (earlier settles may still read theirs)
-      HIP_CHECK(hipStreamSynchronize(stream_b));
-      HIP_CHECK(hipStreamSynchronize(stream));
-      settle_tables.clear();
-    }
-    const std::vector<uint32_t> host = rth::build_window_table(rth::step_power(n));
-    rtr::DevArray<uint32_t> dev(host.size());
-    HIP_CHECK(hipMemcpy(dev.get(), host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return settle_tables.emplace(n, std::move(dev)).first->second.get();
-  }
+  const uint32_t* settle_table(uint32_t n) { return debt.table(n, stream, stream_b); }
   // pays the debt on the stream that orders behind both trace streams; nothing owed: nothing enqueued
   void settle() {
     std::lock_guard<std::recursive_mutex> lk(order_mu);
-    if (owed_draws == 0u) return;
-    const uint32_t* const table = settle_table(owed_draws);
-    HIP_CHECK(rtk::launch_rng_settle(owe_p, owed_draws, table, main_stream()));
+    if (debt.owed_draws == 0u) return;
+    const uint32_t* const table = settle_table(debt.owed_draws);
+    HIP_CHECK(rtk::launch_rng_settle(debt.owe_p, debt.owed_draws, table, main_stream()));
     ++calls.launches;
-    owed_draws = 0u; owing_launches = 0u; ++settles_enqueued;
-  }
-  void drop_debt() {                           // the states are created anew
-    std::lock_guard<std::recursive_mutex> lk(order_mu);
-    owed_draws = 0u; owing_launches = 0u; owe_key.reset();
-  }
-  // Once per launch of `p.samples` x `p.iters` samples (not per half of a split one), with order_mu held until the
-  // launch is enqueued: hands the launch the two words and advances them by what it will do to every pixel.
-  void take_uniform_state(rtk::TraceParams& p) {
-    if (p.flags & rtk::TRACE_ZERO_ACC) count_now = 0u;
-    p.weyl = weyl_now; p.count = count_now;
-    const uint32_t done = p.samples * (p.iters > 1u ? p.iters : 1u);
-    weyl_now += 362437u * 3u * done;
-    count_now += done;
+    debt.paid(); ++debt.settles_enqueued;
   }
   // RT_BUF_RNG / RT_BUF_COUNTS are about to be read: plane 0 / the counts get the current word, on the stream that
   // orders behind both trace streams (no launch touches either plane).  Skipped when the plane already holds it.
   void materialise(int which) {
     std::lock_guard<std::recursive_mutex> lk(order_mu);
     if (which == RT_BUF_RNG && d_rng.get() != nullptr) settle();
-    if (which == RT_BUF_RNG && !(weyl_plane_ok && weyl_plane == weyl_now) && d_rng.get() != nullptr) {
-      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_rng.get()), static_cast<int>(weyl_now), npix(), main_stream()));
-      weyl_plane = weyl_now; weyl_plane_ok = true;
+    if (which == RT_BUF_RNG && words.weyl_plane_stale() && d_rng.get() != nullptr) {
+      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_rng.get()), static_cast<int>(words.weyl_now), npix(), main_stream()));
+      words.weyl_plane_filled();
     }
-    if (which == RT_BUF_COUNTS && !(count_plane_ok && count_plane == count_now) && d_counts.get() != nullptr) {
-      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_counts.get()), static_cast<int>(count_now), npix(), main_stream()));
-      count_plane = count_now; count_plane_ok = true;
+    if (which == RT_BUF_COUNTS && words.count_plane_stale() && d_counts.get() != nullptr) {
+      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_counts.get()), static_cast<int>(words.count_now), npix(), main_stream()));
+      words.count_plane_filled();
     }
   }
-  rtr::PinnedArray<uint32_t> h_image;       // handed to callbacks
-  rtr::PinnedArray<uint32_t> h_image_alt;   // second image: update i+1 is produced while the callback reads update i
-  uint32_t* image_mirror = nullptr; // rt_tracer_set_image_mirror: second target of emitting rt_tracer_launch* / trace_enqueue launches
-  rtr::Event handoff_event;
-  int handoff_next = 0;             // which of the two host images the next emitting launch of a Trace writes
-  rtr::DevArray<float4> d_tri;      // (e2.xyz,e1.x),(e1.yz,v0.xy) records
-  rtr::DevArray<float> d_tri_b;     // v0.z
-  rtr::DevArray<float4> d_tri_color;
-  rtr::DevArray<float4> d_tri_n;    // 3 unpacked vertex normals per triangle, edge-format scenes only
-  uint32_t n_tris = 0;
-  rtr::DevArray<float4> d_spheres;
-  uint32_t n_spheres = 0;
-  // ray queries: grow-only staging of the host-array entry points, and an event behind every query enqueued (on stream_q or
-  // a caller's stream) that covers all earlier ones -- what uploads and destroy wait for before they free the scene's records
-  rtr::DevArray<float> d_q_rays;
-  rtr::DevArray<uint32_t> d_q_pixels;
-  rtr::DevArray<float4> d_q_hits;
-  rtr::DevArray<float> d_q_segs;      // rt_tracer_occluded: n x 8 floats in, n bytes out
-  rtr::DevArray<uint8_t> d_q_occluded;
-  rtr::DevArray<float4> d_q_dirs;     // rt_tracer_exposure: n_dirs directions in (the points: d_q_segs), n masks out
-  rtr::DevArray<uint64_t> d_q_masks;
-  rtr::DevArray<float4> d_q_all_hits; // rt_tracer_intersect_all: n x max_hits records and n counts out
-  rtr::DevArray<uint32_t> d_q_all_counts;
-  rtr::DevArray<float4> d_q_points;   // rt_tracer_closest_point: n x {x, y, z, d2max} in, n records (d_q_hits) out
-  rtr::DevArray<float4> d_q_after;    // rt_tracer_closest_all: n cursor records in (rows and counts: d_q_all_hits, d_q_all_counts)
-  rtr::DevArray<uint2> d_q_sides;     // rt_tracer_signed_distance, rt_tracer_closest_sides: one rt_side per record out
-  rtr::DevArray<int32_t> d_q_cursors; // rt_tracer_overlap: n x 8 floats (d_q_segs) and n cursors in, n x max_hits prims and n totals
-  rtr::DevArray<int32_t> d_q_prims;   // (d_q_all_counts) out
-  rtr::Event query_done;
-  void wait_queries() { if (query_done) HIP_CHECK(hipEventSynchronize(query_done)); }
-  // RT_QUERY_BVH (rt_bvh_host.hpp, rt_bvh.hpp): the tree of the scene of generation bvh_scene, built by the first query in
-  // that mode after an upload (rt_query_api.hpp, under api_mu).  The buffers are grow-only; a rebuild waits for the queries.
-  uint32_t query_accel = RT_QUERY_SCAN;
-  uint32_t query_slack_milli = 1000u;                 // rt_dbg_query_accel_slack: multiplies the box test's rho
-  uint32_t query_stack_cap = UINT32_MAX;              // rt_dbg_query_stack_cap: an upper limit on the walks' stack entries per lane
-  rtr::DevArray<float4> d_bvh_nodes, d_bvh_records;
-  bool bvh_built = false;
-  uint32_t bvh_scene = 0;                             // scene_generation the tree was built for
-  uint64_t bvh_info[6] = {0, 0, 0, 0, 0, 0};          // nodes, leaves, depth, always-tested, build us, device bytes
-  uint32_t bvh_leaf_records = 0;
-  bool bvh_valid() const { return bvh_built && bvh_scene == scene_generation; }
-  // The signed queries (rt_features_host.hpp, rt_sides.hpp): the host copy of the rows of the last upload, which
-  // the feature table is welded from, and the table of the scene of generation features_scene, built by the first signed query
-  // after an upload (rt_query_api.hpp, under api_mu).  The buffer is grow-only; a rebuild waits for the queries.
-  std::vector<float> scene_rows;                      // 12 floats per triangle, as uploaded
-  bool scene_rows_edges = false;
-  rtr::DevArray<float4> d_features;                   // 7 float4 per triangle
-  bool features_built = false;
-  uint32_t features_scene = 0;
-  uint64_t features_info[6] = {0, 0, 0, 0, 0, 0};     // triangles, welded vertices, edges, contributing triangles, build us, bytes
-  bool features_valid() const { return features_built && features_scene == scene_generation; }
-  // RT_ACCEL_REFIT (rt_refit.hpp): what the next query in RT_QUERY_BVH mode does with a tree of an earlier
-  // upload.  bvh_built stays set across uploads -- the device tree keeps its topology, and its record count decides whether
-  // a refit may replace the build; rt_tracer_query_accel_rebuild clears it.
-  uint32_t accel_update = RT_ACCEL_REBUILD;
-  rtr::DevArray<uint32_t> d_bvh_levels;               // the node indices grouped by level, root first (rtb::Tree::level_nodes)
-  std::vector<uint32_t> bvh_level_begin;              // depth + 1 offsets into it
-  rtr::DevArray<uint64_t> d_refit_out;                // {class-change flag, the cost as a double}
-  rtr::PinnedArray<uint64_t> h_refit_out;
-  rtr::Event refit_begin, refit_end;
-  uint64_t refits = 0, refit_fallbacks = 0, refit_us = 0;   // since the last build; over the tracer's life; the last refit's
-  double bvh_cost = 0.0, bvh_cost_built = 0.0;
-
-  // camera + callbacks (guarded by state_mu; snapshotted per launch like the by-value kernel argument)
-  std::mutex state_mu;
-  rtr::Camera cam;
-  rt_callback_fn update_cb = nullptr; void* update_user = nullptr;
-  rt_callback_fn finished_cb = nullptr; void* finished_user = nullptr;
-
-  // render thread
-  std::mutex api_mu;
-  rtr::RenderThread render;
-  std::atomic<bool> stopped{false};
-  std::atomic<bool> completed{false};
-
-  rtr::LaunchClock clock;
-
-  std::mutex err_mu;
-  std::string last_error;
-  uint32_t last_k = 0, last_chunk = 0, last_lds = 0;
+  bool want_interleave() {
+    if (env.row_interleave >= 0) return env.row_interleave != 0;
+    if (h_half_cost.get() == nullptr) return false;
+    const unsigned long long w = *reinterpret_cast<volatile unsigned long long*>(h_half_cost.get());
+    const double u = static_cast<double>(w & 0xFFFFFFFFull), l = static_cast<double>(w >> 32);
+    if (u + l < 16.0) return rows_interleaved;    // nothing (yet) to go by
+    const double ratio = (u > l ? u : l) / ((u > l ? l : u) + 1.0);
+    return rows_interleaved ? ratio > 1.15 : ratio > 1.25;
+  }
+  uint32_t split_row(uint32_t band_rows) const {   // first row of the lower half of a split launch (a multiple of 8); 0 = not split
+    return (split_launches && band_rows >= 128u) ? ((band_rows / 2u + 7u) / 8u) * 8u : 0u;   // (40 / 45 / 55 / 60 % measured: the halves have to cost the same)
+  }
+  void sync_list_stream() { if (stream_l) HIP_CHECK(hipStreamSynchronize(stream_l)); }
+  // rt_tracer_sync: every stream idle, the next split launch staggered again, the sampled launches enqueued so far accounted
+  void sync_all() {
+    const uint64_t seen = clock.seq_now();           // launches enqueued so far; a running render thread may add more
+    HIP_CHECK(hipStreamSynchronize(main_stream()));
+    sync_list_stream();                              // (nothing the caller could read depends on it; a Sync leaves the device idle)
+    stagger_next = true;
+    clock.drain_before(seen);
+  }
 
   void set_error(const std::string& s) {
     { std::lock_guard<std::mutex> lk(err_mu); last_error = s; }
@@ -715,8 +738,8 @@ struct rt_tracer {
   // every stream idle and every sampled launch accounted (destruction: the owning members release the rest)
   void quiesce() {
     (void)hipSetDevice(device);
-    for (const rtr::Stream* s : {&stream_b, &stream, &stream_l, &stream_q}) if (*s) (void)hipStreamSynchronize(*s);
-    if (query_done) (void)hipEventSynchronize(query_done);
+    for (const rtr::Stream* s : {&stream_b, &stream, &stream_l, &queries.stream_q}) if (*s) (void)hipStreamSynchronize(*s);
+    if (queries.done) (void)hipEventSynchronize(queries.done);
     clock.drain();
   }
 
@@ -729,8 +752,8 @@ struct rt_tracer {
     uint32_t* const tables = rtr::jump_device(device);
     std::lock_guard<std::recursive_mutex> lk(order_mu);
     HIP_CHECK(rtk::launch_rng_init(d_rng.get(), npix(), p0, seeded, tables, tables + rtr::kJumpWords, main_stream()));
-    weyl_now = seeded[0]; weyl_plane_ok = false;                         // (the kernel writes v0..v4)
-    drop_debt();
+    words.weyl_now = seeded[0]; words.weyl_plane_ok = false;                         // (the kernel writes v0..v4)
+    debt.dropped();
   }
 
   void create_buffers() {                                                // ctor :33-40, Resize :96-102
@@ -743,7 +766,7 @@ struct rt_tracer {
     // zero them so that reading before a Trace is defined (the counts: materialise())
     HIP_CHECK(hipMemsetAsync(d_render.get(), 0, n * sizeof(float4), main_stream()));
     HIP_CHECK(hipMemsetAsync(d_image.get(), 0, n * sizeof(uint32_t), main_stream()));
-    { std::lock_guard<std::recursive_mutex> lk(order_mu); count_now = 0u; count_plane_ok = false; }
+    { std::lock_guard<std::recursive_mutex> lk(order_mu); words.count_now = 0u; words.count_plane_ok = false; }
     create_states();
     HIP_CHECK(hipStreamSynchronize(main_stream()));
   }
@@ -809,7 +832,7 @@ struct rt_tracer {
     memset(&p, 0, sizeof p);
     rtr::Camera c;
     { std::lock_guard<std::mutex> lk(state_mu); c = cam; }               // *mCamera by value, :221
-    p.render = d_render.get(); p.rng = d_rng.get();             // (weyl, count: take_uniform_state)
+    p.render = d_render.get(); p.rng = d_rng.get();             // (weyl, count: UniformWords::take)
     p.W = W; p.H = H; p.row0 = row0; p.rows = rows; p.npix = npix(); p.samples = samples;
     for (int col = 0; col < 4; ++col)
       for (int r = 0; r < 3; ++r) p.cam[col * 3 + r] = c.M[col * 4 + r];
@@ -864,11 +887,10 @@ struct rt_tracer {
     return samples >= want ? static_cast<int>(want) : samples >= 2 ? 2 : 1;
   }
 
-  // RunTraceKernel, RayTracerImpl.cu:204-234, without the blocking wait.  `flags` are the
-  // TRACE_* fusions: the first launch after the clear treats the accumulators as zero (no
-  // memset, no accumulator read), a launch whose result is handed out also writes BGRA8.
-  // sync_after: 0 = none, 1 = wait for this launch (the reference's behaviour, :228),
-  // N > 1 = keep at most N launches in flight (wait for the launch N-1 back).
+  // RunTraceKernel, RayTracerImpl.cu:204-234, without the blocking wait.  `flags` are the TRACE_* fusions: the first launch after
+  // the clear treats the accumulators as zero (no memset, no accumulator read), a launch whose result is handed out also writes
+  // BGRA8.  sync_after: 0 = none, 1 = wait for this launch (the reference's behaviour, :228), N > 1 = keep at most N launches in
+  // flight (wait for the launch N-1 back).  One body for the launch's 1 or 2 parts ("Where a trace launch's parts are formed").
   void enqueue_trace_launch(uint32_t samples, uint32_t flags, int sync_after, uint32_t iters = 1,
                             uint32_t* host_image = nullptr, bool allow_split = true) {
     const int K = pick_k(samples);
@@ -882,9 +904,9 @@ struct rt_tracer {
     // Owed draws: the launch owes when its key is that of the launch before it; otherwise the debt is paid first -- before
     // the lists the owing launches read are replaced.
     const std::optional<rtr::OweKey> okey = owe_key_of(p, path);
-    const bool owes = okey && owe_key && memcmp(&*okey, &*owe_key, sizeof(rtr::OweKey)) == 0;
+    const bool owes = debt.owes(okey);
     if (!owes) settle();
-    owe_key = okey;
+    debt.key = okey;
     bool have_lists = false;
     const bool build_lists = prepare_tile_lists(p, path, (flags & rtk::TRACE_ZERO_ACC) != 0u, have_lists);
     attach_sure_table(p, have_lists);
@@ -892,32 +914,27 @@ struct rt_tracer {
     last_k = K; last_chunk = p.chunk;
     // (DenseLists: the LDS of the classifying kernel, what rt_tracer_info has always reported for dense scenes)
     last_lds = rtk::trace_lds_bytes(p, path == rtk::TracePath::DenseLists ? rtk::TracePath::ClassifyForms : path);
-    // Tall frames: upper half on the primary stream, lower half on stream_b (see the fields' comment).
-    // The split row is a multiple of 8, each half is a row band of its own (own tile / macro lists).
+    // The launch's parts: the band on the primary stream or, for tall frames, its upper half there and its lower half on stream_b (see
+    // the fields' comment).  The split row is a multiple of 8, each half is a row band of its own (own tile / macro lists).
     const uint32_t r0 = allow_split ? split_row(p.rows) : 0u;
     rtr::EventPair e;                                                    // sampled launches: timing events (LaunchClock)
     const bool timed = clock.start(sync_after == 1, r0 != 0u, e);
-    take_uniform_state(p);
-    if (owes) { owed_draws += 3u * p.samples * (p.iters > 1u ? p.iters : 1u); ++owing_launches; }   // once per launch, not per half
-    const bool settle_now = owes && owing_launches >= owe_period();       // the periodic settle, behind this launch's kernels
-    const uint32_t* const settle_tab = settle_now ? settle_table(owed_draws) : nullptr;
+    words.take(p);
+    if (owes) debt.add(p);
+    const bool settle_now = owes && debt.settle_due();                    // the periodic settle, behind this launch's kernels
+    const uint32_t* const settle_tab = settle_now ? settle_table(debt.owed_draws) : nullptr;
     ++calls.steps;
     // The list ring's free events ride on this launch's trace kernels when those are the last kernels their streams get
     // before the next build (TileListRing): the launch built its lists -- then the next launch that reads lists builds too,
     // or passes lists.carry() itself and withdraws the event -- and no settle kernel follows.
     const bool last_before_build = build_lists && !settle_now;
-    if (r0 == 0u) {
+    const int n_parts = r0 == 0u ? 1 : 2;
+    rtk::TraceParams part[2] = {p, p};
+    const hipStream_t st[2] = {stream, stream_b};
+    bool stagger = false;
+    if (n_parts == 1) {
       (void)main_stream();                                               // a launch on one stream orders behind both
       if (build_lists) build_tile_lists_ahead(p);
-      lists.attach(p, row0, have_lists);
-      if (timed) { HIP_CHECK(hipEventRecord(e.a, stream)); ++calls.records; }
-      if (have_lists) lists.wait(stream, 0);
-      attach_macro_lists(p, path, 0, stream, (flags & rtk::TRACE_ZERO_ACC) != 0u);   // part of the launch: timed with it
-      HIP_CHECK(rtk::launch_trace(p, fma, filter, path, K, stream, &kernels, lists.carry(0, last_before_build)));
-      ++calls.launches;
-      if (timed) { HIP_CHECK(hipEventRecord(e.b, stream)); ++calls.records; }
-      if (owes) owe_p = p;
-      if (settle_now) { HIP_CHECK(rtk::launch_rng_settle(p, owed_draws, settle_tab, stream)); ++settles_enqueued; ++calls.launches; }
     } else {
       if (a_dirty) fork_b();                                             // (order_mu is held: the steady state takes it once per launch)
       if (build_lists) build_tile_lists_ahead(p);
@@ -926,7 +943,7 @@ struct rt_tracer {
       // (measured at C3: 93 instead of 80 us per step, profiles/r03_phase_regimes.txt).  The first split launch after
       // the tracer was idle therefore lets its second kernel start about half a kernel behind its first (a delay wave, or
       // -- before any kernel has been sampled -- behind the first kernel's end).  Later launches free-run.
-      const bool stagger = stagger_next.exchange(false);
+      stagger = stagger_next.exchange(false);
       // Small scenes: the halves are the band's upper and lower rows or its even and odd block rows (want_interleave()).
       // Dense scenes keep row halves (their macro lists are per half, in macro tiles of 8 block rows).
       const bool interleave = have_lists && want_interleave();
@@ -936,33 +953,33 @@ struct rt_tracer {
         rows_interleaved = interleave;
         if (env.log) fprintf(stderr, "[rt_mi355x] split launches: halves by %s\n", interleave ? "even / odd block rows" : "rows");
       }
-      rtk::TraceParams half[2] = {sub_band(p, 0u, r0), sub_band(p, r0, p.rows - r0)};
-      if (interleave) { half[0] = p; half[1] = p; half[0].row_il = half[1].row_il = 1u; half[1].row_phase = 1u; }
-      hipStream_t st[2] = {stream, stream_b};
-      if (timed) { HIP_CHECK(hipEventRecord(e.a, stream)); ++calls.records; }   // the sampled duration is the upper half-frame kernel's
-      for (int h = 0; h < 2; ++h) {
-        lists.attach(half[h], row0, have_lists);
-        if (have_lists) lists.wait(st[h], h);
-        if (h == 1 && stagger) {
-          // half a kernel behind the upper half: by the clock when the tracer knows how long its half-frame kernels take
-          // (0.45 of the last sampled one), else behind the upper half's end
-          const uint32_t us = static_cast<uint32_t>(clock.last_half_ms() * 450.0f);
-          if (us >= 5u) { HIP_CHECK(rtk::launch_delay(us, stream_b)); ++calls.launches; }
-          else { HIP_CHECK(hipStreamWaitEvent(stream_b, stagger_event, 0)); ++calls.waits; }
-        }
-        const rtk::TracePath half_path = trace_path(half[h]);
-        attach_macro_lists(half[h], half_path, h, st[h], (flags & rtk::TRACE_ZERO_ACC) != 0u);
-        HIP_CHECK(rtk::launch_trace(half[h], fma, filter, half_path, K, st[h], &kernels, lists.carry(h, last_before_build)));
-        ++calls.launches;
-        if (h == 0 && stagger) { HIP_CHECK(hipEventRecord(stagger_event, stream)); ++calls.records; }
-      }
-      if (timed) { HIP_CHECK(hipEventRecord(e.b, stream)); HIP_CHECK(hipEventRecord(e.c, stream_b)); calls.records += 2u; }
-      if (owes) { owe_p = p; lists.attach(owe_p, row0, true); }          // (the band as one launch: settle() orders behind both streams)
-      // each half's tiles on that half's own stream, with the geometry of its trace kernel: no join
-      if (settle_now) for (int h = 0; h < 2; ++h) { HIP_CHECK(rtk::launch_rng_settle(half[h], owed_draws, settle_tab, st[h])); ++settles_enqueued; ++calls.launches; }
-      b_dirty = true;
+      if (interleave) { part[0].row_il = part[1].row_il = 1u; part[1].row_phase = 1u; }
+      else { part[0] = sub_band(p, 0u, r0); part[1] = sub_band(p, r0, p.rows - r0); }
     }
-    if (settle_now) { owed_draws = 0u; owing_launches = 0u; }
+    if (timed) { HIP_CHECK(hipEventRecord(e.a, stream)); ++calls.records; }   // (of a split launch the sampled duration is the upper half-frame kernel's)
+    for (int h = 0; h < n_parts; ++h) {
+      lists.attach(part[h], row0, have_lists);
+      if (have_lists) lists.wait(st[h], h);
+      if (h == 1 && stagger) {
+        // half a kernel behind the upper half: by the clock when the tracer knows how long its half-frame kernels take
+        // (0.45 of the last sampled one), else behind the upper half's end
+        const uint32_t us = static_cast<uint32_t>(clock.last_half_ms() * 450.0f);
+        if (us >= 5u) { HIP_CHECK(rtk::launch_delay(us, stream_b)); ++calls.launches; }
+        else { HIP_CHECK(hipStreamWaitEvent(stream_b, stagger_event, 0)); ++calls.waits; }
+      }
+      const rtk::TracePath part_path = trace_path(part[h]);              // (a half's rows decide whether its wave lists fit)
+      attach_macro_lists(part[h], part_path, h, st[h], (flags & rtk::TRACE_ZERO_ACC) != 0u);   // part of the launch: timed with it
+      // (one part: no lists.carry(1, ..) -- main_stream() withdrew what stream_b's last kernel carried)
+      HIP_CHECK(rtk::launch_trace(part[h], fma, filter, part_path, K, st[h], &kernels, lists.carry(h, last_before_build)));
+      ++calls.launches;
+      if (h == 0 && stagger) { HIP_CHECK(hipEventRecord(stagger_event, stream)); ++calls.records; }
+    }
+    for (int h = 0; timed && h < n_parts; ++h) { HIP_CHECK(hipEventRecord(h == 0 ? e.b : e.c, st[h])); ++calls.records; }
+    if (owes) { debt.owe_p = p; lists.attach(debt.owe_p, row0, true); }  // (the band as one launch: settle() orders behind both streams)
+    // the periodic settle: each part's tiles on that part's own stream, with the geometry of its trace kernel: no join
+    for (int h = 0; settle_now && h < n_parts; ++h) { HIP_CHECK(rtk::launch_rng_settle(part[h], debt.owed_draws, settle_tab, st[h])); ++debt.settles_enqueued; ++calls.launches; }
+    if (settle_now) debt.paid();
+    if (n_parts == 2) b_dirty = true;
     uniform_lk.unlock();
     if (timed) clock.enqueued(std::move(e), sync_after);
   }
@@ -981,12 +998,12 @@ struct rt_tracer {
   void clear_accumulators() {                                            // :242-243
     std::lock_guard<std::recursive_mutex> lk(order_mu);
     HIP_CHECK(hipMemsetAsync(d_render.get(), 0, static_cast<size_t>(npix()) * sizeof(float4), main_stream()));
-    count_now = 0u;                                                      // (the count buffer: materialise())
+    words.count_now = 0u;                                                      // (the count buffer: materialise())
   }
 
   void convert() {                                                       // RunConverterKernel :189-202
     std::lock_guard<std::recursive_mutex> lk(order_mu);
-    HIP_CHECK(rtk::launch_convert(d_render.get(), count_now, d_image.get(), npix(), main_stream()));
+    HIP_CHECK(rtk::launch_convert(d_render.get(), words.count_now, d_image.get(), npix(), main_stream()));
   }
 
   // Waits for a stream with the host polling: the end of a Trace is latency, not throughput (the reference's caller re-traces
@@ -1008,45 +1025,6 @@ struct rt_tracer {
                              hipMemcpyDeviceToHost, main_stream()));
     HIP_CHECK(hipStreamSynchronize(main_stream()));                             // :259,:287
   }
-
-  // Candidate lists + certain-winner verdicts of the small scenes' tiles (TracePath::SmallLists): built by tile_lists_kernel
-  // on stream_l into the next slot of a ring, ahead of the launch that needs them, and kept while camera snapshot, lens,
-  // scene, frame, list length and arithmetic mode are unchanged (lists.key; they do not depend on the samples).  The first
-  // launch of a Trace rebuilds them when lists are not kept across Traces (reuse_across_traces: bench.py's headline).
-  rtr::TileListRing lists;            // small scenes: the tile lists, built ahead on stream_l
-  rtr::Event stagger_event;
-  std::atomic<bool> stagger_next{true};   // the next split launch starts from an idle tracer: stagger its halves (enqueue_trace_launch)
-  // Which halves a split small-scene launch uses: the band's upper and lower rows (best when the two cost the same: C3 61.0
-  // against 62.2 us per step) or its even and odd block rows (the same cost whatever the picture: a tilted camera with 57 % /
-  // 22 % ray-generating tiles above / below the split 62.6 against 70.5 us).  The two-level list builder counts the
-  // ray-generating tiles per half and publishes the pair to pinned host memory behind every build; the enqueueing thread
-  // reads the latest pair (a few launches old: the picture does not jump) and switches with hysteresis -- a switch moves
-  // pixels from one stream to the other, so both streams are joined first.
-  rtr::DevArray<uint32_t> d_half_cost;                // two device counters
-  rtr::PinnedArray<unsigned long long> h_half_cost;   // upper | lower << 32 of the latest finished build
-  bool rows_interleaved = false;
-  bool want_interleave() {
-    if (env.row_interleave >= 0) return env.row_interleave != 0;
-    if (h_half_cost.get() == nullptr) return false;
-    const unsigned long long w = *reinterpret_cast<volatile unsigned long long*>(h_half_cost.get());
-    const double u = static_cast<double>(w & 0xFFFFFFFFull), l = static_cast<double>(w >> 32);
-    if (u + l < 16.0) return rows_interleaved;    // nothing (yet) to go by
-    const double ratio = (u > l ? u : l) / ((u > l ? l : u) + 1.0);
-    return rows_interleaved ? ratio > 1.15 : ratio > 1.25;
-  }
-  uint32_t split_row(uint32_t band_rows) const {   // first row of the lower half of a split launch (a multiple of 8); 0 = not split
-    return (split_launches && band_rows >= 128u) ? ((band_rows / 2u + 7u) / 8u) * 8u : 0u;   // (40 / 45 / 55 / 60 % measured: the halves have to cost the same)
-  }
-  void sync_list_stream() { if (stream_l) HIP_CHECK(hipStreamSynchronize(stream_l)); }
-  // rt_tracer_sync: every stream idle, the next split launch staggered again, the sampled launches enqueued so far accounted
-  void sync_all() {
-    const uint64_t seen = clock.seq_now();           // launches enqueued so far; a running render thread may add more
-    HIP_CHECK(hipStreamSynchronize(main_stream()));
-    sync_list_stream();                              // (nothing the caller could read depends on it; a Sync leaves the device idle)
-    stagger_next = true;
-    clock.drain_before(seen);
-  }
-  uint32_t scene_generation = 0;
 
   // the key of lists built for launch `p`; bin_word: the list length (tile lists) or the macro geometry (macro lists)
   rtr::ListKey make_key(const rtk::TraceParams& p, uint32_t bin_word) const {
@@ -1075,9 +1053,6 @@ struct rt_tracer {
   // Small scenes: the per-triangle table of what a certain-winner pixel accumulates in a launch of `samples` samples
   // (rtk::sure_table_kernel), rebuilt when the sample count or the scene changed.  Built on the stream that orders behind
   // both trace streams: earlier launches may still read the previous table.
-  rtr::DevArray<float4> d_sure_table;
-  uint32_t sure_table_samples = 0;
-  uint64_t sure_table_scene = ~0ull;
   void attach_sure_table(rtk::TraceParams& p, bool have) {
     p.sure_table = nullptr;
     if (!have || env.no_sure_table || p.n_tris == 0u) return;
@@ -1113,7 +1088,7 @@ struct rt_tracer {
   // instrumented launches of rt_tracer_trace_stats and rt_dbg_trace_timeline).
   void launch_instrumented(rtk::TraceParams& p, uint32_t samples) {
     const rtk::TracePath path = trace_path(p);
-    { std::lock_guard<std::recursive_mutex> lk(order_mu); settle(); owe_key.reset(); }   // (it rebuilds the lists in place and advances every state)
+    { std::lock_guard<std::recursive_mutex> lk(order_mu); settle(); debt.key.reset(); }   // (it rebuilds the lists in place and advances every state)
     bool have_lists = false;
     (void)prepare_tile_lists(p, path, true, have_lists);
     sync_list_stream();
@@ -1122,7 +1097,7 @@ struct rt_tracer {
     attach_macro_lists(p, path, 0, main_stream());
     {
       std::lock_guard<std::recursive_mutex> lk(order_mu);
-      take_uniform_state(p);
+      words.take(p);
       HIP_CHECK(rtk::launch_trace(p, fma, filter, path, pick_k(samples), main_stream(), &kernels));
     }
     HIP_CHECK(hipStreamSynchronize(main_stream()));
@@ -1131,25 +1106,6 @@ struct rt_tracer {
   // Macro level of the classification (scenes that do not fit the per-wave list): sizes the
   // lists, points the launch at them and runs macro_bin_kernel on the stream ahead of the trace
   // launch.  Every launch re-bins (the camera may have changed; the pass costs N x macro tiles tests).
-  rtr::HalfLists half_lists[2];       // one per half of a split launch
-  bool macro = true;                  // RT_FLAG_NO_MACRO_BINS turns it off
-  bool pretest = true;                // RT_MI355X_NO_PRETEST=1 turns the per-sample forms off
-  bool sure_hit = true;               // RT_FLAG_NO_SURE_HIT: tiles of one certainly-hit triangle run the tests anyway
-  // Stored tile candidate lists (small scenes) survive from one Trace to the next while camera, lens, scene,
-  // frame and arithmetic mode are unchanged -- like any acceleration structure that is rebuilt only when its
-  // inputs change.  rt_tracer_set_list_reuse(t, 0) restricts the reuse to the launches of one Trace.
-  bool reuse_across_traces = true;
-  // the forms pay for themselves on dense scenes only (break-even ~3000 triangles at 1080p; C4: -13 %)
-  static constexpr uint32_t kPretestMinTris = 4096;
-  static constexpr uint32_t kMacroW = 128, kMacroH = 64, kMacroCapMax = 65536;
-  // Dense scenes: a level above the macro tiles (super tiles of kSuperF x kSuperF of them, super_bin_kernel) so that a macro
-  // tile tests its super tile's lists instead of the scene (rt_lists.hpp): C4 10.2 M -> ~1.5 M triangle tests per rebuild.
-#ifndef RT_SUPER_F
-#define RT_SUPER_F 4
-#endif
-  static constexpr uint32_t kSuperF = RT_SUPER_F, kSuperMinTris = 2048;
-  bool super_level = true;            // RT_FLAG_NO_SUPER_BINS turns it off
-
   // Like the small scenes' tile lists the macro lists depend on camera, scene and frame only: a launch re-bins when one of
   // them changed since the lists of this half were built (HalfLists::macro_key) -- or when it is the first launch of a Trace
   // and the lists are not kept across Traces (bench.py's headline: every step bins afresh) -- and reads the kept lists

@@ -203,6 +203,35 @@ def test_ring_events_are_not_calls_of_their_own(R, orc):
     p.g.close()
 
 
+# The runtime calls of 32 counted steps behind 16 uncounted ones, as the library of the commit before the launch's one body
+# issued them (two runs of this sequence with it, selected by RT_MI355X_LIB, agreed in every key).
+CALLS_OF_32_STEPS = {
+    "one_part": (TINY, None, dict(steps=32, launches=66, records=20, waits=48, ready_records=0, free_records=16, stop_events=8, calls=134)),
+    "row_halves": (SPLIT, "0", dict(steps=32, launches=100, records=6, waits=80, ready_records=0, free_records=0, stop_events=16, calls=186)),
+    "block_rows": (SPLIT, "1", dict(steps=32, launches=100, records=6, waits=80, ready_records=0, free_records=0, stop_events=16, calls=186)),
+}
+
+
+@pytest.mark.parametrize("shape", list(CALLS_OF_32_STEPS))
+def test_every_runtime_call_of_32_steps(R, orc, monkeypatch, shape):
+    """Case 7: every counter of DebugEnqueueCalls() for each launch shape enqueue_trace_launch's one body serves -- one part on
+    one stream, two row halves, two halves of interleaved block rows -- over 32 steps with list reuse off behind 16 steps
+    that are not counted.  The 32 steps hold eight builds that need free events, two timing-sampled launches and two periodic
+    settles."""
+    size, interleave, expected = CALLS_OF_32_STEPS[shape]
+    if interleave is not None:
+        monkeypatch.setenv("RT_MI355X_ROW_INTERLEAVE", interleave)
+    p = Pair(R, orc, True, size)
+    p.steps(16)
+    p.g.DebugEnqueueCalls()                                              # (no Sync: it would put the streams' join in between)
+    p.steps_n(32)
+    c = p.g.DebugEnqueueCalls()
+    print("runtime calls over 32 steps, %s:" % shape, c)
+    assert c == expected
+    p.check("after the counted steps, " + shape)
+    p.g.close()
+
+
 if __name__ == "__main__":                                              # the child of test_settles_behind_the_trace_kernels
     assert sys.argv[1] == "owe8" and os.environ.get("RT_MI355X_OWE_PERIOD") == "8"
     import raytracertest_amd as rt

@@ -1,4 +1,4 @@
-"""Owed RNG draws (rt_tracer.hpp: owed_draws, settle; rt_rng_settle.hip).  A small-scene launch whose key equals that of the
+"""Owed RNG draws (rt_tracer.hpp: RngDebt::owed_draws, rt_tracer::settle; rt_rng_settle.hip).  A small-scene launch whose key equals that of the
 launch before it leaves the RNG states of its certain-winner tiles alone and the tracer owes them the draws; whoever needs
 the states -- a reader, a launch under another key, another kernel, every RT_MI355X_OWE_PERIOD-th owing launch -- has them
 advanced first.  Nothing observable may change: after every step of the scenarios below RngStates(), RenderBuffer(),

@@ -1,5 +1,5 @@
-"""Every query in a row on ONE tracer: what the entry points share -- the staging buffers (d_q_hits under Intersect, Pick,
-ClosestPoint and SignedDistance; d_q_all_hits under IntersectAll, ClosestAll and ClosestSides; all grow-only), the one event
+"""Every query in a row on ONE tracer: what the entry points share -- the four staging buffers (QueryState::in[2] and
+::out[2], typed at each call: out[0] holds hits, rows of hits, bytes, masks, prims or sides in turn; all grow-only), the one event
 behind every launch and the one forward of a sharded handle -- must leave each answer as a fresh tracer that made only that
 call gives it, byte for byte: in the scan and the BVH mode, for a smaller batch after a larger one, through the torch tensor
 paths on the current stream, and on two bands.  The other suites pin the fresh answers to the oracle and the helpers."""

@@ -1,6 +1,6 @@
 """The XORWOW Weyl word and the sample count are the same for every pixel of a tracer (tests/test_uniform_state_premise.py),
 so the launches carry them as scalars and the tracer fills plane 0 of RT_BUF_RNG and RT_BUF_COUNTS only when somebody reads
-them (rt_tracer.hpp: take_uniform_state, materialise).  Here: after every step of sequences that go through every way the
+them (rt_tracer.hpp: UniformWords::take, rt_tracer::materialise).  Here: after every step of sequences that go through every way the
 state advances or resets, RngStates() (all six planes), SampleCounts() and the accumulators equal the oracle's bit for bit."""
 import ctypes as C
 

@@ -1,4 +1,4 @@
-"""The premise of carrying two words of the per-pixel state as scalars (rt_tracer.hpp: weyl_now, count_now), pinned to
+"""The premise of carrying two words of the per-pixel state as scalars (rt_tracer.hpp: UniformWords::weyl_now, ::count_now), pinned to
 the reference's arithmetic on the CPU oracle:
 
   * the XORWOW Weyl word d (word 0 of a pixel's RNG state) is the same for every pixel of a band and equals
