@@ -218,6 +218,22 @@ public:
     if (!Overlap(boxes, maxHits, prims, counts)) counts.clear();
     return counts;
   }
+  // Swept query (rt_mi355x.h, rt_tracer_sphere_cast): sweeps holds 8 floats per sweep -- origin, direction (used as given), the
+  // sphere's radius, tmax; the centre runs along o + t*d for 0 <= t <= tmax.  hits[i].t = the time of first contact, u, v the
+  // barycentrics of the contact point on triangle prim (0, 0 for a sphere), prim = RT_PRIM_NONE when nothing is touched.  A
+  // reported contact is within RT_SWEEP_SLACK * (max|c| + r) of touching.  A vector whose size is no multiple of 8: false,
+  // hits untouched.
+  bool SphereCast(const std::vector<float>& sweeps, std::vector<rt_hit>& hits) {
+    if (!mImpl || sweeps.size() % 8 != 0) return false;
+    hits.resize(sweeps.size() / 8);
+    return rt_tracer_sphere_cast(mImpl, sweeps.data(), hits.size(), hits.data()) == RT_OK;
+  }
+  // The same, returning the hits: empty when the vector was rejected or the call failed (LastError()).
+  std::vector<rt_hit> SphereCast(const std::vector<float>& sweeps) {
+    std::vector<rt_hit> hits;
+    if (!SphereCast(sweeps, hits)) hits.clear();
+    return hits;
+  }
   // Signed point query (rt_mi355x.h, rt_tracer_signed_distance): the same points; hits is ClosestPoint's answer bit for bit,
   // sides[i].s > 0 in front of the nearest surface (outside a closed, outward-wound mesh), < 0 behind it, 0 on it or undecided;
   // sides[i].feature names the face, vertex or edge that holds the nearest point (RT_FEATURE_SPHERE for a sphere,

@@ -659,6 +659,74 @@ int  rt_tracer_overlap_device(rt_tracer* t, const float* boxes, const int32_t* a
  * root (the device of band 0) with RCCL over xGMI (grouped ncclSend / ncclRecv; tiles of bands on the root
  * device are written in place by the trace kernel) and handed to the host from there. */
 
+/* ---- swept queries -------------------------------------------------------------------------------
+ * A sphere of radius r moves from o along d: when and where does it first touch the tracer's scene (collision of a moving body --
+ * a camera or character controller, a projectile with a size; clearance along a path; sphere-trace style marching against a mesh).
+ *   sweeps      n x 8 floats with the slots of an rt_tracer_occluded segment: origin xyz, direction xyz (used as given, NOT
+ *               normalised), the RADIUS r in the tmin slot, tmax.  The sphere's centre is c(t) = o + t*d for 0 <= t <= tmax.
+ *               Accepted: r >= 0 and finite, tmax >= 0 (+inf allowed).  A NaN, negative or infinite r, or a NaN or negative tmax,
+ *               accepts nothing.  NaN, infinite or zero directions and origins get whatever the arithmetic below gives.
+ *   hits        hits[i] = rt_hit with t = the time of first contact, u, v = the barycentrics of the contact point (the nearest
+ *               point of the winning triangle to c(t): v0 + u*e1 + v*e2 of its record; 0, 0 for a sphere), prim as in the other
+ *               queries (a triangle's upload index; n_tris + i for sphere i).  No contact: {0, 0, 0, RT_PRIM_NONE}.
+ *   sides       contact is two-sided: no winding, no culling, no hit rule (RT_FLAG_NEAREST_HIT plays no part), as in the point
+ *               queries.  A zero-area triangle collides as the segment or point it is.
+ *   arithmetic  one in RT_MATH_FMA and RT_MATH_STRICT: every operation is one separately rounded fp32 operation, division and sqrt
+ *               correctly rounded, dot products (x*x' + y*y') + z*z', cross products (a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x,
+ *               a.x*b.y - b.x*a.y), min is IEEE minNum.  "closest(p)" below is the triangle rule of rt_tracer_closest_point on the
+ *               same record, giving (t, u, v).
+ *   triangle    on the record the renderer intersects (v0, e1, e2; for edge-format scenes the uploaded rows), with rr = r*r,
+ *               dd = d.d, w = o - v0, wb = w - e1, wc = w - e2:
+ *                 1. Start overlap.  closest(o).t <= rr: the contact is t = 0 with that evaluation's (u, v).
+ *                 2. Otherwise the smallest of seven entry roots, each +inf where its conditions fail (any NaN fails them):
+ *                    ball(m, g, a, q), the line m + t*g against the ball of squared radius q about the origin, a = g.g:
+ *                        b = -(m.g),  l = m + (b/a)*g per component,  disc = q - l.l,  t = (m.m - q) / (b + sqrt(a*disc));
+ *                        conditions  b > 0 && disc >= 0 && t > 0.
+ *                    cyl(m, e), the cylinder of radius r about the edge from m's origin along e:
+ *                        ee = e.e,  s0 = (m.e)/ee,  sd = (d.e)/ee,  m' = m - s0*e,  d' = d - sd*e per component,
+ *                        t = ball(m', d', d'.d', rr),  s = s0 + t*sd;  conditions  0 <= s && s <= 1.
+ *                    face, the triangle moved by r along its unit normal to the side the origin is on:
+ *                        n = e1 x e2,  nn = n.n,  h = n.w,  dn = n.d,  num = |h| - r*sqrt(nn),  den = (h >= 0 ? -dn : dn),
+ *                        t = num/den,  q = w + t*d per component,  u = ((q x e2).n)/nn,  v = ((e1 x q).n)/nn;
+ *                        conditions  num > 0 && den > 0 && t > 0 && u >= 0 && v >= 0 && u + v <= 1.
+ *                    t = min(face, cyl(w, e1), cyl(w, e2), cyl(wb, e2 - e1), ball(w, d, dd, rr), ball(wb, d, dd, rr),
+ *                    ball(wc, d, dd, rr)).  The union's first entry is the minimum over the pieces; the prism's side faces and the
+ *                    cylinders' caps lie inside the edge and vertex pieces and need no test.  t = +inf: no contact.
+ *                 3. Certification.  c = o + t*d per component (the product, then the sum); s = RT_SWEEP_SLACK * (max|c_i| + r);
+ *                    accepted only if closest(c).t <= (r + s)*(r + s); (u, v) are that evaluation's.  A triangle whose smallest
+ *                    root fails yields no contact; its later roots are not tried.
+ *                 4. t <= tmax.
+ *   sphere      a sphere of the scene is its surface, as in rt_tracer_overlap.  Centre C, radius R, w = o - C, ww = w.w,
+ *               dist = sqrt(ww), s0 = |dist - R|:
+ *                 start overlap when s0*s0 <= rr (t = 0);
+ *                 else when dist > R: t = ball(w, d, dd, (R + r)*(R + r));
+ *                 else when dist < R && r < R, the EXIT root against ri = R - r: b, l as in ball, disc = ri*ri - l.l,
+ *                   sq = sqrt(dd*disc), t = (b > 0 ? (b + sq)/dd : (ri*ri - ww)/(sq - b)); conditions disc >= 0 && t > 0;
+ *                 certified by c and s as above and  s1 = |sqrt((c - C).(c - C)) - R|,  s1*s1 <= (r + s)*(r + s);  then t <= tmax.
+ *   winner      the accepted contact with the smallest (t, prim): equal t (==) goes to the lowest prim.  No visiting order is named.
+ *   slack       RT_SWEEP_SLACK is part of the contract: a reported contact is never farther than s from touching (by the point
+ *               query's own arithmetic at c); a graze within s may be reported as a miss.  It is the smallest power of two at least
+ *               four times the largest residual measured (tests/test_spherecast_expect.py measures it again).
+ * No scene: every answer is RT_PRIM_NONE; spheres alone can answer; n = 0 is a no-op; a NULL array with n > 0 is RT_ERR_INVALID.
+ * Scheduling is that of the other queries: never cancels or joins a running Trace, serialised with the other calls, on the query
+ * stream or the caller's, waited for by uploads and destroy; a multi-device handle answers from its first band, a band tracer
+ * locally.
+ * RT_QUERY_SCAN (default): every sweep tests every primitive.  RT_QUERY_BVH: the ray queries' tree (built, or under RT_ACCEL_REFIT
+ * refitted, by the first query after an upload), walked nearest box first, bit for bit the scan's answer with NO conditioning
+ * clause: an accepted contact is certified to lie within r + s of its record, so the line's span through a child's box grown by
+ * r + 4*RT_SWEEP_SLACK*(cmax + r) + rho_s*(max|o| + cmax + r) contains its t, however ill conditioned the root was; a child is
+ * skipped only when that span is empty, ends before t = 0 or begins STRICTLY after min(best t, tmax).  A sweep with a non-finite
+ * component or a zero direction takes no pruning decision (rt_dbg_query_accel_slack scales the allowance beyond r). */
+/* Host arrays: sweeps n*8, hits n.  Returns with the answers in host memory. */
+int  rt_tracer_sphere_cast(rt_tracer* t, const float* sweeps, size_t n, rt_hit* hits);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  sweeps and hits must be 16-byte aligned; otherwise RT_ERR_INVALID. */
+int  rt_tracer_sphere_cast_device(rt_tracer* t, const float* sweeps, size_t n, rt_hit* hits, void* stream);
+#define RT_SWEEP_SLACK 0.00048828125f   /* 2^-11 */
+/* (The swept queries stand behind the banner of the sharded frame and before its entry points: what lies between the region
+ * queries' banner and that banner is the region queries' text alone, which tests/test_overlap_abi.py reads as one section.) */
+
+/* ---- one frame sharded over several GPUs, continued: the entry points --------------------------- */
 /* Same constructor, device list added: band k runs on devices[k] (ordinals may repeat: several bands per
  * device).  The handle is an rt_tracer like any other -- Trace / Stop / Resize / SetCameraParameters /
  * RotateCamera / UploadScene / callbacks keep their meaning, the callbacks receive the WHOLE frame (pinned

@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "rt_tracer_signed_distance", "rt_tracer_signed_distance_device",
     "rt_tracer_closest_sides", "rt_tracer_closest_sides_device", "rt_dbg_feature_normals",
     "rt_tracer_overlap", "rt_tracer_overlap_device",
+    "rt_tracer_sphere_cast", "rt_tracer_sphere_cast_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
     "rt_tracer_set_query_accel_update", "rt_tracer_query_accel_rebuild", "rt_tracer_query_accel_update_info",
     "rt_dbg_bvh_refit", "rt_dbg_query_tree_read", "rt_dbg_bvh_tree_cost", "rt_dbg_query_stack_cap",
@@ -70,6 +71,7 @@ class RtError(RuntimeError):
 PRIM_NONE = -1
 RT_MAX_HITS = 16         # rt_tracer_intersect_all: the longest row
 RT_MAX_DIRS = 64         # rt_tracer_exposure: the longest direction table (one lane per direction)
+RT_SWEEP_SLACK = np.float32(2.0 ** -11)   # rt_tracer_sphere_cast: a contact is within RT_SWEEP_SLACK * (max|c| + r) of touching
 EXPOSURE_LOCAL, EXPOSURE_WORLD = 0, 1
 QUERY_SCAN, QUERY_BVH = 0, 1
 ACCEL_REBUILD, ACCEL_REFIT = 0, 1        # rt_tracer_set_query_accel_update: what an upload does to the tree of QUERY_BVH
@@ -362,6 +364,9 @@ def load_library():
         L.rt_tracer_closest_sides_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
         L.rt_tracer_overlap.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
         L.rt_tracer_overlap_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
+        if hasattr(L, "rt_tracer_sphere_cast"):           # (an older build selected by RT_MI355X_LIB for an A/B has no swept query)
+            L.rt_tracer_sphere_cast.argtypes = [vp, vp, C.c_size_t, vp]
+            L.rt_tracer_sphere_cast_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.rt_dbg_feature_normals.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
         L.rt_tracer_set_query_accel.argtypes = [vp, C.c_uint32]
         L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -1280,6 +1285,57 @@ class RayTracer:
         segs = np.empty((a.shape[0], 8), np.float32)
         segs[:, :3], segs[:, 3:6], segs[:, 6], segs[:, 7] = a, b - a, np.float32(tmin), np.float32(tmax)
         return ~self.Occluded(segs)
+
+    # ---- swept queries (rt_tracer_sphere_cast / _device) ---------------------------------------------------------------
+
+    def SphereCast(self, sweeps):
+        """A moving sphere's first contact (rt_tracer_sphere_cast).  sweeps: (n, 8) float32 {origin, direction (used as given),
+        radius, tmax}: the centre runs along o + t*d for 0 <= t <= tmax.  The answer's t is the time of first contact, u, v the
+        barycentrics of the contact point on the winning triangle (0, 0 for a sphere), prim PRIM_NONE where nothing is touched;
+        a reported contact is within RT_SWEEP_SLACK * (max|c| + r) of touching.  A numpy array -> HIT_DTYPE array, on return.
+        A contiguous torch float32 tensor on the tracer's device -> (n, 4) float32 tensor {t, u, v, bits of prim}, enqueued on
+        torch.cuda.current_stream() without a host synchronisation."""
+        if type(sweeps).__module__.startswith("torch"):
+            return self._sphere_cast_tensor(sweeps)
+        s = self._segs_array("SphereCast", sweeps)
+        hits = np.zeros(s.shape[0], HIT_DTYPE)
+        self._check(self._lib.rt_tracer_sphere_cast(self._h, s.ctypes.data, s.shape[0], hits.ctypes.data))
+        return hits
+
+    def _sphere_cast_tensor(self, sweeps):
+        import torch
+        _, stream = self._segs_tensor("SphereCast", sweeps)
+        hits = torch.empty((sweeps.shape[0], 4), dtype=torch.float32, device=sweeps.device)
+        self._check(self._lib.rt_tracer_sphere_cast_device(self._h, sweeps.data_ptr(), sweeps.shape[0], hits.data_ptr(), stream))
+        return hits
+
+    def SphereCastContacts(self, sweeps, hits):
+        """Where the contacts of a SphereCast call are (host numpy): the sphere's centre at contact c = o + t*d (fp32, the
+        product, then the sum), the contact position on the surface (ClosestPositions' arithmetic at c) and the unit normal
+        (centre - position) / |centre - position| pointing from the surface to the sphere, each (n, 3) float32; NaN where
+        hits["prim"] is PRIM_NONE (and a NaN normal where centre and position coincide)."""
+        s = self._segs_array("SphereCastContacts", sweeps)
+        h = np.asarray(hits).reshape(-1)
+        if h.dtype != HIT_DTYPE or h.shape[0] != s.shape[0]:
+            raise ValueError("SphereCastContacts: expected the sweeps and the HIT_DTYPE answers of one SphereCast call")
+        with np.errstate(all="ignore"):
+            centre = s[:, 0:3] + h["t"][:, None] * s[:, 3:6]
+            centre[h["prim"] < 0] = np.nan
+            position = self.ClosestPositions(centre, h)
+            w = centre - position
+            normal = w / np.sqrt((w * w).sum(axis=1, dtype=np.float32))[:, None]
+        return centre, position, normal
+
+    def Clearance(self, a, b, radius):
+        """Does a sphere of `radius` (a scalar or one per pair) fit along the segment from a[i] to b[i] ((n, 3) each)?  True
+        where SphereCast of o = a, d = b - a (fp32, on the host), tmax = 1 reports no contact: the swept counterpart of Visible."""
+        a = np.asarray(a, np.float32).reshape(-1, 3)
+        b = np.asarray(b, np.float32).reshape(-1, 3)
+        if a.shape != b.shape:
+            raise ValueError("Clearance: %d start points, %d end points" % (a.shape[0], b.shape[0]))
+        sweeps = np.empty((a.shape[0], 8), np.float32)
+        sweeps[:, :3], sweeps[:, 3:6], sweeps[:, 6], sweeps[:, 7] = a, b - a, np.asarray(radius, np.float32), np.float32(1.0)
+        return self.SphereCast(sweeps)["prim"] < 0
 
     def SetQueryAcceleration(self, mode):
         """How Intersect / Pick / FocusAt find their hits: QUERY_SCAN (0 / False, the default: every ray scans every triangle)

@@ -1,6 +1,6 @@
 """Headless front end: `python -m raytracertest_amd.cli`.  The reference's command line
 (OpenGLView/App.cpp:62-184: -w -h -s -i -u -cx -cy -cz -cxa -cya -f -l -a, integer values,
-defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --focus; the image is saved
+defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --spherecast / --focus; the image is saved
 in the reference's BMP format (Common/Bitmap.h).  Same options as tools/rt_cli.cpp."""
 import argparse
 import math
@@ -55,7 +55,10 @@ def build_parser():
     p.add_argument("--overlap", type=_overlap, default=None, metavar="X0,Y0,Z0,X1,Y1,Z1[,K]",
                    help="print `overlap count`, the number of primitives that touch the box with the corners X0,Y0,Z0 and X1,Y1,Z1, "
                         "then one line `prim` for each of the K lowest (default 8)")
-    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --focus through the scene's BVH instead of the scan")
+    p.add_argument("--spherecast", type=_spherecast, default=None, metavar="X,Y,Z,DX,DY,DZ,R[,TMAX]",
+                   help="print `spherecast prim t u v x y z`: the first contact of a sphere of radius R whose centre moves from X,Y,Z "
+                        "along DX,DY,DZ (used as given) for 0 <= t <= TMAX (default unbounded), and the contact point")
+    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --spherecast / --focus through the scene's BVH instead of the scan")
     p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
                    help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
     return p
@@ -110,6 +113,13 @@ def _overlap(s):
     if k < 0:
         raise ValueError(s)
     return tuple(float(x) for x in v[:6]) + (k,)
+
+
+def _spherecast(s):
+    v = [float(x) for x in s.split(",")]
+    if len(v) not in (7, 8):
+        raise ValueError(s)
+    return tuple(v[:7]) + (v[7] if len(v) == 8 else math.inf,)
 
 
 class _Nearest(argparse.Action):
@@ -212,6 +222,14 @@ def main(argv=None):
         print("overlap %d" % counts[0])
         for prim in prims[0, :min(int(counts[0]), a.overlap[6])]:
             print("%d" % prim)
+    if a.spherecast is not None:
+        sw = np.float32([a.spherecast])
+        h = g.SphereCast(sw)
+        if h["prim"][0] < 0:
+            print("spherecast -1")
+        else:
+            q = g.SphereCastContacts(sw, h)[1][0]
+            print("spherecast %d %.9g %.9g %.9g %.9g %.9g %.9g" % (h["prim"][0], h["t"][0], h["u"][0], h["v"][0], q[0], q[1], q[2]))
     if a.focus is not None:
         try:
             f = g.FocusAt(*a.focus)

@@ -213,6 +213,15 @@ hipError_t launch_nearest(const TraceParams& p, const BvhParams* b, float rho_c,
 hipError_t launch_overlap(const TraceParams& p, const BvhParams* b, uint32_t n, const float* boxes, const int* after, uint32_t max_hits,
                           int* prims, uint32_t* counts, hipStream_t st);
 
+// The swept query (rt_spherecast.hpp): n sweeps {origin xyz, direction xyz, radius, tmax}, 16-byte aligned; hits[i] = {t of the
+// first contact, u, v of the contact point, bits of the int32 primitive} of the smallest (t, prim) among the certified contacts
+// with t <= tmax, or {0, 0, 0, -1}.  One arithmetic for both math modes; one sweep per lane in both forms.  slack: the tracer's
+// (rt_dbg_query_accel_slack / 1000), which scales the walk's allowance beyond r (the scan does not read it).
+constexpr float kSweepSlack = 0.00048828125f;   // RT_SWEEP_SLACK = 2^-11 (include/rt_mi355x.h)
+#define RT_SWEEP_RHO 1.52587890625e-05f        // rho_s = 2^-16: DESIGN.md 4.3k derives it
+hipError_t launch_sphere_cast(const TraceParams& p, const BvhParams* b, float slack, uint32_t n, const float* sweeps, float4* hits,
+                              hipStream_t st);
+
 // The side post-pass (rt_sides.hpp): n points, n * per_point records of them (hits, as the point queries wrote them), the feature
 // table (7 float4 per triangle, rt_features_host.hpp) -> n * per_point {s, feature} pairs of 8 bytes.
 hipError_t launch_sides(const TraceParams& p, const float4* table, uint32_t n, uint32_t per_point, const float* pts, const float4* hits,

@@ -1,6 +1,7 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
 // rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_exposure*, rt_tracer_intersect_all*) and the point queries (rt_tracer_closest_point*,
-// rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*) and the region query (rt_tracer_overlap*).
+// rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*) and the region query (rt_tracer_overlap*) and the swept query
+// (rt_tracer_sphere_cast*).
 // Included by rt_tracer.hip.
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
@@ -261,6 +262,15 @@ inline void enqueue_overlap(rt_tracer* t, size_t n, const float* boxes, const in
                             uint32_t* counts, hipStream_t st) {
   enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
     return rtk::launch_overlap(p, b, static_cast<uint32_t>(n), boxes, after, max_hits, prims, counts, st);
+  });
+}
+
+// sweeps -> one record per sweep (rt_spherecast.hpp).  One arithmetic for both math modes and no hit rule: the flags stay 0.  The
+// tree is the ray queries' (ensure_query_tree, so RT_ACCEL_REFIT applies); the walk's allowance beyond r takes the tracer's slack.
+static_assert(RT_SWEEP_SLACK == rtk::kSweepSlack, "include/rt_mi355x.h and rt_kernels.hpp state one slack");
+inline void enqueue_sphere_cast(rt_tracer* t, size_t n, const float* sweeps, float4* hits, hipStream_t st) {
+  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return rtk::launch_sphere_cast(p, b, static_cast<float>(t->queries.slack_milli) / 1000.0f, static_cast<uint32_t>(n), sweeps, hits, st);
   });
 }
 
@@ -693,6 +703,29 @@ int rt_tracer_overlap_device(rt_tracer* t, const float* boxes, const int32_t* af
     if (n == 0u) return;
     t->use_device();
     enqueue_overlap(t, n, boxes, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_sphere_cast(rt_tracer* t, const float* sweeps, size_t n, rt_hit* hits) {
+  if (!t || !query_args_ok(t, n, {sweeps, hits})) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_sphere_cast(b, sweeps, n, hits); }, [&] {
+    if (n == 0u) return;
+    const hipStream_t st = host_query_stream(t);
+    const float* d_sweeps = staged_in<float>(t->queries.in[0], sweeps, n * 8u, st);
+    enqueue_sphere_cast(t, n, d_sweeps, room<float4>(t->queries.out[0], n), st);
+    staged_out<float4>(hits, t->queries.out[0], n, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_sphere_cast_device(rt_tracer* t, const float* sweeps, size_t n, rt_hit* hits, void* stream) {
+  if (!t || !query_args_ok(t, n, {sweeps, hits}) ||
+      !query_aligned_ok(t, n, {{sweeps, 16u}, {hits, 16u}}, "rt_tracer_sphere_cast_device: sweeps and hits must be 16-byte aligned"))
+    return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_sphere_cast_device(b, sweeps, n, hits, stream); }, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_sphere_cast(t, n, sweeps, reinterpret_cast<float4*>(hits), static_cast<hipStream_t>(stream));
   });
 }
 

@@ -27,7 +27,7 @@ struct Args {
   uint64_t seed = 0; bool have_seed = false;
   std::string scene = "demo3", scene_file, out = "image0.bmp";
   bool quiet = false, edges = false, smooth = false, nearest = false;
-  bool pick = false, focus = false, accel = false, hits = false, closest = false, knn = false, sgn = false, exposure = false, overlap = false;
+  bool pick = false, focus = false, accel = false, hits = false, closest = false, knn = false, sgn = false, exposure = false, overlap = false, spherecast = false;
   float exposure_p[7] = {0, 0, 0, 0, 0, 1, INFINITY};   // --exposure: x, y, z, normal, far end of the interval
   uint32_t exposure_k = 64;
   float closest_p[4] = {0, 0, 0, INFINITY};        // x, y, z, search distance
@@ -36,6 +36,7 @@ struct Args {
   uint32_t knn_k = 8;
   float overlap_b[6] = {0, 0, 0, 0, 0, 0};         // --overlap X0,Y0,Z0,X1,Y1,Z1[,K]: lo, hi
   uint32_t overlap_k = 8;
+  float sweep[8] = {0, 0, 0, 0, 0, 0, 0, INFINITY}; // --spherecast X,Y,Z,DX,DY,DZ,R[,TMAX]
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0}, hits_xy[2] = {0, 0}, hits_k = 8;
 };
 
@@ -111,6 +112,20 @@ bool parse_exposure(const char* s, float out[7], uint32_t& k) {
   }
 }
 
+// "X,Y,Z,DX,DY,DZ,R" or "...,TMAX": a sweep as rt_tracer_sphere_cast takes it (out[7] keeps its value when TMAX is absent)
+bool parse_spherecast(const char* s, float out[8]) {
+  int n = 0;
+  for (const char* q = s;; ++n) {
+    char* end = nullptr;
+    const float f = std::strtof(q, &end);
+    if (end == q || n > 7) return false;
+    out[n] = f;
+    if (*end == 0) return n >= 6;
+    if (*end != ',') return false;
+    q = end + 1;
+  }
+}
+
 // "X0,Y0,Z0,X1,Y1,Z1" or "...,K": the two corners of a box and an optional row length (0 to RT_MAX_HITS is checked by the query)
 bool parse_overlap(const char* s, float out[6], uint32_t& k) {
   int n = 0;
@@ -178,7 +193,10 @@ void usage() {
             "       [--overlap X0,Y0,Z0,X1,Y1,Z1[,K]] (prints `overlap count`, the number of primitives that touch the box with the\n"
             "                      corners X0,Y0,Z0 and X1,Y1,Z1, then one line `prim` for each of the K lowest, default 8)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
-            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --focus through the scene's BVH instead of the scan)");
+            "       [--spherecast X,Y,Z,DX,DY,DZ,R[,TMAX]] (prints `spherecast prim t u v x y z`: the first contact of a sphere of radius\n"
+            "                      R whose centre moves from X,Y,Z along DX,DY,DZ for 0 <= t <= TMAX, and the contact point;\n"
+            "                      `spherecast -1` when there is none)\n"
+            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --spherecast / --focus through the scene's BVH instead of the scan)");
 }
 
 }  // namespace
@@ -231,6 +249,10 @@ int main(int argc, char** argv) {
     else if (k == "--hits") {
       if (!parse_xyk(next("--hits"), a.hits_xy, a.hits_k)) { std::fprintf(stderr, "--hits wants X,Y[,K]\n"); return 2; }
       a.hits = true;
+    }
+    else if (k == "--spherecast") {
+      if (!parse_spherecast(next("--spherecast"), a.sweep)) { std::fprintf(stderr, "--spherecast wants X,Y,Z,DX,DY,DZ,R[,TMAX]\n"); return 2; }
+      a.spherecast = true;
     }
     else if (k == "--closest") {
       if (!parse_xyzr(next("--closest"), a.closest_p)) { std::fprintf(stderr, "--closest wants X,Y,Z[,R]\n"); return 2; }
@@ -372,6 +394,28 @@ int main(int argc, char** argv) {
     for (uint32_t j = 0; j < counts[0]; ++j)
       std::printf("%d %.9g %.9g %.9g\n", hits[j].prim, static_cast<double>(std::sqrt(hits[j].t)), static_cast<double>(hits[j].u),
                   static_cast<double>(hits[j].v));
+  }
+  if (a.spherecast) {
+    const std::vector<float> sweeps(a.sweep, a.sweep + 8);
+    std::vector<rt_hit> hits;
+    if (!tracer.SphereCast(sweeps, hits)) {
+      std::fprintf(stderr, "rt_cli: --spherecast: %s\n", tracer.LastError().c_str());
+      return 1;
+    }
+    const rt_hit& h = hits[0];
+    if (h.prim < 0 || static_cast<size_t>(h.prim) >= scene.size() / 3) {
+      std::printf("spherecast -1\n");
+    } else {                                                    // v0 + u*e1 + v*e2 of the record the library intersects
+      const float4 r0 = scene[3 * h.prim], r1 = scene[3 * h.prim + 1], r2 = scene[3 * h.prim + 2];
+      const float v0[3] = {r0.x, r0.y, r0.z}, b[3] = {r1.x, r1.y, r1.z}, c[3] = {r2.x, r2.y, r2.z};
+      float q[3];
+      for (int i = 0; i < 3; ++i) {
+        const float e1 = a.edges ? b[i] : b[i] - v0[i], e2 = a.edges ? c[i] : c[i] - v0[i];
+        q[i] = (v0[i] + h.u * e1) + h.v * e2;
+      }
+      std::printf("spherecast %d %.9g %.9g %.9g %.9g %.9g %.9g\n", h.prim, static_cast<double>(h.t), static_cast<double>(h.u),
+                  static_cast<double>(h.v), static_cast<double>(q[0]), static_cast<double>(q[1]), static_cast<double>(q[2]));
+    }
   }
   if (a.overlap) {
     const float* b = a.overlap_b;
