@@ -218,6 +218,29 @@ public:
     if (!Overlap(boxes, maxHits, prims, counts)) counts.clear();
     return counts;
   }
+  // Triangle-shaped region query (rt_mi355x.h, rt_tracer_overlap_triangles): tris holds 12 floats per query triangle, P0.xyz _
+  // P1.xyz _ P2.xyz _ (the pads are never read).  prims, counts, after and maxHits are Overlap's: row i holds the
+  // min(counts[i], maxHits) lowest primitives that touch triangle i, then RT_PRIM_NONE; counts[i] is their TOTAL behind the
+  // cursor.  Closed: touching counts, and a query corner bit-equal to a corner of a scene triangle's record always touches it; a
+  // query with a non-finite coordinate touches nothing.  A vector whose size is no multiple of 12, or an after of another
+  // length: false, the outputs untouched.
+  bool OverlapTriangles(const std::vector<float>& tris, uint32_t maxHits, std::vector<int32_t>& prims, std::vector<uint32_t>& counts,
+                        const std::vector<int32_t>& after = std::vector<int32_t>()) {
+    if (!mImpl || tris.size() % 12 != 0 || maxHits > RT_MAX_HITS) return false;
+    const size_t n = tris.size() / 12;
+    if (!after.empty() && after.size() != n) return false;
+    prims.resize(n * maxHits);
+    counts.resize(n);
+    return rt_tracer_overlap_triangles(mImpl, tris.data(), after.empty() ? nullptr : after.data(), n, maxHits,
+                                       maxHits != 0 ? prims.data() : nullptr, counts.data()) == RT_OK;
+  }
+  // The same, returning the counts: empty when the arguments were rejected or the call failed (LastError()).
+  std::vector<uint32_t> OverlapTriangles(const std::vector<float>& tris, uint32_t maxHits = 0) {
+    std::vector<int32_t> prims;
+    std::vector<uint32_t> counts;
+    if (!OverlapTriangles(tris, maxHits, prims, counts)) counts.clear();
+    return counts;
+  }
   // Swept query (rt_mi355x.h, rt_tracer_sphere_cast): sweeps holds 8 floats per sweep -- origin, direction (used as given), the
   // sphere's radius, tmax; the centre runs along o + t*d for 0 <= t <= tmax.  hits[i].t = the time of first contact, u, v the
   // barycentrics of the contact point on triangle prim (0, 0 for a sphere), prim = RT_PRIM_NONE when nothing is touched.  A

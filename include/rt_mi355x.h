@@ -650,6 +650,61 @@ int  rt_tracer_overlap(rt_tracer* t, const float* boxes, const int32_t* after, s
  * synchronisation.  boxes must be 16-byte aligned; otherwise RT_ERR_INVALID. */
 int  rt_tracer_overlap_device(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                               uint32_t* counts, void* stream);
+/* Which primitives of the tracer's scene touch a TRIANGLE (the narrow phase of mesh against mesh, a cut plane or a portal given
+ * as two triangles, a scene's own self-intersections).
+ *   tris        n x 12 floats: P0.x P0.y P0.z _ P1.x P1.y P1.z _ P2.x P2.y P2.z _ (three 16-byte loads).  The three pad floats
+ *               are never read into any arithmetic: NaNs there change nothing.
+ *   max_hits, after, prims, counts
+ *               exactly as in rt_tracer_overlap: max_hits 0 .. RT_MAX_HITS (above that RT_ERR_INVALID; 0: counts only, prims
+ *               may be NULL); row i holds the min(counts[i], max_hits) LOWEST accepted prims in ascending order, then
+ *               RT_PRIM_NONE; counts[i] is the TOTAL behind the cursor, not capped; after[i] = the row's last prim continues:
+ *               nothing repeats and nothing is lost.
+ *   triangle    one arithmetic in RT_MATH_FMA and RT_MATH_STRICT: every operation is one separately rounded fp32 operation, dot
+ *               products are (x*x' + y*y') + z*z', cross products (a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x, a.x*b.y - b.x*a.y);
+ *               min and max are IEEE minNum / maxNum.  On the record the renderer intersects (v0, e1, e2; for edge-format scenes
+ *               the uploaded rows), with corners A = v0, B = fl(v0 + e1), C = fl(v0 + e2):
+ *                 1. Box step.  All nine query coordinates are finite: otherwise the query accepts NOTHING, spheres included.
+ *                    Neither B nor C is a NaN (a NaN A makes both one).  Per axis, with tmin = min(min(A, B), C),
+ *                    tmax = max(max(A, B), C), qmin = min(min(P0, P1), P2), qmax = max(max(P0, P1), P2): tmin <= qmax and
+ *                    tmax >= qmin.  Plain comparisons, closed: touching counts.
+ *                 2. Move by -P0.  a = A - P0, b = B - P0, c = C - P0, p1 = P1 - P0, p2 = P2 - P0 per component; the query's own
+ *                    corner P0 is the literal 0.
+ *                 3. Seventeen axes.  With f = {e1, c - b, a - c}, g = {p1, p2 - p1, p2}, n = e1 x e2 and m = p1 x p2:
+ *                      n;  m;  the nine f_i x g_j;  the three n x f_i;  the three m x g_j
+ *                    (the last six lie in the two triangles' planes: they are what decides a coplanar pair).  On an axis x the
+ *                    record projects to x.a, x.b, x.c and the query to 0, x.p1, x.p2.  Separated on x when EVERY record
+ *                    projection is > EVERY query projection, or every one is <: nine plain comparisons each way, so a NaN
+ *                    projection makes its comparisons false and the axis never separates.
+ *               A triangle is accepted when step 1 accepts and no axis separates.  All six points are projected on every axis
+ *               (this is not the two-corner shortcut of rt_tracer_overlap), which buys a guarantee: a query corner that is
+ *               bit-equal to A, B or C of a record makes that record accepted, whatever the rounding elsewhere -- the shared
+ *               point's projections are the same fp32 operations on the same operands on both sides, so on no axis is every
+ *               record projection strictly beyond every query projection, and step 1 is closed.  (P0 against A, B or C: the
+ *               moved corner is the difference of equal numbers, +0, against the literal 0.)  Zero-area triangles on either
+ *               side get what this arithmetic gives them (a zero axis projects everything to 0 and never separates); they are
+ *               not special-cased.
+ *   sphere      a sphere of the scene is its surface, as in rt_tracer_overlap.  Centre S, radius r:  d2min = the t of
+ *               rt_tracer_closest_point's triangle rule for the point S on the query's own record (v0 = P0, e1 = p1, e2 = p2);
+ *               d2max = max(max(w0.w0, w1.w1), w2.w2) with w_i = P_i - S.  Accepted when the query is finite and
+ *               d2min <= r*r && r*r <= d2max.  A triangle wholly inside the ball touches nothing.
+ *   accuracy    as measured (tests/test_trioverlap_expect.py): against an independently written separating-axis
+ *               test in float64 on the same fp32 corners, and against an edge-through-triangle test in float64.
+ * Everything else -- no scene, spheres alone, n = 0, NULL arrays (RT_ERR_INVALID, outputs untouched), scheduling, multi-device
+ * handles, RT_ACCEL_REFIT -- is rt_tracer_overlap's.
+ * RT_QUERY_BVH: a child is entered when its box and the query triangle's BOUNDING BOX [qmin, qmax] overlap -- clo <= qmax &&
+ * chi >= qmin per axis, the same closed comparisons, NO inflation -- and the result is bit for bit the scan's rows and counts for
+ * every input whatsoever, by the argument above: step 1's [tmin, tmax] lies inside the record's tree box, a child the walk skips
+ * holds only triangles step 1 rejects, acceptance is a pure function of (query, record, cursor), non-finite records go through
+ * the always-tested list, and a walk whose stack overflowed recomputes from every leaf record, restarting the list and the count.
+ * There is no rho, no slack and no conditioning clause: rt_dbg_query_accel_slack has no effect on this query either. */
+/* Host arrays: tris n*12, after n or NULL, prims n*max_hits (NULL allowed when max_hits = 0), counts n.  Returns with the
+ * results in host memory. */
+int  rt_tracer_overlap_triangles(rt_tracer* t, const float* tris, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                                 uint32_t* counts);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  tris must be 16-byte aligned; otherwise RT_ERR_INVALID. */
+int  rt_tracer_overlap_triangles_device(rt_tracer* t, const float* tris, const int32_t* after, size_t n, uint32_t max_hits,
+                                        int32_t* prims, uint32_t* counts, void* stream);
 
 /* ---- one frame sharded over several GPUs --------------------------------------
  * The reference builds ONE rt::RayTracer pinned to device 0 (OpenGLView/MainFrame.cpp:44-45,

@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "rt_tracer_signed_distance", "rt_tracer_signed_distance_device",
     "rt_tracer_closest_sides", "rt_tracer_closest_sides_device", "rt_dbg_feature_normals",
     "rt_tracer_overlap", "rt_tracer_overlap_device",
+    "rt_tracer_overlap_triangles", "rt_tracer_overlap_triangles_device",
     "rt_tracer_sphere_cast", "rt_tracer_sphere_cast_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
     "rt_tracer_set_query_accel_update", "rt_tracer_query_accel_rebuild", "rt_tracer_query_accel_update_info",
@@ -364,6 +365,9 @@ def load_library():
         L.rt_tracer_closest_sides_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
         L.rt_tracer_overlap.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
         L.rt_tracer_overlap_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
+        if hasattr(L, "rt_tracer_overlap_triangles"):     # (an older build selected by RT_MI355X_LIB for an A/B has no triangle regions)
+            L.rt_tracer_overlap_triangles.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
+            L.rt_tracer_overlap_triangles_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
         if hasattr(L, "rt_tracer_sphere_cast"):           # (an older build selected by RT_MI355X_LIB for an A/B has no swept query)
             L.rt_tracer_sphere_cast.argtypes = [vp, vp, C.c_size_t, vp]
             L.rt_tracer_sphere_cast_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
@@ -1169,6 +1173,124 @@ class RayTracer:
         boxes = self.voxel_boxes(origin, spacing, shape)
         _, counts = self.Overlap(boxes, 0)
         return (counts > 0).reshape(tuple(int(v) for v in shape))
+
+    # ---- triangle-shaped regions (rt_tracer_overlap_triangles / _device) ---------------------------------------------------
+    @staticmethod
+    def _triangles_array(who, triangles):
+        """-> contiguous (n, 12) float32 {P0 xyz, 0, P1 xyz, 0, P2 xyz, 0}: from (n, 12) as it is (the pads are never read), from
+        (n, 3, 3) or from (n, 9) {P0 xyz, P1 xyz, P2 xyz}."""
+        t = np.asarray(triangles, np.float32)
+        if t.ndim >= 2 and t.shape[-2:] == (3, 3):
+            t = t.reshape(-1, 9)
+        if t.ndim == 0 or t.shape[-1] not in (9, 12):
+            raise ValueError("%s: expected (n, 3, 3), (n, 9) or (n, 12) float32 triangles, got shape %s" % (who, t.shape))
+        if t.shape[-1] == 9:
+            t = t.reshape(-1, 3, 3)
+            q = np.zeros((t.shape[0], 3, 4), np.float32)
+            q[:, :, :3] = t
+            t = q
+        return np.ascontiguousarray(t).reshape(-1, 12)
+
+    def OverlapTriangles(self, triangles, max_hits=RT_MAX_HITS, after=None):
+        """The primitives that touch each query triangle (rt_tracer_overlap_triangles).  triangles: (n, 3, 3) or (n, 9) float32
+        corners, or (n, 12) {P0 xyz, -, P1 xyz, -, P2 xyz, -}; closed, touching counts; a query with a non-finite coordinate
+        touches nothing.  max_hits, after and the returned (prims (n, max_hits) int32, counts (n,) uint32) are Overlap's: the
+        lowest touching prims in ascending order, then PRIM_NONE, and the TOTAL behind the cursor (OverlapTrianglesAll chains
+        it).  A query corner bit-equal to a corner of a scene triangle's record always touches that triangle.  Independent of
+        the tracer's arithmetic mode and hit rule; a sphere is its surface.  numpy in, numpy out, on return.  A contiguous
+        (n, 12) float32 torch tensor on the tracer's device -> ((n, max_hits) int32, (n,) int32) tensors, enqueued on
+        torch.cuda.current_stream() without a host synchronisation; after is then a contiguous (n,) int32 tensor."""
+        if type(triangles).__module__.startswith("torch"):
+            return self._overlap_triangles_tensor(triangles, max_hits, after)
+        t = self._triangles_array("OverlapTriangles", triangles)
+        k = self._overlap_hits(max_hits)
+        a = None
+        if after is not None:
+            a = np.ascontiguousarray(after, np.int32).reshape(-1)
+            if a.shape[0] != t.shape[0]:
+                raise ValueError("OverlapTriangles: after must hold one int32 cursor per triangle")
+        prims = np.full((t.shape[0], k), PRIM_NONE, np.int32)
+        counts = np.zeros(t.shape[0], np.uint32)
+        self._check(self._lib.rt_tracer_overlap_triangles(self._h, t.ctypes.data, None if a is None else a.ctypes.data, t.shape[0], k,
+                                                          prims.ctypes.data if k else None, counts.ctypes.data))
+        return prims, counts
+
+    def _overlap_triangles_tensor(self, triangles, max_hits=RT_MAX_HITS, after=None):
+        import torch
+        if triangles.dtype != torch.float32 or triangles.dim() != 2 or triangles.shape[1] != 12 or not triangles.is_contiguous():
+            raise ValueError("OverlapTriangles: expected a contiguous (n, 12) float32 tensor")
+        k = self._overlap_hits(max_hits)
+        stream = self._stream_of("OverlapTriangles", "triangles", triangles)
+        n = triangles.shape[0]
+        if after is not None:
+            if (not type(after).__module__.startswith("torch") or after.dtype != torch.int32 or tuple(after.shape) != (n,) or
+                    not after.is_contiguous() or after.device != triangles.device):
+                raise ValueError("OverlapTriangles: after must be a contiguous (n,) int32 tensor on the triangles' device")
+        prims = torch.empty((n, k), dtype=torch.int32, device=triangles.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=triangles.device)
+        self._check(self._lib.rt_tracer_overlap_triangles_device(self._h, triangles.data_ptr(), None if after is None else after.data_ptr(),
+                                                                 n, k, prims.data_ptr() if k else None, counts.data_ptr(), stream))
+        return prims, counts
+
+    def OverlapTrianglesAll(self, triangles, max_hits=RT_MAX_HITS):
+        """Every primitive that touches each query triangle, numpy only: OverlapTriangles repeated with the cursor while a count
+        exceeds max_hits (1 <= max_hits <= RT_MAX_HITS is the row length of one round).  Returns (prims, offsets) as OverlapAll
+        does: triangle i's prims, ascending, are prims[offsets[i]:offsets[i + 1]]."""
+        t = self._triangles_array("OverlapTrianglesAll", triangles)
+        k = self._max_hits("OverlapTrianglesAll", max_hits)
+        n = t.shape[0]
+        live = np.arange(n)                                                # the triangles that have more
+        after = None
+        parts, owners = [], []
+        while live.size:
+            prims, counts = self.OverlapTriangles(t[live], k, after=after)
+            stored = np.minimum(counts, k)
+            keep = np.arange(k)[None, :] < stored[:, None]
+            parts.append(prims[keep])
+            owners.append(np.repeat(live, stored))
+            more = counts > k
+            after = np.ascontiguousarray(prims[more, k - 1])
+            live = live[more]
+        owner = np.concatenate(owners) if owners else np.zeros(0, np.int64)
+        flat = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+        order = np.argsort(owner, kind="stable")                           # rounds are in order within a triangle already
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(np.bincount(owner, minlength=n), out=offsets[1:])
+        return flat[order], offsets
+
+    @staticmethod
+    def scene_corners(rows, edges=False):
+        """(T, 3, 3) float32: the corners SelfIntersections queries and compares -- the uploaded vertices of the vertex layout;
+        A = v0, fl(v0 + e1), fl(v0 + e2) of the edge layout (the corners the rule itself works on)."""
+        r = np.asarray(rows, np.float32).reshape(-1, 3, 4)[:, :, :3].copy()
+        if edges:
+            r[:, 1], r[:, 2] = r[:, 0] + r[:, 1], r[:, 0] + r[:, 2]
+        return r
+
+    def SelfIntersections(self):
+        """The pairs (i, j), i < j, of the scene's own triangles that touch without sharing a corner, (m, 2) int32 in ascending
+        order: every triangle of the last upload queried against the scene (OverlapTrianglesAll), spheres left out.  Two
+        triangles share a corner when any corner of one == (on values) any corner of the other, corners as scene_corners
+        gives them; neighbours of a mesh therefore never count, and a FOLD BETWEEN NEIGHBOURS (two triangles that share an edge
+        or a vertex and also cross or lie on each other) is not reported.  What is reported is what makes Contains and
+        SignedDistance untrustworthy on a mesh: parts that pass through each other."""
+        if self._scene_rows is None or self._scene_rows.shape[0] == 0:
+            return np.zeros((0, 2), np.int32)
+        c = self.scene_corners(self._scene_rows, self._scene_edges)
+        return self.self_pairs(c, *self.OverlapTrianglesAll(c))
+
+    @staticmethod
+    def self_pairs(corners, prims, offsets):
+        """SelfIntersections' second half: from the scene's corners (T, 3, 3) and OverlapTrianglesAll's answer for them, the
+        pairs i < j of triangles that are accepted and share no corner (== on values), (m, 2) int32."""
+        c = np.asarray(corners, np.float32).reshape(-1, 3, 3)
+        i = np.repeat(np.arange(c.shape[0]), np.diff(offsets))
+        j = np.asarray(prims).astype(np.int64)
+        keep = (j > i) & (j < c.shape[0])                                  # each pair once; no spheres
+        i, j = i[keep], j[keep]
+        with np.errstate(invalid="ignore"):
+            shared = (c[i][:, :, None, :] == c[j][:, None, :, :]).all(axis=3).any(axis=(1, 2))
+        return np.stack([i[~shared], j[~shared]], axis=1).astype(np.int32)
 
     # ---- signed point queries (rt_tracer_signed_distance / rt_tracer_closest_sides, and their _device forms) -------------
     def SignedDistance(self, points, max_distance=np.inf):

@@ -13,6 +13,7 @@
 //   closest_*kernel    <- the nearest surface point to a caller's point (rt_closest.hpp)
 //   nearest_*kernel    <- a point's k nearest primitives in order, with a continuation cursor (rt_nearest.hpp)
 //   overlap_*kernel    <- the primitives that touch a caller's box, lowest first, and how many (rt_overlap.hpp)
+//   trioverlap_*kernel <- the primitives that touch a caller's triangle, lowest first, and how many (rt_trioverlap.hpp)
 //   spherecast_*kernel <- a moving sphere's first contact with the scene (rt_spherecast.hpp)
 //   sides_kernel       <- the side of the surface a point query's records lie on (rt_sides.hpp)
 //   refit_*kernel      <- the tree's boxes recomputed for a re-uploaded scene of the same size (rt_refit.hpp)
@@ -28,6 +29,7 @@
 #include "rt_closest.hpp"
 #include "rt_nearest.hpp"
 #include "rt_overlap.hpp"
+#include "rt_trioverlap.hpp"
 #include "rt_spherecast.hpp"
 #include "rt_sides.hpp"
 #include "rt_refit.hpp"

@@ -213,6 +213,12 @@ hipError_t launch_nearest(const TraceParams& p, const BvhParams* b, float rho_c,
 hipError_t launch_overlap(const TraceParams& p, const BvhParams* b, uint32_t n, const float* boxes, const int* after, uint32_t max_hits,
                           int* prims, uint32_t* counts, hipStream_t st);
 
+// The triangle-shaped region query (rt_trioverlap.hpp): n query triangles {P0 xyz, -, P1 xyz, -, P2 xyz, -}, 16-byte aligned;
+// after, max_hits, prims and counts as launch_overlap's.  One arithmetic for both math modes; one query per lane in both forms.
+// The tree form reads neither b->rho nor a slack: its prune is exact.
+hipError_t launch_overlap_triangles(const TraceParams& p, const BvhParams* b, uint32_t n, const float* tris, const int* after,
+                                    uint32_t max_hits, int* prims, uint32_t* counts, hipStream_t st);
+
 // The swept query (rt_spherecast.hpp): n sweeps {origin xyz, direction xyz, radius, tmax}, 16-byte aligned; hits[i] = {t of the
 // first contact, u, v of the contact point, bits of the int32 primitive} of the smallest (t, prim) among the certified contacts
 // with t <= tmax, or {0, 0, 0, -1}.  One arithmetic for both math modes; one sweep per lane in both forms.  slack: the tracer's

@@ -1,6 +1,6 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
 // rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_exposure*, rt_tracer_intersect_all*) and the point queries (rt_tracer_closest_point*,
-// rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*) and the region query (rt_tracer_overlap*) and the swept query
+// rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*) and the region queries (rt_tracer_overlap*, rt_tracer_overlap_triangles*) and the swept query
 // (rt_tracer_sphere_cast*).
 // Included by rt_tracer.hip.
 //
@@ -265,6 +265,15 @@ inline void enqueue_overlap(rt_tracer* t, size_t n, const float* boxes, const in
   });
 }
 
+// query triangles (and their cursors, or nullptr) -> rows of max_hits prims and one total per triangle (rt_trioverlap.hpp), with
+// enqueue_overlap's tree and flags
+inline void enqueue_overlap_triangles(rt_tracer* t, size_t n, const float* tris, const int32_t* after, uint32_t max_hits, int32_t* prims,
+                                      uint32_t* counts, hipStream_t st) {
+  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return rtk::launch_overlap_triangles(p, b, static_cast<uint32_t>(n), tris, after, max_hits, prims, counts, st);
+  });
+}
+
 // sweeps -> one record per sweep (rt_spherecast.hpp).  One arithmetic for both math modes and no hit rule: the flags stay 0.  The
 // tree is the ray queries' (ensure_query_tree, so RT_ACCEL_REFIT applies); the walk's allowance beyond r takes the tracer's slack.
 static_assert(RT_SWEEP_SLACK == rtk::kSweepSlack, "include/rt_mi355x.h and rt_kernels.hpp state one slack");
@@ -274,7 +283,8 @@ inline void enqueue_sphere_cast(rt_tracer* t, size_t n, const float* sweeps, flo
   });
 }
 
-// the arguments of the overlap entry points: max_hits checked whatever n is (0 is allowed: counts only), then the arrays
+// the arguments of the overlap entry points (boxes or query triangles): max_hits checked whatever n is (0 is allowed: counts
+// only), then the arrays
 inline bool overlap_args_ok(rt_tracer* t, const char* who, size_t n, const float* boxes, uint32_t max_hits, const int32_t* prims,
                             const uint32_t* counts) {
   if (max_hits > RT_MAX_HITS) { t->set_error(fmt("%s: max_hits = %u (0 to %u)", who, max_hits, RT_MAX_HITS)); return false; }
@@ -703,6 +713,35 @@ int rt_tracer_overlap_device(rt_tracer* t, const float* boxes, const int32_t* af
     if (n == 0u) return;
     t->use_device();
     enqueue_overlap(t, n, boxes, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_overlap_triangles(rt_tracer* t, const float* tris, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                                uint32_t* counts) {
+  if (!t || !overlap_args_ok(t, "rt_tracer_overlap_triangles", n, tris, max_hits, prims, counts)) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap_triangles(b, tris, after, n, max_hits, prims, counts); }, [&] {
+    if (n == 0u) return;
+    const hipStream_t st = host_query_stream(t);
+    const float* d_tris = staged_in<float>(t->queries.in[0], tris, n * 12u, st);
+    const int32_t* d_after = after ? staged_in<int32_t>(t->queries.in[1], after, n, st) : nullptr;
+    int32_t* d_prims = max_hits != 0u ? room<int32_t>(t->queries.out[0], n * max_hits) : nullptr;
+    enqueue_overlap_triangles(t, n, d_tris, d_after, max_hits, d_prims, room<uint32_t>(t->queries.out[1], n), st);
+    if (max_hits != 0u) staged_out<int32_t>(prims, t->queries.out[0], n * max_hits, st);
+    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_overlap_triangles_device(rt_tracer* t, const float* tris, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                                       uint32_t* counts, void* stream) {
+  if (!t || !overlap_args_ok(t, "rt_tracer_overlap_triangles_device", n, tris, max_hits, prims, counts) ||
+      !query_aligned_ok(t, n, {{tris, 16u}, {after, 4u}, {prims, 4u}, {counts, 4u}},
+                        "rt_tracer_overlap_triangles_device: tris must be 16-byte aligned, after, prims and counts 4-byte aligned"))
+    return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap_triangles_device(b, tris, after, n, max_hits, prims, counts, stream); }, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_overlap_triangles(t, n, tris, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
   });
 }
 

@@ -36,6 +36,9 @@ struct Args {
   uint32_t knn_k = 8;
   float overlap_b[6] = {0, 0, 0, 0, 0, 0};         // --overlap X0,Y0,Z0,X1,Y1,Z1[,K]: lo, hi
   uint32_t overlap_k = 8;
+  bool overlap_tri = false;
+  float overlap_t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // --overlap-tri X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,K]: the three corners
+  uint32_t overlap_tri_k = 8;
   float sweep[8] = {0, 0, 0, 0, 0, 0, 0, INFINITY}; // --spherecast X,Y,Z,DX,DY,DZ,R[,TMAX]
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0}, hits_xy[2] = {0, 0}, hits_k = 8;
 };
@@ -126,12 +129,13 @@ bool parse_spherecast(const char* s, float out[8]) {
   }
 }
 
-// "X0,Y0,Z0,X1,Y1,Z1" or "...,K": the two corners of a box and an optional row length (0 to RT_MAX_HITS is checked by the query)
-bool parse_overlap(const char* s, float out[6], uint32_t& k) {
+// "X0,Y0,Z0,X1,Y1,Z1" or "...,K": the two corners of a box (m = 6) or the three of a triangle (m = 9) and an optional row
+// length (0 to RT_MAX_HITS is checked by the query)
+bool parse_overlap(const char* s, float* out, uint32_t& k, int m = 6) {
   int n = 0;
   for (const char* q = s;; ++n) {
     char* end = nullptr;
-    if (n == 6) {
+    if (n == m) {
       if (*q == '-' || *q == '+') return false;
       const unsigned long kk = std::strtoul(q, &end, 10);
       if (end == q || *end != 0) return false;
@@ -141,7 +145,7 @@ bool parse_overlap(const char* s, float out[6], uint32_t& k) {
     const float f = std::strtof(q, &end);
     if (end == q) return false;
     out[n] = f;
-    if (*end == 0) return n == 5;
+    if (*end == 0) return n == m - 1;
     if (*end != ',') return false;
     q = end + 1;
   }
@@ -192,11 +196,13 @@ void usage() {
             "                      [1e-3, R] -- the mask in hex, bit j = direction j, and their count)\n"
             "       [--overlap X0,Y0,Z0,X1,Y1,Z1[,K]] (prints `overlap count`, the number of primitives that touch the box with the\n"
             "                      corners X0,Y0,Z0 and X1,Y1,Z1, then one line `prim` for each of the K lowest, default 8)\n"
+            "       [--overlap-tri X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,K]] (prints `overlap-tri count`, the number of primitives that touch the\n"
+            "                      triangle with those three corners, then one line `prim` for each of the K lowest, default 8)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
             "       [--spherecast X,Y,Z,DX,DY,DZ,R[,TMAX]] (prints `spherecast prim t u v x y z`: the first contact of a sphere of radius\n"
             "                      R whose centre moves from X,Y,Z along DX,DY,DZ for 0 <= t <= TMAX, and the contact point;\n"
             "                      `spherecast -1` when there is none)\n"
-            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --spherecast / --focus through the scene's BVH instead of the scan)");
+            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --spherecast / --focus through the scene's BVH instead of the scan)");
 }
 
 }  // namespace
@@ -249,6 +255,10 @@ int main(int argc, char** argv) {
     else if (k == "--hits") {
       if (!parse_xyk(next("--hits"), a.hits_xy, a.hits_k)) { std::fprintf(stderr, "--hits wants X,Y[,K]\n"); return 2; }
       a.hits = true;
+    }
+    else if (k == "--overlap-tri") {
+      if (!parse_overlap(next("--overlap-tri"), a.overlap_t, a.overlap_tri_k, 9)) { std::fprintf(stderr, "--overlap-tri wants X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,K]\n"); return 2; }
+      a.overlap_tri = true;
     }
     else if (k == "--spherecast") {
       if (!parse_spherecast(next("--spherecast"), a.sweep)) { std::fprintf(stderr, "--spherecast wants X,Y,Z,DX,DY,DZ,R[,TMAX]\n"); return 2; }
@@ -428,6 +438,18 @@ int main(int argc, char** argv) {
     }
     std::printf("overlap %u\n", counts[0]);
     for (uint32_t j = 0; j < a.overlap_k && j < counts[0]; ++j) std::printf("%d\n", prims[j]);
+  }
+  if (a.overlap_tri) {
+    const float* c = a.overlap_t;
+    const std::vector<float> tris = {c[0], c[1], c[2], 0.0f, c[3], c[4], c[5], 0.0f, c[6], c[7], c[8], 0.0f};
+    std::vector<int32_t> prims;
+    std::vector<uint32_t> counts;
+    if (!tracer.OverlapTriangles(tris, a.overlap_tri_k, prims, counts)) {
+      std::fprintf(stderr, "rt_cli: --overlap-tri: %s\n", a.overlap_tri_k > RT_MAX_HITS ? "K out of range" : tracer.LastError().c_str());
+      return 1;
+    }
+    std::printf("overlap-tri %u\n", counts[0]);
+    for (uint32_t j = 0; j < a.overlap_tri_k && j < counts[0]; ++j) std::printf("%d\n", prims[j]);
   }
   if (a.focus) {
     float focal = 0.0f;
