@@ -945,6 +945,11 @@ int rt_dbg_owed_state(rt_tracer* t, uint64_t out[4]);
  * out = {trace launches (steps) enqueued, kernel launches, event records, stream waits, list_ready events recorded as a call of
  * their own, list_free events recorded as a call of their own, events a kernel launch carried as its stop event instead, 0} */
 int rt_dbg_enqueue_calls(rt_tracer* t, uint64_t out[8]);
+/* the tile-list builds of a plain tracer's small scenes (up to 256 triangles) since it was created, by the builder kernel that
+ * ran: out = {region pairs (<= 32 triangles, corner-bounded tiles), regions (33..256, corner-bounded tiles), one-level tiles
+ * (<= 32), one-level tiles (33..256)}.  Which one runs depends on the scene's size and on the frame's height and lens
+ * ("The small-scene kernels' options, tested"); reading clears nothing */
+int rt_dbg_list_builds(rt_tracer* t, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -43,7 +43,7 @@ ABI_SYMBOLS = [
     "rt_tracer_device_pointer", "rt_tracer_buffer_bytes", "rt_tracer_info",
     "rt_tracer_last_error", "rt_last_error", "rt_device_count", "rt_version",
     "rt_dbg_hit_triangle", "rt_dbg_sincos", "rt_dbg_valu_peak", "rt_dbg_check_midrange", "rt_dbg_trace_occupancy", "rt_dbg_uniform", "rt_dbg_get_ray",
-    "rt_dbg_rng_init_host", "rt_dbg_rng_advance_host", "rt_dbg_rng_advance_host_n", "rt_dbg_owed_state", "rt_dbg_enqueue_calls",
+    "rt_dbg_rng_init_host", "rt_dbg_rng_advance_host", "rt_dbg_rng_advance_host_n", "rt_dbg_owed_state", "rt_dbg_enqueue_calls", "rt_dbg_list_builds",
     "rt_tracer_create_multi", "rt_group_unique_id", "rt_tracer_join_group", "rt_tracer_leave_group",
     "rt_tracer_gather_time", "rt_tracer_band_count", "rt_tracer_band_info",
     "rt_tracer_join_group_bands", "rt_balance_rows", "rt_tracer_rebalance", "rt_tracer_set_band", "rt_dbg_read_tile_lists", "rt_dbg_wave_list_counts", "rt_dbg_focal_boxes", "rt_dbg_classify",
@@ -326,6 +326,8 @@ def load_library():
             L.rt_dbg_owed_state.argtypes = [vp, C.POINTER(C.c_uint64)]
         if hasattr(L, "rt_dbg_enqueue_calls"):            # (nor has an older build this one)
             L.rt_dbg_enqueue_calls.argtypes = [vp, C.POINTER(C.c_uint64)]
+        if hasattr(L, "rt_dbg_list_builds"):              # (nor this one)
+            L.rt_dbg_list_builds.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_tracer_create_multi.argtypes = [u32p, f32p, f32p, C.c_float, C.c_float, C.c_float, C.POINTER(Options),
                                              C.POINTER(C.c_int32), C.c_uint32, C.POINTER(vp)]
         L.rt_group_unique_id.argtypes = [C.c_char_p]
@@ -704,6 +706,13 @@ class RayTracer:
         d = dict(zip(("steps", "launches", "records", "waits", "ready_records", "free_records", "stop_events"), (int(x) for x in out)))
         d["calls"] = d["launches"] + d["records"] + d["waits"]
         return d
+
+    def DebugListBuilds(self):
+        """rt_dbg_list_builds: the small-scene list builds since the tracer was created, per builder kernel -- [region pairs,
+        regions, one-level tiles of up to 32 triangles, one-level tiles]."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.rt_dbg_list_builds(self._h, out))
+        return [int(x) for x in out]
 
     def DebugWaveListCounts(self, half=0):
         """(counts, capacity): candidate count per tile (grid order of the half's launch; 0xFFFFFFFF = overflow) of a dense scene's

@@ -257,4 +257,13 @@ int rt_dbg_enqueue_calls(rt_tracer* t, uint64_t out[8]) {
   return RT_OK;
 }
 
+// out[kind] = list builds of a small scene by the builder launched (rtk::launch_tile_lists: 0 region pairs, 1 regions, 2 tiles of
+// up to 32 triangles, 3 tiles) since the tracer was created; reading changes nothing
+int rt_dbg_list_builds(rt_tracer* t, uint64_t out[4]) {
+  if (!t || t->mg || !out) return RT_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lk(t->order_mu);
+  for (int k = 0; k < 4; ++k) out[k] = t->list_builds[k];
+  return RT_OK;
+}
+
 }  // extern "C"

@@ -542,7 +542,7 @@ hipError_t launch_sure_table(const float4* colors, uint32_t n_tris, uint32_t sam
   return hipGetLastError();
 }
 
-hipError_t launch_tile_lists(const TraceParams& p, bool fma, hipStream_t st, KernelTable* table, hipEvent_t stop) {
+hipError_t launch_tile_lists(const TraceParams& p, bool fma, hipStream_t st, KernelTable* table, hipEvent_t stop, int* kind_out) {
   if (p.tile_lists == nullptr || p.rows == 0u || p.W == 0u) return stop != nullptr ? hipEventRecord(stop, st) : hipSuccess;
   // 0: two levels, two regions per wave; 1: two levels, region -> tiles (its LDS candidate list holds 256);
   // 2: one level, two tiles per wave; 3: one level, a tile per wave
@@ -565,6 +565,7 @@ hipError_t launch_tile_lists(const TraceParams& p, bool fma, hipStream_t st, Ker
     }
   }, &f);
   if (e != hipSuccess) return e;
+  if (kind_out != nullptr) *kind_out = kind;
   return launch_with_params(f, grid, 0, st, p, stop);
 }
 

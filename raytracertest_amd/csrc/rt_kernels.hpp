@@ -257,8 +257,10 @@ hipError_t launch_publish_half_cost(uint32_t* half_cost, unsigned long long* hos
 // small scenes: the per-triangle table TraceParams::sure_table for launches of `samples` samples
 hipError_t launch_sure_table(const float4* colors, uint32_t n_tris, uint32_t samples, float4* out, hipStream_t st);
 // small scenes: the tiles' candidate lists + certain-winner verdicts of the (half-)launch `p` into p.tile_lists
-// (table, stop: as launch_trace takes them)
-hipError_t launch_tile_lists(const TraceParams& p, bool fma, hipStream_t st, KernelTable* table = nullptr, hipEvent_t stop = nullptr);
+// (table, stop: as launch_trace takes them).  kind: where a builder was launched, which of the four (0: region pairs, 1: regions,
+// 2: tiles of up to 32 triangles, 3: tiles of up to 64 per step); untouched where nothing was
+hipError_t launch_tile_lists(const TraceParams& p, bool fma, hipStream_t st, KernelTable* table = nullptr, hipEvent_t stop = nullptr,
+                             int* kind = nullptr);
 hipError_t launch_dbg_check_midrange(unsigned long long* out, hipStream_t st);
 hipError_t launch_dbg_focal_boxes(bool fma, const TraceParams& p, float* boxes, float* focal, hipStream_t st);
 hipError_t launch_dbg_classify(bool fma, bool forms, uint32_t slack_milli, const TraceParams& p, uint32_t level, uint32_t n_regions,

@@ -584,6 +584,7 @@ struct rt_tracer {
   // advance them (recursive: a launch is enqueued under it and asks for main_stream() / fork_b() on the way).
   std::recursive_mutex order_mu;
   rtr::EnqueueCalls calls;            // guarded by order_mu
+  uint64_t list_builds[4] = {};       // small-scene list builds by builder kind (rtk::launch_tile_lists) since creation (rt_dbg_list_builds; guarded by order_mu)
   // ---- render buffers and scene
   rtk::KernelTable kernels;           // launch descriptors of this tracer's device
   rtr::DevArray<float4> d_render;
@@ -1078,8 +1079,10 @@ struct rt_tracer {
     // (counted by every 32nd build only: the atomics and the publishing kernel cost 3.5 us per step when every build has
     //  them -- and nothing to decide when the mode is pinned)
     if (sr != 0u && d_half_cost.get() != nullptr && env.row_interleave < 0 && (m % 32u) == 0u) { q.half_cost = d_half_cost.get(); q.cost_split_brow = sr / 8u; }
-    HIP_CHECK(rtk::launch_tile_lists(q, fma, stream_l, &kernels, lists.ready_event()));   // list_ready: the build kernel's stop event
+    int kind = -1;
+    HIP_CHECK(rtk::launch_tile_lists(q, fma, stream_l, &kernels, lists.ready_event(), &kind));   // list_ready: the build kernel's stop event
     ++calls.launches;
+    if (kind >= 0) ++list_builds[kind];
     lists.built();
     if (q.half_cost != nullptr) { HIP_CHECK(rtk::launch_publish_half_cost(d_half_cost.get(), h_half_cost.get(), stream_l)); ++calls.launches; }   // (behind list_ready: nobody waits for it)
   }
@@ -1093,7 +1096,12 @@ struct rt_tracer {
     (void)prepare_tile_lists(p, path, true, have_lists);
     sync_list_stream();
     lists.attach(p, row0, have_lists);
-    if (have_lists) HIP_CHECK(rtk::launch_tile_lists(p, fma, main_stream(), &kernels));
+    if (have_lists) {
+      int kind = -1;
+      HIP_CHECK(rtk::launch_tile_lists(p, fma, main_stream(), &kernels, nullptr, &kind));
+      std::lock_guard<std::recursive_mutex> lk(order_mu);
+      if (kind >= 0) ++list_builds[kind];
+    }
     attach_macro_lists(p, path, 0, main_stream());
     {
       std::lock_guard<std::recursive_mutex> lk(order_mu);
