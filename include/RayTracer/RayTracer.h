@@ -241,6 +241,25 @@ public:
     if (!OverlapTriangles(tris, maxHits, prims, counts)) counts.clear();
     return counts;
   }
+  // Triangle distance (rt_mi355x.h, rt_tracer_triangle_distance): tris holds 12 floats per query triangle, P0.xyz d2max P1.xyz _
+  // P2.xyz _ -- OverlapTriangles' layout with the SQUARED search radius in the first pad (+inf = unbounded).  hits[i] is
+  // ClosestPoint's record for the nearest primitive of triangle i (t = the squared distance, u, v on the scene's triangle prim,
+  // RT_PRIM_NONE when nothing lies within the radius); witness[i] is the nearest point ON THE QUERY triangle and the index of
+  // the candidate that found it (-1: none).  (t, u, v) is ClosestPoint's answer for the point witness[i] on that prim, bit for
+  // bit.  A vector whose size is no multiple of 12: false, the outputs untouched.
+  bool TriangleDistance(const std::vector<float>& tris, std::vector<rt_hit>& hits, std::vector<rt_witness>& witness) {
+    if (!mImpl || tris.size() % 12 != 0) return false;
+    hits.resize(tris.size() / 12);
+    witness.resize(tris.size() / 12);
+    return rt_tracer_triangle_distance(mImpl, tris.data(), hits.size(), hits.data(), witness.data()) == RT_OK;
+  }
+  // The same, returning the hits: empty when the vector was rejected or the call failed (LastError()).
+  std::vector<rt_hit> TriangleDistance(const std::vector<float>& tris) {
+    std::vector<rt_hit> hits;
+    std::vector<rt_witness> witness;
+    if (!TriangleDistance(tris, hits, witness)) hits.clear();
+    return hits;
+  }
   // Swept query (rt_mi355x.h, rt_tracer_sphere_cast): sweeps holds 8 floats per sweep -- origin, direction (used as given), the
   // sphere's radius, tmax; the centre runs along o + t*d for 0 <= t <= tmax.  hits[i].t = the time of first contact, u, v the
   // barycentrics of the contact point on triangle prim (0, 0 for a sphere), prim = RT_PRIM_NONE when nothing is touched.  A

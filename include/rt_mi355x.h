@@ -781,6 +781,77 @@ int  rt_tracer_sphere_cast_device(rt_tracer* t, const float* sweeps, size_t n, r
 /* (The swept queries stand behind the banner of the sharded frame and before its entry points: what lies between the region
  * queries' banner and that banner is the region queries' text alone, which tests/test_overlap_abi.py reads as one section.) */
 
+/* ---- proximity of triangles ------------------------------------------------------------------------
+ * How far is a TRIANGLE from the tracer's scene, and where (clearance and tolerance between parts, a collision margin before
+ * contact, the nearest pair between a tool mesh and the scene, a one-sided mesh distance that cannot miss a minimum in the
+ * interior of a face or an edge).  The triangle counterpart of rt_tracer_closest_point.
+ *   tris        n x 12 floats: P0.x P0.y P0.z d2max P1.x P1.y P1.z _ P2.x P2.y P2.z _ (rt_tracer_overlap_triangles' layout; the
+ *               first pad float carries the SQUARED search radius, +inf = unbounded, as the point query's fourth column does).
+ *               The other two pad floats are never read into any arithmetic.  A query accepts NOTHING, spheres included, when any
+ *               of its nine coordinates is non-finite or when d2max is a NaN or negative.
+ *   hits        hits[i] = rt_hit exactly as rt_tracer_closest_point's: t = the squared distance, u, v = the barycentrics of the
+ *               nearest point ON THE SCENE'S record (v0 + u*e1 + v*e2; 0, 0 for a sphere), prim.  No winner: {0, 0, 0,
+ *               RT_PRIM_NONE}.
+ *   witness     witness[i] = rt_witness {x, y, z, where}: the winning point ON THE QUERY triangle and the index k of the candidate
+ *               below that produced it.  No winner: {0, 0, 0, -1}.
+ *   arithmetic  one in RT_MATH_FMA and RT_MATH_STRICT: every operation is one separately rounded fp32 operation, division and sqrt
+ *               correctly rounded, dot products (x*x' + y*y') + z*z', cross products (a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x,
+ *               a.x*b.y - b.x*a.y), min and max IEEE minNum / maxNum, clamp(x) = min(max(x, 0), 1) (a NaN becomes 0).
+ *               "closest(x) on (v0, e1, e2)" is the triangle rule of rt_tracer_closest_point, giving (t, u, v).
+ *   per query   p1 = P1 - P0, p2 = P2 - P0, m = p1 x p2; the edges G_j -> G_j+1 of the corners (P0, P1), (P1, P2), (P2, P0) with
+ *               d_j = G_j+1 - G_j (d_0 is p1) and a_j = d_j.d_j; qmin, qmax per axis as rt_tracer_overlap_triangles' step 1
+ *               computes them; qabs = the largest |coordinate| of the three corners.
+ *   triangle    on the record the renderer intersects (v0, e1, e2), A = v0, B = fl(v0 + e1), C = fl(v0 + e2), n = e1 x e2, the
+ *               record's edges R_i -> R_i+1 of (A, B), (B, C), (C, A) with r_i = R_i+1 - R_i.  21 candidate points x_k on the query:
+ *                 k = 0..2    the corners P0, P1, P2.
+ *                 k = 3..5    proj(A), proj(B), proj(C), where proj(Y): (t', u', v') = closest(Y) on (P0, p1, p2), then
+ *                             x = (P0 + u'*p1) + v'*p2 per component.
+ *                 k = 6+3i+j  the point of query edge j nearest to record edge i (Ericson, closest points of two segments, with
+ *                             the query edge as the first segment): w = G_j - R_i, a = a_j, e = r_i.r_i, f = r_i.w, c = d_j.w,
+ *                             b = d_j.r_i, denom = a*e - b*b; s0 = clamp((b*f - c*e)/denom), but 0 when denom == 0;
+ *                             tnom = b*s0 + f; s = clamp(-c/a) when tnom < 0 || e == 0, else clamp((b - c)/a) when tnom > e, else
+ *                             s0; and s = 0 when a == 0.  x = G_j + s*d_j per component (the product, then the sum).
+ *                 k = 15+j    where query edge j crosses the record's plane: da = n.(G_j - A), db = n.(G_j+1 - A); PRESENT only when
+ *                             da*db <= 0 && da != db; s = clamp(da/(da - db)), x = G_j + s*d_j.
+ *                 k = 18+i    where record edge i crosses the query's plane: da = m.(R_i - P0), db = m.(R_i+1 - P0), present as
+ *                             above, Y = R_i + s*r_i, x = proj(Y).
+ *               A candidate that is absent or has a NaN coordinate is not considered.  Then every x_k is clamped per axis into
+ *               [qmin, qmax] (max with qmin, then min with qmax: exact; a query collapsed to a point makes every candidate that
+ *               point).  t_k, u_k, v_k = closest(x_k) on the record.  The pair's answer is the smallest t_k (a NaN t_k never), equal
+ *               t going to the lowest k, with that evaluation's (u, v); no candidate left: no answer.
+ *   sphere      a sphere of the scene is its surface; prim = n_tris + i.  Centre S, radius r.  Four candidates: where = 0..2 the
+ *               corners, where = 3 proj(S), considered and clamped as above; t_k = s*s with s = |sqrt(w.w) - r|, w = x_k - S (the
+ *               point query's sphere rule); the smallest, equal t to the lowest k.  When rt_tracer_overlap_triangles' sphere
+ *               condition holds (d2min <= r*r && r*r <= d2max in its arithmetic), t = 0 at that same candidate.  u = v = 0.
+ *   winner      a pair is accepted when t <= d2max (plain fp32; a NaN never).  The winner is the accepted pair with the smallest
+ *               (t, prim): equal t (==) goes to the lowest prim.  No visiting order is named.
+ *   what it means
+ *               (t, u, v) is, bit for bit, closest(witness.xyz) on record prim: the answer can be checked with
+ *               rt_tracer_closest_point, and t is an upper bound of the true squared distance up to the point query's rounding -- a
+ *               reported pair is really that close.  From below it is as accurate as measured (DESIGN.md 4.3m;
+ *               tests/test_tridistance_expect.py): with scale = qabs + the largest |vertex coordinate| and eps = 2^-24,
+ *               sqrt(t) >= D - K*eps*scale for every pair and |sqrt(t) - D| <= K*eps*scale where both triangles are well shaped
+ *               (smallest corner-angle sine >= 2^-6), K = 8 (measured 1.98), D the float64 distance of the fp32 corners.
+ *               t == 0 is guaranteed where a query corner is bit-equal to a record's v0, not for every intersecting pair:
+ *               rt_tracer_overlap_triangles is the touching verdict.
+ * No scene, spheres alone, n = 0, NULL arrays (RT_ERR_INVALID, outputs untouched), scheduling, multi-device handles and
+ * RT_ACCEL_REFIT are rt_tracer_closest_point's.
+ * RT_QUERY_BVH: the ray queries' tree, walked nearest box first.  Per child box [lo, hi] with cmax its largest |coordinate|:
+ *     pad = rho_c * (qabs + cmax);  g = max(max(lo - qmax, qmin - hi, 0) - pad, 0) per axis;
+ *     lb = ((gx*gx + gy*gy) + gz*gz) * (1 - 2^-21)
+ * with rho_c the point query's.  A child is skipped only when lb > best STRICTLY, at the visit and again when it is taken from the
+ * stack; best starts at d2max; a NaN lb takes no pruning decision.  The always-tested list and the spheres follow the walk; a walk
+ * whose stack overflowed recomputes from every leaf record.  The answer is bit for bit the scan's two arrays under the point
+ * query's own invariant (its sliver premise included): every x_k lies in [qmin, qmax], and for every x there each
+ * term above is, by the monotonicity of fp32 subtraction, multiplication and max, at most the term the point query computes for
+ * x -- so lb is at most the point query's bound, which every record inside the child answers with a t at least as large. */
+typedef struct rt_witness { float x, y, z; int32_t where; } rt_witness;
+/* Host arrays: tris n*12, hits n, witness n.  Returns with the answers in host memory. */
+int  rt_tracer_triangle_distance(rt_tracer* t, const float* tris, size_t n, rt_hit* hits, rt_witness* witness);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  tris, hits and witness must be 16-byte aligned; otherwise RT_ERR_INVALID. */
+int  rt_tracer_triangle_distance_device(rt_tracer* t, const float* tris, size_t n, rt_hit* hits, rt_witness* witness, void* stream);
+
 /* ---- one frame sharded over several GPUs, continued: the entry points --------------------------- */
 /* Same constructor, device list added: band k runs on devices[k] (ordinals may repeat: several bands per
  * device).  The handle is an rt_tracer like any other -- Trace / Stop / Resize / SetCameraParameters /

@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "rt_tracer_overlap", "rt_tracer_overlap_device",
     "rt_tracer_overlap_triangles", "rt_tracer_overlap_triangles_device",
     "rt_tracer_sphere_cast", "rt_tracer_sphere_cast_device",
+    "rt_tracer_triangle_distance", "rt_tracer_triangle_distance_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
     "rt_tracer_set_query_accel_update", "rt_tracer_query_accel_rebuild", "rt_tracer_query_accel_update_info",
     "rt_dbg_bvh_refit", "rt_dbg_query_tree_read", "rt_dbg_bvh_tree_cost", "rt_dbg_query_stack_cap",
@@ -131,6 +132,8 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), (
 # rt_side: the side half of a signed point query's answer
 SIDE_DTYPE = np.dtype([("s", np.float32), ("feature", np.int32)])
 FEATURE_NONE, FEATURE_FACE, FEATURE_SPHERE = -1, 0, 7
+# rt_witness: the query-side half of a triangle distance query's answer
+WITNESS_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("where", np.int32)])
 _FEATURE_KEYS = ("triangles", "vertices", "edges", "contributing", "build_us", "bytes")
 
 
@@ -373,6 +376,9 @@ def load_library():
         if hasattr(L, "rt_tracer_sphere_cast"):           # (an older build selected by RT_MI355X_LIB for an A/B has no swept query)
             L.rt_tracer_sphere_cast.argtypes = [vp, vp, C.c_size_t, vp]
             L.rt_tracer_sphere_cast_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        if hasattr(L, "rt_tracer_triangle_distance"):     # (an older build selected by RT_MI355X_LIB for an A/B has no triangle distance)
+            L.rt_tracer_triangle_distance.argtypes = [vp, vp, C.c_size_t, vp, vp]
+            L.rt_tracer_triangle_distance_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
         L.rt_dbg_feature_normals.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
         L.rt_tracer_set_query_accel.argtypes = [vp, C.c_uint32]
         L.rt_tracer_query_accel_info.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -1467,6 +1473,69 @@ class RayTracer:
         sweeps = np.empty((a.shape[0], 8), np.float32)
         sweeps[:, :3], sweeps[:, 3:6], sweeps[:, 6], sweeps[:, 7] = a, b - a, np.asarray(radius, np.float32), np.float32(1.0)
         return self.SphereCast(sweeps)["prim"] < 0
+
+    # ---- proximity of triangles (rt_tracer_triangle_distance / _device) ----------------------------------------------------
+
+    def TriangleDistance(self, triangles, max_distance=np.inf):
+        """The nearest primitive of the scene to each query triangle (rt_tracer_triangle_distance).  triangles: (n, 3, 3) or
+        (n, 9) float32 corners, searched within max_distance (squared on the host in fp32, as ClosestPoint does), or (n, 12)
+        {P0 xyz, d2max, P1 xyz, -, P2 xyz, -} with each triangle's SQUARED search radius in column 3 (+inf = unbounded).  ->
+        (hits, witness): hits as ClosestPoint's (t the squared distance, u, v on the scene's record, prim or PRIM_NONE); witness
+        the winning point on the query triangle and the index of the candidate that produced it (-1: none).  (t, u, v) is
+        ClosestPoint's answer for the point witness.xyz on that prim, bit for bit.  A query with a non-finite coordinate accepts
+        nothing.  numpy in -> (HIT_DTYPE (n,), WITNESS_DTYPE (n,)), on return.  A contiguous (n, 12) float32 torch tensor on the
+        tracer's device -> two (n, 4) float32 tensors {t, u, v, prim bits}, {x, y, z, where bits}, enqueued on
+        torch.cuda.current_stream() without a host synchronisation."""
+        if type(triangles).__module__.startswith("torch"):
+            return self._triangle_distance_tensor(triangles)
+        t = self._distance_triangles("TriangleDistance", triangles, max_distance)
+        hits = np.zeros(t.shape[0], HIT_DTYPE)
+        witness = np.zeros(t.shape[0], WITNESS_DTYPE)
+        self._check(self._lib.rt_tracer_triangle_distance(self._h, t.ctypes.data, t.shape[0], hits.ctypes.data, witness.ctypes.data))
+        return hits, witness
+
+    @staticmethod
+    def _distance_triangles(who, triangles, max_distance):
+        """_triangles_array, with _d2max(max_distance) in column 3 of triangles that came without a radius."""
+        had_radius = np.ndim(triangles) >= 1 and np.shape(triangles)[-1] == 12
+        t = RayTracer._triangles_array(who, triangles)
+        if not had_radius:
+            t[:, 3] = RayTracer._d2max(max_distance)
+        return t
+
+    def _triangle_distance_tensor(self, triangles):
+        import torch
+        if triangles.dtype != torch.float32 or triangles.dim() != 2 or triangles.shape[1] != 12 or not triangles.is_contiguous():
+            raise ValueError("TriangleDistance: expected a contiguous (n, 12) float32 tensor")
+        stream = self._stream_of("TriangleDistance", "triangles", triangles)
+        n = triangles.shape[0]
+        hits = torch.empty((n, 4), dtype=torch.float32, device=triangles.device)
+        witness = torch.empty((n, 4), dtype=torch.float32, device=triangles.device)
+        self._check(self._lib.rt_tracer_triangle_distance_device(self._h, triangles.data_ptr(), n, hits.data_ptr(), witness.data_ptr(), stream))
+        return hits, witness
+
+    def TriangleDistancePositions(self, hits, witness):
+        """Both ends of TriangleDistance's answers (host numpy), each (n, 3) float32: the point on the query triangle (the
+        witness) and the point on the scene (ClosestPositions at the witness); NaN where hits["prim"] is PRIM_NONE."""
+        h = np.asarray(hits).reshape(-1)
+        w = np.asarray(witness).reshape(-1)
+        if h.dtype != HIT_DTYPE or w.dtype != WITNESS_DTYPE or h.shape != w.shape:
+            raise ValueError("TriangleDistancePositions: expected the HIT_DTYPE and WITNESS_DTYPE answers of one TriangleDistance call")
+        on_query = np.stack([w["x"], w["y"], w["z"]], axis=1).astype(np.float32)
+        on_query[h["prim"] < 0] = np.nan
+        return on_query, self.ClosestPositions(on_query, h)
+
+    def MeshDistance(self, triangles, max_distance=np.inf):
+        """The nearest pair between a whole query mesh and the scene, numpy only: TriangleDistance of every triangle, the
+        smallest (t, query index) wins.  -> dict(distance (sqrt of t, float), query (the triangle's index), prim, on_query,
+        on_scene ((3,) float32 each)), or None when nothing lies within max_distance."""
+        hits, witness = self.TriangleDistance(triangles, max_distance)
+        ok = np.nonzero(hits["prim"] >= 0)[0]
+        if ok.size == 0:
+            return None
+        i = int(ok[np.argmin(hits["t"][ok])])                              # (argmin: the first of the smallest)
+        a, b = self.TriangleDistancePositions(hits[i:i + 1], witness[i:i + 1])
+        return {"distance": float(np.sqrt(np.float64(hits["t"][i]))), "query": i, "prim": int(hits["prim"][i]), "on_query": a[0], "on_scene": b[0]}
 
     def SetQueryAcceleration(self, mode):
         """How Intersect / Pick / FocusAt find their hits: QUERY_SCAN (0 / False, the default: every ray scans every triangle)

@@ -219,6 +219,13 @@ hipError_t launch_overlap(const TraceParams& p, const BvhParams* b, uint32_t n, 
 hipError_t launch_overlap_triangles(const TraceParams& p, const BvhParams* b, uint32_t n, const float* tris, const int* after,
                                     uint32_t max_hits, int* prims, uint32_t* counts, hipStream_t st);
 
+// The triangle-shaped proximity query (rt_tridistance.hpp): n query triangles {P0 xyz, d2max, P1 xyz, -, P2 xyz, -}, 16-byte
+// aligned; hits[i] as launch_closest's for the nearest primitive of the triangle, witness[i] = {the winning point on the query
+// triangle, bits of its int32 candidate index}, or {0, 0, 0, -1} in both.  One arithmetic for both math modes; one query per lane
+// in both forms.  rho_c as launch_closest's.
+hipError_t launch_triangle_distance(const TraceParams& p, const BvhParams* b, float rho_c, uint32_t n, const float* tris, float4* hits,
+                                    float4* witness, hipStream_t st);
+
 // The swept query (rt_spherecast.hpp): n sweeps {origin xyz, direction xyz, radius, tmax}, 16-byte aligned; hits[i] = {t of the
 // first contact, u, v of the contact point, bits of the int32 primitive} of the smallest (t, prim) among the certified contacts
 // with t <= tmax, or {0, 0, 0, -1}.  One arithmetic for both math modes; one sweep per lane in both forms.  slack: the tracer's

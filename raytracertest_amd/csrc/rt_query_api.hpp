@@ -1,7 +1,7 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
 // rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_exposure*, rt_tracer_intersect_all*) and the point queries (rt_tracer_closest_point*,
 // rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*) and the region queries (rt_tracer_overlap*, rt_tracer_overlap_triangles*) and the swept query
-// (rt_tracer_sphere_cast*).
+// (rt_tracer_sphere_cast*) and the triangle-shaped proximity query (rt_tracer_triangle_distance*).
 // Included by rt_tracer.hip.
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
@@ -280,6 +280,13 @@ static_assert(RT_SWEEP_SLACK == rtk::kSweepSlack, "include/rt_mi355x.h and rt_ke
 inline void enqueue_sphere_cast(rt_tracer* t, size_t n, const float* sweeps, float4* hits, hipStream_t st) {
   enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
     return rtk::launch_sphere_cast(p, b, static_cast<float>(t->queries.slack_milli) / 1000.0f, static_cast<uint32_t>(n), sweeps, hits, st);
+  });
+}
+
+// query triangles -> one record and one witness per triangle (rt_tridistance.hpp), with enqueue_closest's tree, flags and rho_c
+inline void enqueue_triangle_distance(rt_tracer* t, size_t n, const float* tris, float4* hits, float4* witness, hipStream_t st) {
+  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return rtk::launch_triangle_distance(p, b, closest_rho(t), static_cast<uint32_t>(n), tris, hits, witness, st);
   });
 }
 
@@ -765,6 +772,31 @@ int rt_tracer_sphere_cast_device(rt_tracer* t, const float* sweeps, size_t n, rt
     if (n == 0u) return;
     t->use_device();
     enqueue_sphere_cast(t, n, sweeps, reinterpret_cast<float4*>(hits), static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_triangle_distance(rt_tracer* t, const float* tris, size_t n, rt_hit* hits, rt_witness* witness) {
+  if (!t || !query_args_ok(t, n, {tris, hits, witness})) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_triangle_distance(b, tris, n, hits, witness); }, [&] {
+    if (n == 0u) return;
+    const hipStream_t st = host_query_stream(t);
+    const float* d_tris = staged_in<float>(t->queries.in[0], tris, n * 12u, st);
+    enqueue_triangle_distance(t, n, d_tris, room<float4>(t->queries.out[0], n), room<float4>(t->queries.out[1], n), st);
+    staged_out<float4>(hits, t->queries.out[0], n, st);
+    staged_out<float4>(witness, t->queries.out[1], n, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_triangle_distance_device(rt_tracer* t, const float* tris, size_t n, rt_hit* hits, rt_witness* witness, void* stream) {
+  if (!t || !query_args_ok(t, n, {tris, hits, witness}) ||
+      !query_aligned_ok(t, n, {{tris, 16u}, {hits, 16u}, {witness, 16u}},
+                        "rt_tracer_triangle_distance_device: tris, hits and witness must be 16-byte aligned"))
+    return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_triangle_distance_device(b, tris, n, hits, witness, stream); }, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_triangle_distance(t, n, tris, reinterpret_cast<float4*>(hits), reinterpret_cast<float4*>(witness), static_cast<hipStream_t>(stream));
   });
 }
 

@@ -13,7 +13,11 @@ list's last entry: ClosestAll with max_hits 4 and 16, rows and counts, scan agai
 --spherecast: the same sweep for the swept query, whose allowance beyond r (4 * RT_SWEEP_SLACK * (cmax + r) +
 rho_s * (max|o| + cmax + r)) the same slack scales: SphereCast, scan against BVH, on 2^LOG2 sweeps of
 tests/spherecast_expect.random_sweeps (narrow and wide radii, a share cut at tmax) on C4's scene and the lattice scene.
-Usage: bvh_margin.py [--closest | --nearest | --spherecast] [--out FILE.json] [--rays LOG2]"""
+--tridistance: the --closest sweep for the triangle distance query, which prunes with the point query's allowance
+rho_c against the query triangle's bounding box: TriangleDistance, hits and witnesses, scan against BVH, on 2^LOG2 queries of
+tests/tridistance_expect.mixed_queries (and the lattice's tie queries), unbounded and within the median distance, C4's scene and
+the lattice scene.
+Usage: bvh_margin.py [--closest | --nearest | --spherecast | --tridistance] [--out FILE.json] [--rays LOG2]"""
 import argparse
 import json
 import os
@@ -95,6 +99,42 @@ def nearest_margin(R, scenes, log2_points):
         g.close()
     res["smallest_slack_milli_at_which_bvh_equals_scan"] = smallest_equal
     return res
+
+
+def tridistance_margin(R, scenes, log2_queries):
+    import lattice_cases as lc
+    import tridistance_expect as td
+    res = {"version": R.api.load_library().rt_version().decode(), "rho_c": 2.0 ** -18, "slacks": list(SLACKS), "scenes": {}}
+    smallest_equal = {}
+    for name, rows in (("c4_10k", scenes.random_triangles(10000, 12345)), ("lattice_rooms", lc.rooms())):
+        g = R.RayTracer((64, 48), (0, 0, 0), (0.0, 0.0), 70.0, 3.0, 0.05, seed=1)
+        assert g.UploadScene(rows)
+        q = td.mixed_queries(rows, 1 << log2_queries, 85)
+        if name == "lattice_rooms":
+            q = np.concatenate([td.lattice_queries(), q])
+        first = g.TriangleDistance(q)[0]
+        median = np.float32(np.median(first["t"][first["prim"] >= 0]))
+        batches = {"unbounded": q, "median": td.with_radius(q, median)}
+        scan = {k: g.TriangleDistance(b) for k, b in batches.items()}
+        g.SetQueryAcceleration(True)
+        out, equal = {}, []
+        for slack in SLACKS:
+            g.DebugQueryAccelSlack(slack)
+            per = {}
+            for k, b in batches.items():
+                differ = td.differing(g.TriangleDistance(b), scan[k])
+                per[k] = {"queries": int(b.shape[0]), "answers": int((scan[k][0]["prim"] >= 0).sum()), "differ": int(differ.size)}
+            out[str(slack)] = per
+            if all(v["differ"] == 0 for v in per.values()):
+                equal.append(slack)
+        smallest_equal[name] = min(equal) if equal else None
+        res["scenes"][name] = out
+        g.DebugQueryAccelSlack(1000)
+        g.close()
+    res["smallest_slack_milli_at_which_bvh_equals_scan"] = smallest_equal
+    return res
+
+
 def spherecast_margin(R, scenes, log2_sweeps):
     import lattice_cases as lc
     import spherecast_expect as se
@@ -136,11 +176,13 @@ def main():
     ap.add_argument("--closest", action="store_true")
     ap.add_argument("--nearest", action="store_true")
     ap.add_argument("--spherecast", action="store_true")
+    ap.add_argument("--tridistance", action="store_true")
     a = ap.parse_args()
     import raytracertest_amd as R
     from raytracertest_amd import scenes
-    if a.closest or a.nearest or a.spherecast:
-        txt = json.dumps((spherecast_margin if a.spherecast else nearest_margin if a.nearest else closest_margin)(R, scenes, a.rays), indent=1)
+    if a.closest or a.nearest or a.spherecast or a.tridistance:
+        margin = tridistance_margin if a.tridistance else spherecast_margin if a.spherecast else nearest_margin if a.nearest else closest_margin
+        txt = json.dumps(margin(R, scenes, a.rays), indent=1)
         print(txt)
         if a.out:
             with open(a.out, "w") as f:

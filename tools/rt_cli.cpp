@@ -39,6 +39,8 @@ struct Args {
   bool overlap_tri = false;
   float overlap_t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // --overlap-tri X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,K]: the three corners
   uint32_t overlap_tri_k = 8;
+  bool tri_distance = false;
+  float tri_distance_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, INFINITY};   // --tri-distance X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,R]: the corners, search distance
   float sweep[8] = {0, 0, 0, 0, 0, 0, 0, INFINITY}; // --spherecast X,Y,Z,DX,DY,DZ,R[,TMAX]
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0}, hits_xy[2] = {0, 0}, hits_k = 8;
 };
@@ -151,6 +153,21 @@ bool parse_overlap(const char* s, float* out, uint32_t& k, int m = 6) {
   }
 }
 
+// "X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2" or "...,R": the three corners of a triangle and an optional search distance (out[9] keeps its
+// value when R is absent)
+bool parse_tri_distance(const char* s, float out[10]) {
+  int n = 0;
+  for (const char* q = s;; ++n) {
+    char* end = nullptr;
+    const float f = std::strtof(q, &end);
+    if (end == q || n > 9) return false;
+    out[n] = f;
+    if (*end == 0) return n >= 8;
+    if (*end != ',') return false;
+    q = end + 1;
+  }
+}
+
 // what follows --nearest is the point of a k-nearest query (a number), not the next option
 bool looks_like_number(const char* s) {
   if (*s == '+' || *s == '-') ++s;
@@ -198,11 +215,14 @@ void usage() {
             "                      corners X0,Y0,Z0 and X1,Y1,Z1, then one line `prim` for each of the K lowest, default 8)\n"
             "       [--overlap-tri X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,K]] (prints `overlap-tri count`, the number of primitives that touch the\n"
             "                      triangle with those three corners, then one line `prim` for each of the K lowest, default 8)\n"
+            "       [--tri-distance X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,R]] (prints `tri-distance prim distance where xq yq zq xs ys zs`: the\n"
+            "                      nearest primitive to the triangle with those corners within the distance R when given, the candidate\n"
+            "                      that found it, the nearest point on the triangle and on the scene; `tri-distance -1` when there is none)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
             "       [--spherecast X,Y,Z,DX,DY,DZ,R[,TMAX]] (prints `spherecast prim t u v x y z`: the first contact of a sphere of radius\n"
             "                      R whose centre moves from X,Y,Z along DX,DY,DZ for 0 <= t <= TMAX, and the contact point;\n"
             "                      `spherecast -1` when there is none)\n"
-            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --spherecast / --focus through the scene's BVH instead of the scan)");
+            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --tri-distance / --spherecast / --focus through the scene's BVH instead of the scan)");
 }
 
 }  // namespace
@@ -259,6 +279,10 @@ int main(int argc, char** argv) {
     else if (k == "--overlap-tri") {
       if (!parse_overlap(next("--overlap-tri"), a.overlap_t, a.overlap_tri_k, 9)) { std::fprintf(stderr, "--overlap-tri wants X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,K]\n"); return 2; }
       a.overlap_tri = true;
+    }
+    else if (k == "--tri-distance") {
+      if (!parse_tri_distance(next("--tri-distance"), a.tri_distance_t)) { std::fprintf(stderr, "--tri-distance wants X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,R]\n"); return 2; }
+      a.tri_distance = true;
     }
     else if (k == "--spherecast") {
       if (!parse_spherecast(next("--spherecast"), a.sweep)) { std::fprintf(stderr, "--spherecast wants X,Y,Z,DX,DY,DZ,R[,TMAX]\n"); return 2; }
@@ -450,6 +474,32 @@ int main(int argc, char** argv) {
     }
     std::printf("overlap-tri %u\n", counts[0]);
     for (uint32_t j = 0; j < a.overlap_tri_k && j < counts[0]; ++j) std::printf("%d\n", prims[j]);
+  }
+  if (a.tri_distance) {
+    const float* c = a.tri_distance_t;
+    const std::vector<float> tris = {c[0], c[1], c[2], std::copysign(c[9] * c[9], c[9]), c[3], c[4], c[5], 0.0f, c[6], c[7], c[8], 0.0f};
+    std::vector<rt_hit> hits;
+    std::vector<rt_witness> witness;
+    if (!tracer.TriangleDistance(tris, hits, witness)) {
+      std::fprintf(stderr, "rt_cli: --tri-distance: %s\n", tracer.LastError().c_str());
+      return 1;
+    }
+    const rt_hit& h = hits[0];
+    const rt_witness& w = witness[0];
+    if (h.prim < 0 || static_cast<size_t>(h.prim) >= scene.size() / 3) {
+      std::printf("tri-distance -1\n");
+    } else {                                                    // --closest's position at the witness
+      const float4 r0 = scene[3 * h.prim], r1 = scene[3 * h.prim + 1], r2 = scene[3 * h.prim + 2];
+      const float v0[3] = {r0.x, r0.y, r0.z}, b[3] = {r1.x, r1.y, r1.z}, cc[3] = {r2.x, r2.y, r2.z};
+      float q[3];
+      for (int i = 0; i < 3; ++i) {
+        const float e1 = a.edges ? b[i] : b[i] - v0[i], e2 = a.edges ? cc[i] : cc[i] - v0[i];
+        q[i] = (v0[i] + h.u * e1) + h.v * e2;
+      }
+      std::printf("tri-distance %d %.9g %d %.9g %.9g %.9g %.9g %.9g %.9g\n", h.prim, static_cast<double>(std::sqrt(h.t)), w.where,
+                  static_cast<double>(w.x), static_cast<double>(w.y), static_cast<double>(w.z), static_cast<double>(q[0]),
+                  static_cast<double>(q[1]), static_cast<double>(q[2]));
+    }
   }
   if (a.focus) {
     float focal = 0.0f;
