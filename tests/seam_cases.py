@@ -18,10 +18,17 @@ and v are exact under both arithmetic contracts and a tie is a tie bit for bit.
 Two layouts.  The issue asks for the records S - 1 and S to be isolated targets, members of a stack of eight distinct depths,
 AND bit-identical twins; one scene cannot hold all three, so the scene comes in two layouts that differ in ONE record:
 "stack" is the scene above; "tie" overwrites record S (where the scene has it) with a copy of record S - 1, vertex for vertex:
-the last record of one chunk and the first of the next are the same triangle.  The populations are the same in both."""
+the last record of one chunk and the first of the next are the same triangle.  The populations are the same in both.
+
+sweep_batch and triangle_batch (SphereCast, TriangleDistance) tag every targeted row with the primitive it must name on the stack
+layout; sweep_table / triangle_table, sweep_winners / triangle_winners and lose_columns restate the answers from
+spherecast_expect and tridistance_expect, with the same two ways to break them as `winners` has for the rays."""
 import numpy as np
 
 import closest_expect as ce
+import spherecast_expect as spe
+import tridistance_expect as tde
+from trioverlap_expect import queries_of
 from lattice_cases import ray_segments
 from occluded_expect import with_interval
 from query_expect import FLT_MAX, HIT_DTYPE, adversarial_rays, edge_rows  # noqa: F401  (edge_rows: for the tests)
@@ -285,6 +292,166 @@ def tie_cursor(pts, tags, exp_closest):
         if t[0] in ("near", "under") and t[2] == t[1] - 1:
             after[j] = exp_closest[j]
     return after
+
+
+# ---- sweeps ---------------------------------------------------------------------------------------------------------------
+
+SWEEP_R = 1.0 / 32                             # the targeted sweeps' radius: a petal's neighbours are many radii away
+
+
+def _pad(items, tags):
+    """More than 256 items and no multiple of 64: the batch ends in a partial wave of a second block."""
+    assert len(items) > 256
+    if len(items) % 64 == 0:
+        items.append(items[0])
+        tags.append(tags[0])
+
+
+def sweep_batch(n_tris, rows):
+    """-> (sweeps (n, 8) float32 {origin, direction, radius, tmax}, tags), n > 256 and no multiple of 64, shuffled.  rows: the
+    STACK layout's.  tags[j] = (kind, S, index), index = the primitive the sweep must name on the stack layout, -1 = none:
+      down        from (petal_point(index), z = 0) along (0, 0, -1), r = 1/32, tmax = inf: that petal alone, on its face
+      up          the same from z = -16 along (0, 0, +1): the petal again, from behind
+      start       from 1/16 above the petal's point with r = 1/8: the sweep starts in overlap, t = 0 and that petal
+      axis_down / axis_up   along the stack's axis from z = 0 and from z = -16: the highest member (a record of the SECOND chunk
+                  where the seam has one) and the lowest
+      cut         the axis_down sweep with tmax == the t of its contact (closed: index = that petal) and one ulp below it (-1)
+      bad         the down sweeps with a negative radius, a NaN radius and tmax < 0 (-1)
+      general     260 of spherecast_expect.batch of the whole scene (its fixed populations are some 2 500 sweeps, so the batch is
+                  drawn at 3 000 and, being shuffled, cut at 260), index -1 without meaning
+    Every coordinate of the targeted sweeps is dyadic: their t are exact and a tie is a tie bit for bit."""
+    sw, tags = [], []
+    r = SWEEP_R
+    for S in placed_seams(n_tris):
+        m = members(n_tris, S)
+        cx, cy = CENTRE[S]
+        for i in m:
+            x, y = petal_point(i, S)
+            down = [x, y, ABOVE, 0, 0, -1, r, np.inf]
+            for kind, s in (("down", down), ("up", [x, y, BELOW, 0, 0, 1, r, np.inf]),
+                            ("start", [x, y, petal_z(i, S) + 0.0625, 0, 0, -1, 0.125, np.inf])):
+                sw.append(s)
+                tags.append((kind, S, i))
+            for slot, val in ((6, -r), (6, np.nan), (7, -1.0)):
+                s = list(down)
+                s[slot] = val
+                sw.append(s)
+                tags.append(("bad", S, -1))
+        axis = [cx, cy, ABOVE, 0, 0, -1, r, np.inf]
+        sw += [axis, [cx, cy, BELOW, 0, 0, 1, r, np.inf]]
+        tags += [("axis_down", S, m[-1]), ("axis_up", S, m[0])]
+        t = spe.table(f32([axis]), rows)[0][0, m[-1]]
+        assert t == f32(ABOVE - petal_z(m[-1], S) - r)
+        sw += [axis[:7] + [t], axis[:7] + [np.nextafter(t, f32(0))]]
+        tags += [("cut", S, m[-1]), ("cut", S, -1)]
+    general = spe.batch(rows, 3000, 51 + n_tris)[:260]
+    sw.extend(general.tolist())
+    tags += [("general", 0, -1)] * general.shape[0]
+    _pad(sw, tags)
+    order = np.random.default_rng(5).permutation(len(sw))
+    return np.ascontiguousarray(f32(sw)[order]), [tags[j] for j in order]
+
+
+def sweep_table(sweeps, rows, edges=False, spheres=None):
+    """spherecast_expect.table, read-only."""
+    tab = spe.table(sweeps, rows, edges, spheres)
+    for x in tab:
+        x.setflags(write=False)
+    return tab
+
+
+def sweep_winners(tab, sweeps, drop=(), tie_high=False):
+    """spherecast_expect.winners' records.  For tests of the tests: drop -- primitives the scan leaves out; tie_high -- the
+    LATER of two equal t wins."""
+    tab = lose_columns(tab, drop, INF)
+    if not tie_high:
+        return spe.winners(tab, sweeps)[0]
+    out = spe.winners(tuple(x[:, ::-1] for x in tab), sweeps)[0]
+    out["prim"] = np.where(out["prim"] >= 0, tab[0].shape[1] - 1 - out["prim"], -1)
+    return out
+
+
+# ---- query triangles ------------------------------------------------------------------------------------------------------
+
+def _corner_triangle(x, y, z, up):
+    """A small dyadic triangle whose corner P0 = (x, y, z) is its lowest (up = 1) or highest (up = -1) point."""
+    return [[x, y, z], [x + 0.03125, y, z + up * 0.0625], [x, y + 0.03125, z + up * 0.0625]]
+
+
+def triangle_batch(n_tris, rows):
+    """-> (queries (n, 12) float32 {P0 xyz, d2max, P1 xyz, -, P2 xyz, -}, tags), n > 256 and no multiple of 64, shuffled.  rows:
+    the STACK layout's.  tags[j] = (kind, S, index), index = the primitive the query must name on the stack layout, -1 = none:
+      near        a small triangle whose nearest corner is 1/16 above petal `index`'s point, d2max = inf: t = 2^-8, that petal
+      under       the same 1/16 below the point of petal S - 1: equidistant from both twins in the tie layout
+      beside      on the stack's axis, 1/2 above the highest petal and 1/2 below the lowest
+      fourth      the beside triangles with d2max == the squared distance of the 4th petal from there (S from above, S - 1
+                  from below; closed, so the bound cuts the stack on the seam; stacks of eight only)
+      nan / negative   the near triangles with d2max NaN and -1 (-1)
+      general     tridistance_expect.mixed_queries of the whole scene, 260 of them, index -1 without meaning"""
+    tri, d2, tags = [], [], []
+    for S in placed_seams(n_tris):
+        m = members(n_tris, S)
+        cx, cy = CENTRE[S]
+        for i in m:
+            x, y = petal_point(i, S)
+            for kind, radius in (("near", np.inf), ("nan", np.nan), ("negative", -1.0)):
+                tri.append(_corner_triangle(x, y, petal_z(i, S) + 0.0625, 1))
+                d2.append(radius)
+                tags.append((kind, S, i if kind == "near" else -1))
+        if S - 1 in m:
+            x, y = petal_point(S - 1, S)
+            tri.append(_corner_triangle(x, y, petal_z(S - 1, S) - 0.0625, -1))
+            d2.append(np.inf)
+            tags.append(("under", S, S - 1))
+        above = _corner_triangle(cx, cy, petal_z(m[-1], S) + 0.5, 1)
+        below = _corner_triangle(cx, cy, Z0 - 0.5, -1)
+        tri += [above, below]
+        d2 += [np.inf, np.inf]
+        tags += [("beside", S, m[-1]), ("beside", S, m[0])]
+        if len(m) == 8:
+            for q, fourth, winner in ((above, S, m[-1]), (below, S - 1, m[0])):
+                t = tde.table(tde.with_radius(queries_of([q]), INF), rows)["t"][0, fourth]
+                assert t == f32(q[0][2] - petal_z(fourth, S)) ** 2
+                tri.append(q)
+                d2.append(t)
+                tags.append(("fourth", S, winner))
+    q = tde.with_radius(queries_of(tri), f32(d2)) if tri else np.zeros((0, 12), f32)
+    general = tde.mixed_queries(rows, 260, 61 + n_tris)
+    q = q.tolist() + general.tolist()
+    tags += [("general", 0, -1)] * general.shape[0]
+    _pad(q, tags)
+    order = np.random.default_rng(6).permutation(len(q))
+    return np.ascontiguousarray(f32(q)[order]), [tags[j] for j in order]
+
+
+def triangle_table(queries, rows, edges=False, spheres=None):
+    """tridistance_expect.table as a tuple (t, u, v, where, x), read-only: tie_table and lose_columns take it as they take the
+    others."""
+    tab = tde.table(queries, rows, edges, spheres)
+    out = tuple(tab[k] for k in ("t", "u", "v", "where", "x"))
+    for x in out:
+        x.setflags(write=False)
+    return out
+
+
+def triangle_winners(tab, d2max, drop=(), tie_high=False):
+    """tridistance_expect.winners' (hits, witness) on triangle_table's tuple; drop and tie_high as sweep_winners'."""
+    tab = lose_columns(tab, drop, f32(np.nan))
+    if tie_high:
+        tab = tuple(x[:, ::-1] for x in tab)
+    hits, wit = tde.winners(dict(zip(("t", "u", "v", "where", "x"), tab)), d2max)
+    if tie_high:
+        hits["prim"] = np.where(hits["prim"] >= 0, tab[0].shape[1] - 1 - hits["prim"], -1)
+    return hits, wit
+
+
+def lose_columns(tab, drop, never):
+    """A table (t first) whose primitives `drop` answer `never` (the t no query accepts): a scan that loses those records."""
+    if not drop:
+        return tab
+    out = tuple(x.copy() for x in tab)
+    out[0][:, list(drop)] = never
+    return out
 
 
 # ---- exposure points ------------------------------------------------------------------------------------------------------

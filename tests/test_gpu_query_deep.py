@@ -3,7 +3,10 @@ has 16 levels and whose populations hold all 48 entries of the stack in each of 
 asserts the restated marks, Exposure's included), every BVH query equals the scan on the same tracer under
 that query's own check, in both layouts, both arithmetic modes and both hit rules; the device refit of 16 levels is the host's;
 and with the stack shortened by DebugQueryStackCap every lane that needs one entry more answers from every leaf record -- the
-overflow path, which no tree of the builder reaches on its own -- under the same checks."""
+overflow path, which no tree of the builder reaches on its own -- under the same checks.  The four newer walkers on the same
+bvh_walk (overlap_bvh_kernel, trioverlap_bvh_kernel, spherecast_bvh_kernel, tridistance_bvh_kernel), each with an overflow
+restart of its own, go through every one of these cases with region_pops' boxes, query triangles and sweeps: they equal the
+scan byte for byte by contract, every row, at every cap."""
 import numpy as np
 import pytest
 
@@ -12,7 +15,11 @@ import deep_cases as dc
 import exposure_expect as ee
 import lattice_cases as lc
 import nearest_expect as ne
+import overlap_expect as oe
 import refit_cases as rc
+import spherecast_expect as spe
+import tridistance_expect as td
+import trioverlap_expect as te
 from allhits_expect import check_bvh_all_hits, same_rows, sets_from_oracle
 from occluded_expect import check_bvh_occluded
 from query_accel_expect import check_against_scan, check_tree, walk_tree
@@ -23,6 +30,9 @@ pytestmark = pytest.mark.gpu
 ONE_RAY = np.array([[0, 0, 0, 0.1, 0.2, -1]], np.float32)
 ADV_SPHERES = np.array([[0.5, 0.3, -6.0, 1.0], [0.5, 0.3, -6.0, 1.0], [-1.5, 1.0, -4.0, 0.7], [0.0, 0.0, 4.0, 1.5]], np.float32)
 MAX_HITS = (1, 4, 16)
+REGION_HITS = (0, 4, 16)                                                 # Overlap's and OverlapTriangles' three list capacities
+BYTE_EQUAL = ("overlap", "trioverlap", "spherecast", "tridistance")      # tree == scan by contract: no exclusion
+ROW_POPULATIONS = ("rays", "segs", "points", "exposure", "boxes", "tris", "sweeps")
 _cache = {}
 
 
@@ -43,6 +53,10 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint8).tobytes()
 
 
+def _row_bytes(a):
+    return np.ascontiguousarray(a).reshape(a.shape[0], -1).view(np.uint8)
+
+
 def deep_spheres(mirror):
     """Four spheres of the ladder's scales: a small one on the axis, and a middle one, its copy and a large one beside it (the
     rays along the axis pass them: a lane that a sphere finishes never walks the tree)."""
@@ -54,6 +68,44 @@ def deep_spheres(mirror):
                      np.r_[s[-3] * (axis + [0.0, 1.5, 0.0]), 0.5 * s[-3]]], np.float32)
 
 
+def region_pops(rows, seed, n=160):
+    """{boxes, tris, sweeps} for Overlap, OverlapTriangles / TriangleDistance and SphereCast: n boxes around and n query triangles
+    beside the scene's own finite triangles, and n sweeps of spherecast_expect.random_sweeps(rel=True), all in units of the
+    chosen triangle's extent (the ladder spans 2^69).  A box's half widths and a query's size are 2^-2 .. 2^5 extents: the small
+    ones touch a leaf or nothing, the large ones reach every root child and, on the ladder, cover the origin and with it every
+    smaller cluster.  Every sixteenth box and query triangle spans the whole scene, by a different margin each: its walk enters all
+    four children at every level, the fullest stack there is (48 of 48 entries on the ladder), beside neighbours in the wave that
+    hold a few; sixteen sweeps of 3 .. 30 extents' radius start in overlap with many records, which all tie at t = 0.  A quarter
+    of the query triangles search within half an extent.  Then the rows that accept nothing: an inverted and a NaN box, a NaN corner, a
+    negative and a NaN radius, and spherecast_expect.bad_sweeps."""
+    rng = np.random.default_rng(seed)
+    t = np.asarray(rows, np.float64).reshape(-1, 3, 4)[:, :, :3]
+    with np.errstate(invalid="ignore"):
+        fin = np.nonzero(np.isfinite(t).all(axis=(1, 2)) & (np.abs(t) < 1e30).all(axis=(1, 2)))[0]
+    k = fin[rng.integers(0, fin.size, n)]
+    cen = t[k].mean(axis=1)
+    ext = np.abs(t[k] - cen[:, None, :]).max(axis=(1, 2))[:, None]
+    c = cen + ext * rng.uniform(-1.0, 1.0, (n, 3))
+    half = ext * 2.0 ** rng.uniform(-2.0, 5.0, (n, 1)) * rng.uniform(0.25, 1.0, (n, 3))
+    boxes = oe.boxes_of(c - half, c + half)
+    boxes[0, 0], boxes[0, 4] = boxes[0, 4], boxes[0, 0]                  # inverted on x
+    boxes[1, 5] = np.nan
+    size = (ext * 2.0 ** rng.uniform(-2.0, 5.0, (n, 1)))[:, :, None]
+    tris = te.queries_of((cen + ext * rng.uniform(-1.5, 1.5, (n, 3)))[:, None, :] + size * rng.uniform(-1.0, 1.0, (n, 3, 3)))
+    tris = td.with_radius(tris, np.where(np.arange(n) % 4 == 3, (0.5 * ext[:, 0]) ** 2, np.inf))
+    lo, hi = t[fin].min(axis=(0, 1)), t[fin].max(axis=(0, 1))
+    for j in range(8, n, 16):                                            # the whole scene
+        d = (hi - lo) * 2.0 ** (j // 16 - 3)
+        boxes[j] = oe.boxes_of(lo - d, hi + d)[0]
+        tris[j] = td.with_radius(te.queries_of([[lo - d, hi + d, [lo[0] - d[0], hi[1] + d[1], 0.5 * (lo[2] + hi[2])]]]), np.inf)[0]
+    tris[0, 5], tris[1, 3], tris[2, 3] = np.nan, -1.0, np.nan
+    with np.errstate(over="ignore"):
+        sweeps = np.concatenate([spe.random_sweeps(rows, n - 16, seed + 1, rel=True),
+                                 spe.random_sweeps(rows, 16, seed + 2, rmin=0.5, rmax=1.5, rel=True)])
+    return {"boxes": boxes, "tris": np.ascontiguousarray(tris, np.float32),
+            "sweeps": np.ascontiguousarray(np.concatenate([sweeps, spe.bad_sweeps(sweeps[0])]), np.float32)}
+
+
 def deep_pops(mirror):
     """The ladder's populations as the queries take them, once per session."""
     key = ("deep", mirror)
@@ -61,7 +113,8 @@ def deep_pops(mirror):
         from raytracertest_amd import api
         rays = dc.rays(mirror=mirror)
         _cache[key] = {"rays": rays, "segs": dc.segments(rays), "points": dc.points(mirror=mirror),
-                       "exposure": dc.exposure_points(mirror=mirror), "dirs": ee.as_dirs4(api.hemisphere_directions(64))}
+                       "exposure": dc.exposure_points(mirror=mirror), "dirs": ee.as_dirs4(api.hemisphere_directions(64)),
+                       **region_pops(dc.deep_scene(mirror=mirror), 43)}
     return _cache[key]
 
 
@@ -84,7 +137,7 @@ def scene_pops(rows, seed, n=200):
     nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
     expo = np.ascontiguousarray(np.c_[cen, nrm, np.full(24, 1e-3), np.full(24, np.inf)], np.float32)
     return {"rays": rays, "segs": np.ascontiguousarray(np.concatenate([segs, dead]), np.float32), "points": np.ascontiguousarray(pts, np.float32),
-            "exposure": expo, "dirs": ee.as_dirs4(api.hemisphere_directions(64))}
+            "exposure": expo, "dirs": ee.as_dirs4(api.hemisphere_directions(64)), **region_pops(rows, seed + 2, min(n, 160))}
 
 
 def answers(g, pops, intersect=True):
@@ -109,6 +162,12 @@ def answers(g, pops, intersect=True):
         out["exposure5"] = g.Exposure(pops["exposure"], dc.SHORT_TABLE, world=True)
         out["exposure64_occluded"] = g.Occluded(ee.exposure_segments(pops["exposure"], pops["dirs"]))
         out["exposure5_occluded"] = g.Occluded(ee.exposure_segments(pops["exposure"], dc.SHORT_TABLE, world=True))
+        for name, query, batch in (("overlap", g.Overlap, pops["boxes"]), ("trioverlap", g.OverlapTriangles, pops["tris"])):
+            for m in REGION_HITS:
+                out["%s%d" % (name, m)] = query(batch, m)
+            out[name + "4_after"] = query(batch, 4, after=np.ascontiguousarray(out[name + "4"][0][:, 3]))    # the cursor, chained once
+        out["spherecast"] = g.SphereCast(pops["sweeps"])
+        out["tridistance"] = g.TriangleDistance(pops["tris"])
     return out
 
 
@@ -136,12 +195,38 @@ def check_answers(got, scan, pops, rows, orc, spheres=None, contract=None, label
         for key in ("nearest%d" % m, "nearest%d_after" % m):
             assert ne.differing_rows(got[key][0], scan[key][0], got[key][1], scan[key][1]).size == 0, (label, key)
         assert got["nearest%d_after" % m][1][3] == 0, label             # the NaN cursor
+    assert_region_bytes(got, scan, label)                                # the four newer walkers: the scan's bytes, every row
     for key, dirs, world in (("exposure64", pops["dirs"], False), ("exposure5", dc.SHORT_TABLE, True)):
         for ans in (got, scan):
             want = ee.pack_masks(~ans[key + "_occluded"].reshape(-1, dirs.shape[0]))
             assert np.array_equal(ans[key], want), (label, key)
         segs = ee.exposure_segments(pops["exposure"], dirs, world=world)
         check_bvh_occluded(got[key + "_occluded"], scan[key + "_occluded"], segs, rows, orc, spheres, contract, label="%s %s" % (label, key))
+
+
+def assert_region_bytes(got, want, label):
+    """The answers of Overlap, OverlapTriangles, SphereCast and TriangleDistance in `got` against those in `want`, byte for byte."""
+    keys = [k for k in got if k.startswith(BYTE_EQUAL)]
+    assert len(keys) == 2 * (len(REGION_HITS) + 1) + 2, keys
+    for key in keys:
+        parts = [(got[key], want[key])] if not isinstance(got[key], tuple) else list(zip(got[key], want[key]))
+        for a, b in parts:
+            bad = np.nonzero((_row_bytes(a) != _row_bytes(b)).any(axis=1))[0]
+            assert a.dtype == b.dtype and a.shape == b.shape and bad.size == 0, (label, key, bad[:5], a[bad[:3]], b[bad[:3]])
+
+
+def restated_regions(pops, rows, edges, spheres):
+    """What answers() must give for the four newer queries, by brute force over the numpy restatements' tables."""
+    up = edge_rows(rows) if edges else rows
+    out = {}
+    with np.errstate(all="ignore"):
+        for name, acc in (("overlap", oe.table(pops["boxes"], up, edges, spheres)), ("trioverlap", te.table(pops["tris"], up, edges, spheres))):
+            for m in REGION_HITS:
+                out["%s%d" % (name, m)] = oe.rows_of_table(acc, m)
+            out[name + "4_after"] = oe.rows_of_table(acc, 4, out[name + "4"][0][:, 3])
+        out["spherecast"] = spe.expected(pops["sweeps"], up, edges, spheres)
+        out["tridistance"] = td.expected(pops["tris"], up, edges, spheres)
+    return out
 
 
 def scan_and_tree(g, pops, intersect=True):
@@ -234,7 +319,7 @@ def test_device_refit_of_sixteen_levels_equals_the_host_refit(orc, name):
         host_cost = api.tree_cost(tree2[0])
         assert abs(u2["cost"] - host_cost) <= 1e-12 * host_cost
         print("%s edges=%d: refits of 16 levels %d and %d us, cost %.6g -> %.6g -> %.6g" % (name, edges, u1["refit_us"], u2["refit_us"], u0["cost"], u1["cost"], u2["cost"]))
-        sub = {k: (v[::3] if k in ("rays", "segs", "points", "exposure") else v) for k, v in pops.items()}
+        sub = {k: (v[::3] if k in ROW_POPULATIONS else v) for k, v in pops.items()}
         scan, got = scan_and_tree(g, sub)
         check_answers(got, scan, sub, moved, orc, label="%s edges=%d after two refits" % (name, edges), edges=edges)
         g.DebugQueryStackCap(1)                                           # the refit walks no stack: the hook leaves it alone
@@ -275,7 +360,8 @@ def _fallback_case(orc, name):
     pts = ce.lattice_points()
     pops = {"rays": rays, "segs": lc.ray_segments(rays), "points": np.concatenate([ce.with_radius(pts, ce.INF), ce.with_radius(pts, 0.25)]),
             "exposure": np.ascontiguousarray(np.c_[pts[:24] + np.float32(0.125), np.tile([0.0, 0.0, 1.0], (24, 1)), np.zeros(24), np.full(24, np.inf)], np.float32),
-            "dirs": ee.as_dirs4(lc.DIRECTIONS)}
+            "dirs": ee.as_dirs4(lc.DIRECTIONS), **region_pops(rows, 13)}
+    pops["tris"] = np.ascontiguousarray(np.concatenate([pops["tris"], td.lattice_queries()[::8]]))   # and the lattice's own: ties by the dozen
     return rows, pops, None, True
 
 
@@ -296,6 +382,13 @@ def test_a_shortened_stack_answers_from_every_leaf_record(orc, name):
     share = {k: float((m > 0).mean()) for k, m in marks.items()}
     print("%s: share of each restated walk's lanes that hold an entry at all: %s" % (name, {k: round(v, 2) for k, v in share.items()}))
     assert all(v > 0.5 for k, v in share.items() if not k.endswith("open lanes")), share
+    newer, wide = region_marks(nodes, recs, info, pops, rows, spheres)
+    print("%s: the fullest stacks of the newer walks' restatements (every fourth lane): %s; sweeps whose box meets more than one root child: %d of %d"
+          % (name, {k: int(m.max()) for k, m in newer.items()}, int(wide.sum()), wide.shape[0]))
+    assert all((m > 0).any() for m in newer.values())
+    if name == "deep":                                                   # lanes that only the one-entry-short cap overflows
+        assert all(m.max() == 3 * info["depth"] and (m < 3 * (info["depth"] - 1)).any() for m in newer.values()), newer
+    marks.update(newer)
     for math_mode, edges in ((0, False), (1, True)):
         contract = orc.FMA if math_mode == 0 else orc.STRICT
         g = _tracer(math_mode)
@@ -306,6 +399,7 @@ def test_a_shortened_stack_answers_from_every_leaf_record(orc, name):
         depth = g.QueryAccelInfo()["depth"]
         assert depth == info["depth"]
         check_answers(before, scan, pops, rows, orc, spheres, contract, "%s product" % name, exact, edges)
+        assert_region_bytes(scan, restated_regions(pops, rows, edges, spheres), "%s scan against the restatement" % name)
         try:
             for cap in (0, 1, 3, 3 * (depth - 1), 3 * depth - 1):
                 g.DebugQueryStackCap(cap)
@@ -319,6 +413,28 @@ def test_a_shortened_stack_answers_from_every_leaf_record(orc, name):
             g.DebugQueryStackCap(None)
         assert same_answers(answers(g, pops), before), name             # the product again, byte for byte
         g.close()
+
+
+def region_marks(nodes, recs, info, pops, rows, spheres):
+    """({walk: the most stack entries each lane's restated walk holds}, every fourth box and query triangle, for overlap_bvh_kernel,
+    trioverlap_bvh_kernel and tridistance_bvh_kernel; for spherecast_bvh_kernel, which has no restated walk, the sweeps whose
+    box (both ends, widened by the radius) meets more than one child of the root: a device-independent lower bound on the
+    lanes that hold an entry)."""
+    from query_accel_expect import EMPTY
+    out = {}
+    boxes, tris, sw = pops["boxes"][::4], pops["tris"][::4], pops["sweeps"]
+    with np.errstate(all="ignore"):
+        for key, walk in (("overlap16", lambda st: oe.walk_tree_overlap(nodes, recs, info, boxes, rows, 16, spheres=spheres, stats=st)),
+                          ("trioverlap16", lambda st: te.walk_tree_triangles(nodes, recs, info, tris, rows, 16, spheres=spheres, stats=st)),
+                          ("tridistance", lambda st: td.walk_tree_tridistance(nodes, recs, info, tris, rows, spheres=spheres, stats=st))):
+            stats = {}
+            walk(stats)
+            out[key] = np.asarray(stats["high_water_per"])
+        a, b = sw[:, :3], sw[:, :3] + sw[:, 3:6]
+        lo, hi = np.minimum(a, b) - sw[:, 6:7], np.maximum(a, b) + sw[:, 6:7]
+        root = nodes[0]
+        met = ((root["lo"][None] <= hi[:, :, None]) & (root["hi"][None] >= lo[:, :, None])).all(axis=1) & (root["child"] != EMPTY)[None]
+    return out, met.sum(axis=1) > 1
 
 
 def restated_marks(orc, nodes, recs, info, pops, rows, spheres):

@@ -4,7 +4,10 @@ nearest_kernel) at the seams of their LDS chunks of kQueryChunk = 1024 records, 
 (test_seam_cases.py asserts that without a device, with a reference that loses such a record as its teeth).  Every scan-mode
 answer is compared byte for byte with the oracle's brute force or the numpy restatement, no ray excluded; then the same
 populations go through the BVH kernels on the same tracer under each query's own check, the targeted ones without an exclusion.
-Last, the K that query_k() picks on its own at 524 288 and 1 048 576 rays, which every other test forces."""
+spherecast_kernel and tridistance_kernel carry a running best through the same chunk loop: their sweeps and query triangles
+(seam_cases.sweep_batch, triangle_batch) are compared with the numpy restatements' winners through the scan and the tree, which
+equal each other by construction, so no row has an exclusion.  Last, the K that query_k() picks on its own at 524 288 and
+1 048 576 rays, which every other test forces."""
 import numpy as np
 import pytest
 
@@ -13,11 +16,14 @@ import exposure_expect as ee
 import nearest_expect as ne
 import seam_cases as sc
 import signed_expect as se
+import spherecast_expect as spe
+import tridistance_expect as td
 from allhits_expect import check_bvh_all_hits, expected_all_hits, hit_table_uv, same_rows, sets_from_table, truncated
 from lattice_cases import ray_segments
 from occluded_expect import check_bvh_occluded, expected_occluded, interval_families
 from query_accel_expect import EXCLUSION_CAP, check_against_scan
 from query_expect import HIT_DTYPE, adversarial_rays, adversarial_scene, edge_rows, expected_hits, same_hits
+from trioverlap_expect import queries_of
 
 pytestmark = pytest.mark.gpu
 
@@ -310,6 +316,111 @@ def test_point_queries_find_the_records_on_the_seams(n_tris, math_mode, edges):
         g.close()
 
 
+# ---- SphereCast, TriangleDistance -------------------------------------------------------------------------------------------
+
+def _append_columns(tab, more):
+    return tuple(np.concatenate([a, b], axis=1) for a, b in zip(tab, more))
+
+
+def swept_refs(n_tris, edges):
+    """The sweeps and query triangles of the seams and the restatements' tables of the STACK layout in one upload format, once
+    per session (neither query depends on the arithmetic mode); the tie layout's tables follow from them (seam_cases.tie_table,
+    which test_seam_cases.py checks against the restatement itself)."""
+    key = ("swept", n_tris, edges)
+    if key not in _cache:
+        rows = sc.seam_scene(n_tris)[0]
+        up = edge_rows(rows) if edges else rows
+        sw, stags = sc.sweep_batch(n_tris, rows)
+        q, qtags = sc.triangle_batch(n_tris, rows)
+        for a in (sw, q):
+            a.setflags(write=False)
+        _cache[key] = {"sweeps": sw, "stags": stags, "queries": q, "qtags": qtags, "sweep_table": sc.sweep_table(sw, up, edges),
+                       "triangle_table": sc.triangle_table(q, up, edges)}
+    return _cache[key]
+
+
+def _named(kind, S, i, twin):
+    """The primitive a targeted sweep or query triangle must name (None: no claim): its tag's on the stack layout; on the tie
+    layout the twin's own place is empty for a sweep, and a stack whose highest petal was the twin has S - 1 on top."""
+    if kind == "general":
+        return None
+    if twin and i == S:
+        return -1 if kind in ("down", "up", "start", "cut") else S - 1 if kind in ("axis_down", "beside") else None
+    return i
+
+
+def _check_names(prim, tags, info, label):
+    for j, (kind, S, i) in enumerate(tags):
+        want = _named(kind, S, i, kind != "general" and info["seams"][S]["tie"])
+        assert want is None or prim[j] == want, (label, kind, S, i, prim[j])
+
+
+def _swept_case(n_tris, edges, query):
+    """-> per layout: rows, info, the batch, its tags and the layout's table."""
+    r = swept_refs(n_tris, edges)
+    batch, tags, tab = (r["sweeps"], r["stags"], r["sweep_table"]) if query == "sweep" else (r["queries"], r["qtags"], r["triangle_table"])
+    for layout in sc.layouts(n_tris):
+        rows, info = sc.seam_scene(n_tris, layout)
+        yield layout, rows, info, batch, tags, (tab if layout == "stack" else sc.tie_table(tab, info))
+
+
+@uploads
+@sizes
+def test_sphere_cast_finds_the_records_on_the_seams(n_tris, edges):
+    for layout, rows, info, sw, tags, tab in _swept_case(n_tris, edges, "sweep"):
+        exp = sc.sweep_winners(tab, sw)
+        _check_names(exp["prim"], tags, info, "the restatement")
+        blobs = set()
+        for math_mode in ((0, 1) if n_tris == 2049 else (0,)):           # the arithmetic mode must not change a byte
+            g = _tracer(math_mode)
+            _upload(g, rows, edges)
+            with np.errstate(all="ignore"):
+                for accel in (False, True):                              # the scan, then the same tracer through the tree: the same bytes
+                    g.SetQueryAcceleration(accel)
+                    lab = "n=%d %s mm=%d edges=%d accel=%d" % (n_tris, layout, math_mode, edges, accel)
+                    got = g.SphereCast(sw)
+                    bad = ce.differing(got, exp)
+                    assert got.dtype == HIT_DTYPE and bad.size == 0, (lab, bad[:5], [tags[j] for j in bad[:5]], got[bad[:3]], exp[bad[:3]])
+                    for n in (257, 1):
+                        assert ce.same_hits(g.SphereCast(sw[:n]), exp[:n]), (lab, n)
+                    _check_names(got["prim"], tags, info, lab)
+                    blobs.add(got.tobytes())
+            g.close()
+        assert len(blobs) == 1
+
+
+@uploads
+@sizes
+def test_triangle_distance_finds_the_records_on_the_seams(n_tris, edges):
+    for layout, rows, info, q, tags, tab in _swept_case(n_tris, edges, "triangle"):
+        exp = sc.triangle_winners(tab, q[:, 3])
+        _check_names(exp[0]["prim"], tags, info, "the restatement")
+        blobs = set()
+        for math_mode in ((0, 1) if n_tris == 2049 else (0,)):
+            g = _tracer(math_mode)
+            _upload(g, rows, edges)
+            with np.errstate(all="ignore"):
+                for accel in (False, True):
+                    g.SetQueryAcceleration(accel)
+                    lab = "n=%d %s mm=%d edges=%d accel=%d" % (n_tris, layout, math_mode, edges, accel)
+                    got = g.TriangleDistance(q)
+                    bad = td.differing(got, exp)
+                    assert got[0].dtype == HIT_DTYPE and got[1].dtype == td.WITNESS_DTYPE and td.same(got, exp), \
+                        (lab, bad[:5], [tags[j] for j in bad[:5]], got[0][bad[:3]], exp[0][bad[:3]], got[1][bad[:3]], exp[1][bad[:3]])
+                    for n in (257, 1):
+                        assert td.same(g.TriangleDistance(q[:n]), (exp[0][:n], exp[1][:n])), (lab, n)
+                    _check_names(got[0]["prim"], tags, info, lab)
+                    blobs.add(got[0].tobytes() + got[1].tobytes())
+            g.close()
+        assert len(blobs) == 1
+
+
+def over_the_third_sphere():
+    """One query triangle whose nearest corner is 1/16 above the top of seam_cases.SPHERES[2]."""
+    x, y, z, r = sc.SPHERES[2].tolist()
+    return td.with_radius(queries_of([[[x, y, z + r + 0.0625], [x + 0.03125, y, z + r + 0.125], [x, y + 0.03125, z + r + 0.125]]]), np.inf)
+
+
 # ---- Exposure ---------------------------------------------------------------------------------------------------------------
 
 @uploads
@@ -384,6 +495,18 @@ def test_spheres_are_numbered_from_a_seam_sized_n_tris(orc, n_tris, math_mode):
                 assert ne.differing_rows(got4[0], near4[0], got4[1], near4[1]).size == 0 and (near4[0]["prim"] >= n_tris).any(), label
                 occ = expected_occluded(orc, c["expo_segs"], rows, sph, contract, (ehit, et)).reshape(4, 64)
                 assert np.array_equal(g.Exposure(c["expo"], c["dirs"]), ee.pack_masks(~occ[[0, 1, 2, 3, 0]])), label
+                # the sweeps and query triangles: the down sweep of petal 1020 meets the third sphere first, the sweep down the axis
+                # of seam 1024 the first of the coincident pair; one more triangle sits 1/16 above the third sphere
+                r = swept_refs(n_tris, False)
+                sw, q = r["sweeps"], np.concatenate([r["queries"], over_the_third_sphere()])
+                swept = sc.sweep_winners(_append_columns(r["sweep_table"], spe.table(sw, None, spheres=sph)), sw)
+                assert ce.same_hits(g.SphereCast(sw), swept) and {n_tris, n_tris + 2} <= set(swept["prim"].tolist()), label
+                assert swept["prim"][sc.find(r["stags"], "down", 1024, 1020)[0]] == n_tris + 2
+                tab = _append_columns(tuple(np.concatenate([a, b]) for a, b in zip(r["triangle_table"], sc.triangle_table(q[-1:], rows))),
+                                      sc.triangle_table(q, None, spheres=sph))
+                near = sc.triangle_winners(tab, q[:, 3])
+                assert td.same(g.TriangleDistance(q), near), label
+                assert near[0]["prim"][-1] == n_tris + 2 and near[0]["t"][-1] == np.float32(0.0625) ** 2, label
                 g.close()
 
 

@@ -2,7 +2,13 @@
 ::out[2], typed at each call: out[0] holds hits, rows of hits, bytes, masks, prims or sides in turn; all grow-only), the one event
 behind every launch and the one forward of a sharded handle -- must leave each answer as a fresh tracer that made only that
 call gives it, byte for byte: in the scan and the BVH mode, for a smaller batch after a larger one, through the torch tensor
-paths on the current stream, and on two bands.  The other suites pin the fresh answers to the oracle and the helpers."""
+paths on the current stream, and on two bands.  The other suites pin the fresh answers to the oracle and the helpers.
+
+Every query entry point takes part.  The steps are ordered so that each follows one of another output type: uint64
+masks behind hits and before bytes, int32 rows (whose tail behind `count` the kernel itself fills with -1) behind float4 hits,
+a max_hits == 0 call that passes no prims at all, TriangleDistance's two float4 outputs in out[0] and out[1] at once behind
+masks.  The first batch of the scan mode is the largest, 300: every later one runs in buffers larger than it needs, which hold
+another query's bytes."""
 import functools
 
 import numpy as np
@@ -11,11 +17,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 N, SMALL, K = 70, 5, 3                                                   # one wave and six lanes; a smaller batch behind it
+LARGE = 300                                                              # two blocks; the first batch, so the buffers never grow again
 SIZE = (96, 64)
 SPHERE = np.array([[0.1, -0.5, -1.6, 0.3]], np.float32)
-STEPS = ("Intersect", "ClosestPoint", "SignedDistance", "Occluded", "IntersectAll", "ClosestAll", "ClosestAll after", "ClosestSides",
-         "Pick", "Intersect again")
-BATCHES = [(accel, n) for accel in (False, True) for n in (N, SMALL)]    # the order one tracer runs them in
+WORLD5 = np.float32([[0, 0, 1], [0.6, 0, 0.8], [-0.6, 0, 0.8], [0, 0.6, 0.8], [0, -1, 0]])
+STEPS = ("Intersect", "Exposure", "Occluded", "Overlap 0", "ClosestPoint", "Overlap", "SignedDistance", "Overlap after", "IntersectAll",
+         "Overlap 16", "ClosestAll", "ClosestAll after", "OverlapTriangles", "ClosestSides", "OverlapTriangles after", "SphereCast",
+         "Exposure world", "TriangleDistance", "Pick", "Intersect again", "FocusAt")
+BATCHES = [(False, LARGE)] + [(accel, n) for accel in (False, True) for n in (N, SMALL)]    # the order one tracer runs them in
 
 
 def _tracer(**kw):
@@ -27,63 +36,120 @@ def _tracer(**kw):
     return g
 
 
+def _draw(n, seed, first):
+    """n items of every population around the Cornell room, drawn with a fixed generator; first: the index of the first item."""
+    rng = np.random.default_rng(seed)
+    rays = np.zeros((n, 6), np.float32)
+    rays[:, :3] = rng.uniform(-0.05, 0.05, (n, 3))
+    rays[:, 3:5], rays[:, 5] = rng.uniform(-0.6, 0.6, (n, 2)), -1.0
+    segs = np.zeros((n, 8), np.float32)
+    segs[:, :6], segs[:, 6], segs[:, 7] = rays, 1e-3, rng.uniform(0.5, 4.0, n)    # some end in front of the room
+    pts = rng.uniform((-1.2, -1.2, -3.2), (1.2, 1.2, -0.8), (n, 3)).astype(np.float32)   # three columns: the radius is filled in
+    at = first + np.arange(n)
+    pix = np.stack([(at * 37) % SIZE[0], (at * 11) % SIZE[1]], 1).astype(np.uint32)
+    # the five later queries: points with normals, boxes, query triangles, sweeps
+    nrm = rng.normal(0, 1, (n, 3))
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    expo = np.zeros((n, 8), np.float32)
+    expo[:, :3], expo[:, 3:6], expo[:, 6], expo[:, 7] = pts, nrm, 1e-3, np.where(rng.uniform(0, 1, n) < 0.5, np.inf, 1.0)
+    centre = rng.uniform((-1.2, -1.2, -3.2), (1.2, 1.2, -0.8), (n, 3))
+    half = rng.uniform(0.0, 1.0, (n, 1)) ** 2 * rng.uniform(0.2, 1.0, (n, 3))    # many small boxes (they touch nothing), some of half the room
+    boxes = np.zeros((n, 8), np.float32)
+    boxes[:, 0:3], boxes[:, 4:7] = centre - half, centre + half
+    tris = np.zeros((n, 3, 4), np.float32)                               # (n, 12) {P0 xyz, d2max, P1 xyz, -, P2 xyz, -}
+    size = rng.uniform(0.0, 1.0, (n, 1, 1)) ** 2 * 1.5                   # many small triangles, as the boxes
+    tris[:, :, :3] = rng.uniform((-1.2, -1.2, -3.2), (1.2, 1.2, -0.8), (n, 1, 3)) + size * rng.uniform(-1, 1, (n, 3, 3))
+    tris[:, 0, 3] = np.where(rng.uniform(0, 1, n) < 0.5, np.inf, 0.01)   # unbounded, or within 0.1
+    sweeps = np.zeros((n, 8), np.float32)
+    sweeps[:, :3], sweeps[:, 3:6] = pts, rng.uniform(-1, 1, (n, 3))
+    sweeps[:, 6], sweeps[:, 7] = rng.uniform(0.01, 0.2, n), rng.uniform(0.1, 1.5, n)
+    return {"rays": rays, "segs": segs, "pts": pts, "pix": pix, "expo": expo, "boxes": boxes, "tris": tris.reshape(n, 12), "sweeps": sweeps}
+
+
 @functools.lru_cache(maxsize=None)
 def _inputs():
-    rng = np.random.default_rng(70)
-    rays = np.zeros((N, 6), np.float32)
-    rays[:, :3] = rng.uniform(-0.05, 0.05, (N, 3))
-    rays[:, 3:5], rays[:, 5] = rng.uniform(-0.6, 0.6, (N, 2)), -1.0
-    segs = np.zeros((N, 8), np.float32)
-    segs[:, :6], segs[:, 6], segs[:, 7] = rays, 1e-3, rng.uniform(0.5, 4.0, N)    # some end in front of the room
-    pts = rng.uniform((-1.2, -1.2, -3.2), (1.2, 1.2, -0.8), (N, 3)).astype(np.float32)   # three columns: the radius is filled in
-    pix = np.stack([(np.arange(N) * 37) % SIZE[0], (np.arange(N) * 11) % SIZE[1]], 1).astype(np.uint32)
-    d = {"rays": rays, "segs": segs, "pts": pts, "pix": pix}
+    from raytracertest_amd import api
+    a, b = _draw(N, 70, 0), _draw(LARGE - N, 71, N)
+    d = {k: np.ascontiguousarray(np.concatenate([a[k], b[k]])) for k in a}
+    d["dirs64"] = np.zeros((64, 4), np.float32)
+    d["dirs64"][:, :3] = api.hemisphere_directions(64)
+    d["dirs5"] = np.zeros((5, 4), np.float32)
+    d["dirs5"][:, :3] = WORLD5
     for a in d.values():
         a.setflags(write=False)
     return d
 
 
-def _call(g, step, d, n, rows, dev=None):
-    """Step `step` of the sequence on the first n items -> what the method returned.  rows: ClosestAll's answer of step 5, which
-    steps 6 and 7 take their cursor and records from.  dev: the tensor paths (Pick has none)."""
-    def arg(name):
-        a = d[name][:n]
+def _hit_pixel(picked):
+    """The first pixel of a Pick answer that hit in front of the camera."""
+    hits, _ = picked
+    return int(np.nonzero((hits["prim"] >= 0) & (hits["t"] > 0))[0][0])
+
+
+def _call(g, step, d, n, prev, dev=None):
+    """Step `step` of the sequence on the first n items -> what the method returned.  prev: the earlier answers of the same
+    sequence by step name, from which the "after" steps, ClosestSides and FocusAt take their cursor, records or pixel.  dev: the tensor paths (Pick and
+    FocusAt have none: they take pixels, not arrays of a device)."""
+    def arg(name, rows=True):
+        a = d[name][:n] if rows else d[name]
         if dev is None:
             return a
         import torch
         return torch.from_numpy(np.array(a)).to(dev)
-    if step in (0, 9):
+
+    def last_column(rows):
+        last = rows[:, K - 1]
+        return np.ascontiguousarray(last) if dev is None else last.contiguous()
+
+    if step in ("Intersect", "Intersect again"):
         return g.Intersect(arg("rays"))
-    if step == 1:
-        return g.ClosestPoint(arg("pts"))
-    if step == 2:
-        return g.SignedDistance(arg("pts"))
-    if step == 3:
+    if step == "Exposure":
+        return g.Exposure(arg("expo"), arg("dirs64", False))
+    if step == "Exposure world":
+        return g.Exposure(arg("expo"), arg("dirs5", False), world=True)
+    if step == "Occluded":
         return g.Occluded(arg("segs"))
-    if step == 4:
+    if step in ("Overlap 0", "Overlap", "Overlap 16"):
+        return g.Overlap(arg("boxes"), {"Overlap 0": 0, "Overlap": K, "Overlap 16": 16}[step])
+    if step == "Overlap after":
+        return g.Overlap(arg("boxes"), K, after=last_column(prev["Overlap"][0]))
+    if step == "ClosestPoint":
+        return g.ClosestPoint(arg("pts"))
+    if step == "SignedDistance":
+        return g.SignedDistance(arg("pts"))
+    if step == "IntersectAll":
         return g.IntersectAll(arg("segs"), K)
-    if step == 5:
+    if step == "ClosestAll":
         return g.ClosestAll(arg("pts"), K)
-    if step == 6:
-        last = rows[0][:, K - 1]
-        return g.ClosestAll(arg("pts"), K, after=np.ascontiguousarray(last) if dev is None else last.contiguous())
-    if step == 7:
-        return g.ClosestSides(arg("pts"), rows[0])
-    return g.Pick(d["pix"][:n], return_rays=True)
+    if step == "ClosestAll after":
+        return g.ClosestAll(arg("pts"), K, after=last_column(prev["ClosestAll"][0]))
+    if step == "ClosestSides":
+        return g.ClosestSides(arg("pts"), prev["ClosestAll"][0])
+    if step == "OverlapTriangles":
+        return g.OverlapTriangles(arg("tris"), K)
+    if step == "OverlapTriangles after":
+        return g.OverlapTriangles(arg("tris"), K, after=last_column(prev["OverlapTriangles"][0]))
+    if step == "SphereCast":
+        return g.SphereCast(arg("sweeps"))
+    if step == "TriangleDistance":
+        return g.TriangleDistance(arg("tris"))
+    if step == "Pick":
+        return g.Pick(d["pix"][:n], return_rays=True)
+    assert step == "FocusAt"
+    x, y = d["pix"][_hit_pixel(prev["Pick"])]
+    return g.FocusAt(int(x), int(y))
 
 
 def _sequence(g, d, n, dev=None):
-    out, rows = [], None
-    for step in range(len(STEPS)):
-        out.append(_call(g, step, d, n, rows, dev))
-        if step == 5:
-            rows = out[-1]
-    return out
+    prev = {}
+    for step in STEPS:
+        prev[step] = _call(g, step, d, n, prev, dev)
+    return [prev[step] for step in STEPS]
 
 
 def _blob(answer):
     parts = answer if isinstance(answer, tuple) else (answer,)
-    return b"".join((p if isinstance(p, np.ndarray) else p.cpu().numpy()).tobytes() for p in parts)
+    return b"".join((p.cpu().numpy() if type(p).__module__.startswith("torch") else np.asarray(p)).tobytes() for p in parts)
 
 
 @functools.lru_cache(maxsize=None)
@@ -91,18 +157,33 @@ def _fresh():
     """{(accel, n): the bytes of each step on a tracer of its own that made only that call}."""
     d, out = _inputs(), {}
     for accel, n in BATCHES:
-        answers, rows = [], None
-        for step in range(len(STEPS)):
+        prev = {}
+        for step in STEPS:
             g = _tracer()
             g.SetQueryAcceleration(accel)
-            answers.append(_call(g, step, d, n, rows))
+            prev[step] = _call(g, step, d, n, prev)
             g.close()
-            if step == 5:
-                rows = answers[-1]
-        hits, (all_hits, counts), occ = answers[0], answers[5], answers[3]
+        hits, (all_hits, counts), occ = prev["Intersect"], prev["ClosestAll"], prev["Occluded"]
         assert (hits["prim"] >= 0).any() and (counts == K).all() and all_hits.shape == (n, K)
-        assert answers[6][0].tobytes() != all_hits.tobytes() and (n < N or (occ.any() and not occ.all()))
-        out[(accel, n)] = [_blob(a) for a in answers]
+        assert prev["ClosestAll after"][0].tobytes() != all_hits.tobytes() and (n < N or (occ.any() and not occ.all()))
+        # the five later queries: masks of both tables, all three list capacities, a cursor that moves, hits and misses
+        assert prev["Exposure"].dtype == np.uint64 and prev["Exposure world"].dtype == np.uint64 and (prev["Exposure world"] < 32).all()
+        assert prev["Overlap 0"][0].shape == (n, 0) and np.array_equal(prev["Overlap 0"][1], prev["Overlap"][1])
+        assert np.array_equal(prev["Overlap 16"][0][:, :K], prev["Overlap"][0]) and prev["Overlap"][0].dtype == np.int32
+        assert prev["TriangleDistance"][0].shape == prev["TriangleDistance"][1].shape == (n,) and prev["FocusAt"] > 0
+        if n >= N:
+            assert prev["Exposure"].any() and len(set(prev["Exposure"].tolist())) > 8 and prev["Exposure world"].any()
+            for key in ("Overlap", "OverlapTriangles"):                  # mixed rows: a row's tail behind its count must be -1
+                prims, c = prev[key]
+                assert (c == 0).any() and ((c > 0) & (c < K)).any() and (c > K).any(), (key, np.bincount(np.minimum(c, K + 1)))
+                assert ((prims >= 0).sum(axis=1) == np.minimum(c, K)).all() and (prims[c < K, K - 1] == -1).all()
+                more, c2 = prev[key + " after"]
+                assert np.array_equal(c2[c < K], c[c < K]) and np.array_equal(c2[c >= K], c[c >= K] - K)     # no cursor; K prims behind it
+                assert (more[c > K, 0] > prims[c > K, K - 1]).all()
+            cast, near = prev["SphereCast"], prev["TriangleDistance"][0]
+            assert (cast["prim"] >= 0).any() and (cast["prim"] < 0).any() and (cast["t"][cast["prim"] >= 0] > 0).any()
+            assert (near["prim"] >= 0).any() and (near["prim"] < 0).any() and (prev["TriangleDistance"][1]["where"][near["prim"] >= 0] >= 0).all()
+        out[(accel, n)] = [_blob(prev[step]) for step in STEPS]
     return out
 
 
@@ -115,8 +196,8 @@ def _assert_sequences(g, dev=None):
         import torch
         torch.cuda.synchronize()                                          # the only one the test makes
     for key, answers in got.items():
-        for step, (a, exp) in enumerate(zip(answers, _fresh()[key])):
-            assert _blob(a) == exp, (key, STEPS[step])
+        for step, a, exp in zip(STEPS, answers, _fresh()[key]):
+            assert _blob(a) == exp, (key, step)
 
 
 def test_one_tracer_answers_the_sequence_as_fresh_tracers_answer_each_call():
@@ -139,5 +220,5 @@ def test_two_bands_answer_the_sequence_as_one_tracer_and_report_a_bad_pick():
         m.Pick([[SIZE[0], 0]])                                           # one column to the right of the image
     assert "outside" in m.LastError()
     m.SetQueryAcceleration(False)
-    assert _blob(m.Pick(_inputs()["pix"], return_rays=True)) == _fresh()[(False, N)][8]
+    assert _blob(m.Pick(_inputs()["pix"][:N], return_rays=True)) == _fresh()[(False, N)][STEPS.index("Pick")]
     m.close()

@@ -1,7 +1,8 @@
 """seam_cases.py under the oracle and the numpy restatements, without a device: for every size and both arithmetic contracts
 each designated record -- the last of a chunk, the first of the next, the last of the scene -- is its ray's, segment's or point's
 unique answer or exact tie, so test_gpu_query_seams.py aims where it says; and a reference that loses such a record, or lets
-the later record keep a tie, answers the targeted populations differently, so a kernel that does either cannot pass there."""
+the later record keep a tie, answers the targeted populations differently, so a kernel that does either cannot pass there.
+The same for the sweeps and query triangles of SphereCast and TriangleDistance, against spherecast_expect and tridistance_expect."""
 import numpy as np
 import pytest
 
@@ -280,3 +281,134 @@ def test_the_exposure_points_see_the_last_record_and_the_sky(orc, n_tris):
         masks = ee.pack_masks(~blocked)
         less = ee.pack_masks(~in_interval(segs, (lost[0], lost[1])).any(axis=1).reshape(4, 64))
         assert masks[0] != less[0] and ee.popcount(less[:1])[0] - ee.popcount(masks[:1])[0] == only_last.sum()
+
+
+# ---- sweeps and query triangles -------------------------------------------------------------------------------------------
+
+def _same_tables(a, b):
+    return all(np.ascontiguousarray(x).tobytes() == np.ascontiguousarray(y).tobytes() for x, y in zip(a, b))
+
+
+def _seam_records(n_tris):
+    """The records whose loss the targeted rows must notice: S - 1 and S of every seam, as far as the scene has them, and the
+    scene's last."""
+    return sorted({i for S in sc.SEAMS for i in (S - 1, S) if i < n_tris} | {n_tris - 1})
+
+
+def _check_named(tags, prim, t, linfo, label):
+    """Every targeted row against its tag under one layout -> the rows aimed at a twin pair's first record.  On the tie layout
+    the twin's own place is empty (a sweep finds nothing, a query triangle its neighbour), a row aimed at S - 1 answers S - 1,
+    and a stack whose highest petal was record S has S - 1 on top."""
+    twins = {S: s["tie"] for S, s in linfo["seams"].items() if s["tie"]}
+    pair_rows = []
+    for j, (kind, S, i) in enumerate(tags):
+        if kind == "general":
+            continue
+        if S in twins and i == S:                                        # aimed at the record that moved away
+            if kind in ("down", "up", "start", "cut"):
+                assert prim[j] == -1, (label, kind, i, prim[j])
+            elif kind in ("axis_down", "beside"):
+                assert prim[j] == S - 1, (label, kind, i, prim[j])
+                pair_rows.append(j)
+            elif kind == "near":
+                assert prim[j] not in (-1, S), (label, kind, i, prim[j])
+            continue
+        assert prim[j] == i, (label, kind, S, i, prim[j])
+        if S in twins and i == S - 1:
+            pair_rows.append(j)
+    for j in pair_rows:
+        S = tags[j][1]
+        assert prim[j] == S - 1 and _bits(t[j, S - 1:S]) == _bits(t[j, S:S + 1]) and np.isfinite(t[j, S]), (label, tags[j])
+    return pair_rows
+
+
+def _check_reach(tags, prim, n_tris):
+    aimed = {int(prim[j]) for j, tg in enumerate(tags) if tg[0] != "general"}
+    assert n_tris - 1 in aimed and (n_tris < 1024 or 1023 in aimed) and (n_tris < 1025 or 1024 in aimed), (n_tris, sorted(aimed))
+
+
+@pytest.mark.parametrize("n_tris", sc.SIZES)
+def test_every_targeted_sweep_has_its_designated_contact(n_tris):
+    rows, info = sc.seam_scene(n_tris)
+    sw, tags = sc.sweep_batch(n_tris, rows)
+    assert sw.shape[0] > 256 and sw.shape[0] % 64 != 0 and len(tags) == sw.shape[0]
+    aimed = np.array([tg[0] != "general" for tg in tags])
+    kinds = {tg[0] for tg in tags}
+    assert kinds == {"down", "up", "start", "axis_down", "axis_up", "cut", "bad", "general"}
+    tab = sc.sweep_table(sw, rows)
+    exp = sc.sweep_winners(tab, sw)
+    assert ce.same_hits(exp, sc.spe.expected(sw, rows))
+    _check_named(tags, exp["prim"], tab[0], info, (n_tris, "stack"))
+    _check_reach(tags, exp["prim"], n_tris)
+    r = np.float32(sc.SWEEP_R)
+    for j, (kind, S, i) in enumerate(tags):                              # the exact t of the dyadic sweeps
+        if kind == "down":
+            assert exp["t"][j] == np.float32(sc.ABOVE - sc.petal_z(i, S)) - r and np.isinf(np.delete(tab[0][j], i)).all()
+        elif kind == "up":
+            assert exp["t"][j] == np.float32(sc.petal_z(i, S) - sc.BELOW) - r and np.isinf(np.delete(tab[0][j], i)).all()
+        elif kind == "start":
+            assert exp["t"][j] == 0 and (np.delete(tab[0][j], i) > 0).all()
+        elif kind == "cut" and i >= 0:
+            assert exp["t"][j] == sw[j, 7]
+        elif kind in ("axis_down", "axis_up"):
+            m = sc.members(n_tris, S)
+            assert np.nonzero(np.isfinite(tab[0][j]))[0].tolist() == m and np.unique(tab[0][j, m]).size == len(m)
+    # teeth: a scan that loses a record beside a seam, or the scene's last, answers targeted sweeps differently
+    for lost in _seam_records(n_tris):
+        less = sc.sweep_winners(tab, sw, drop={lost})
+        changed = set(ce.differing(less, exp).tolist())
+        mine = {j for j, tg in enumerate(tags) if tg[0] != "general" and tg[2] == lost}
+        assert mine and mine <= changed, (n_tris, lost)
+        assert all(less["prim"][j] != lost for j in mine)
+    for layout in sc.layouts(n_tris)[1:]:                                # the twins
+        lrows, linfo = sc.seam_scene(n_tris, layout)
+        tt = sc.tie_table(tab, linfo)
+        assert _same_tables([x[aimed] for x in tt], sc.sweep_table(sw[aimed], lrows))    # the restatement itself on the twins' scene
+        w = sc.sweep_winners(tt, sw)
+        pair_rows = _check_named(tags, w["prim"], tt[0], linfo, (n_tris, layout))
+        assert {tags[j][0] for j in pair_rows} >= {"down", "up", "start"}
+        high = sc.sweep_winners(tt, sw, tie_high=True)                   # teeth: the later record must not win
+        assert all(high["prim"][j] == tags[j][1] for j in pair_rows)
+        assert (high["prim"][aimed] != w["prim"][aimed]).sum() == len(pair_rows)
+
+
+@pytest.mark.parametrize("n_tris", sc.SIZES)
+def test_every_targeted_query_triangle_has_its_designated_answer(n_tris):
+    rows, info = sc.seam_scene(n_tris)
+    q, tags = sc.triangle_batch(n_tris, rows)
+    assert q.shape[0] > 256 and q.shape[0] % 64 != 0 and len(tags) == q.shape[0]
+    aimed = np.array([tg[0] != "general" for tg in tags])
+    kinds = {tg[0] for tg in tags}
+    assert kinds == {"near", "beside", "nan", "negative", "general"} | {k for k, n in (("under", 1024), ("fourth", 2048)) if n_tris >= n}
+    tab = sc.triangle_table(q, rows)
+    exp = sc.triangle_winners(tab, q[:, 3])
+    assert sc.tde.same(exp, sc.tde.expected(q, rows))
+    hits = exp[0]
+    _check_named(tags, hits["prim"], tab[0], info, (n_tris, "stack"))
+    _check_reach(tags, hits["prim"], n_tris)
+    for j, (kind, S, i) in enumerate(tags):
+        order = np.argsort(tab[0][j], kind="stable")
+        if kind in ("near", "under"):
+            assert hits["t"][j] == np.float32(0.0625) ** 2 and tab[0][j, order[0]] < tab[0][j, order[1]]     # the unique minimum
+            assert (exp[1]["x"][j], exp[1]["y"][j], exp[1]["z"][j]) == (q[j, 0], q[j, 1], q[j, 2])           # ... from the corner P0
+        elif kind == "fourth":
+            fourth = S if i > S else S - 1
+            assert q[j, 3] == tab[0][j, fourth] and (tab[0][j] <= q[j, 3]).sum() == 4                        # closed: four petals, cut on the seam
+            assert sorted(np.nonzero(tab[0][j] <= q[j, 3])[0].tolist()) == ([S, S + 1, S + 2, S + 3] if i > S else [S - 4, S - 3, S - 2, S - 1])
+    for lost in _seam_records(n_tris):                                   # teeth, as for the sweeps
+        less = sc.triangle_winners(tab, q[:, 3], drop={lost})
+        changed = set(sc.tde.differing(less, exp).tolist())
+        mine = {j for j, tg in enumerate(tags) if tg[0] != "general" and tg[2] == lost}
+        assert mine and mine <= changed, (n_tris, lost)
+        assert all(less[0]["prim"][j] != lost for j in mine)
+    for layout in sc.layouts(n_tris)[1:]:
+        lrows, linfo = sc.seam_scene(n_tris, layout)
+        tt = sc.tie_table(tab, linfo)
+        assert _same_tables([x[aimed] for x in tt], sc.triangle_table(q[aimed], lrows))
+        w = sc.triangle_winners(tt, q[:, 3])
+        pair_rows = _check_named(tags, w[0]["prim"], tt[0], linfo, (n_tris, layout))
+        assert {tags[j][0] for j in pair_rows} >= {"near", "under"}
+        high = sc.triangle_winners(tt, q[:, 3], tie_high=True)
+        assert all(high[0]["prim"][j] == tags[j][1] for j in pair_rows)
+        flipped = np.nonzero(aimed & (high[0]["prim"] != w[0]["prim"]))[0]              # (the triangle at the twin's empty place as well)
+        assert set(pair_rows) <= set(flipped.tolist()) and all(high[0]["prim"][j] == w[0]["prim"][j] + 1 == tags[j][1] for j in flipped)
