@@ -260,6 +260,30 @@ public:
     if (!TriangleDistance(tris, hits, witness)) hits.clear();
     return hits;
   }
+  // Hexahedron-shaped region query (rt_mi355x.h, rt_tracer_overlap_hexahedra): hexa holds 32 floats per region, eight rows
+  // C_k.xyz _ (the pads are never read) in box-like order: bit 0 of k is the side along the region's first direction, bit 1 the
+  // second, bit 2 the third -- an oriented or sheared box, a frustum (C0..C3 the near rectangle, C4..C7 the far one), a pyramid,
+  // a segment.  prims, counts, after and maxHits are Overlap's: row i holds the min(counts[i], maxHits) lowest primitives that
+  // touch region i, then RT_PRIM_NONE; counts[i] is their TOTAL behind the cursor.  Closed: touching counts; a region with a
+  // non-finite coordinate touches nothing.  A vector whose size is no multiple of 32, or an after of another length: false,
+  // the outputs untouched.
+  bool OverlapHexahedra(const std::vector<float>& hexa, uint32_t maxHits, std::vector<int32_t>& prims, std::vector<uint32_t>& counts,
+                        const std::vector<int32_t>& after = std::vector<int32_t>()) {
+    if (!mImpl || hexa.size() % 32 != 0 || maxHits > RT_MAX_HITS) return false;
+    const size_t n = hexa.size() / 32;
+    if (!after.empty() && after.size() != n) return false;
+    prims.resize(n * maxHits);
+    counts.resize(n);
+    return rt_tracer_overlap_hexahedra(mImpl, hexa.data(), after.empty() ? nullptr : after.data(), n, maxHits,
+                                       maxHits != 0 ? prims.data() : nullptr, counts.data()) == RT_OK;
+  }
+  // The same, returning the counts: empty when the arguments were rejected or the call failed (LastError()).
+  std::vector<uint32_t> OverlapHexahedra(const std::vector<float>& hexa, uint32_t maxHits = 0) {
+    std::vector<int32_t> prims;
+    std::vector<uint32_t> counts;
+    if (!OverlapHexahedra(hexa, maxHits, prims, counts)) counts.clear();
+    return counts;
+  }
   // Swept query (rt_mi355x.h, rt_tracer_sphere_cast): sweeps holds 8 floats per sweep -- origin, direction (used as given), the
   // sphere's radius, tmax; the centre runs along o + t*d for 0 <= t <= tmax.  hits[i].t = the time of first contact, u, v the
   // barycentrics of the contact point on triangle prim (0, 0 for a sphere), prim = RT_PRIM_NONE when nothing is touched.  A

@@ -705,6 +705,80 @@ int  rt_tracer_overlap_triangles(rt_tracer* t, const float* tris, const int32_t*
  * synchronisation.  tris must be 16-byte aligned; otherwise RT_ERR_INVALID. */
 int  rt_tracer_overlap_triangles_device(rt_tracer* t, const float* tris, const int32_t* after, size_t n, uint32_t max_hits,
                                         int32_t* prims, uint32_t* counts, void* stream);
+/* Which primitives of the tracer's scene touch a HEXAHEDRON: the convex hull of eight corners in a box-like order.  An oriented
+ * or sheared box, a frustum (a rectangle of pixels between near and far, what a camera, light or portal sees, a froxel), a
+ * pyramid (the near corners all at the apex), a wedge, an axis-aligned box and a segment (near corners equal, far corners equal)
+ * are all instances.
+ *   hexa        n x 32 floats: eight rows C_k.x C_k.y C_k.z _, k = 0 .. 7 (eight 16-byte loads).  The eight pad floats are never
+ *               read into any arithmetic: NaNs there change nothing.  The corner order is box-like: bit 0 of k is the side along
+ *               the region's first direction, bit 1 along the second, bit 2 along the third; C0 .. C3 are one cap (a frustum's
+ *               near rectangle) and C4 .. C7 the other.
+ *   max_hits, after, prims, counts
+ *               exactly as in rt_tracer_overlap: max_hits 0 .. RT_MAX_HITS (above that RT_ERR_INVALID; 0: counts only, prims
+ *               may be NULL); row i holds the min(counts[i], max_hits) LOWEST accepted prims in ascending order, then
+ *               RT_PRIM_NONE; counts[i] is the TOTAL behind the cursor, not capped; after[i] = the row's last prim continues:
+ *               nothing repeats and nothing is lost.
+ *   triangle    one arithmetic in RT_MATH_FMA and RT_MATH_STRICT: every operation is one separately rounded fp32 operation, dot
+ *               products are (x*x' + y*y') + z*z', cross products (a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x, a.x*b.y - b.x*a.y);
+ *               min and max are IEEE minNum / maxNum.  On the record the renderer intersects (v0, e1, e2; for edge-format scenes
+ *               the uploaded rows), with corners A = v0, B = fl(v0 + e1), C = fl(v0 + e2):
+ *                 1. Box step.  All 24 corner coordinates are finite: otherwise the query accepts NOTHING, spheres included.
+ *                    Neither B nor C is a NaN (a NaN A makes both one).  Per axis, with tmin = min(min(A, B), C),
+ *                    tmax = max(max(A, B), C), qmin = min_k C_k, qmax = max_k C_k: tmin <= qmax and tmax >= qmin.  Plain
+ *                    comparisons, closed: touching counts.
+ *                 2. Move by -C0.  a = A - C0, b = B - C0, c = C - C0, h_k = C_k - C0 per component; the region's own corner
+ *                    C0 is the literal 0 (h_0 = 0: h_k - h_0 below is h_k).
+ *                 3. Forty-three axes.  With f = {e1, c - b, a - c}:
+ *                      the record's normal e1 x e2;
+ *                      six face normals, each the cross product of the face's two diagonals, (h_d - h_a) x (h_c - h_b), for the
+ *                      faces (a, b, c, d) = (0,2,4,6), (1,3,5,7), (0,1,4,5), (2,3,6,7), (0,1,2,3), (4,5,6,7);
+ *                      the 36 crosses f_i x g_e, g_e = h_j - h_i for the twelve edges (i, j) = (0,1), (2,3), (4,5), (6,7),
+ *                      (0,2), (1,3), (4,6), (5,7), (0,4), (1,5), (2,6), (3,7).
+ *                 4. Projection.  On an axis x the record projects to x.a, x.b, x.c and the region to 0, x.h_1 .. x.h_7.  The
+ *                    axis separates when the record's minimum is > the region's maximum, or its maximum < the region's
+ *                    minimum, and none of the ten projections is a NaN: a NaN projection never separates.  A degenerate face
+ *                    or edge gives a zero axis, which projects everything to 0 and separates nothing.
+ *               A triangle is accepted when step 1 accepts and no axis separates.  The region's own projections on its six face
+ *               normals do not depend on the record; an implementation may compute them once per query (the same operations
+ *               on the same operands).
+ *               What this promises.  For a region with volume whose faces are planar the 43 axes are the complete set of
+ *               separating axes of two convex polyhedra (face normals of both, edge crosses): this is the exact closed touching
+ *               test, up to fp32 rounding.  For ANY eight finite corners it is a pure function of (corners, record, cursor),
+ *               identical in scan and tree.  A region WITHOUT volume (all corners in one plane, or on one line) that lies in a
+ *               record's own plane may be accepted though the two are apart: the in-plane edge normals of a flat region are
+ *               not among the axes.  A non-planar face is read as its two diagonals' cross product; the test then answers for
+ *               a region close to, not exactly, the hull.
+ *   sphere      a sphere of the scene is its surface, as in rt_tracer_overlap.  Centre S, radius r, s = S - C0:
+ *                 inside = none of the six face normals x separates s from the corners: !(x.s > max(0, x.h_k) or
+ *                          x.s < min(0, x.h_k)), the region's projections as in step 4, a NaN never separating;
+ *                 d2min  = inside ? 0 : the smallest (minNum) t of rt_tracer_closest_point's triangle rule for the point S over
+ *                          the twelve face triangles (a, b, d) and (a, d, c) of each face above, each as the record
+ *                          v0 = C_a, e1 = C_b - C_a, e2 = C_d - C_a (resp. C_d - C_a, C_c - C_a), on the corners as given;
+ *                 d2max  = max_k (C_k - S).(C_k - S).
+ *               Accepted when the query is finite and d2min <= r*r && r*r <= d2max.  A sphere wholly inside the region is
+ *               accepted (the region is a solid); a region wholly inside the ball touches nothing.  A region WITHOUT volume
+ *               (a segment, a flat quadrilateral) has face normals that are all zero or all parallel, which separate no
+ *               centre, or only along one direction: every centre counts as inside a segment, and a sphere is then accepted
+ *               whenever the region's farthest corner is outside the ball, though the two may be apart.
+ *   accuracy    as measured (tests/test_hexoverlap_expect.py): against an independently written separating-axis
+ *               test in float64 on the same fp32 corners, against a float64 clipping of the record by the six face planes, and
+ *               for segments against a float64 segment-through-triangle test.
+ * Everything else -- no scene, spheres alone, n = 0, NULL arrays (RT_ERR_INVALID, outputs untouched), scheduling, multi-device
+ * handles, RT_ACCEL_REFIT -- is rt_tracer_overlap's.
+ * RT_QUERY_BVH: a child is entered when its box and the region's BOUNDING BOX [qmin, qmax] overlap -- clo <= qmax &&
+ * chi >= qmin per axis, the same closed comparisons, NO inflation -- and the result is bit for bit the scan's rows and counts for
+ * every input whatsoever: step 1's [tmin, tmax] lies inside the record's tree box, a child the walk skips holds only triangles
+ * step 1 rejects, acceptance is a pure function of (corners, record, cursor), non-finite records go through the always-tested
+ * list, and a walk whose stack overflowed recomputes from every leaf record, restarting the list and the count.  There is
+ * no rho, no slack and no conditioning clause: rt_dbg_query_accel_slack has no effect on this query either. */
+/* Host arrays: hexa n*32, after n or NULL, prims n*max_hits (NULL allowed when max_hits = 0), counts n.  Returns with the
+ * results in host memory. */
+int  rt_tracer_overlap_hexahedra(rt_tracer* t, const float* hexa, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                                 uint32_t* counts);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  hexa must be 16-byte aligned; otherwise RT_ERR_INVALID. */
+int  rt_tracer_overlap_hexahedra_device(rt_tracer* t, const float* hexa, const int32_t* after, size_t n, uint32_t max_hits,
+                                        int32_t* prims, uint32_t* counts, void* stream);
 
 /* ---- one frame sharded over several GPUs --------------------------------------
  * The reference builds ONE rt::RayTracer pinned to device 0 (OpenGLView/MainFrame.cpp:44-45,

@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "rt_tracer_closest_sides", "rt_tracer_closest_sides_device", "rt_dbg_feature_normals",
     "rt_tracer_overlap", "rt_tracer_overlap_device",
     "rt_tracer_overlap_triangles", "rt_tracer_overlap_triangles_device",
+    "rt_tracer_overlap_hexahedra", "rt_tracer_overlap_hexahedra_device",
     "rt_tracer_sphere_cast", "rt_tracer_sphere_cast_device",
     "rt_tracer_triangle_distance", "rt_tracer_triangle_distance_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
@@ -373,6 +374,9 @@ def load_library():
         if hasattr(L, "rt_tracer_overlap_triangles"):     # (an older build selected by RT_MI355X_LIB for an A/B has no triangle regions)
             L.rt_tracer_overlap_triangles.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
             L.rt_tracer_overlap_triangles_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
+        if hasattr(L, "rt_tracer_overlap_hexahedra"):     # (an older build selected by RT_MI355X_LIB for an A/B has no hexahedron regions)
+            L.rt_tracer_overlap_hexahedra.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
+            L.rt_tracer_overlap_hexahedra_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
         if hasattr(L, "rt_tracer_sphere_cast"):           # (an older build selected by RT_MI355X_LIB for an A/B has no swept query)
             L.rt_tracer_sphere_cast.argtypes = [vp, vp, C.c_size_t, vp]
             L.rt_tracer_sphere_cast_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
@@ -1306,6 +1310,181 @@ class RayTracer:
         with np.errstate(invalid="ignore"):
             shared = (c[i][:, :, None, :] == c[j][:, None, :, :]).all(axis=3).any(axis=(1, 2))
         return np.stack([i[~shared], j[~shared]], axis=1).astype(np.int32)
+
+    # ---- hexahedron-shaped regions: frusta, oriented boxes (rt_tracer_overlap_hexahedra / _device) -------------------------
+    @staticmethod
+    def _hexahedra_array(who, corners):
+        """-> contiguous (n, 32) float32, eight rows {C_k xyz, 0}: from (n, 32) or (n, 8, 4) as it is (the pads are never read),
+        or from (n, 8, 3)."""
+        c = np.asarray(corners, np.float32)
+        if c.ndim >= 2 and c.shape[-2:] == (8, 4):
+            c = c.reshape(-1, 32)
+        elif c.ndim >= 2 and c.shape[-2:] == (8, 3):
+            q = np.zeros((c.size // 24, 8, 4), np.float32)
+            q[:, :, :3] = c.reshape(-1, 8, 3)
+            c = q.reshape(-1, 32)
+        if c.ndim == 0 or c.shape[-1] != 32:
+            raise ValueError("%s: expected (n, 8, 3), (n, 8, 4) or (n, 32) float32 corners, got shape %s" % (who, c.shape))
+        return np.ascontiguousarray(c).reshape(-1, 32)
+
+    def OverlapHexahedra(self, corners, max_hits=RT_MAX_HITS, after=None):
+        """The primitives that touch each hexahedron (rt_tracer_overlap_hexahedra): the convex hull of eight corners in box-like
+        order -- bit 0 of the corner index is the side along the region's first direction, bit 1 the second, bit 2 the third
+        (box_corners, oriented_box_corners and frustum_corners build them).  corners: (n, 8, 3), (n, 8, 4) or (n, 32) float32
+        {C_k xyz, -}; closed, touching counts; a region with a non-finite coordinate touches nothing.  max_hits, after and the
+        returned (prims (n, max_hits) int32, counts (n,) uint32) are Overlap's: the lowest touching prims in ascending order,
+        then PRIM_NONE, and the TOTAL behind the cursor (OverlapHexahedraAll chains it).  Independent of the tracer's arithmetic
+        mode and hit rule; a sphere is its surface.  numpy in, numpy out, on return.  A contiguous (n, 32) float32 torch tensor
+        on the tracer's device -> ((n, max_hits) int32, (n,) int32) tensors, enqueued on torch.cuda.current_stream() without a
+        host synchronisation; after is then a contiguous (n,) int32 tensor."""
+        if type(corners).__module__.startswith("torch"):
+            return self._overlap_hexahedra_tensor(corners, max_hits, after)
+        h = self._hexahedra_array("OverlapHexahedra", corners)
+        k = self._overlap_hits(max_hits)
+        a = None
+        if after is not None:
+            a = np.ascontiguousarray(after, np.int32).reshape(-1)
+            if a.shape[0] != h.shape[0]:
+                raise ValueError("OverlapHexahedra: after must hold one int32 cursor per region")
+        prims = np.full((h.shape[0], k), PRIM_NONE, np.int32)
+        counts = np.zeros(h.shape[0], np.uint32)
+        self._check(self._lib.rt_tracer_overlap_hexahedra(self._h, h.ctypes.data, None if a is None else a.ctypes.data, h.shape[0], k,
+                                                          prims.ctypes.data if k else None, counts.ctypes.data))
+        return prims, counts
+
+    def _overlap_hexahedra_tensor(self, corners, max_hits=RT_MAX_HITS, after=None):
+        import torch
+        if corners.dtype != torch.float32 or corners.dim() != 2 or corners.shape[1] != 32 or not corners.is_contiguous():
+            raise ValueError("OverlapHexahedra: expected a contiguous (n, 32) float32 tensor")
+        k = self._overlap_hits(max_hits)
+        stream = self._stream_of("OverlapHexahedra", "corners", corners)
+        n = corners.shape[0]
+        if after is not None:
+            if (not type(after).__module__.startswith("torch") or after.dtype != torch.int32 or tuple(after.shape) != (n,) or
+                    not after.is_contiguous() or after.device != corners.device):
+                raise ValueError("OverlapHexahedra: after must be a contiguous (n,) int32 tensor on the corners' device")
+        prims = torch.empty((n, k), dtype=torch.int32, device=corners.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=corners.device)
+        self._check(self._lib.rt_tracer_overlap_hexahedra_device(self._h, corners.data_ptr(), None if after is None else after.data_ptr(),
+                                                                 n, k, prims.data_ptr() if k else None, counts.data_ptr(), stream))
+        return prims, counts
+
+    def OverlapHexahedraAll(self, corners, max_hits=RT_MAX_HITS):
+        """Every primitive that touches each hexahedron, numpy only: OverlapHexahedra repeated with the cursor while a count
+        exceeds max_hits (1 <= max_hits <= RT_MAX_HITS is the row length of one round).  Returns (prims, offsets) as OverlapAll
+        does: region i's prims, ascending, are prims[offsets[i]:offsets[i + 1]]."""
+        h = self._hexahedra_array("OverlapHexahedraAll", corners)
+        k = self._max_hits("OverlapHexahedraAll", max_hits)
+        n = h.shape[0]
+        live = np.arange(n)                                                # the regions that have more
+        after = None
+        parts, owners = [], []
+        while live.size:
+            prims, counts = self.OverlapHexahedra(h[live], k, after=after)
+            stored = np.minimum(counts, k)
+            keep = np.arange(k)[None, :] < stored[:, None]
+            parts.append(prims[keep])
+            owners.append(np.repeat(live, stored))
+            more = counts > k
+            after = np.ascontiguousarray(prims[more, k - 1])
+            live = live[more]
+        owner = np.concatenate(owners) if owners else np.zeros(0, np.int64)
+        flat = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+        order = np.argsort(owner, kind="stable")                           # rounds are in order within a region already
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(np.bincount(owner, minlength=n), out=offsets[1:])
+        return flat[order], offsets
+
+    @staticmethod
+    def box_corners(lo, hi):
+        """(n, 8, 3) float32: the corners of axis-aligned boxes lo, hi ((3,) or (n, 3)) in OverlapHexahedra's order; no
+        arithmetic, C_k takes hi's component where bit 0 / 1 / 2 of k is set (x / y / z) and lo's elsewhere."""
+        lo, hi = np.asarray(lo, np.float32).reshape(-1, 3), np.asarray(hi, np.float32).reshape(-1, 3)
+        out = np.empty((lo.shape[0], 8, 3), np.float32)
+        for k in range(8):
+            for ax in range(3):
+                out[:, k, ax] = (hi if (k >> ax) & 1 else lo)[:, ax]
+        return out
+
+    @staticmethod
+    def oriented_box_corners(centre, axes):
+        """(n, 8, 3) float32: the corners of boxes with centre (3,) or (n, 3) and half-axis vectors axes (3, 3) or (n, 3, 3)
+        (rows; they need be neither unit nor orthogonal: a sheared box is a region too), in float32, one rounding per
+        operation: C_k = ((centre + s0*axes[0]) + s1*axes[1]) + s2*axes[2] with s_j = +1 where bit j of k is set, else -1
+        (the products are exact)."""
+        c = np.asarray(centre, np.float32).reshape(-1, 3)
+        a = np.asarray(axes, np.float32).reshape(-1, 3, 3)
+        out = np.empty((max(c.shape[0], a.shape[0]), 8, 3), np.float32)
+        for k in range(8):
+            v = c
+            for j in range(3):
+                v = (v + a[:, j] if (k >> j) & 1 else v - a[:, j]).astype(np.float32)
+            out[:, k] = v
+        return out
+
+    @staticmethod
+    def frustum_corners(rays4, near, far):
+        """(n, 8, 3) float32: the frustum between four rays, cut at the ray parameters near and far.  rays4: (4, 6) or (n, 4, 6)
+        {origin, direction} in the order (x0, y0), (x1, y0), (x0, y1), (x1, y1); near, far: scalars or (n,) -- one parameter for
+        the four rays -- or (n, 4), one per ray.  In float32, one rounding per operation: C_k = o_k + near*d_k and
+        C_{k+4} = o_k + far*d_k, k = 0 .. 3.  The caps are the flat quadrilaterals through those points: with unit directions and
+        one parameter for all four, a point at parameter t on a ray strictly between the four lies inside only for
+        near/cos(a) <= t <= far*cos(a), a the largest angle between that ray and a corner ray (cap_parameters gives per-ray
+        parameters whose caps enclose everything between near and far)."""
+        r = np.asarray(rays4, np.float32).reshape(-1, 4, 6)
+        o, d = r[:, :, :3], r[:, :, 3:]
+        n = r.shape[0]
+
+        def per_ray(v):
+            v = np.asarray(v, np.float32)
+            v = v.reshape(-1, 4) if v.ndim and v.shape[-1] == 4 and v.size == 4 * n else v.reshape(-1, 1)
+            return np.broadcast_to(v, (n, 4))[:, :, None]
+        out = np.empty((n, 8, 3), np.float32)
+        with np.errstate(all="ignore"):
+            out[:, :4] = o + (per_ray(near) * d).astype(np.float32)
+            out[:, 4:] = o + (per_ray(far) * d).astype(np.float32)
+        return out
+
+    @staticmethod
+    def cap_parameters(rays4, near, far):
+        """Per-ray parameters (near_k, far_k), each (n, 4) float32, whose flat caps ENCLOSE every point o + t*d with
+        near <= t <= far on every unit direction d between the four rays (the rays share their origin): the caps lie in planes
+        perpendicular to w = ((d0 + d1) + d2) + d3.  With c_k = d_k.w (dot products (x*x' + y*y') + z*z'), cmin = min_k c_k and
+        |w| = sqrt(w.w), in float32, one rounding per operation:  near_k = (near * cmin) / c_k  (the direction farthest from w
+        is a corner),  far_k = (far * |w|) / c_k  (the direction along w reaches farthest)."""
+        d = np.asarray(rays4, np.float32).reshape(-1, 4, 6)[:, :, 3:]
+        f32 = np.float32
+        with np.errstate(all="ignore"):
+            w = ((d[:, 0] + d[:, 1]) + d[:, 2]) + d[:, 3]
+            dot = lambda a, b: (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+            c = dot(d, w[:, None, :])
+            cmin = np.minimum(np.minimum(np.minimum(c[:, 0], c[:, 1]), c[:, 2]), c[:, 3])
+            wl = np.sqrt(dot(w, w))
+            nr = (np.asarray(near, f32).reshape(-1) * cmin)[:, None] / c
+            fr = (np.asarray(far, f32).reshape(-1) * wl)[:, None] / c
+        assert nr.dtype == f32 and fr.dtype == f32
+        return nr, fr
+
+    def PixelFrustum(self, x0, y0, x1, y1, near, far):
+        """(8, 3) float32: the frustum of the pixel rectangle [x0, x1] x [y0, y1] (full-image pixels, corners included) that
+        holds everything its pixels' pinhole rays meet at ray parameters between near and far: frustum_corners on the rays
+        through the CENTRES of the four corner pixels, exactly as Pick(..., return_rays=True) reports them for the camera the
+        tracer holds, at cap_parameters' per-ray parameters -- the pinhole directions are unit vectors, so the flat caps
+        through the points AT near and far would leave out what the middle of a wide rectangle sees just short of far.  A hit
+        that Pick reports with near <= t <= far for a pixel inside the rectangle lies inside this frustum.  The thin lens's
+        aperture does not widen it."""
+        x0, x1 = sorted((int(x0), int(x1)))
+        y0, y1 = sorted((int(y0), int(y1)))
+        _, rays = self.Pick([[x0, y0], [x1, y0], [x0, y1], [x1, y1]], return_rays=True)
+        return self.frustum_corners(rays, *self.cap_parameters(rays, near, far))[0]
+
+    def SelectRect(self, x0, y0, x1, y1, near=0.0, *, far):
+        """Marquee selection: the sorted prims (int32) that touch the frustum of the pixel rectangle between near and far
+        (PixelFrustum, OverlapHexahedraAll).  far is required and must be finite."""
+        if not (np.isfinite(far) and np.isfinite(near)):
+            raise ValueError("SelectRect: near and far must be finite")
+        prims, _ = self.OverlapHexahedraAll(self.PixelFrustum(x0, y0, x1, y1, near, far)[None])
+        return prims
 
     # ---- signed point queries (rt_tracer_signed_distance / rt_tracer_closest_sides, and their _device forms) -------------
     def SignedDistance(self, points, max_distance=np.inf):

@@ -64,6 +64,12 @@ def build_parser():
     p.add_argument("--tri-distance", type=_tri_distance, default=None, metavar="X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,R]", dest="tri_distance",
                    help="print `tri-distance prim distance where xq yq zq xs ys zs`: the nearest primitive to the triangle with those "
                         "corners (within the distance R), the candidate that found it, the nearest point on the triangle and on the scene")
+    p.add_argument("--overlap-hexa", type=_overlap_hexa, default=None, metavar="X0,Y0,Z0,...,X7,Y7,Z7[,K]", dest="overlap_hexa",
+                   help="print `overlap-hexa count`, the number of primitives that touch the hexahedron with those eight corners in "
+                        "box-like order, then one line `prim` for each of the K lowest (default 8)")
+    p.add_argument("--select", type=_select, default=None, metavar="X0,Y0,X1,Y1,FAR[,NEAR]",
+                   help="print `select count`, then one line `prim` for every primitive that touches the frustum of the pixel "
+                        "rectangle X0,Y0 .. X1,Y1 between the ray parameters NEAR (default 0) and FAR")
     p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --tri-distance / --spherecast / --focus through the scene's BVH instead of the scan")
     p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
                    help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
@@ -130,6 +136,21 @@ def _tri_distance(s):
     if len(v) not in (9, 10):
         raise ValueError(s)
     return tuple(v[:9]) + (v[9] if len(v) == 10 else math.inf,)
+
+
+def _overlap_hexa(s):
+    return _overlap(s, 24)
+
+
+def _select(s):
+    v = s.split(",")
+    if len(v) not in (5, 6):
+        raise ValueError(s)
+    px = tuple(int(x) for x in v[:4])
+    far, near = float(v[4]), float(v[5]) if len(v) == 6 else 0.0
+    if min(px) < 0 or not (math.isfinite(far) and math.isfinite(near)):
+        raise ValueError(s)
+    return px + (far, near)
 
 
 def _spherecast(s):
@@ -254,6 +275,22 @@ def main(argv=None):
             print("tri-distance -1")
         else:
             print("tri-distance %d %.9g %d %.9g %.9g %.9g %.9g %.9g %.9g" % ((h["prim"][0], np.sqrt(h["t"][0]), w["where"][0]) + tuple(on_query[0]) + tuple(on_scene[0])))
+    if a.overlap_hexa is not None:
+        try:
+            prims, counts = g.OverlapHexahedra(np.float32([a.overlap_hexa[:24]]).reshape(1, 8, 3), a.overlap_hexa[24])
+        except Exception as e:
+            sys.exit("--overlap-hexa: %s" % e)
+        print("overlap-hexa %d" % counts[0])
+        for prim in prims[0, :min(int(counts[0]), a.overlap_hexa[24])]:
+            print("%d" % prim)
+    if a.select is not None:
+        try:
+            prims = g.SelectRect(*a.select[:4], near=a.select[5], far=a.select[4])
+        except Exception as e:
+            sys.exit("--select: %s" % e)
+        print("select %d" % prims.shape[0])
+        for prim in prims:
+            print("%d" % prim)
     if a.spherecast is not None:
         sw = np.float32([a.spherecast])
         h = g.SphereCast(sw)

@@ -14,6 +14,7 @@
 //   nearest_*kernel    <- a point's k nearest primitives in order, with a continuation cursor (rt_nearest.hpp)
 //   overlap_*kernel    <- the primitives that touch a caller's box, lowest first, and how many (rt_overlap.hpp)
 //   trioverlap_*kernel <- the primitives that touch a caller's triangle, lowest first, and how many (rt_trioverlap.hpp)
+//   hexoverlap_*kernel <- the primitives that touch a caller's hexahedron (frustum, oriented box), lowest first, and how many (rt_hexoverlap.hpp)
 //   tridistance_*kernel <- the primitive nearest to a caller's triangle, and where on both (rt_tridistance.hpp)
 //   spherecast_*kernel <- a moving sphere's first contact with the scene (rt_spherecast.hpp)
 //   sides_kernel       <- the side of the surface a point query's records lie on (rt_sides.hpp)
@@ -31,6 +32,7 @@
 #include "rt_nearest.hpp"
 #include "rt_overlap.hpp"
 #include "rt_trioverlap.hpp"
+#include "rt_hexoverlap.hpp"
 #include "rt_tridistance.hpp"
 #include "rt_spherecast.hpp"
 #include "rt_sides.hpp"

@@ -219,6 +219,12 @@ hipError_t launch_overlap(const TraceParams& p, const BvhParams* b, uint32_t n, 
 hipError_t launch_overlap_triangles(const TraceParams& p, const BvhParams* b, uint32_t n, const float* tris, const int* after,
                                     uint32_t max_hits, int* prims, uint32_t* counts, hipStream_t st);
 
+// The hexahedron-shaped region query (rt_hexoverlap.hpp): n regions of eight corners {C_k xyz, -}, k = 0 .. 7 in box-like order,
+// 16-byte aligned; after, max_hits, prims and counts as launch_overlap's.  One arithmetic for both math modes; one query per
+// lane in both forms.  The tree form reads neither b->rho nor a slack: its prune is exact.
+hipError_t launch_overlap_hexahedra(const TraceParams& p, const BvhParams* b, uint32_t n, const float* hexa, const int* after,
+                                    uint32_t max_hits, int* prims, uint32_t* counts, hipStream_t st);
+
 // The triangle-shaped proximity query (rt_tridistance.hpp): n query triangles {P0 xyz, d2max, P1 xyz, -, P2 xyz, -}, 16-byte
 // aligned; hits[i] as launch_closest's for the nearest primitive of the triangle, witness[i] = {the winning point on the query
 // triangle, bits of its int32 candidate index}, or {0, 0, 0, -1} in both.  One arithmetic for both math modes; one query per lane

@@ -1,6 +1,6 @@
 // rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
 // rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_exposure*, rt_tracer_intersect_all*) and the point queries (rt_tracer_closest_point*,
-// rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*) and the region queries (rt_tracer_overlap*, rt_tracer_overlap_triangles*) and the swept query
+// rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*) and the region queries (rt_tracer_overlap*, rt_tracer_overlap_triangles*, rt_tracer_overlap_hexahedra*) and the swept query
 // (rt_tracer_sphere_cast*) and the triangle-shaped proximity query (rt_tracer_triangle_distance*).
 // Included by rt_tracer.hip.
 //
@@ -274,6 +274,15 @@ inline void enqueue_overlap_triangles(rt_tracer* t, size_t n, const float* tris,
   });
 }
 
+// regions of eight corners (and their cursors, or nullptr) -> rows of max_hits prims and one total per region (rt_hexoverlap.hpp),
+// with enqueue_overlap's tree and flags
+inline void enqueue_overlap_hexahedra(rt_tracer* t, size_t n, const float* hexa, const int32_t* after, uint32_t max_hits, int32_t* prims,
+                                      uint32_t* counts, hipStream_t st) {
+  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+    return rtk::launch_overlap_hexahedra(p, b, static_cast<uint32_t>(n), hexa, after, max_hits, prims, counts, st);
+  });
+}
+
 // sweeps -> one record per sweep (rt_spherecast.hpp).  One arithmetic for both math modes and no hit rule: the flags stay 0.  The
 // tree is the ray queries' (ensure_query_tree, so RT_ACCEL_REFIT applies); the walk's allowance beyond r takes the tracer's slack.
 static_assert(RT_SWEEP_SLACK == rtk::kSweepSlack, "include/rt_mi355x.h and rt_kernels.hpp state one slack");
@@ -290,7 +299,7 @@ inline void enqueue_triangle_distance(rt_tracer* t, size_t n, const float* tris,
   });
 }
 
-// the arguments of the overlap entry points (boxes or query triangles): max_hits checked whatever n is (0 is allowed: counts
+// the arguments of the overlap entry points (boxes, query triangles or hexahedra): max_hits checked whatever n is (0 is allowed: counts
 // only), then the arrays
 inline bool overlap_args_ok(rt_tracer* t, const char* who, size_t n, const float* boxes, uint32_t max_hits, const int32_t* prims,
                             const uint32_t* counts) {
@@ -749,6 +758,35 @@ int rt_tracer_overlap_triangles_device(rt_tracer* t, const float* tris, const in
     if (n == 0u) return;
     t->use_device();
     enqueue_overlap_triangles(t, n, tris, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_tracer_overlap_hexahedra(rt_tracer* t, const float* hexa, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                                uint32_t* counts) {
+  if (!t || !overlap_args_ok(t, "rt_tracer_overlap_hexahedra", n, hexa, max_hits, prims, counts)) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap_hexahedra(b, hexa, after, n, max_hits, prims, counts); }, [&] {
+    if (n == 0u) return;
+    const hipStream_t st = host_query_stream(t);
+    const float* d_hexa = staged_in<float>(t->queries.in[0], hexa, n * 32u, st);   // 128 bytes per query
+    const int32_t* d_after = after ? staged_in<int32_t>(t->queries.in[1], after, n, st) : nullptr;
+    int32_t* d_prims = max_hits != 0u ? room<int32_t>(t->queries.out[0], n * max_hits) : nullptr;
+    enqueue_overlap_hexahedra(t, n, d_hexa, d_after, max_hits, d_prims, room<uint32_t>(t->queries.out[1], n), st);
+    if (max_hits != 0u) staged_out<int32_t>(prims, t->queries.out[0], n * max_hits, st);
+    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int rt_tracer_overlap_hexahedra_device(rt_tracer* t, const float* hexa, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                                       uint32_t* counts, void* stream) {
+  if (!t || !overlap_args_ok(t, "rt_tracer_overlap_hexahedra_device", n, hexa, max_hits, prims, counts) ||
+      !query_aligned_ok(t, n, {{hexa, 16u}, {after, 4u}, {prims, 4u}, {counts, 4u}},
+                        "rt_tracer_overlap_hexahedra_device: hexa must be 16-byte aligned, after, prims and counts 4-byte aligned"))
+    return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap_hexahedra_device(b, hexa, after, n, max_hits, prims, counts, stream); }, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_overlap_hexahedra(t, n, hexa, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
   });
 }
 

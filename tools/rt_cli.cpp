@@ -39,6 +39,11 @@ struct Args {
   bool overlap_tri = false;
   float overlap_t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // --overlap-tri X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,K]: the three corners
   uint32_t overlap_tri_k = 8;
+  bool overlap_hexa = false;
+  float overlap_h[24] = {0};                        // --overlap-hexa 24 floats[,K]: the eight corners C0 .. C7
+  uint32_t overlap_hexa_k = 8;
+  bool select = false;
+  float select_v[6] = {0, 0, 0, 0, 0, 0};           // --select X0,Y0,X1,Y1,FAR[,NEAR]
   bool tri_distance = false;
   float tri_distance_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, INFINITY};   // --tri-distance X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,R]: the corners, search distance
   float sweep[8] = {0, 0, 0, 0, 0, 0, 0, INFINITY}; // --spherecast X,Y,Z,DX,DY,DZ,R[,TMAX]
@@ -131,7 +136,8 @@ bool parse_spherecast(const char* s, float out[8]) {
   }
 }
 
-// "X0,Y0,Z0,X1,Y1,Z1" or "...,K": the two corners of a box (m = 6) or the three of a triangle (m = 9) and an optional row
+// "X0,Y0,Z0,X1,Y1,Z1" or "...,K": the two corners of a box (m = 6), the three of a triangle (m = 9) or the eight of a
+// hexahedron (m = 24) and an optional row
 // length (0 to RT_MAX_HITS is checked by the query)
 bool parse_overlap(const char* s, float* out, uint32_t& k, int m = 6) {
   int n = 0;
@@ -192,6 +198,28 @@ std::vector<float4> load_f4(const std::string& path) {
   return v;
 }
 
+// "X0,Y0,X1,Y1,FAR" or "...,NEAR": two corner pixels (non-negative integers), a finite far and an optional finite near (default 0)
+bool parse_select(const char* s, float out[6]) {
+  out[5] = 0.0f;
+  int n = 0;
+  for (const char* q = s;; ++n) {
+    char* end = nullptr;
+    if (n >= 6) return false;
+    if (n < 4) {
+      if (*q == '-' || *q == '+') return false;
+      const unsigned long v = std::strtoul(q, &end, 10);
+      if (end == q || v > 0xFFFFFFul) return false;
+      out[n] = static_cast<float>(v);
+    } else {
+      out[n] = std::strtof(q, &end);
+      if (end == q || !std::isfinite(out[n])) return false;
+    }
+    if (*end == 0) return n >= 4;
+    if (*end != ',') return false;
+    q = end + 1;
+  }
+}
+
 void usage() {
   std::puts("rt_cli [-w W] [-h H] [-s samples] [-i iterations] [-u updateInterval] [-cx N -cy N -cz N]\n"
             "       [-cxa deg] [-cya deg] [-f fovDeg] [-l focalLength] [-a aperture]      (reference flags, integers)\n"
@@ -218,6 +246,10 @@ void usage() {
             "       [--tri-distance X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,R]] (prints `tri-distance prim distance where xq yq zq xs ys zs`: the\n"
             "                      nearest primitive to the triangle with those corners within the distance R when given, the candidate\n"
             "                      that found it, the nearest point on the triangle and on the scene; `tri-distance -1` when there is none)\n"
+            "       [--overlap-hexa X0,Y0,Z0,...,X7,Y7,Z7[,K]] (prints `overlap-hexa count`, the number of primitives that touch the hexahedron\n"
+            "                      with those eight corners in box-like order, then one line `prim` for each of the K lowest, default 8)\n"
+            "       [--select X0,Y0,X1,Y1,FAR[,NEAR]] (prints `select count`, then one line `prim` for every primitive that touches the frustum\n"
+            "                      of the pixel rectangle X0,Y0 .. X1,Y1 between the ray parameters NEAR, default 0, and FAR)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
             "       [--spherecast X,Y,Z,DX,DY,DZ,R[,TMAX]] (prints `spherecast prim t u v x y z`: the first contact of a sphere of radius\n"
             "                      R whose centre moves from X,Y,Z along DX,DY,DZ for 0 <= t <= TMAX, and the contact point;\n"
@@ -283,6 +315,14 @@ int main(int argc, char** argv) {
     else if (k == "--tri-distance") {
       if (!parse_tri_distance(next("--tri-distance"), a.tri_distance_t)) { std::fprintf(stderr, "--tri-distance wants X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,R]\n"); return 2; }
       a.tri_distance = true;
+    }
+    else if (k == "--overlap-hexa") {
+      if (!parse_overlap(next("--overlap-hexa"), a.overlap_h, a.overlap_hexa_k, 24)) { std::fprintf(stderr, "--overlap-hexa wants X0,Y0,Z0,...,X7,Y7,Z7[,K]\n"); return 2; }
+      a.overlap_hexa = true;
+    }
+    else if (k == "--select") {
+      if (!parse_select(next("--select"), a.select_v)) { std::fprintf(stderr, "--select wants X0,Y0,X1,Y1,FAR[,NEAR]\n"); return 2; }
+      a.select = true;
     }
     else if (k == "--spherecast") {
       if (!parse_spherecast(next("--spherecast"), a.sweep)) { std::fprintf(stderr, "--spherecast wants X,Y,Z,DX,DY,DZ,R[,TMAX]\n"); return 2; }
@@ -500,6 +540,78 @@ int main(int argc, char** argv) {
                   static_cast<double>(w.x), static_cast<double>(w.y), static_cast<double>(w.z), static_cast<double>(q[0]),
                   static_cast<double>(q[1]), static_cast<double>(q[2]));
     }
+  }
+  if (a.overlap_hexa) {
+    std::vector<float> hexa(32, 0.0f);
+    for (int k = 0; k < 8; ++k)
+      for (int c = 0; c < 3; ++c) hexa[4 * k + c] = a.overlap_h[3 * k + c];
+    std::vector<int32_t> prims;
+    std::vector<uint32_t> counts;
+    if (!tracer.OverlapHexahedra(hexa, a.overlap_hexa_k, prims, counts)) {
+      std::fprintf(stderr, "rt_cli: --overlap-hexa: %s\n", a.overlap_hexa_k > RT_MAX_HITS ? "K out of range" : tracer.LastError().c_str());
+      return 1;
+    }
+    std::printf("overlap-hexa %u\n", counts[0]);
+    for (uint32_t j = 0; j < a.overlap_hexa_k && j < counts[0]; ++j) std::printf("%d\n", prims[j]);
+  }
+  if (a.select) {
+    // the frustum between the pinhole rays of the four corner pixels (x0,y0), (x1,y0), (x0,y1), (x1,y1) that holds everything
+    // those pixels' rays meet between near and far: flat caps perpendicular to w = ((d0 + d1) + d2) + d3, per ray
+    // near_k = (near * min_k c_k) / c_k and far_k = (far * |w|) / c_k with c_k = d_k.w, then C_k = o + near_k*d_k,
+    // C_{k+4} = o + far_k*d_k; every operation rounded to float (RayTracer.cap_parameters of the Python class).  Then the
+    // cursor until the count is within the row.
+    const uint32_t x0 = static_cast<uint32_t>(std::min(a.select_v[0], a.select_v[2])), x1 = static_cast<uint32_t>(std::max(a.select_v[0], a.select_v[2]));
+    const uint32_t y0 = static_cast<uint32_t>(std::min(a.select_v[1], a.select_v[3])), y1 = static_cast<uint32_t>(std::max(a.select_v[1], a.select_v[3]));
+    const uint32_t px[4][2] = {{x0, y0}, {x1, y0}, {x0, y1}, {x1, y1}};
+    float o[4][3], d[4][3];
+    for (int k = 0; k < 4; ++k) {
+      rt_hit hit;
+      math::vec3 ray[2];
+      if (!tracer.Pick(math::uvec2(px[k][0], px[k][1]), hit, ray)) {
+        std::fprintf(stderr, "rt_cli: --select: %s\n", tracer.LastError().c_str());
+        return 1;
+      }
+      o[k][0] = ray[0].x; o[k][1] = ray[0].y; o[k][2] = ray[0].z;
+      d[k][0] = ray[1].x; d[k][1] = ray[1].y; d[k][2] = ray[1].z;
+    }
+    volatile float t;                                                     // (every operation rounded to float before the next)
+    const auto dot = [&t](const float* u, const float* v) { t = u[0] * v[0]; volatile float s = u[1] * v[1]; t = t + s; s = u[2] * v[2]; t = t + s; return static_cast<float>(t); };
+    float w[3], c[4];
+    for (int i = 0; i < 3; ++i) { t = d[0][i] + d[1][i]; t = t + d[2][i]; t = t + d[3][i]; w[i] = t; }
+    for (int k = 0; k < 4; ++k) c[k] = dot(d[k], w);
+    const float cmin = std::min(std::min(std::min(c[0], c[1]), c[2]), c[3]);
+    t = std::sqrt(dot(w, w));
+    const float wl = t;
+    t = a.select_v[5] * cmin;
+    const float near_c = t;
+    t = a.select_v[4] * wl;
+    const float far_c = t;
+    std::vector<float> hexa(32, 0.0f);
+    for (int k = 0; k < 4; ++k) {
+      t = near_c / c[k];
+      const float nk = t;
+      t = far_c / c[k];
+      const float fk = t;
+      for (int i = 0; i < 3; ++i) {
+        t = nk * d[k][i];
+        hexa[4 * k + i] = o[k][i] + t;
+        t = fk * d[k][i];
+        hexa[4 * (k + 4) + i] = o[k][i] + t;
+      }
+    }
+    std::vector<int32_t> all, prims, after;
+    std::vector<uint32_t> counts;
+    for (;;) {
+      if (!tracer.OverlapHexahedra(hexa, RT_MAX_HITS, prims, counts, after)) {
+        std::fprintf(stderr, "rt_cli: --select: %s\n", tracer.LastError().c_str());
+        return 1;
+      }
+      for (uint32_t j = 0; j < RT_MAX_HITS && j < counts[0]; ++j) all.push_back(prims[j]);
+      if (counts[0] <= RT_MAX_HITS) break;
+      after.assign(1, prims[RT_MAX_HITS - 1]);
+    }
+    std::printf("select %zu\n", all.size());
+    for (const int32_t prim : all) std::printf("%d\n", prim);
   }
   if (a.focus) {
     float focal = 0.0f;
