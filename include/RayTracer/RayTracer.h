@@ -203,13 +203,7 @@ public:
   // outputs untouched.
   bool Overlap(const std::vector<float>& boxes, uint32_t maxHits, std::vector<int32_t>& prims, std::vector<uint32_t>& counts,
                const std::vector<int32_t>& after = std::vector<int32_t>()) {
-    if (!mImpl || boxes.size() % 8 != 0 || maxHits > RT_MAX_HITS) return false;
-    const size_t n = boxes.size() / 8;
-    if (!after.empty() && after.size() != n) return false;
-    prims.resize(n * maxHits);
-    counts.resize(n);
-    return rt_tracer_overlap(mImpl, boxes.data(), after.empty() ? nullptr : after.data(), n, maxHits,
-                             maxHits != 0 ? prims.data() : nullptr, counts.data()) == RT_OK;
+    return Region(rt_tracer_overlap, 8, boxes, maxHits, prims, counts, after);
   }
   // The same, returning the counts: empty when the arguments were rejected or the call failed (LastError()).
   std::vector<uint32_t> Overlap(const std::vector<float>& boxes, uint32_t maxHits = 0) {
@@ -226,13 +220,7 @@ public:
   // length: false, the outputs untouched.
   bool OverlapTriangles(const std::vector<float>& tris, uint32_t maxHits, std::vector<int32_t>& prims, std::vector<uint32_t>& counts,
                         const std::vector<int32_t>& after = std::vector<int32_t>()) {
-    if (!mImpl || tris.size() % 12 != 0 || maxHits > RT_MAX_HITS) return false;
-    const size_t n = tris.size() / 12;
-    if (!after.empty() && after.size() != n) return false;
-    prims.resize(n * maxHits);
-    counts.resize(n);
-    return rt_tracer_overlap_triangles(mImpl, tris.data(), after.empty() ? nullptr : after.data(), n, maxHits,
-                                       maxHits != 0 ? prims.data() : nullptr, counts.data()) == RT_OK;
+    return Region(rt_tracer_overlap_triangles, 12, tris, maxHits, prims, counts, after);
   }
   // The same, returning the counts: empty when the arguments were rejected or the call failed (LastError()).
   std::vector<uint32_t> OverlapTriangles(const std::vector<float>& tris, uint32_t maxHits = 0) {
@@ -269,13 +257,7 @@ public:
   // the outputs untouched.
   bool OverlapHexahedra(const std::vector<float>& hexa, uint32_t maxHits, std::vector<int32_t>& prims, std::vector<uint32_t>& counts,
                         const std::vector<int32_t>& after = std::vector<int32_t>()) {
-    if (!mImpl || hexa.size() % 32 != 0 || maxHits > RT_MAX_HITS) return false;
-    const size_t n = hexa.size() / 32;
-    if (!after.empty() && after.size() != n) return false;
-    prims.resize(n * maxHits);
-    counts.resize(n);
-    return rt_tracer_overlap_hexahedra(mImpl, hexa.data(), after.empty() ? nullptr : after.data(), n, maxHits,
-                                       maxHits != 0 ? prims.data() : nullptr, counts.data()) == RT_OK;
+    return Region(rt_tracer_overlap_hexahedra, 32, hexa, maxHits, prims, counts, after);
   }
   // The same, returning the counts: empty when the arguments were rejected or the call failed (LastError()).
   std::vector<uint32_t> OverlapHexahedra(const std::vector<float>& hexa, uint32_t maxHits = 0) {
@@ -379,6 +361,18 @@ private:
     rt::CallBackFunction f;
     { std::lock_guard<std::mutex> lk(me->mCallbackMutex); f = me->mFinished; }
     if (f) f(image, size);
+  }
+  // the three region queries: `floats` per query, one C entry point each
+  bool Region(int (*query)(rt_tracer*, const float*, const int32_t*, size_t, uint32_t, int32_t*, uint32_t*), size_t floats,
+              const std::vector<float>& queries, uint32_t maxHits, std::vector<int32_t>& prims, std::vector<uint32_t>& counts,
+              const std::vector<int32_t>& after) {
+    if (!mImpl || queries.size() % floats != 0 || maxHits > RT_MAX_HITS) return false;
+    const size_t n = queries.size() / floats;
+    if (!after.empty() && after.size() != n) return false;
+    prims.resize(n * maxHits);
+    counts.resize(n);
+    return query(mImpl, queries.data(), after.empty() ? nullptr : after.data(), n, maxHits, maxHits != 0 ? prims.data() : nullptr,
+                 counts.data()) == RT_OK;
   }
 
   rt_tracer* mImpl;

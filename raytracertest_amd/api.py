@@ -1096,6 +1096,63 @@ class RayTracer:
             raise ValueError("Overlap: max_hits = %r (0 to %d)" % (max_hits, RT_MAX_HITS))
         return k
 
+    def _region_query(self, name, noun, array, fn, queries, max_hits, after):
+        """The numpy form of the three region queries: `array` lays the queries out, `fn` is the C entry point."""
+        q = array(name, queries)
+        k = self._overlap_hits(max_hits)
+        a = None
+        if after is not None:
+            a = np.ascontiguousarray(after, np.int32).reshape(-1)
+            if a.shape[0] != q.shape[0]:
+                raise ValueError("%s: after must hold one int32 cursor per %s" % (name, noun))
+        prims = np.full((q.shape[0], k), PRIM_NONE, np.int32)
+        counts = np.zeros(q.shape[0], np.uint32)
+        self._check(fn(self._h, q.ctypes.data, None if a is None else a.ctypes.data, q.shape[0], k,
+                       prims.ctypes.data if k else None, counts.ctypes.data))
+        return prims, counts
+
+    def _region_tensor(self, name, arg, floats, fn, queries, max_hits, after):
+        """Their torch form: a contiguous (n, floats) tensor called `arg`, `fn` the _device entry point."""
+        import torch
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != floats or not queries.is_contiguous():
+            raise ValueError("%s: expected a contiguous (n, %d) float32 tensor" % (name, floats))
+        k = self._overlap_hits(max_hits)
+        stream = self._stream_of(name, arg, queries)
+        n = queries.shape[0]
+        if after is not None:
+            if (not type(after).__module__.startswith("torch") or after.dtype != torch.int32 or tuple(after.shape) != (n,) or
+                    not after.is_contiguous() or after.device != queries.device):
+                raise ValueError("%s: after must be a contiguous (n,) int32 tensor on the %s' device" % (name, arg))
+        prims = torch.empty((n, k), dtype=torch.int32, device=queries.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=queries.device)
+        self._check(fn(self._h, queries.data_ptr(), None if after is None else after.data_ptr(), n, k,
+                       prims.data_ptr() if k else None, counts.data_ptr(), stream))
+        return prims, counts
+
+    def _region_all(self, query, array, name, queries, max_hits):
+        """Their cursor chain: `query` repeated with the cursor while a count exceeds the row length."""
+        q = array(name, queries)
+        k = self._max_hits(name, max_hits)
+        n = q.shape[0]
+        live = np.arange(n)                                                # the queries that have more
+        after = None
+        parts, owners = [], []
+        while live.size:
+            prims, counts = query(q[live], k, after=after)
+            stored = np.minimum(counts, k)
+            keep = np.arange(k)[None, :] < stored[:, None]
+            parts.append(prims[keep])
+            owners.append(np.repeat(live, stored))
+            more = counts > k
+            after = np.ascontiguousarray(prims[more, k - 1])
+            live = live[more]
+        owner = np.concatenate(owners) if owners else np.zeros(0, np.int64)
+        flat = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+        order = np.argsort(owner, kind="stable")                           # rounds are in order within a query already
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(np.bincount(owner, minlength=n), out=offsets[1:])
+        return flat[order], offsets
+
     def Overlap(self, boxes, max_hits=RT_MAX_HITS, after=None):
         """The primitives that touch each axis-aligned box (rt_tracer_overlap).  boxes: (n, 8) float32 {lo xyz, -, hi xyz, -},
         (n, 6) {lo xyz, hi xyz}, or a (lo, hi) pair of (n, 3) arrays; closed boxes, touching counts; a NaN bound or lo > hi on
@@ -1108,62 +1165,17 @@ class RayTracer:
         after is then a contiguous (n,) int32 tensor."""
         if type(boxes).__module__.startswith("torch"):
             return self._overlap_tensor(boxes, max_hits, after)
-        b = self._boxes_array("Overlap", boxes)
-        k = self._overlap_hits(max_hits)
-        a = None
-        if after is not None:
-            a = np.ascontiguousarray(after, np.int32).reshape(-1)
-            if a.shape[0] != b.shape[0]:
-                raise ValueError("Overlap: after must hold one int32 cursor per box")
-        prims = np.full((b.shape[0], k), PRIM_NONE, np.int32)
-        counts = np.zeros(b.shape[0], np.uint32)
-        self._check(self._lib.rt_tracer_overlap(self._h, b.ctypes.data, None if a is None else a.ctypes.data, b.shape[0], k,
-                                                prims.ctypes.data if k else None, counts.ctypes.data))
-        return prims, counts
+        return self._region_query("Overlap", "box", self._boxes_array, self._lib.rt_tracer_overlap, boxes, max_hits, after)
 
     def _overlap_tensor(self, boxes, max_hits=RT_MAX_HITS, after=None):
-        import torch
-        if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 8 or not boxes.is_contiguous():
-            raise ValueError("Overlap: expected a contiguous (n, 8) float32 tensor")
-        k = self._overlap_hits(max_hits)
-        stream = self._stream_of("Overlap", "boxes", boxes)
-        n = boxes.shape[0]
-        if after is not None:
-            if (not type(after).__module__.startswith("torch") or after.dtype != torch.int32 or tuple(after.shape) != (n,) or
-                    not after.is_contiguous() or after.device != boxes.device):
-                raise ValueError("Overlap: after must be a contiguous (n,) int32 tensor on the boxes' device")
-        prims = torch.empty((n, k), dtype=torch.int32, device=boxes.device)
-        counts = torch.empty((n,), dtype=torch.int32, device=boxes.device)
-        self._check(self._lib.rt_tracer_overlap_device(self._h, boxes.data_ptr(), None if after is None else after.data_ptr(), n, k,
-                                                       prims.data_ptr() if k else None, counts.data_ptr(), stream))
-        return prims, counts
+        return self._region_tensor("Overlap", "boxes", 8, self._lib.rt_tracer_overlap_device, boxes, max_hits, after)
 
     def OverlapAll(self, boxes, max_hits=RT_MAX_HITS):
         """Every primitive that touches each box, numpy only: Overlap repeated with the cursor while a count exceeds max_hits
         (1 <= max_hits <= RT_MAX_HITS is the row length of one round).  Returns (prims, offsets): the touching prims of all
         boxes, flat, int32, each box's in ascending order; box i's are prims[offsets[i]:offsets[i + 1]], offsets (n + 1,)
         int64."""
-        b = self._boxes_array("OverlapAll", boxes)
-        k = self._max_hits("OverlapAll", max_hits)
-        n = b.shape[0]
-        live = np.arange(n)                                                # the boxes that have more
-        after = None
-        parts, owners = [], []
-        while live.size:
-            prims, counts = self.Overlap(b[live], k, after=after)
-            stored = np.minimum(counts, k)
-            keep = np.arange(k)[None, :] < stored[:, None]
-            parts.append(prims[keep])
-            owners.append(np.repeat(live, stored))
-            more = counts > k
-            after = np.ascontiguousarray(prims[more, k - 1])
-            live = live[more]
-        owner = np.concatenate(owners) if owners else np.zeros(0, np.int64)
-        flat = np.concatenate(parts) if parts else np.zeros(0, np.int32)
-        order = np.argsort(owner, kind="stable")                           # rounds are in order within a box already
-        offsets = np.zeros(n + 1, np.int64)
-        np.cumsum(np.bincount(owner, minlength=n), out=offsets[1:])
-        return flat[order], offsets
+        return self._region_all(self.Overlap, self._boxes_array, "OverlapAll", boxes, max_hits)
 
     @staticmethod
     def voxel_boxes(origin, spacing, shape):
@@ -1221,61 +1233,18 @@ class RayTracer:
         torch.cuda.current_stream() without a host synchronisation; after is then a contiguous (n,) int32 tensor."""
         if type(triangles).__module__.startswith("torch"):
             return self._overlap_triangles_tensor(triangles, max_hits, after)
-        t = self._triangles_array("OverlapTriangles", triangles)
-        k = self._overlap_hits(max_hits)
-        a = None
-        if after is not None:
-            a = np.ascontiguousarray(after, np.int32).reshape(-1)
-            if a.shape[0] != t.shape[0]:
-                raise ValueError("OverlapTriangles: after must hold one int32 cursor per triangle")
-        prims = np.full((t.shape[0], k), PRIM_NONE, np.int32)
-        counts = np.zeros(t.shape[0], np.uint32)
-        self._check(self._lib.rt_tracer_overlap_triangles(self._h, t.ctypes.data, None if a is None else a.ctypes.data, t.shape[0], k,
-                                                          prims.ctypes.data if k else None, counts.ctypes.data))
-        return prims, counts
+        return self._region_query("OverlapTriangles", "triangle", self._triangles_array, self._lib.rt_tracer_overlap_triangles, triangles,
+                                  max_hits, after)
 
     def _overlap_triangles_tensor(self, triangles, max_hits=RT_MAX_HITS, after=None):
-        import torch
-        if triangles.dtype != torch.float32 or triangles.dim() != 2 or triangles.shape[1] != 12 or not triangles.is_contiguous():
-            raise ValueError("OverlapTriangles: expected a contiguous (n, 12) float32 tensor")
-        k = self._overlap_hits(max_hits)
-        stream = self._stream_of("OverlapTriangles", "triangles", triangles)
-        n = triangles.shape[0]
-        if after is not None:
-            if (not type(after).__module__.startswith("torch") or after.dtype != torch.int32 or tuple(after.shape) != (n,) or
-                    not after.is_contiguous() or after.device != triangles.device):
-                raise ValueError("OverlapTriangles: after must be a contiguous (n,) int32 tensor on the triangles' device")
-        prims = torch.empty((n, k), dtype=torch.int32, device=triangles.device)
-        counts = torch.empty((n,), dtype=torch.int32, device=triangles.device)
-        self._check(self._lib.rt_tracer_overlap_triangles_device(self._h, triangles.data_ptr(), None if after is None else after.data_ptr(),
-                                                                 n, k, prims.data_ptr() if k else None, counts.data_ptr(), stream))
-        return prims, counts
+        return self._region_tensor("OverlapTriangles", "triangles", 12, self._lib.rt_tracer_overlap_triangles_device, triangles, max_hits,
+                                   after)
 
     def OverlapTrianglesAll(self, triangles, max_hits=RT_MAX_HITS):
         """Every primitive that touches each query triangle, numpy only: OverlapTriangles repeated with the cursor while a count
         exceeds max_hits (1 <= max_hits <= RT_MAX_HITS is the row length of one round).  Returns (prims, offsets) as OverlapAll
         does: triangle i's prims, ascending, are prims[offsets[i]:offsets[i + 1]]."""
-        t = self._triangles_array("OverlapTrianglesAll", triangles)
-        k = self._max_hits("OverlapTrianglesAll", max_hits)
-        n = t.shape[0]
-        live = np.arange(n)                                                # the triangles that have more
-        after = None
-        parts, owners = [], []
-        while live.size:
-            prims, counts = self.OverlapTriangles(t[live], k, after=after)
-            stored = np.minimum(counts, k)
-            keep = np.arange(k)[None, :] < stored[:, None]
-            parts.append(prims[keep])
-            owners.append(np.repeat(live, stored))
-            more = counts > k
-            after = np.ascontiguousarray(prims[more, k - 1])
-            live = live[more]
-        owner = np.concatenate(owners) if owners else np.zeros(0, np.int64)
-        flat = np.concatenate(parts) if parts else np.zeros(0, np.int32)
-        order = np.argsort(owner, kind="stable")                           # rounds are in order within a triangle already
-        offsets = np.zeros(n + 1, np.int64)
-        np.cumsum(np.bincount(owner, minlength=n), out=offsets[1:])
-        return flat[order], offsets
+        return self._region_all(self.OverlapTriangles, self._triangles_array, "OverlapTrianglesAll", triangles, max_hits)
 
     @staticmethod
     def scene_corners(rows, edges=False):
@@ -1339,61 +1308,18 @@ class RayTracer:
         host synchronisation; after is then a contiguous (n,) int32 tensor."""
         if type(corners).__module__.startswith("torch"):
             return self._overlap_hexahedra_tensor(corners, max_hits, after)
-        h = self._hexahedra_array("OverlapHexahedra", corners)
-        k = self._overlap_hits(max_hits)
-        a = None
-        if after is not None:
-            a = np.ascontiguousarray(after, np.int32).reshape(-1)
-            if a.shape[0] != h.shape[0]:
-                raise ValueError("OverlapHexahedra: after must hold one int32 cursor per region")
-        prims = np.full((h.shape[0], k), PRIM_NONE, np.int32)
-        counts = np.zeros(h.shape[0], np.uint32)
-        self._check(self._lib.rt_tracer_overlap_hexahedra(self._h, h.ctypes.data, None if a is None else a.ctypes.data, h.shape[0], k,
-                                                          prims.ctypes.data if k else None, counts.ctypes.data))
-        return prims, counts
+        return self._region_query("OverlapHexahedra", "region", self._hexahedra_array, self._lib.rt_tracer_overlap_hexahedra, corners,
+                                  max_hits, after)
 
     def _overlap_hexahedra_tensor(self, corners, max_hits=RT_MAX_HITS, after=None):
-        import torch
-        if corners.dtype != torch.float32 or corners.dim() != 2 or corners.shape[1] != 32 or not corners.is_contiguous():
-            raise ValueError("OverlapHexahedra: expected a contiguous (n, 32) float32 tensor")
-        k = self._overlap_hits(max_hits)
-        stream = self._stream_of("OverlapHexahedra", "corners", corners)
-        n = corners.shape[0]
-        if after is not None:
-            if (not type(after).__module__.startswith("torch") or after.dtype != torch.int32 or tuple(after.shape) != (n,) or
-                    not after.is_contiguous() or after.device != corners.device):
-                raise ValueError("OverlapHexahedra: after must be a contiguous (n,) int32 tensor on the corners' device")
-        prims = torch.empty((n, k), dtype=torch.int32, device=corners.device)
-        counts = torch.empty((n,), dtype=torch.int32, device=corners.device)
-        self._check(self._lib.rt_tracer_overlap_hexahedra_device(self._h, corners.data_ptr(), None if after is None else after.data_ptr(),
-                                                                 n, k, prims.data_ptr() if k else None, counts.data_ptr(), stream))
-        return prims, counts
+        return self._region_tensor("OverlapHexahedra", "corners", 32, self._lib.rt_tracer_overlap_hexahedra_device, corners, max_hits,
+                                   after)
 
     def OverlapHexahedraAll(self, corners, max_hits=RT_MAX_HITS):
         """Every primitive that touches each hexahedron, numpy only: OverlapHexahedra repeated with the cursor while a count
         exceeds max_hits (1 <= max_hits <= RT_MAX_HITS is the row length of one round).  Returns (prims, offsets) as OverlapAll
         does: region i's prims, ascending, are prims[offsets[i]:offsets[i + 1]]."""
-        h = self._hexahedra_array("OverlapHexahedraAll", corners)
-        k = self._max_hits("OverlapHexahedraAll", max_hits)
-        n = h.shape[0]
-        live = np.arange(n)                                                # the regions that have more
-        after = None
-        parts, owners = [], []
-        while live.size:
-            prims, counts = self.OverlapHexahedra(h[live], k, after=after)
-            stored = np.minimum(counts, k)
-            keep = np.arange(k)[None, :] < stored[:, None]
-            parts.append(prims[keep])
-            owners.append(np.repeat(live, stored))
-            more = counts > k
-            after = np.ascontiguousarray(prims[more, k - 1])
-            live = live[more]
-        owner = np.concatenate(owners) if owners else np.zeros(0, np.int64)
-        flat = np.concatenate(parts) if parts else np.zeros(0, np.int32)
-        order = np.argsort(owner, kind="stable")                           # rounds are in order within a region already
-        offsets = np.zeros(n + 1, np.int64)
-        np.cumsum(np.bincount(owner, minlength=n), out=offsets[1:])
-        return flat[order], offsets
+        return self._region_all(self.OverlapHexahedra, self._hexahedra_array, "OverlapHexahedraAll", corners, max_hits)
 
     @staticmethod
     def box_corners(lo, hi):

@@ -2,32 +2,30 @@
 // tracer's scene that touch the convex hull of eight corners in a box-like order (an oriented or sheared box, a frustum, a
 // pyramid, a wedge, a segment), the max_hits lowest of them in ascending prim order behind an optional cursor, and the total
 // number of them.  Included by rt_kernels.hip only, behind rt_trioverlap.hpp, whose query check (tri_finite) is used as it is, as
-// are rt_overlap.hpp's list (OverlapList<CAP>), cursor (overlap_cursor, overlap_behind) and box-axis comparison (overlap_axis1).
+// are rt_overlap.hpp's list (OverlapList<CAP>), cursor (overlap_cursor, overlap_behind), box-axis comparison (overlap_axis1) and
+// kernels (region_kernel, region_bvh_kernel): this file states the rule, as the shape HexRegion.
 //
 // Acceptance is a pure function of (corners, record, cursor), the text of include/rt_mi355x.h operation by operation: ONE
 // arithmetic, every operation rounded separately (the library is compiled with -ffp-contract=off).  On the record the renderer
 // intersects, A = v0, B = fl(v0 + e1), C = fl(v0 + e2), against the corners C0 .. C7 (bit 0 of k = the side along the region's
 // first direction, bit 1 the second, bit 2 the third):
-//   step 1 (hex_step1)       all 24 coordinates finite, neither B nor C a NaN, per axis min(A, B, C) <= max_k C_k and
+//   step 1 (HexRegion::step1) all 24 coordinates finite, neither B nor C a NaN, per axis min(A, B, C) <= max_k C_k and
 //                            max(A, B, C) >= min_k C_k
 //   step 2                   a = A - C0, b = B - C0, c = C - C0, h_k = C_k - C0; the region's own corner 0 is the literal 0
-//   step 3 (hex_separated)   43 axes: n = e1 x e2; the six face normals (h_d - h_a) x (h_c - h_b), the cross product of a face's
+//   step 3 (separated)       43 axes: n = e1 x e2; the six face normals (h_d - h_a) x (h_c - h_b), the cross product of a face's
 //                            two diagonals; the 36 crosses f_i x g_e of f = e1, c - b, a - c and the twelve edges g_e = h_j - h_i
 // On an axis x the record projects to x.a, x.b, x.c and the region to 0, x.h_1 .. x.h_7; it separates when the record's minimum
 // is > the region's maximum or its maximum < the region's minimum, and no projection is a NaN (hex_axis masks the verdict as
 // tri_axis does).  The region's own projections on its six face normals do not depend on the record: hex_query computes them
 // once (HexQuery::fmn, fmx; a NaN among them is kept as the interval [-inf, +inf], which separates nothing: the same verdicts).
-// A sphere is its surface (hex_sphere): inside the six face slabs or closest_triangle's t to the twelve face triangles against
+// A sphere is its surface (HexRegion::sphere): inside the six face slabs or closest_triangle's t to the twelve face triangles against
 // r*r, and the farthest corner.
 //
 // Why the tree prunes exactly, with no slack: the argument of rt_overlap.hpp with the region's bounding box in the place of the
 // caller's box.  Step 1's record interval lies inside rtb::detail::tri_box; a child is entered when its box and the region's
 // bounding box overlap under the same closed comparisons.  b.rho is not read.
 //
-// hexoverlap_kernel<CAP> (RT_QUERY_SCAN) and hexoverlap_bvh_kernel<CAP> (RT_QUERY_BVH) have the shapes of trioverlap_kernel and
-// trioverlap_bvh_kernel: 256-thread blocks over LDS chunks of kQueryChunk records with a per-record ballot exit after step 1; one
-// wave per block over bvh_walk<64, false>, then the overflow redo, the always-tested list and the spheres.  The query is eight
-// 16-byte loads.  Corners and list slots sit behind compile-time indices only; the edge axes are evaluated in groups of three
+// The query is eight 16-byte loads.  Corners and list slots sit behind compile-time indices only; the edge axes are evaluated in groups of three
 // (one g_e against the three f), every axis a block of its own.  The corners as given are needed by the sphere rule alone and
 // are loaded again for it, so the triangle loop does not carry them.  All six kernels are bounded to RT_HEX_WAVES = 4 waves per
 // SIMD: 128 VGPRs and 52 - 152 B of scratch (12 - 139 registers spilled), which measured 1.2 - 1.6 times faster than the 196 -
@@ -107,13 +105,6 @@ __device__ __forceinline__ HexQuery hex_query(float4 c0, float4 c1, float4 c2, f
   return q;
 }
 
-// step 1: overlap_step1's comparisons against the region's bounding box
-__device__ __forceinline__ bool hex_step1(const HexQuery& q, V3 A, V3 B, V3 C) {
-  const bool x = overlap_axis1(A.x, B.x, C.x, q.lo.x, q.hi.x), y = overlap_axis1(A.y, B.y, C.y, q.lo.y, q.hi.y);
-  const bool z = overlap_axis1(A.z, B.z, C.z, q.lo.z, q.hi.z);
-  return q.valid & x & y & z;
-}
-
 // the record's side of one axis against a region interval [qmin, qmax] that holds no NaN
 __device__ __forceinline__ bool hex_record_axis(V3 x, V3 a, V3 b, V3 c, float qmin, float qmax) {
   using M = Math<false>;
@@ -137,33 +128,6 @@ __device__ __forceinline__ bool hex_axes3(const HexQuery& q, V3 g, V3 f0, V3 f1,
   if (hex_axis(q, M::cross(f0, g), a, b, c)) return true;
   if (hex_axis(q, M::cross(f1, g), a, b, c)) return true;
   return hex_axis(q, M::cross(f2, g), a, b, c);
-}
-
-// steps 2 and 3: true when one of the forty-three axes separates the record from the region
-__device__ __forceinline__ bool hex_separated(const HexQuery& q, V3 A, V3 B, V3 C, V3 e1, V3 e2) {
-  using M = Math<false>;
-  const V3 a = rtd::sub(A, q.C0), b = rtd::sub(B, q.C0), c = rtd::sub(C, q.C0);
-  const V3 f0 = e1, f1 = rtd::sub(c, b), f2 = rtd::sub(a, c);
-  // An axis that separates ends the test for its lane: the verdict is the OR of the same forty-three verdicts, and a wave whose
-  // live lanes are all separated skips the rest.  The face normals, whose region side hex_query has ready, go first.
-  bool s = false;
-#pragma unroll
-  for (int f = 0; f < 6; ++f) s |= hex_record_axis(q.fn[f], a, b, c, q.fmn[f], q.fmx[f]);
-  if (s) return true;
-  if (hex_axis(q, M::cross(e1, e2), a, b, c)) return true;
-  // the twelve edges (0,1), (2,3), (4,5), (6,7), (0,2), (1,3), (4,6), (5,7), (0,4), (1,5), (2,6), (3,7)
-  if (hex_axes3(q, q.h[1], f0, f1, f2, a, b, c)) return true;
-  if (hex_axes3(q, rtd::sub(q.h[3], q.h[2]), f0, f1, f2, a, b, c)) return true;
-  if (hex_axes3(q, rtd::sub(q.h[5], q.h[4]), f0, f1, f2, a, b, c)) return true;
-  if (hex_axes3(q, rtd::sub(q.h[7], q.h[6]), f0, f1, f2, a, b, c)) return true;
-  if (hex_axes3(q, q.h[2], f0, f1, f2, a, b, c)) return true;
-  if (hex_axes3(q, rtd::sub(q.h[3], q.h[1]), f0, f1, f2, a, b, c)) return true;
-  if (hex_axes3(q, rtd::sub(q.h[6], q.h[4]), f0, f1, f2, a, b, c)) return true;
-  if (hex_axes3(q, rtd::sub(q.h[7], q.h[5]), f0, f1, f2, a, b, c)) return true;
-  if (hex_axes3(q, q.h[4], f0, f1, f2, a, b, c)) return true;
-  if (hex_axes3(q, rtd::sub(q.h[5], q.h[1]), f0, f1, f2, a, b, c)) return true;
-  if (hex_axes3(q, rtd::sub(q.h[6], q.h[2]), f0, f1, f2, a, b, c)) return true;
-  return hex_axes3(q, rtd::sub(q.h[7], q.h[3]), f0, f1, f2, a, b, c);
 }
 
 // the corners as given, for the sphere rule
@@ -190,161 +154,100 @@ __device__ __forceinline__ float hex_face_t(V3 S, V3 P, V3 Q, V3 R) {
 
 // the two triangles (a, b, d) and (a, d, c) of the face (a, b, c, d): true when one of them comes within rr of S
 __device__ __forceinline__ bool hex_face_near(V3 S, float rr, V3 Ca, V3 Cb, V3 Cc, V3 Cd) {
-  __builtin_amdgcn_sched_barrier(0);                               // (keeps this face a block of its own: see hex_sphere)
+  __builtin_amdgcn_sched_barrier(0);                               // (keeps this face a block of its own: see HexRegion::sphere)
   return fminf(hex_face_t(S, Ca, Cb, Cd), hex_face_t(S, Ca, Cd, Cc)) <= rr;
 }
 
-// the sphere rule: the surface touches the region when the region's nearest point is inside the ball and its farthest corner
-// is not.  d2min <= r*r is decided face by face -- the smallest t is within r*r exactly when one of the twelve is (minNum drops a
-// NaN, and a NaN compares false) -- and a face that decides ends it.  Left to itself the compiler flattens the six faces into
-// one block (the point query is branchless) and the scheduler interleaves the twelve of them past the register file; the
-// scheduling barrier in hex_face_near cannot be speculated, so every face stays a block of its own.
-__device__ __forceinline__ bool hex_sphere(const HexQuery& q, const HexCorners& K, float4 sph) {
-  using M = Math<false>;
-  const V3 S = {sph.x, sph.y, sph.z};
-  const V3 s = rtd::sub(S, q.C0);
-  const float rr = sph.w * sph.w;
-  float d2max = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const V3 w = rtd::sub(K.C[k], S);
-    const float d2 = M::dot(w, w);
-    d2max = k == 0 ? d2 : fmaxf(d2max, d2);
-  }
-  if (!(q.valid & (rr <= d2max))) return false;
-  bool out = false;                                                // a face normal separates the centre from the corners
-#pragma unroll
-  for (int f = 0; f < 6; ++f) {
-    const float ps = M::dot(q.fn[f], s);
-    out |= !__builtin_isunordered(ps, ps) & ((ps > q.fmx[f]) | (ps < q.fmn[f]));
-  }
-  if (!out) return 0.0f <= rr;                                     // inside: d2min = 0 (a NaN radius touches nothing)
-  if (hex_face_near(S, rr, K.C[0], K.C[2], K.C[4], K.C[6])) return true;
-  if (hex_face_near(S, rr, K.C[1], K.C[3], K.C[5], K.C[7])) return true;
-  if (hex_face_near(S, rr, K.C[0], K.C[1], K.C[4], K.C[5])) return true;
-  if (hex_face_near(S, rr, K.C[2], K.C[3], K.C[6], K.C[7])) return true;
-  if (hex_face_near(S, rr, K.C[0], K.C[1], K.C[2], K.C[3])) return true;
-  return hex_face_near(S, rr, K.C[4], K.C[5], K.C[6], K.C[7]);
-}
+// The hexahedron as a region shape (rt_overlap.hpp's skeleton).
+struct HexRegion {
+  static constexpr int kFloat4s = 8;
+  static constexpr int kScanWaves = RT_HEX_WAVES, kTreeWaves = RT_HEX_WAVES;
+  using Query = HexQuery;
+  using SphereCtx = HexCorners;                                    // loaded once there are spheres and the query is valid
+  static constexpr bool kSphereCtx = true;
 
-template <int CAP>
-__global__ __launch_bounds__(256, RT_HEX_WAVES) void hexoverlap_kernel(const TraceParams p, uint32_t n, const float4* __restrict__ hexa,
-                                                             const int* __restrict__ after, uint32_t max_hits,
-                                                             int* __restrict__ prims, uint32_t* __restrict__ counts) {
-  extern __shared__ float4 s_mem[];
-  const uint32_t tid = threadIdx.x;
-  const size_t base = static_cast<size_t>(blockIdx.x) * 256u;           // first query of the block
-  const uint32_t nb = (n - base < 256u) ? static_cast<uint32_t>(n - base) : 256u;
-
-  const float inf = __builtin_inff();
-  float4 c0 = {inf, inf, inf, 0.0f}, c1 = c0, c2 = c0, c3 = c0, c4 = c0, c5 = c0, c6 = c0, c7 = c0;   // padding lanes: a non-finite query accepts nothing
-  if (tid < nb) {
-    const float4* const h = hexa + 8u * (base + tid);
-    c0 = h[0]; c1 = h[1]; c2 = h[2]; c3 = h[3]; c4 = h[4]; c5 = h[5]; c6 = h[6]; c7 = h[7];
-  }
-  const HexQuery q = hex_query(c0, c1, c2, c3, c4, c5, c6, c7);
-  const int cur = overlap_cursor(after, base + tid, tid < nb);
-
-  OverlapList<CAP> L;
-  L.init_scan();
-
-  // the triangles, staged into LDS chunk by chunk; every chunk is scanned
-  const uint32_t nt = p.n_tris;
-  const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
-  float4* const sA = s_mem;                                        // 2 float4 per triangle
-  float* const sB = reinterpret_cast<float*>(s_mem + 2u * cap);    // v0.z
-  for (uint32_t k0 = 0; k0 < nt; k0 += kQueryChunk) {
-    const uint32_t cn = (nt - k0 < kQueryChunk) ? nt - k0 : kQueryChunk;
-    __syncthreads();                                               // the previous chunk is read
-    for (uint32_t i = tid; i < 2u * cn; i += 256u) sA[i] = p.tri_a[2u * k0 + i];
-    for (uint32_t i = tid; i < cn; i += 256u) sB[i] = p.tri_b[k0 + i];
-    __syncthreads();
-    if (__builtin_amdgcn_ballot_w64(q.valid) == 0ull) continue;    // no query of this wave accepts; it still helps staging
-    for (uint32_t j = 0; j < cn; ++j) {
-      const float4 A0 = sA[2u * j], A1 = sA[2u * j + 1u];
-      const V3 e2 = {A0.x, A0.y, A0.z}, e1 = {A0.w, A1.x, A1.y}, A = {A1.z, A1.w, sB[j]};
-      const V3 B = rtd::add(A, e1), C = rtd::add(A, e2);
-      const int prim = static_cast<int>(k0 + j);
-      const bool behind = overlap_behind(prim, cur);
-      const bool in1 = hex_step1(q, A, B, C) & behind;
-      if (__builtin_amdgcn_ballot_w64(in1) == 0ull) continue;      // step 1 rejects it for every query of the wave
-      if (in1 && !hex_separated(q, A, B, C, e1, e2)) L.append(prim, max_hits);
+  __device__ static __forceinline__ void load(Query& q, const float4* hexa, size_t base, uint32_t lane, bool live) {
+    const float inf = __builtin_inff();
+    float4 c0 = {inf, inf, inf, 0.0f}, c1 = c0, c2 = c0, c3 = c0, c4 = c0, c5 = c0, c6 = c0, c7 = c0;   // padding lanes: a non-finite query accepts nothing
+    if (live) {
+      const float4* const h = hexa + 8u * (base + lane);
+      c0 = h[0]; c1 = h[1]; c2 = h[2]; c3 = h[3]; c4 = h[4]; c5 = h[5]; c6 = h[6]; c7 = h[7];
     }
+    q = hex_query(c0, c1, c2, c3, c4, c5, c6, c7);
   }
-  if (p.n_spheres != 0u && q.valid) {                              // (a valid query is no padding lane; no barrier below)
-    const HexCorners K = hex_corners(hexa + 8u * (base + tid));
-    for (uint32_t si = 0; si < p.n_spheres; ++si) {
-      const int prim = static_cast<int>(nt + si);
-      if (hex_sphere(q, K, p.spheres[si]) && overlap_behind(prim, cur)) L.append(prim, max_hits);
+  __device__ static __forceinline__ SphereCtx sphere_ctx(const float4* hexa, size_t base, uint32_t lane) { return hex_corners(hexa + 8u * (base + lane)); }
+
+  // step 1: BoxRegion::step1's comparisons against the region's bounding box
+  __device__ static __forceinline__ bool step1(const Query& q, V3 A, V3 B, V3 C) {
+    const bool x = overlap_axis1(A.x, B.x, C.x, q.lo.x, q.hi.x), y = overlap_axis1(A.y, B.y, C.y, q.lo.y, q.hi.y);
+    const bool z = overlap_axis1(A.z, B.z, C.z, q.lo.z, q.hi.z);
+    return q.valid & x & y & z;
+  }
+
+  // steps 2 and 3: true when one of the forty-three axes separates the record from the region
+  __device__ static __forceinline__ bool separated(const Query& q, V3 A, V3 B, V3 C, V3 e1, V3 e2) {
+    using M = Math<false>;
+    const V3 a = rtd::sub(A, q.C0), b = rtd::sub(B, q.C0), c = rtd::sub(C, q.C0);
+    const V3 f0 = e1, f1 = rtd::sub(c, b), f2 = rtd::sub(a, c);
+    // An axis that separates ends the test for its lane: the verdict is the OR of the same forty-three verdicts, and a wave whose
+    // live lanes are all separated skips the rest.  The face normals, whose region side hex_query has ready, go first.
+    bool s = false;
+  #pragma unroll
+    for (int f = 0; f < 6; ++f) s |= hex_record_axis(q.fn[f], a, b, c, q.fmn[f], q.fmx[f]);
+    if (s) return true;
+    if (hex_axis(q, M::cross(e1, e2), a, b, c)) return true;
+    // the twelve edges (0,1), (2,3), (4,5), (6,7), (0,2), (1,3), (4,6), (5,7), (0,4), (1,5), (2,6), (3,7)
+    if (hex_axes3(q, q.h[1], f0, f1, f2, a, b, c)) return true;
+    if (hex_axes3(q, rtd::sub(q.h[3], q.h[2]), f0, f1, f2, a, b, c)) return true;
+    if (hex_axes3(q, rtd::sub(q.h[5], q.h[4]), f0, f1, f2, a, b, c)) return true;
+    if (hex_axes3(q, rtd::sub(q.h[7], q.h[6]), f0, f1, f2, a, b, c)) return true;
+    if (hex_axes3(q, q.h[2], f0, f1, f2, a, b, c)) return true;
+    if (hex_axes3(q, rtd::sub(q.h[3], q.h[1]), f0, f1, f2, a, b, c)) return true;
+    if (hex_axes3(q, rtd::sub(q.h[6], q.h[4]), f0, f1, f2, a, b, c)) return true;
+    if (hex_axes3(q, rtd::sub(q.h[7], q.h[5]), f0, f1, f2, a, b, c)) return true;
+    if (hex_axes3(q, q.h[4], f0, f1, f2, a, b, c)) return true;
+    if (hex_axes3(q, rtd::sub(q.h[5], q.h[1]), f0, f1, f2, a, b, c)) return true;
+    if (hex_axes3(q, rtd::sub(q.h[6], q.h[2]), f0, f1, f2, a, b, c)) return true;
+    return hex_axes3(q, rtd::sub(q.h[7], q.h[3]), f0, f1, f2, a, b, c);
+  }
+
+  // the sphere rule: the surface touches the region when the region's nearest point is inside the ball and its farthest corner
+  // is not.  d2min <= r*r is decided face by face -- the smallest t is within r*r exactly when one of the twelve is (minNum drops a
+  // NaN, and a NaN compares false) -- and a face that decides ends it.  Left to itself the compiler flattens the six faces into
+  // one block (the point query is branchless) and the scheduler interleaves the twelve of them past the register file; the
+  // scheduling barrier in hex_face_near cannot be speculated, so every face stays a block of its own.
+  __device__ static __forceinline__ bool sphere(const Query& q, const SphereCtx& K, float4 sph) {
+    using M = Math<false>;
+    const V3 S = {sph.x, sph.y, sph.z};
+    const V3 s = rtd::sub(S, q.C0);
+    const float rr = sph.w * sph.w;
+    float d2max = 0.0f;
+  #pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const V3 w = rtd::sub(K.C[k], S);
+      const float d2 = M::dot(w, w);
+      d2max = k == 0 ? d2 : fmaxf(d2max, d2);
     }
-  }
-
-  if (tid < nb) L.store_scan(max_hits, prims + (base + tid) * max_hits, counts + base + tid);
-}
-
-// one 48-byte record against one query
-template <int CAP>
-__device__ __forceinline__ void hexoverlap_test_record(const float4* __restrict__ rec, const HexQuery& q, int cur, OverlapList<CAP>& L) {
-  const BvhRecord r = bvh_record(rec);
-  const V3 B = rtd::add(r.v0, r.e1), C = rtd::add(r.v0, r.e2);
-  if (hex_step1(q, r.v0, B, C) && overlap_behind(r.idx, cur) && !hex_separated(q, r.v0, B, C, r.e1, r.e2)) L.insert(r.idx);
-}
-
-template <int CAP>
-__global__ __launch_bounds__(64, RT_HEX_WAVES) void hexoverlap_bvh_kernel(const TraceParams p, const BvhParams b, uint32_t n,
-                                                             const float4* __restrict__ hexa, const int* __restrict__ after,
-                                                             uint32_t max_hits, int* __restrict__ prims, uint32_t* __restrict__ counts) {
-  extern __shared__ float4 s_mem[];
-  const uint32_t lane = threadIdx.x;
-  const size_t i = static_cast<size_t>(blockIdx.x) * 64u + lane;
-  if (i >= n) return;                                              // (no barrier and no cross-lane operation below)
-  const float4* const h = hexa + 8u * i;
-  const HexQuery q = hex_query(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
-  const int cur = overlap_cursor(after, i, true);
-
-  OverlapList<CAP> L;
-  L.init_tree(max_hits);
-
-  const float inf = __builtin_inff();
-  // the child's box against the region's bounding box: step 1's comparisons, no inflation; the key is constant
-  auto child = [&](const BvhNode& nd, int c) {
-    const bool in = (nd.lo[0][c] <= q.hi.x) & (nd.hi[0][c] >= q.lo.x) & (nd.lo[1][c] <= q.hi.y) & (nd.hi[1][c] >= q.lo.y) &
-                    (nd.lo[2][c] <= q.hi.z) & (nd.hi[2][c] >= q.lo.z);
-    return in ? 0.0f : -inf;
-  };
-  auto leaf = [&](const float4* rec) { hexoverlap_test_record<CAP>(rec, q, cur, L); return false; };
-  const bool overflow = bvh_walk<64u, false>(b, s_mem, lane, q.valid, child, leaf, [](float) { return false; });
-  if (overflow) {                                                  // an entry was not kept: every leaf record, from an empty list and count
-    L.init_tree(max_hits);
-    for (uint32_t j = 0; j < b.n_leaf_records; ++j) hexoverlap_test_record<CAP>(b.records + 3u * j, q, cur, L);
-  }
-  if (q.valid) {
-    for (uint32_t j = 0; j < b.n_always; ++j) hexoverlap_test_record<CAP>(b.records + 3u * (b.n_leaf_records + j), q, cur, L);
-    if (p.n_spheres != 0u) {
-      const HexCorners K = hex_corners(h);
-      for (uint32_t si = 0; si < p.n_spheres; ++si) {
-        const int prim = static_cast<int>(p.n_tris + si);
-        if (hex_sphere(q, K, p.spheres[si]) && overlap_behind(prim, cur)) L.insert(prim);
-      }
+    if (!(q.valid & (rr <= d2max))) return false;
+    bool out = false;                                                // a face normal separates the centre from the corners
+  #pragma unroll
+    for (int f = 0; f < 6; ++f) {
+      const float ps = M::dot(q.fn[f], s);
+      out |= !__builtin_isunordered(ps, ps) & ((ps > q.fmx[f]) | (ps < q.fmn[f]));
     }
+    if (!out) return 0.0f <= rr;                                     // inside: d2min = 0 (a NaN radius touches nothing)
+    if (hex_face_near(S, rr, K.C[0], K.C[2], K.C[4], K.C[6])) return true;
+    if (hex_face_near(S, rr, K.C[1], K.C[3], K.C[5], K.C[7])) return true;
+    if (hex_face_near(S, rr, K.C[0], K.C[1], K.C[4], K.C[5])) return true;
+    if (hex_face_near(S, rr, K.C[2], K.C[3], K.C[6], K.C[7])) return true;
+    if (hex_face_near(S, rr, K.C[0], K.C[1], K.C[2], K.C[3])) return true;
+    return hex_face_near(S, rr, K.C[4], K.C[5], K.C[6], K.C[7]);
   }
-  L.store_tree(max_hits, prims + i * max_hits, counts + i);
-}
+};
 
-// CAP = 0 for max_hits 0, 4 for 1 .. 4, else 16, in both forms
 hipError_t launch_overlap_hexahedra(const TraceParams& p, const BvhParams* b, uint32_t n, const float* hexa, const int* after,
                                     uint32_t max_hits, int* prims, uint32_t* counts, hipStream_t st) {
-  if (n == 0u) return hipSuccess;
-  if (max_hits > kAllHitsMax || hexa == nullptr || counts == nullptr || (prims == nullptr && max_hits != 0u)) return hipErrorInvalidValue;
-  const float4* const h4 = reinterpret_cast<const float4*>(hexa);
-  if (b != nullptr) {                                              // one wave per block, lane = query, the reference alone on the stack
-    const uint32_t lds = bvh_stack_lds_bytes(b->stack_cap, 64u, false);
-    if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
-    const auto walk = max_hits == 0u ? hexoverlap_bvh_kernel<0> : max_hits <= 4u ? hexoverlap_bvh_kernel<4> : hexoverlap_bvh_kernel<16>;
-    return launch_blocks(walk, n, 64u, 64u, lds, st, p, *b, n, h4, after, max_hits, prims, counts);
-  }
-  const auto scan = max_hits == 0u ? hexoverlap_kernel<0> : max_hits <= 4u ? hexoverlap_kernel<4> : hexoverlap_kernel<16>;
-  return launch_blocks(scan, n, 256u, 256u, query_chunk_lds_bytes(p.n_tris), st, p, n, h4, after, max_hits, prims, counts);
+  return launch_region<HexRegion>(p, b, n, hexa, after, max_hits, prims, counts, st);
 }
 
 }  // namespace rtk

@@ -12,9 +12,8 @@
 //   allhits_*kernel    <- the first k hits within a caller's t interval, in order (rt_allhits.hpp)
 //   closest_*kernel    <- the nearest surface point to a caller's point (rt_closest.hpp)
 //   nearest_*kernel    <- a point's k nearest primitives in order, with a continuation cursor (rt_nearest.hpp)
-//   overlap_*kernel    <- the primitives that touch a caller's box, lowest first, and how many (rt_overlap.hpp)
-//   trioverlap_*kernel <- the primitives that touch a caller's triangle, lowest first, and how many (rt_trioverlap.hpp)
-//   hexoverlap_*kernel <- the primitives that touch a caller's hexahedron (frustum, oriented box), lowest first, and how many (rt_hexoverlap.hpp)
+//   region_*kernel     <- the primitives that touch a caller's box (rt_overlap.hpp, which holds the two kernels), triangle
+//                         (rt_trioverlap.hpp) or hexahedron (frustum, oriented box; rt_hexoverlap.hpp), lowest first, and how many
 //   tridistance_*kernel <- the primitive nearest to a caller's triangle, and where on both (rt_tridistance.hpp)
 //   spherecast_*kernel <- a moving sphere's first contact with the scene (rt_spherecast.hpp)
 //   sides_kernel       <- the side of the surface a point query's records lie on (rt_sides.hpp)

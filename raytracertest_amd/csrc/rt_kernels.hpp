@@ -206,6 +206,7 @@ hipError_t launch_closest(const TraceParams& p, const BvhParams* b, float rho_c,
 hipError_t launch_nearest(const TraceParams& p, const BvhParams* b, float rho_c, uint32_t n, const float* pts, const float4* after,
                           uint32_t max_hits, float4* hits, uint32_t* counts, hipStream_t st);
 
+// The three region queries are launch_region<Shape> (rt_overlap.hpp) for one shape each.
 // The region query (rt_overlap.hpp): n boxes {lo xyz, -, hi xyz, -}, 16-byte aligned; after (or nullptr) n int32 cursors; row i
 // of prims (max_hits int32) holds the min(counts[i], max_hits) lowest accepted prims behind the cursor in ascending order, then
 // -1; counts[i] is the total, not capped.  0 <= max_hits <= 16 (0: prims may be nullptr); one arithmetic for both math modes;

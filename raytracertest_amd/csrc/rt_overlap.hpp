@@ -6,27 +6,31 @@
 // Acceptance is a pure function of (box, record, cursor), the text of include/rt_mi355x.h operation by operation; there is no
 // reference arithmetic to be faithful to, so there is ONE arithmetic, every operation rounded separately (the library is
 // compiled with -ffp-contract=off).  On the record the renderer intersects, A = v0, B = fl(v0 + e1), C = fl(v0 + e2):
-//   step 1 (overlap_step1)      per axis  lo <= hi,  neither B nor C a NaN,  min(A, B, C) <= hi,  max(A, B, C) >= lo
-//   step 2 (overlap_separated)  c = 0.5*lo + 0.5*hi, h = 0.5*hi - 0.5*lo, n = e1 x e2:  separated when |n.(A - c)| > h.|n|
+//   step 1 (BoxRegion::step1)  per axis  lo <= hi,  neither B nor C a NaN,  min(A, B, C) <= hi,  max(A, B, C) >= lo
+//   step 2 (separated)          c = 0.5*lo + 0.5*hi, h = 0.5*hi - 0.5*lo, n = e1 x e2:  separated when |n.(A - c)| > h.|n|
 //   step 3 (overlap_axes)       the nine axes unit_k x f of f = e1, C' - B', A' - C' (corners moved by -c), each on two corners
 // A step rejects when its "separated" is TRUE, so a NaN in steps 2-3 (overflow near FLT_MAX) never rejects; every comparison
-// of step 1 is false on a NaN, so a NaN there always rejects.  A sphere is its surface (overlap_sphere).
+// of step 1 is false on a NaN, so a NaN there always rejects.  A sphere is its surface (BoxRegion::sphere).
 //
 // Why the tree prunes exactly, with no slack: a leaf record's tree box is rtb::detail::tri_box -- the corners in double,
 // rounded outward -- so step 1's [min, max] lies inside it and inside every ancestor's child box.  A child is entered when its
 // box and the query box overlap under the same closed comparisons; a child the walk skips holds only records step 1 rejects.
 // b.rho is not read: rt_dbg_query_accel_slack has no effect here.
 //
-// overlap_kernel<CAP> (RT_QUERY_SCAN): closest_kernel's outer shape -- 256-thread blocks, lane = box, the box is two 16-byte
-// loads, the triangles staged through LDS in ascending chunks of kQueryChunk 36-byte records, spheres after the triangles.
-// Prims arrive in ascending order: the first max_hits accepted are stored (compile-time slots, selected by the count), the
-// count runs on.  A record no lane's step 1 passes is left by ballot before steps 2-3.
+// The kernels are written once for the three region shapes (the box here, the triangle of rt_trioverlap.hpp, the hexahedron of
+// rt_hexoverlap.hpp); a shape is a policy type of static members (BoxRegion below) that states its rule and nothing else.
 //
-// overlap_bvh_kernel<CAP> (RT_QUERY_BVH): one wave per block, lane = box, bvh_walk with 4-byte entries and a constant key for
-// an overlapping child.  Records arrive in tree order: the list is rt_allhits.hpp's idiom on prims alone -- CAP ints behind
-// compile-time indices, the leading CAP - max_hits slots pinned at -1, a new prim replaces the last slot when it is lower and
-// is bubbled up.  A walk visits every record at most once, so the count is exact.  After the walk: the overflow redo (which
-// RESTARTS list and count from every leaf record), the always-tested list, the spheres.
+// region_kernel<Shape, CAP> (RT_QUERY_SCAN): closest_kernel's outer shape -- 256-thread blocks, lane = query, the query is
+// Shape::kFloat4s 16-byte loads, the triangles staged through LDS in ascending chunks of kQueryChunk 36-byte records, spheres
+// after the triangles.  Prims arrive in ascending order: the first max_hits accepted are stored (compile-time slots, selected by
+// the count), the count runs on.  A record no lane's step 1 passes is left by ballot before steps 2-3.  A padding lane holds a
+// query that accepts nothing and stores nothing.
+//
+// region_bvh_kernel<Shape, CAP> (RT_QUERY_BVH): one wave per block, lane = query, bvh_walk with 4-byte entries and a constant key
+// for a child whose box overlaps the query's bounding box.  Records arrive in tree order: the list is rt_allhits.hpp's idiom on
+// prims alone -- CAP ints behind compile-time indices, the leading CAP - max_hits slots pinned at -1, a new prim replaces the last
+// slot when it is lower and is bubbled up.  A walk visits every record at most once, so the count is exact.  After the walk: the
+// overflow redo (which RESTARTS list and count from every leaf record), the always-tested list, the spheres.
 //
 // CAP = 0 is max_hits = 0: no list, no row, the count alone.
 #pragma once
@@ -59,12 +63,6 @@ __device__ __forceinline__ bool overlap_axis1(float a, float b, float c, float l
   return (!__builtin_isunordered(b, c)) & (mn <= hi) & (mx >= lo);
 }
 
-__device__ __forceinline__ bool overlap_step1(const OverlapBox& q, V3 A, V3 B, V3 C) {
-  const bool x = overlap_axis1(A.x, B.x, C.x, q.lo.x, q.hi.x), y = overlap_axis1(A.y, B.y, C.y, q.lo.y, q.hi.y);
-  const bool z = overlap_axis1(A.z, B.z, C.z, q.lo.z, q.hi.z);
-  return q.valid & x & y & z;
-}
-
 // step 3 for one edge vector f on the two corners P, Q (moved by -c) whose projections differ: the axes unit_x x f, unit_y x f,
 // unit_z x f.  Four plain comparisons per axis: a NaN never separates.
 __device__ __forceinline__ bool overlap_axes(V3 f, V3 P, V3 Q, V3 h) {
@@ -76,29 +74,53 @@ __device__ __forceinline__ bool overlap_axes(V3 f, V3 P, V3 Q, V3 h) {
          ((pz0 > rz) & (pz1 > rz)) | ((pz0 < -rz) & (pz1 < -rz));
 }
 
-// steps 2 and 3: true when the plane or one of the nine axes separates the triangle from the box
-__device__ __forceinline__ bool overlap_separated(const OverlapBox& q, V3 A, V3 B, V3 C, V3 e1, V3 e2) {
-  using M = Math<false>;
-  const V3 n = M::cross(e1, e2);
-  const V3 a = rtd::sub(A, q.c), b = rtd::sub(B, q.c), c = rtd::sub(C, q.c);
-  const float s = M::dot(n, a);
-  const float r = M::dot(q.h, {fabsf(n.x), fabsf(n.y), fabsf(n.z)});
-  const bool s0 = overlap_axes(e1, a, c, q.h), s1 = overlap_axes(rtd::sub(c, b), a, b, q.h), s2 = overlap_axes(rtd::sub(a, c), a, b, q.h);
-  return (fabsf(s) > r) | s0 | s1 | s2;
-}
+// The box as a region shape: what region_kernel and region_bvh_kernel (below) ask of a shape, static members only.
+struct NoSphereCtx {};
+struct BoxRegion {
+  static constexpr int kFloat4s = 2;                               // 16-byte loads per query
+  static constexpr int kScanWaves = 4, kTreeWaves = 0;             // waves per SIMD of the two kernels (0: no bound)
+  using Query = OverlapBox;
+  using SphereCtx = NoSphereCtx;                                   // what the sphere rule alone needs of the query as given
+  static constexpr bool kSphereCtx = false;
 
-// the sphere rule: the surface touches the box when the box's nearest point is inside the ball and its farthest corner is not
-__device__ __forceinline__ bool overlap_sphere(const OverlapBox& q, float4 sph) {
-  const float ax = q.lo.x - sph.x, bx = sph.x - q.hi.x;
-  const float ay = q.lo.y - sph.y, by = sph.y - q.hi.y;
-  const float az = q.lo.z - sph.z, bz = sph.z - q.hi.z;
-  const float gx = fmaxf(fmaxf(ax, bx), 0.0f), gy = fmaxf(fmaxf(ay, by), 0.0f), gz = fmaxf(fmaxf(az, bz), 0.0f);
-  const float fx = fmaxf(fabsf(ax), fabsf(bx)), fy = fmaxf(fabsf(ay), fabsf(by)), fz = fmaxf(fabsf(az), fabsf(bz));
-  const float d2min = (gx * gx + gy * gy) + gz * gz;
-  const float d2max = (fx * fx + fy * fy) + fz * fz;
-  const float rr = sph.w * sph.w;
-  return q.valid & (d2min <= rr) & (rr <= d2max);
-}
+  // query base + lane; a lane that is not live is a padding lane
+  __device__ static __forceinline__ void load(Query& q, const float4* boxes, size_t base, uint32_t lane, bool live) {
+    float4 b0 = {1.0f, 1.0f, 1.0f, 0.0f}, b1 = {0.0f, 0.0f, 0.0f, 0.0f};   // padding lanes: lo > hi accepts nothing
+    if (live) { b0 = boxes[2u * (base + lane)]; b1 = boxes[2u * (base + lane) + 1u]; }
+    q = overlap_box(b0, b1);
+  }
+  __device__ static __forceinline__ SphereCtx sphere_ctx(const float4*, size_t, uint32_t) { return {}; }
+
+  __device__ static __forceinline__ bool step1(const Query& q, V3 A, V3 B, V3 C) {
+    const bool x = overlap_axis1(A.x, B.x, C.x, q.lo.x, q.hi.x), y = overlap_axis1(A.y, B.y, C.y, q.lo.y, q.hi.y);
+    const bool z = overlap_axis1(A.z, B.z, C.z, q.lo.z, q.hi.z);
+    return q.valid & x & y & z;
+  }
+
+  // steps 2 and 3: true when the plane or one of the nine axes separates the triangle from the box
+  __device__ static __forceinline__ bool separated(const Query& q, V3 A, V3 B, V3 C, V3 e1, V3 e2) {
+    using M = Math<false>;
+    const V3 n = M::cross(e1, e2);
+    const V3 a = rtd::sub(A, q.c), b = rtd::sub(B, q.c), c = rtd::sub(C, q.c);
+    const float s = M::dot(n, a);
+    const float r = M::dot(q.h, {fabsf(n.x), fabsf(n.y), fabsf(n.z)});
+    const bool s0 = overlap_axes(e1, a, c, q.h), s1 = overlap_axes(rtd::sub(c, b), a, b, q.h), s2 = overlap_axes(rtd::sub(a, c), a, b, q.h);
+    return (fabsf(s) > r) | s0 | s1 | s2;
+  }
+
+  // the sphere rule: the surface touches the box when the box's nearest point is inside the ball and its farthest corner is not
+  __device__ static __forceinline__ bool sphere(const Query& q, SphereCtx, float4 sph) {
+    const float ax = q.lo.x - sph.x, bx = sph.x - q.hi.x;
+    const float ay = q.lo.y - sph.y, by = sph.y - q.hi.y;
+    const float az = q.lo.z - sph.z, bz = sph.z - q.hi.z;
+    const float gx = fmaxf(fmaxf(ax, bx), 0.0f), gy = fmaxf(fmaxf(ay, by), 0.0f), gz = fmaxf(fmaxf(az, bz), 0.0f);
+    const float fx = fmaxf(fabsf(ax), fabsf(bx)), fy = fmaxf(fabsf(ay), fabsf(by)), fz = fmaxf(fabsf(az), fabsf(bz));
+    const float d2min = (gx * gx + gy * gy) + gz * gz;
+    const float d2max = (fx * fx + fy * fy) + fz * fz;
+    const float rr = sph.w * sph.w;
+    return q.valid & (d2min <= rr) & (rr <= d2max);
+  }
+};
 
 // the continuation cursor of one box: RT_PRIM_NONE accepts every prim
 __device__ __forceinline__ int overlap_cursor(const int* __restrict__ after, size_t i, bool valid) {
@@ -164,18 +186,30 @@ struct OverlapList {
   }
 };
 
-template <int CAP>
-__global__ __launch_bounds__(256, 4) void overlap_kernel(const TraceParams p, uint32_t n, const float4* __restrict__ boxes,
-                                                          const int* __restrict__ after, uint32_t max_hits, int* __restrict__ prims,
-                                                          uint32_t* __restrict__ counts) {
+// ---- what every region shape shares: one scan kernel, one tree kernel, one launch ----
+// A shape (BoxRegion above, TriRegion in rt_trioverlap.hpp, HexRegion in rt_hexoverlap.hpp) states:
+//   kFloat4s                            16-byte loads per query (2 / 3 / 8)
+//   Query, load(q, queries, base, lane, live)
+//                                       query base + lane as the rule reads it, with lo, hi (its bounding box) and valid; a lane
+//                                       that is not live is a padding lane, whose query accepts nothing
+//   step1(q, A, B, C), separated(q, A, B, C, e1, e2)
+//   SphereCtx, kSphereCtx, sphere_ctx(queries, base, lane), sphere(q, K, sph)
+//                                       the sphere rule, and what it alone needs of the query as given: nothing (kSphereCtx false,
+//                                       an empty K passed by value) but for the hexahedron, which loads its corners again once
+//                                       there are spheres and the query is valid, so that the triangle loop does not carry them
+//   kScanWaves, kTreeWaves              the waves-per-SIMD bound of the two kernels (0: none)
+// The rule's functions ARE the policy's members: a forwarding layer in between changes the generated code.
+template <class Shape, int CAP>
+__global__ __launch_bounds__(256, Shape::kScanWaves) void region_kernel(const TraceParams p, uint32_t n, const float4* __restrict__ queries,
+                                                                         const int* __restrict__ after, uint32_t max_hits,
+                                                                         int* __restrict__ prims, uint32_t* __restrict__ counts) {
   extern __shared__ float4 s_mem[];
   const uint32_t tid = threadIdx.x;
-  const size_t base = static_cast<size_t>(blockIdx.x) * 256u;           // first box of the block
+  const size_t base = static_cast<size_t>(blockIdx.x) * 256u;           // first query of the block
   const uint32_t nb = (n - base < 256u) ? static_cast<uint32_t>(n - base) : 256u;
 
-  float4 b0 = {1.0f, 1.0f, 1.0f, 0.0f}, b1 = {0.0f, 0.0f, 0.0f, 0.0f};   // padding lanes: lo > hi accepts nothing
-  if (tid < nb) { b0 = boxes[2u * (base + tid)]; b1 = boxes[2u * (base + tid) + 1u]; }
-  const OverlapBox q = overlap_box(b0, b1);
+  typename Shape::Query q;
+  Shape::load(q, queries, base, tid, tid < nb);
   const int cur = overlap_cursor(after, base + tid, tid < nb);
 
   OverlapList<CAP> L;
@@ -192,85 +226,100 @@ __global__ __launch_bounds__(256, 4) void overlap_kernel(const TraceParams p, ui
     for (uint32_t i = tid; i < 2u * cn; i += 256u) sA[i] = p.tri_a[2u * c0 + i];
     for (uint32_t i = tid; i < cn; i += 256u) sB[i] = p.tri_b[c0 + i];
     __syncthreads();
-    if (__builtin_amdgcn_ballot_w64(q.valid) == 0ull) continue;    // no box of this wave accepts; it still helps staging
+    if (__builtin_amdgcn_ballot_w64(q.valid) == 0ull) continue;    // no query of this wave accepts; it still helps staging
     for (uint32_t j = 0; j < cn; ++j) {
       const float4 A0 = sA[2u * j], A1 = sA[2u * j + 1u];
       const V3 e2 = {A0.x, A0.y, A0.z}, e1 = {A0.w, A1.x, A1.y}, A = {A1.z, A1.w, sB[j]};
       const V3 B = rtd::add(A, e1), C = rtd::add(A, e2);
       const int prim = static_cast<int>(c0 + j);
       const bool behind = overlap_behind(prim, cur);
-      const bool in1 = overlap_step1(q, A, B, C) & behind;
-      if (__builtin_amdgcn_ballot_w64(in1) == 0ull) continue;      // step 1 rejects it for every box of the wave
-      if (in1 && !overlap_separated(q, A, B, C, e1, e2)) L.append(prim, max_hits);
+      const bool in1 = Shape::step1(q, A, B, C) & behind;
+      if (__builtin_amdgcn_ballot_w64(in1) == 0ull) continue;      // step 1 rejects it for every query of the wave
+      if (in1 && !Shape::separated(q, A, B, C, e1, e2)) L.append(prim, max_hits);
     }
   }
-  for (uint32_t si = 0; si < p.n_spheres; ++si) {
-    const int prim = static_cast<int>(nt + si);
-    if (overlap_sphere(q, p.spheres[si]) && overlap_behind(prim, cur)) L.append(prim, max_hits);
+  if (!Shape::kSphereCtx || (p.n_spheres != 0u && q.valid)) {      // (a valid query is no padding lane; no barrier below)
+    const typename Shape::SphereCtx K = Shape::sphere_ctx(queries, base, tid);
+    for (uint32_t si = 0; si < p.n_spheres; ++si) {
+      const int prim = static_cast<int>(nt + si);
+      if (Shape::sphere(q, K, p.spheres[si]) && overlap_behind(prim, cur)) L.append(prim, max_hits);
+    }
   }
 
   if (tid < nb) L.store_scan(max_hits, prims + (base + tid) * max_hits, counts + base + tid);
 }
 
-// one 48-byte record against one box
-template <int CAP>
-__device__ __forceinline__ void overlap_test_record(const float4* __restrict__ rec, const OverlapBox& q, int cur, OverlapList<CAP>& L) {
+// one 48-byte record against one query
+template <class Shape, int CAP>
+__device__ __forceinline__ void region_test_record(const float4* __restrict__ rec, const typename Shape::Query& q, int cur,
+                                                   OverlapList<CAP>& L) {
   const BvhRecord r = bvh_record(rec);
   const V3 B = rtd::add(r.v0, r.e1), C = rtd::add(r.v0, r.e2);
-  if (overlap_step1(q, r.v0, B, C) && overlap_behind(r.idx, cur) && !overlap_separated(q, r.v0, B, C, r.e1, r.e2)) L.insert(r.idx);
+  if (Shape::step1(q, r.v0, B, C) && overlap_behind(r.idx, cur) && !Shape::separated(q, r.v0, B, C, r.e1, r.e2)) L.insert(r.idx);
 }
 
-template <int CAP>
-__global__ __launch_bounds__(64) void overlap_bvh_kernel(const TraceParams p, const BvhParams b, uint32_t n,
-                                                          const float4* __restrict__ boxes, const int* __restrict__ after,
-                                                          uint32_t max_hits, int* __restrict__ prims, uint32_t* __restrict__ counts) {
+template <class Shape, int CAP>
+__global__ __launch_bounds__(64, Shape::kTreeWaves) void region_bvh_kernel(const TraceParams p, const BvhParams b, uint32_t n,
+                                                                            const float4* __restrict__ queries,
+                                                                            const int* __restrict__ after, uint32_t max_hits,
+                                                                            int* __restrict__ prims, uint32_t* __restrict__ counts) {
   extern __shared__ float4 s_mem[];
   const uint32_t lane = threadIdx.x;
-  const size_t i = static_cast<size_t>(blockIdx.x) * 64u + lane;
+  const size_t base = static_cast<size_t>(blockIdx.x) * 64u, i = base + lane;
   if (i >= n) return;                                              // (no barrier and no cross-lane operation below)
-  const OverlapBox q = overlap_box(boxes[2u * i], boxes[2u * i + 1u]);
+  typename Shape::Query q;
+  Shape::load(q, queries, base, lane, true);
   const int cur = overlap_cursor(after, i, true);
 
   OverlapList<CAP> L;
   L.init_tree(max_hits);
 
   const float inf = __builtin_inff();
-  // the child's box against the query box: step 1's comparisons, no inflation; the key is constant (nothing is ordered)
+  // the child's box against the query's bounding box: step 1's comparisons, no inflation; the key is constant (nothing is ordered)
   auto child = [&](const BvhNode& nd, int c) {
     const bool in = (nd.lo[0][c] <= q.hi.x) & (nd.hi[0][c] >= q.lo.x) & (nd.lo[1][c] <= q.hi.y) & (nd.hi[1][c] >= q.lo.y) &
                     (nd.lo[2][c] <= q.hi.z) & (nd.hi[2][c] >= q.lo.z);
     return in ? 0.0f : -inf;
   };
-  auto leaf = [&](const float4* rec) { overlap_test_record<CAP>(rec, q, cur, L); return false; };
+  auto leaf = [&](const float4* rec) { region_test_record<Shape, CAP>(rec, q, cur, L); return false; };
   const bool overflow = bvh_walk<64u, false>(b, s_mem, lane, q.valid, child, leaf, [](float) { return false; });
   if (overflow) {                                                  // an entry was not kept: every leaf record, from an empty list and count
     L.init_tree(max_hits);
-    for (uint32_t j = 0; j < b.n_leaf_records; ++j) overlap_test_record<CAP>(b.records + 3u * j, q, cur, L);
+    for (uint32_t j = 0; j < b.n_leaf_records; ++j) region_test_record<Shape, CAP>(b.records + 3u * j, q, cur, L);
   }
   if (q.valid) {
-    for (uint32_t j = 0; j < b.n_always; ++j) overlap_test_record<CAP>(b.records + 3u * (b.n_leaf_records + j), q, cur, L);
-    for (uint32_t si = 0; si < p.n_spheres; ++si) {
-      const int prim = static_cast<int>(p.n_tris + si);
-      if (overlap_sphere(q, p.spheres[si]) && overlap_behind(prim, cur)) L.insert(prim);
+    for (uint32_t j = 0; j < b.n_always; ++j) region_test_record<Shape, CAP>(b.records + 3u * (b.n_leaf_records + j), q, cur, L);
+    if (!Shape::kSphereCtx || p.n_spheres != 0u) {
+      const typename Shape::SphereCtx K = Shape::sphere_ctx(queries, base, lane);
+      for (uint32_t si = 0; si < p.n_spheres; ++si) {
+        const int prim = static_cast<int>(p.n_tris + si);
+        if (Shape::sphere(q, K, p.spheres[si]) && overlap_behind(prim, cur)) L.insert(prim);
+      }
     }
   }
   L.store_tree(max_hits, prims + i * max_hits, counts + i);
 }
 
 // CAP = 0 for max_hits 0, 4 for 1 .. 4, else 16, in both forms
-hipError_t launch_overlap(const TraceParams& p, const BvhParams* b, uint32_t n, const float* boxes, const int* after, uint32_t max_hits,
-                          int* prims, uint32_t* counts, hipStream_t st) {
+template <class Shape>
+hipError_t launch_region(const TraceParams& p, const BvhParams* b, uint32_t n, const float* queries, const int* after, uint32_t max_hits,
+                         int* prims, uint32_t* counts, hipStream_t st) {
   if (n == 0u) return hipSuccess;
-  if (max_hits > kAllHitsMax || boxes == nullptr || counts == nullptr || (prims == nullptr && max_hits != 0u)) return hipErrorInvalidValue;
-  const float4* const b4 = reinterpret_cast<const float4*>(boxes);
-  if (b != nullptr) {                                              // one wave per block, lane = box, the reference alone on the stack
+  if (max_hits > kAllHitsMax || queries == nullptr || counts == nullptr || (prims == nullptr && max_hits != 0u)) return hipErrorInvalidValue;
+  const float4* const q4 = reinterpret_cast<const float4*>(queries);
+  if (b != nullptr) {                                              // one wave per block, lane = query, the reference alone on the stack
     const uint32_t lds = bvh_stack_lds_bytes(b->stack_cap, 64u, false);
     if (!bvh_stack_fits(lds)) return hipErrorInvalidValue;
-    const auto walk = max_hits == 0u ? overlap_bvh_kernel<0> : max_hits <= 4u ? overlap_bvh_kernel<4> : overlap_bvh_kernel<16>;
-    return launch_blocks(walk, n, 64u, 64u, lds, st, p, *b, n, b4, after, max_hits, prims, counts);
+    const auto walk = max_hits == 0u ? region_bvh_kernel<Shape, 0> : max_hits <= 4u ? region_bvh_kernel<Shape, 4> : region_bvh_kernel<Shape, 16>;
+    return launch_blocks(walk, n, 64u, 64u, lds, st, p, *b, n, q4, after, max_hits, prims, counts);
   }
-  const auto scan = max_hits == 0u ? overlap_kernel<0> : max_hits <= 4u ? overlap_kernel<4> : overlap_kernel<16>;
-  return launch_blocks(scan, n, 256u, 256u, query_chunk_lds_bytes(p.n_tris), st, p, n, b4, after, max_hits, prims, counts);
+  const auto scan = max_hits == 0u ? region_kernel<Shape, 0> : max_hits <= 4u ? region_kernel<Shape, 4> : region_kernel<Shape, 16>;
+  return launch_blocks(scan, n, 256u, 256u, query_chunk_lds_bytes(p.n_tris), st, p, n, q4, after, max_hits, prims, counts);
+}
+
+hipError_t launch_overlap(const TraceParams& p, const BvhParams* b, uint32_t n, const float* boxes, const int* after, uint32_t max_hits,
+                          int* prims, uint32_t* counts, hipStream_t st) {
+  return launch_region<BoxRegion>(p, b, n, boxes, after, max_hits, prims, counts, st);
 }
 
 }  // namespace rtk

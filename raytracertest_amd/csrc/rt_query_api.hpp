@@ -256,30 +256,24 @@ inline void enqueue_closest_all(rt_tracer* t, size_t n, const float* pts, const 
   });
 }
 
-// boxes (and their cursors, or nullptr) -> rows of max_hits prims and one total per box (rt_overlap.hpp).  One arithmetic for both
-// math modes: the flags stay 0.  The tree is the ray queries' (ensure_query_tree, so RT_ACCEL_REFIT applies); no rho is passed.
-inline void enqueue_overlap(rt_tracer* t, size_t n, const float* boxes, const int32_t* after, uint32_t max_hits, int32_t* prims,
-                            uint32_t* counts, hipStream_t st) {
-  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return rtk::launch_overlap(p, b, static_cast<uint32_t>(n), boxes, after, max_hits, prims, counts, st);
-  });
-}
+// What the entry points of one region shape (boxes, query triangles, hexahedra) differ in: the floats per query, the array's name in
+// the alignment message, the launch function, and the entry points themselves, which query_call forwards to on a band's tracer.
+struct RegionShape {
+  size_t floats;
+  const char* array;
+  hipError_t (*launch)(const rtk::TraceParams&, const rtk::BvhParams*, uint32_t, const float*, const int*, uint32_t, int*, uint32_t*,
+                       hipStream_t);
+  int (*host)(rt_tracer*, const float*, const int32_t*, size_t, uint32_t, int32_t*, uint32_t*);
+  int (*device)(rt_tracer*, const float*, const int32_t*, size_t, uint32_t, int32_t*, uint32_t*, void*);
+};
 
-// query triangles (and their cursors, or nullptr) -> rows of max_hits prims and one total per triangle (rt_trioverlap.hpp), with
-// enqueue_overlap's tree and flags
-inline void enqueue_overlap_triangles(rt_tracer* t, size_t n, const float* tris, const int32_t* after, uint32_t max_hits, int32_t* prims,
-                                      uint32_t* counts, hipStream_t st) {
+// queries (and their cursors, or nullptr) -> rows of max_hits prims and one total per query (rt_overlap.hpp, rt_trioverlap.hpp,
+// rt_hexoverlap.hpp).  One arithmetic for both math modes: the flags stay 0.  The tree is the ray queries' (ensure_query_tree, so
+// RT_ACCEL_REFIT applies); no rho is passed.
+inline void enqueue_region(rt_tracer* t, const RegionShape& s, size_t n, const float* queries, const int32_t* after, uint32_t max_hits,
+                           int32_t* prims, uint32_t* counts, hipStream_t st) {
   enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return rtk::launch_overlap_triangles(p, b, static_cast<uint32_t>(n), tris, after, max_hits, prims, counts, st);
-  });
-}
-
-// regions of eight corners (and their cursors, or nullptr) -> rows of max_hits prims and one total per region (rt_hexoverlap.hpp),
-// with enqueue_overlap's tree and flags
-inline void enqueue_overlap_hexahedra(rt_tracer* t, size_t n, const float* hexa, const int32_t* after, uint32_t max_hits, int32_t* prims,
-                                      uint32_t* counts, hipStream_t st) {
-  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return rtk::launch_overlap_hexahedra(p, b, static_cast<uint32_t>(n), hexa, after, max_hits, prims, counts, st);
+    return s.launch(p, b, static_cast<uint32_t>(n), queries, after, max_hits, prims, counts, st);
   });
 }
 
@@ -307,6 +301,37 @@ inline bool overlap_args_ok(rt_tracer* t, const char* who, size_t n, const float
   if (!query_args_ok(t, n, {boxes, counts})) return false;
   if (n != 0u && max_hits != 0u && !prims) { t->set_error("query: null array"); return false; }
   return true;
+}
+
+// the staged host form of a region query
+inline int region_host(rt_tracer* t, const RegionShape& s, const char* who, const float* queries, const int32_t* after, size_t n,
+                       uint32_t max_hits, int32_t* prims, uint32_t* counts) {
+  if (!t || !overlap_args_ok(t, who, n, queries, max_hits, prims, counts)) return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return s.host(b, queries, after, n, max_hits, prims, counts); }, [&] {
+    if (n == 0u) return;
+    const hipStream_t st = host_query_stream(t);
+    const float* d_queries = staged_in<float>(t->queries.in[0], queries, n * s.floats, st);
+    const int32_t* d_after = after ? staged_in<int32_t>(t->queries.in[1], after, n, st) : nullptr;
+    int32_t* d_prims = max_hits != 0u ? room<int32_t>(t->queries.out[0], n * max_hits) : nullptr;
+    enqueue_region(t, s, n, d_queries, d_after, max_hits, d_prims, room<uint32_t>(t->queries.out[1], n), st);
+    if (max_hits != 0u) staged_out<int32_t>(prims, t->queries.out[0], n * max_hits, st);
+    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+// and its _device form
+inline int region_device(rt_tracer* t, const RegionShape& s, const char* who, const float* queries, const int32_t* after, size_t n,
+                         uint32_t max_hits, int32_t* prims, uint32_t* counts, void* stream) {
+  if (!t || !overlap_args_ok(t, who, n, queries, max_hits, prims, counts) ||
+      !query_aligned_ok(t, n, {{queries, 16u}, {after, 4u}, {prims, 4u}, {counts, 4u}},
+                        fmt("%s: %s must be 16-byte aligned, after, prims and counts 4-byte aligned", who, s.array).c_str()))
+    return RT_ERR_INVALID;
+  return query_call(t, [&](rt_tracer* b) { return s.device(b, queries, after, n, max_hits, prims, counts, stream); }, [&] {
+    if (n == 0u) return;
+    t->use_device();
+    enqueue_region(t, s, n, queries, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
+  });
 }
 
 // The signed queries' feature table (rt_features_host.hpp) of the current scene: built on the host from the
@@ -703,91 +728,38 @@ int rt_tracer_closest_sides_device(rt_tracer* t, const float* pts, const rt_hit*
   });
 }
 
+static const RegionShape kBoxes{8u, "boxes", rtk::launch_overlap, rt_tracer_overlap, rt_tracer_overlap_device};
+static const RegionShape kTriangles{12u, "tris", rtk::launch_overlap_triangles, rt_tracer_overlap_triangles, rt_tracer_overlap_triangles_device};
+static const RegionShape kHexahedra{32u, "hexa", rtk::launch_overlap_hexahedra, rt_tracer_overlap_hexahedra, rt_tracer_overlap_hexahedra_device};   // 128 bytes per query
+
 int rt_tracer_overlap(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                       uint32_t* counts) {
-  if (!t || !overlap_args_ok(t, "rt_tracer_overlap", n, boxes, max_hits, prims, counts)) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap(b, boxes, after, n, max_hits, prims, counts); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_boxes = staged_in<float>(t->queries.in[0], boxes, n * 8u, st);
-    const int32_t* d_after = after ? staged_in<int32_t>(t->queries.in[1], after, n, st) : nullptr;
-    int32_t* d_prims = max_hits != 0u ? room<int32_t>(t->queries.out[0], n * max_hits) : nullptr;
-    enqueue_overlap(t, n, d_boxes, d_after, max_hits, d_prims, room<uint32_t>(t->queries.out[1], n), st);
-    if (max_hits != 0u) staged_out<int32_t>(prims, t->queries.out[0], n * max_hits, st);
-    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+  return region_host(t, kBoxes, "rt_tracer_overlap", boxes, after, n, max_hits, prims, counts);
 }
 
 int rt_tracer_overlap_device(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                              uint32_t* counts, void* stream) {
-  if (!t || !overlap_args_ok(t, "rt_tracer_overlap_device", n, boxes, max_hits, prims, counts) ||
-      !query_aligned_ok(t, n, {{boxes, 16u}, {after, 4u}, {prims, 4u}, {counts, 4u}},
-                        "rt_tracer_overlap_device: boxes must be 16-byte aligned, after, prims and counts 4-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap_device(b, boxes, after, n, max_hits, prims, counts, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_overlap(t, n, boxes, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
-  });
+  return region_device(t, kBoxes, "rt_tracer_overlap_device", boxes, after, n, max_hits, prims, counts, stream);
 }
 
 int rt_tracer_overlap_triangles(rt_tracer* t, const float* tris, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                                 uint32_t* counts) {
-  if (!t || !overlap_args_ok(t, "rt_tracer_overlap_triangles", n, tris, max_hits, prims, counts)) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap_triangles(b, tris, after, n, max_hits, prims, counts); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_tris = staged_in<float>(t->queries.in[0], tris, n * 12u, st);
-    const int32_t* d_after = after ? staged_in<int32_t>(t->queries.in[1], after, n, st) : nullptr;
-    int32_t* d_prims = max_hits != 0u ? room<int32_t>(t->queries.out[0], n * max_hits) : nullptr;
-    enqueue_overlap_triangles(t, n, d_tris, d_after, max_hits, d_prims, room<uint32_t>(t->queries.out[1], n), st);
-    if (max_hits != 0u) staged_out<int32_t>(prims, t->queries.out[0], n * max_hits, st);
-    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+  return region_host(t, kTriangles, "rt_tracer_overlap_triangles", tris, after, n, max_hits, prims, counts);
 }
 
 int rt_tracer_overlap_triangles_device(rt_tracer* t, const float* tris, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                                        uint32_t* counts, void* stream) {
-  if (!t || !overlap_args_ok(t, "rt_tracer_overlap_triangles_device", n, tris, max_hits, prims, counts) ||
-      !query_aligned_ok(t, n, {{tris, 16u}, {after, 4u}, {prims, 4u}, {counts, 4u}},
-                        "rt_tracer_overlap_triangles_device: tris must be 16-byte aligned, after, prims and counts 4-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap_triangles_device(b, tris, after, n, max_hits, prims, counts, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_overlap_triangles(t, n, tris, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
-  });
+  return region_device(t, kTriangles, "rt_tracer_overlap_triangles_device", tris, after, n, max_hits, prims, counts, stream);
 }
 
 int rt_tracer_overlap_hexahedra(rt_tracer* t, const float* hexa, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                                 uint32_t* counts) {
-  if (!t || !overlap_args_ok(t, "rt_tracer_overlap_hexahedra", n, hexa, max_hits, prims, counts)) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap_hexahedra(b, hexa, after, n, max_hits, prims, counts); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_hexa = staged_in<float>(t->queries.in[0], hexa, n * 32u, st);   // 128 bytes per query
-    const int32_t* d_after = after ? staged_in<int32_t>(t->queries.in[1], after, n, st) : nullptr;
-    int32_t* d_prims = max_hits != 0u ? room<int32_t>(t->queries.out[0], n * max_hits) : nullptr;
-    enqueue_overlap_hexahedra(t, n, d_hexa, d_after, max_hits, d_prims, room<uint32_t>(t->queries.out[1], n), st);
-    if (max_hits != 0u) staged_out<int32_t>(prims, t->queries.out[0], n * max_hits, st);
-    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+  return region_host(t, kHexahedra, "rt_tracer_overlap_hexahedra", hexa, after, n, max_hits, prims, counts);
 }
 
 int rt_tracer_overlap_hexahedra_device(rt_tracer* t, const float* hexa, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                                        uint32_t* counts, void* stream) {
-  if (!t || !overlap_args_ok(t, "rt_tracer_overlap_hexahedra_device", n, hexa, max_hits, prims, counts) ||
-      !query_aligned_ok(t, n, {{hexa, 16u}, {after, 4u}, {prims, 4u}, {counts, 4u}},
-                        "rt_tracer_overlap_hexahedra_device: hexa must be 16-byte aligned, after, prims and counts 4-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_overlap_hexahedra_device(b, hexa, after, n, max_hits, prims, counts, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_overlap_hexahedra(t, n, hexa, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
-  });
+  return region_device(t, kHexahedra, "rt_tracer_overlap_hexahedra_device", hexa, after, n, max_hits, prims, counts, stream);
 }
 
 int rt_tracer_sphere_cast(rt_tracer* t, const float* sweeps, size_t n, rt_hit* hits) {

@@ -1,7 +1,7 @@
 // rt_tridistance.hpp -- the triangle-shaped proximity query (rt_tracer_triangle_distance*): the primitive of the
 // tracer's scene nearest to query triangle i within that triangle's own squared search radius, where on the primitive, and where
 // on the query triangle.  Included by rt_kernels.hip only, behind rt_trioverlap.hpp, whose TriQuery (corners, p1, p2, bounding
-// box, validity) and sphere verdict (tri_sphere) are used as they are, as are rt_closest.hpp's closest_triangle and closest_keep.
+// box, validity) and sphere verdict (TriRegion::sphere) are used as they are, as are rt_closest.hpp's closest_triangle and closest_keep.
 //
 // The rule is the text of include/rt_mi355x.h operation by operation: ONE arithmetic, every operation rounded separately (the
 // library is compiled with -ffp-contract=off), division correctly rounded, min and max IEEE minNum / maxNum.  Against a record
@@ -16,7 +16,7 @@
 // every distance this query reports is the point query's own for a point inside the query's bounding box, which is what lets
 // the tree prune by the point query's bound (4.3f) with the box in the place of the point: no new rounding proof.
 // A sphere has four candidates (the corners and the centre's projection) under closest_finish's sphere arithmetic; t = 0 when
-// OverlapTriangles' sphere condition (tri_sphere) holds.  Winner: closest_keep's (t, prim) rule, best starting at d2max.
+// OverlapTriangles' sphere condition (TriRegion::sphere) holds.  Winner: closest_keep's (t, prim) rule, best starting at d2max.
 //
 // tridistance_kernel (RT_QUERY_SCAN): 256-thread blocks, lane = query, the query is three 16-byte loads; the triangles staged
 // through LDS in ascending chunks of kQueryChunk as closest_kernel stages them; spheres after the triangles.  The loop carries
@@ -166,7 +166,7 @@ __device__ __forceinline__ TdPair td_sphere(const TdQuery& d, float4 sph) {
   };
   attempt(q.P0, 0); attempt(q.P1, 1); attempt(q.P2, 2); attempt(td_project(q, ctr), 3);
   if (b.k < 0) b.t = __builtin_nanf("");
-  else if (tri_sphere(q, sph)) b.t = 0.0f;                         // the surface touches the query: OverlapTriangles' verdict
+  else if (TriRegion::sphere(q, {}, sph)) b.t = 0.0f;                         // the surface touches the query: OverlapTriangles' verdict
   return b;
 }
 

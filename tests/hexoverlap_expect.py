@@ -7,8 +7,8 @@ and needs no device."""
 import numpy as np
 
 import closest_expect as ce
-from overlap_expect import EPS, K, MAX_HITS, NONE, accepted_sets, chain, corners, random_scene, rows_of_table, same  # noqa: F401  (re-exported)
-from query_accel_expect import EMPTY, LEAF, leaf_span, note_high_water, records_of_rows
+from overlap_expect import EPS, K, MAX_HITS, NONE, accepted_sets, chain, corners, random_scene, rows_of_table, same, walk_tree  # noqa: F401  (re-exported)
+from query_accel_expect import records_of_rows
 from trioverlap_expect import _cross, _dot, _segment_hits64, _sub
 
 f32 = np.float32
@@ -195,67 +195,16 @@ def expected(queries, rows, max_hits, after=None, edges=False, spheres=None):
 
 def walk_tree_hexahedra(nodes, recs, info, queries, rows, max_hits, after=None, edges=False, spheres=None, closed=True,
                         stack_cap=None, stats=None, acc=None):
-    """hexoverlap_bvh_kernel in numpy over a dumped tree (nodes, recs, info of api.bvh_build / query_tree): a child is entered
-    when its box and the region's bounding box overlap (closed comparisons, no inflation), every record met goes through the
-    rule (looked up in table(), or in acc when given), then the always-tested list, then the spheres.  Returns (prims, counts,
-    triangle tests made).  closed=False enters a child only on STRICT overlap, which breaks it.  stack_cap: the number of
-    entries the stack holds (default 3 * depth, which never overflows); a walk that had to drop an entry starts again from
-    every leaf record, as the kernel's overflow redo does."""
+    """overlap_expect.walk_tree (region_bvh_kernel in numpy) for hexahedra: the bounding box of the eight corners, all of them
+    finite; the rule is looked up in table(), or in acc when given.  closed and stack_cap are walk_tree's."""
     queries = np.asarray(queries, f32).reshape(-1, 32)
-    n = queries.shape[0]
     if acc is None:
         acc = table(queries, rows, edges, spheres)
     H = corners_of(queries)
-    n_tris = recs.shape[0]
-    n_leaf = n_tris - info["always_tested"]
-    index = recs["index"].astype(np.int64)
-    met = np.zeros(acc.shape, bool)
-    tests = 0
-    cap = 3 * max(info["depth"], 1) if stack_cap is None else stack_cap
-    with np.errstate(invalid="ignore"):
-        for i in range(n):
-            if not np.isfinite(H[i]).all():
-                note_high_water(stats, 0)
-                continue
-            lo, hi = H[i].min(axis=0), H[i].max(axis=0)
-            stack, mark, overflow = [], 0, False
-            cur = 0 if nodes.shape[0] else EMPTY
-            while True:
-                if cur == EMPTY:
-                    if not stack:
-                        break
-                    cur = stack.pop()
-                if cur & LEAF:
-                    first, count = leaf_span(cur)
-                    for j in index[first:first + count]:
-                        assert not met[i, j]                             # a walk visits every record at most once
-                        met[i, j] = True
-                        tests += 1
-                    cur = EMPTY
-                    continue
-                nd = nodes[cur]
-                if closed:
-                    inn = ((nd["lo"] <= hi[:, None]) & (nd["hi"] >= lo[:, None])).all(axis=0)
-                else:
-                    inn = ((nd["lo"] < hi[:, None]) & (nd["hi"] > lo[:, None])).all(axis=0)
-                kids = [int(nd["child"][c]) for c in range(4) if int(nd["child"][c]) != EMPTY and inn[c]]
-                cur = kids[0] if kids else EMPTY
-                for k in reversed(kids[1:]):
-                    if len(stack) < cap:
-                        stack.append(k)
-                    else:
-                        overflow = True
-                mark = max(mark, len(stack))
-            note_high_water(stats, mark)
-            if overflow:                                                 # from an empty list and count: every leaf record
-                met[i, :n_tris] = False
-                met[i, index[:n_leaf]] = True
-                tests += n_leaf
-            met[i, index[n_leaf:]] = True
-            tests += n_tris - n_leaf
-            met[i, n_tris:] = True                                       # the spheres, after the triangles
-    prims, counts = rows_of_table(acc & met, max_hits, after)
-    return prims, counts, tests
+
+    def bounds(i):
+        return (H[i].min(axis=0), H[i].max(axis=0)) if np.isfinite(H[i]).all() else None
+    return walk_tree(nodes, recs, info, acc, bounds, max_hits, after, closed, stack_cap, stats)
 
 
 # ---- float64, written independently ---------------------------------------------------------------------------------------

@@ -165,29 +165,28 @@ def same(a, b):
 
 # ---- the traversal, restated ------------------------------------------------------------------------------------------------
 
-def walk_tree_overlap(nodes, recs, info, boxes, rows, max_hits, after=None, edges=False, spheres=None, closed=True, box_step=True,
-                      stats=None):
-    """overlap_bvh_kernel in numpy over a dumped tree (nodes, recs, info of api.bvh_build / query_tree): a child is entered when
-    its box and the query box overlap (closed comparisons, no inflation), every record met goes through the rule (looked up in
-    table(): the same function on the same operands), then the always-tested list, then the spheres.  Returns (prims, counts,
-    triangle tests made).  Switches that break one thing each, for tests of the tests: closed=False enters a child only on
-    STRICT overlap; box_step=False walks with the rule that lacks step 1."""
-    boxes = np.asarray(boxes, f32).reshape(-1, 8)
-    n = boxes.shape[0]
-    acc = table(boxes, rows, edges, spheres, box_step=box_step)
+def walk_tree(nodes, recs, info, acc, bounds, max_hits, after=None, closed=True, stack_cap=None, stats=None):
+    """region_bvh_kernel in numpy over a dumped tree (nodes, recs, info of api.bvh_build / query_tree), for every region shape:
+    acc is the shape's rule as a table (queries x prims), bounds(i) the bounding box (lo, hi) of query i, or None for a query that
+    accepts nothing.  A child is entered when its box and the query's bounding box overlap (closed comparisons, no inflation),
+    every record met goes through the rule, then the always-tested list, then the spheres.  Returns (prims, counts, triangle
+    tests made).  closed=False enters a child only on STRICT overlap, which breaks it.  stack_cap: the number of entries the
+    stack holds (default 3 * depth, which never overflows); a walk that had to drop an entry starts again from every leaf
+    record, as the kernel's overflow redo does."""
     n_tris = recs.shape[0]
     n_leaf = n_tris - info["always_tested"]
     index = recs["index"].astype(np.int64)
     met = np.zeros(acc.shape, bool)
     tests = 0
-    cap = 3 * max(info["depth"], 1)
+    cap = 3 * max(info["depth"], 1) if stack_cap is None else stack_cap
     with np.errstate(invalid="ignore"):
-        for i in range(n):
-            lo, hi = boxes[i, 0:3], boxes[i, 4:7]
-            if not (lo <= hi).all():
+        for i in range(acc.shape[0]):
+            box = bounds(i)
+            if box is None:
                 note_high_water(stats, 0)
                 continue
-            stack, mark = [], 0
+            lo, hi = box
+            stack, mark, overflow = [], 0, False
             cur = 0 if nodes.shape[0] else EMPTY
             while True:
                 if cur == EMPTY:
@@ -210,15 +209,35 @@ def walk_tree_overlap(nodes, recs, info, boxes, rows, max_hits, after=None, edge
                 kids = [int(nd["child"][c]) for c in range(4) if int(nd["child"][c]) != EMPTY and inn[c]]
                 cur = kids[0] if kids else EMPTY
                 for k in reversed(kids[1:]):
-                    stack.append(k)
-                assert len(stack) <= cap
+                    if len(stack) < cap:
+                        stack.append(k)
+                    else:
+                        overflow = True
+                assert stack_cap is not None or not overflow             # 3 * depth entries always suffice
                 mark = max(mark, len(stack))
             note_high_water(stats, mark)
+            if overflow:                                                 # from an empty list and count: every leaf record
+                met[i, :n_tris] = False
+                met[i, index[:n_leaf]] = True
+                tests += n_leaf
             met[i, index[n_leaf:]] = True
             tests += n_tris - n_leaf
             met[i, n_tris:] = True                                       # the spheres, after the triangles
     prims, counts = rows_of_table(acc & met, max_hits, after)
     return prims, counts, tests
+
+
+def walk_tree_overlap(nodes, recs, info, boxes, rows, max_hits, after=None, edges=False, spheres=None, closed=True, box_step=True,
+                      stats=None):
+    """walk_tree for boxes: the query's bounding box is the box itself, lo <= hi on every axis.  Switches that break one thing
+    each, for tests of the tests: closed=False; box_step=False walks with the rule that lacks step 1."""
+    boxes = np.asarray(boxes, f32).reshape(-1, 8)
+
+    def bounds(i):
+        lo, hi = boxes[i, 0:3], boxes[i, 4:7]
+        return (lo, hi) if (lo <= hi).all() else None
+    return walk_tree(nodes, recs, info, table(boxes, rows, edges, spheres, box_step=box_step), bounds, max_hits, after, closed,
+                     stats=stats)
 
 
 # ---- float64, written independently ---------------------------------------------------------------------------------------

@@ -16,7 +16,7 @@ import lattice_cases as lc
 import overlap_expect as oe
 import seam_cases as sc
 from query_expect import edge_rows
-from test_gpu_overlap import COUNTS, SPHERES, _assert_rows, _tracer
+from test_gpu_overlap import COUNTS, SPHERES, _assert_rows, _tracer, assert_block_edges
 
 pytestmark = pytest.mark.gpu
 
@@ -40,6 +40,16 @@ def regions_around(rows, n, seed, grow=2.0, edges=False):
                            he.aligned_boxes(np.zeros((n, 3)), seed + 5, 1.0)[4::5]])
     order = rng.permutation(n)
     return he.queries_of(unit[order].astype(np.float64) * size[:, None, None] + centres[:, None, :])
+
+
+def test_query_counts_at_the_wave_and_block_edges():
+    rows = he.random_scene(1025, seed=79, span=3.0, edge=0.6)            # one triangle past a chunk, one sphere
+    queries = np.concatenate([he.regions_near(rows, 250, 5, size=1.0), he.bad_queries(he.regions_near(rows, 1, 6)[0])])[:257]
+    g = _tracer()
+    assert g.UploadScene(rows)
+    g.UploadSpheres(SPHERES[:1])
+    assert_block_edges(g, g.OverlapHexahedra, queries, he.table(queries, rows, spheres=SPHERES[:1]), he.rows_of_table)
+    g.close()
 
 
 @functools.lru_cache(maxsize=None)

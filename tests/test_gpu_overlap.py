@@ -36,6 +36,33 @@ def _assert_rows(got, exp, label):
     assert bad.size == 0, (label, bad.size, bad[:5], prims[bad[:2]], exp[0][bad[:2]], counts[bad[:3]], exp[1][bad[:3]])
 
 
+EDGE_COUNTS = (1, 63, 64, 65, 255, 256, 257)       # the tree kernel's i >= n return; the last block of the scan, whose padding lanes
+#                                                    must accept nothing and store nothing
+
+
+def assert_block_edges(g, query, queries, acc, rows_of_table):
+    """query (a bound method of g over 257 queries, acc their verdict table) at every count of EDGE_COUNTS, scan and tree, with
+    no list and with one; the rows behind the count stay the caller's."""
+    assert queries.shape[0] == 257
+    exp = {k: rows_of_table(acc, k) for k in (0, 4)}
+    assert (exp[0][1] > 4).any() and (exp[0][1] == 0).any()
+    for accel in (False, True):
+        g.SetQueryAcceleration(accel)
+        for k in (0, 4):
+            for n in EDGE_COUNTS:
+                _assert_rows(query(queries[:n], k), (exp[k][0][:n], exp[k][1][:n]), "accel=%d k=%d n=%d" % (accel, k, n))
+
+
+def test_query_counts_at_the_wave_and_block_edges():
+    rows = oe.random_scene(1025, seed=77, span=3.0, edge=0.6)            # one triangle past a chunk, one sphere
+    boxes = np.concatenate([oe.random_boxes(rows, 250, 5, width=1.5), oe.bad_boxes(oe.whole_box(rows)[0])])[:257]
+    g = _tracer()
+    assert g.UploadScene(rows)
+    g.UploadSpheres(SPHERES[:1])
+    assert_block_edges(g, g.Overlap, boxes, oe.table(boxes, rows, spheres=SPHERES[:1]), oe.rows_of_table)
+    g.close()
+
+
 def boxes_around(rows, n, seed, grow=2.0, edges=False):
     """n boxes, each the bounds of a random finite triangle grown on every side by up to `grow` times its largest extent (scale
     free: the deep ladder's clusters span 2^-28 .. 2^41)."""

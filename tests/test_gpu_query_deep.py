@@ -4,7 +4,7 @@ asserts the restated marks, Exposure's included), every BVH query equals the sca
 that query's own check, in both layouts, both arithmetic modes and both hit rules; the device refit of 16 levels is the host's;
 and with the stack shortened by DebugQueryStackCap every lane that needs one entry more answers from every leaf record -- the
 overflow path, which no tree of the builder reaches on its own -- under the same checks.  The four newer walkers on the same
-bvh_walk (overlap_bvh_kernel, trioverlap_bvh_kernel, spherecast_bvh_kernel, tridistance_bvh_kernel), each with an overflow
+bvh_walk (region_bvh_kernel for boxes and triangles, spherecast_bvh_kernel, tridistance_bvh_kernel), each with an overflow
 restart of its own, go through every one of these cases with region_pops' boxes, query triangles and sweeps: they equal the
 scan byte for byte by contract, every row, at every cap."""
 import numpy as np
@@ -416,8 +416,8 @@ def test_a_shortened_stack_answers_from_every_leaf_record(orc, name):
 
 
 def region_marks(nodes, recs, info, pops, rows, spheres):
-    """({walk: the most stack entries each lane's restated walk holds}, every fourth box and query triangle, for overlap_bvh_kernel,
-    trioverlap_bvh_kernel and tridistance_bvh_kernel; for spherecast_bvh_kernel, which has no restated walk, the sweeps whose
+    """({walk: the most stack entries each lane's restated walk holds}, every fourth box and query triangle, for region_bvh_kernel (boxes, triangles)
+    and tridistance_bvh_kernel; for spherecast_bvh_kernel, which has no restated walk, the sweeps whose
     box (both ends, widened by the radius) meets more than one child of the root: a device-independent lower bound on the
     lanes that hold an entry)."""
     from query_accel_expect import EMPTY

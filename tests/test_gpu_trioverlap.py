@@ -14,7 +14,7 @@ import lattice_cases as lc
 import seam_cases as sc
 import trioverlap_expect as te
 from query_expect import edge_rows
-from test_gpu_overlap import COUNTS, KS, SPHERES, _assert_rows, _tracer
+from test_gpu_overlap import COUNTS, KS, SPHERES, _assert_rows, _tracer, assert_block_edges
 
 pytestmark = pytest.mark.gpu
 
@@ -32,6 +32,16 @@ def queries_around(rows, n, seed, grow=2.0, edges=False):
     ext = (mx - mn).max(axis=1, keepdims=True)
     g = rng.uniform(0.0, grow, (n, 1)) * ext
     return te.queries_of((mn - g)[:, None, :] + rng.uniform(0.0, 1.0, (n, 3, 3)) * (mx - mn + 2 * g)[:, None, :])
+
+
+def test_query_counts_at_the_wave_and_block_edges():
+    rows = te.random_scene(1025, seed=78, span=3.0, edge=0.6)            # one triangle past a chunk, one sphere
+    queries = np.concatenate([te.queries_near(rows, 250, 5, edge=5.0), te.bad_queries(te.queries_near(rows, 1, 6)[0])])[:257]
+    g = _tracer()
+    assert g.UploadScene(rows)
+    g.UploadSpheres(SPHERES[:1])
+    assert_block_edges(g, g.OverlapTriangles, queries, te.table(queries, rows, spheres=SPHERES[:1]), te.rows_of_table)
+    g.close()
 
 
 @functools.lru_cache(maxsize=None)

@@ -6,8 +6,8 @@ the query populations of the tests.  A helper, not a test.  Everything is determ
 import numpy as np
 
 import closest_expect as ce
-from overlap_expect import EPS, K, MAX_HITS, NONE, accepted_sets, chain, corners, random_scene, rows_of_table, same  # noqa: F401  (re-exported)
-from query_accel_expect import EMPTY, LEAF, leaf_span, note_high_water, records_of_rows
+from overlap_expect import EPS, K, MAX_HITS, NONE, accepted_sets, chain, corners, random_scene, rows_of_table, same, walk_tree  # noqa: F401  (re-exported)
+from query_accel_expect import records_of_rows
 
 f32 = np.float32
 INF = f32(np.inf)
@@ -153,59 +153,15 @@ def expected(queries, rows, max_hits, after=None, edges=False, spheres=None):
 
 def walk_tree_triangles(nodes, recs, info, queries, rows, max_hits, after=None, edges=False, spheres=None, closed=True,
                         box_step=True, stats=None):
-    """trioverlap_bvh_kernel in numpy over a dumped tree (nodes, recs, info of api.bvh_build / query_tree): a child is entered when
-    its box and the query triangle's bounding box overlap (closed comparisons, no inflation), every record met goes through the
-    rule (looked up in table()), then the always-tested list, then the spheres.  Returns (prims, counts, triangle tests made).
-    Switches that break one thing each: closed=False enters a child only on STRICT overlap; box_step=False walks with the rule
-    that lacks step 1."""
+    """overlap_expect.walk_tree (region_bvh_kernel in numpy) for query triangles: the bounding box of the corners, all of them
+    finite.  Switches that break one thing each: closed=False; box_step=False walks with the rule that lacks step 1."""
     queries = np.asarray(queries, f32).reshape(-1, 12)
-    n = queries.shape[0]
-    acc = table(queries, rows, edges, spheres, box_step=box_step)
     P = corners_of(queries)
-    n_tris = recs.shape[0]
-    n_leaf = n_tris - info["always_tested"]
-    index = recs["index"].astype(np.int64)
-    met = np.zeros(acc.shape, bool)
-    tests = 0
-    cap = 3 * max(info["depth"], 1)
-    with np.errstate(invalid="ignore"):
-        for i in range(n):
-            if not np.isfinite(P[i]).all():
-                note_high_water(stats, 0)
-                continue
-            lo, hi = P[i].min(axis=0), P[i].max(axis=0)
-            stack, mark = [], 0
-            cur = 0 if nodes.shape[0] else EMPTY
-            while True:
-                if cur == EMPTY:
-                    if not stack:
-                        break
-                    cur = stack.pop()
-                if cur & LEAF:
-                    first, count = leaf_span(cur)
-                    for j in index[first:first + count]:
-                        assert not met[i, j]                             # a walk visits every record at most once
-                        met[i, j] = True
-                        tests += 1
-                    cur = EMPTY
-                    continue
-                nd = nodes[cur]
-                if closed:
-                    inn = ((nd["lo"] <= hi[:, None]) & (nd["hi"] >= lo[:, None])).all(axis=0)
-                else:
-                    inn = ((nd["lo"] < hi[:, None]) & (nd["hi"] > lo[:, None])).all(axis=0)
-                kids = [int(nd["child"][c]) for c in range(4) if int(nd["child"][c]) != EMPTY and inn[c]]
-                cur = kids[0] if kids else EMPTY
-                for k in reversed(kids[1:]):
-                    stack.append(k)
-                assert len(stack) <= cap
-                mark = max(mark, len(stack))
-            note_high_water(stats, mark)
-            met[i, index[n_leaf:]] = True
-            tests += n_tris - n_leaf
-            met[i, n_tris:] = True                                       # the spheres, after the triangles
-    prims, counts = rows_of_table(acc & met, max_hits, after)
-    return prims, counts, tests
+
+    def bounds(i):
+        return (P[i].min(axis=0), P[i].max(axis=0)) if np.isfinite(P[i]).all() else None
+    return walk_tree(nodes, recs, info, table(queries, rows, edges, spheres, box_step=box_step), bounds, max_hits, after, closed,
+                     stats=stats)
 
 
 # ---- float64, written independently ---------------------------------------------------------------------------------------

@@ -257,6 +257,21 @@ void usage() {
             "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --tri-distance / --spherecast / --focus through the scene's BVH instead of the scan)");
 }
 
+// one region query of the command line: `label count`, then up to k of its prims; false, with the error line, when it fails
+using RegionQuery = bool (rt::RayTracer::*)(const std::vector<float>&, uint32_t, std::vector<int32_t>&, std::vector<uint32_t>&,
+                                            const std::vector<int32_t>&);
+bool print_region(rt::RayTracer& tracer, RegionQuery query, const char* label, const std::vector<float>& queries, uint32_t k) {
+  std::vector<int32_t> prims;
+  std::vector<uint32_t> counts;
+  if (!(tracer.*query)(queries, k, prims, counts, std::vector<int32_t>())) {
+    std::fprintf(stderr, "rt_cli: --%s: %s\n", label, k > RT_MAX_HITS ? "K out of range" : tracer.LastError().c_str());
+    return false;
+  }
+  std::printf("%s %u\n", label, counts[0]);
+  for (uint32_t j = 0; j < k && j < counts[0]; ++j) std::printf("%d\n", prims[j]);
+  return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -494,26 +509,12 @@ int main(int argc, char** argv) {
   if (a.overlap) {
     const float* b = a.overlap_b;
     const std::vector<float> boxes = {b[0], b[1], b[2], 0.0f, b[3], b[4], b[5], 0.0f};
-    std::vector<int32_t> prims;
-    std::vector<uint32_t> counts;
-    if (!tracer.Overlap(boxes, a.overlap_k, prims, counts)) {
-      std::fprintf(stderr, "rt_cli: --overlap: %s\n", a.overlap_k > RT_MAX_HITS ? "K out of range" : tracer.LastError().c_str());
-      return 1;
-    }
-    std::printf("overlap %u\n", counts[0]);
-    for (uint32_t j = 0; j < a.overlap_k && j < counts[0]; ++j) std::printf("%d\n", prims[j]);
+    if (!print_region(tracer, &rt::RayTracer::Overlap, "overlap", boxes, a.overlap_k)) return 1;
   }
   if (a.overlap_tri) {
     const float* c = a.overlap_t;
     const std::vector<float> tris = {c[0], c[1], c[2], 0.0f, c[3], c[4], c[5], 0.0f, c[6], c[7], c[8], 0.0f};
-    std::vector<int32_t> prims;
-    std::vector<uint32_t> counts;
-    if (!tracer.OverlapTriangles(tris, a.overlap_tri_k, prims, counts)) {
-      std::fprintf(stderr, "rt_cli: --overlap-tri: %s\n", a.overlap_tri_k > RT_MAX_HITS ? "K out of range" : tracer.LastError().c_str());
-      return 1;
-    }
-    std::printf("overlap-tri %u\n", counts[0]);
-    for (uint32_t j = 0; j < a.overlap_tri_k && j < counts[0]; ++j) std::printf("%d\n", prims[j]);
+    if (!print_region(tracer, &rt::RayTracer::OverlapTriangles, "overlap-tri", tris, a.overlap_tri_k)) return 1;
   }
   if (a.tri_distance) {
     const float* c = a.tri_distance_t;
@@ -545,14 +546,7 @@ int main(int argc, char** argv) {
     std::vector<float> hexa(32, 0.0f);
     for (int k = 0; k < 8; ++k)
       for (int c = 0; c < 3; ++c) hexa[4 * k + c] = a.overlap_h[3 * k + c];
-    std::vector<int32_t> prims;
-    std::vector<uint32_t> counts;
-    if (!tracer.OverlapHexahedra(hexa, a.overlap_hexa_k, prims, counts)) {
-      std::fprintf(stderr, "rt_cli: --overlap-hexa: %s\n", a.overlap_hexa_k > RT_MAX_HITS ? "K out of range" : tracer.LastError().c_str());
-      return 1;
-    }
-    std::printf("overlap-hexa %u\n", counts[0]);
-    for (uint32_t j = 0; j < a.overlap_hexa_k && j < counts[0]; ++j) std::printf("%d\n", prims[j]);
+    if (!print_region(tracer, &rt::RayTracer::OverlapHexahedra, "overlap-hexa", hexa, a.overlap_hexa_k)) return 1;
   }
   if (a.select) {
     // the frustum between the pinhole rays of the four corner pixels (x0,y0), (x1,y0), (x0,y1), (x1,y1) that holds everything
