@@ -7,8 +7,9 @@ import ctypes as C
 import numpy as np
 
 from occluded_expect import conditioning_matrix
-from query_accel_expect import EMPTY, LEAF, RHO, WELL_CONDITIONED, leaf_span, note_box_arithmetic, note_high_water
+from query_accel_expect import RHO, WELL_CONDITIONED
 from query_expect import HIT_DTYPE
+from tree_walk_expect import EMPTY, keys_of, note_box_arithmetic, note_high_water, ray_slab, walk
 
 INF = np.float32(np.inf)
 MAX_HITS = 16                                                            # RT_MAX_HITS
@@ -247,50 +248,25 @@ def walk_tree_all_hits(orc, nodes, recs, info, segs, rows, max_hits, spheres=Non
             prunes = bool(np.isfinite(segs[i, :6]).all()) and bool((d != 0).any())
             inv = f32(1.0) / d
             omax = np.abs(o).max()
-            stack = []
             seen = {}
-            mark = 0
-            cur = 0 if (nodes.shape[0] and active) else EMPTY
-            while True:
-                if cur == EMPTY:
-                    if not stack:
-                        break
-                    g, cur = stack.pop()
-                    if (g < -t_last()) if strict else (g <= -t_last()):
-                        cur = EMPTY
-                        continue
-                if cur & LEAF:
-                    first, count = leaf_span(cur)
-                    for j in index[first:first + count]:
-                        tests += 1
-                        test(j)
-                    cur = EMPTY
-                    continue
-                nd = nodes[cur]
-                pad = rho * (omax + nd["cmax"])                                   # (4,) float32
-                t1 = ((nd["lo"] - pad) - o[:, None]) * inv[:, None]               # (3, 4)
-                t2 = ((nd["hi"] + pad) - o[:, None]) * inv[:, None]
-                assert t1.dtype == np.float32 and pad.dtype == np.float32
-                nan = (np.isnan(t1) | np.isnan(t2)).any(axis=0)
-                enter = np.fmax.reduce(np.fmin(t1, t2), axis=0)
-                exit_ = np.fmin.reduce(np.fmax(t1, t2), axis=0)
+
+            def stale(g):
+                return (g < -t_last()) if strict else (g <= -t_last())
+
+            def leaf(k):
+                nonlocal tests
+                tests += 1
+                test(index[k])
+
+            def child(nd):
+                enter, exit_, nan, t1, t2 = ray_slab(nd, o, inv, omax, rho)
                 skip = (exit_ < enter) | (exit_ < tmin) | (enter > tmax) | (enter > t_last())
                 if not strict:
                     skip |= (exit_ == tmin) | (enter == tmax) | (enter == t_last())
                 note_box_arithmetic(stats, seen, t1, t2, nd["child"] != EMPTY)
-                decided = prunes & ~nan
-                kids = []
-                for c in range(4):
-                    ref = int(nd["child"][c])
-                    if ref == EMPTY or (decided[c] and skip[c]):
-                        continue
-                    kids.append((np.fmax(-enter[c], -np.finfo(np.float32).max) if decided[c] else inf, ref))
-                kids.sort(key=lambda k: -k[0])
-                cur = kids[0][1] if kids else EMPTY
-                for k in reversed(kids[1:]):
-                    stack.append(k)
-                assert len(stack) <= cap
-                mark = max(mark, len(stack))
+                return keys_of(-enter, prunes & ~nan, skip)
+
+            mark, _ = walk(nodes, cap, active, child, leaf, stale)
             note_high_water(stats, mark)
             if active:
                 for j in index[n_leaf:]:

@@ -5,13 +5,13 @@ the traversal restated over a dumped tree; and the point populations of the test
 deterministic and needs no device."""
 import numpy as np
 
-from query_accel_expect import EMPTY, LEAF, leaf_span, note_high_water, records_of_rows
-from query_expect import HIT_DTYPE
+from query_accel_expect import records_of_rows
+from query_expect import HIT_DTYPE, dot3 as _dot, tri_rows as _rows
+from tree_walk_expect import DEFLATE, box_gap_lb, keys_of, note_high_water, walk  # noqa: F401  (DEFLATE: re-exported)
 
 f32 = np.float32
 INF = f32(np.inf)
 RHO_C = f32(2.0 ** -18)                 # RT_CLOSEST_RHO (csrc/rt_kernels.hpp; DESIGN.md 4.3f)
-DEFLATE = f32(1.0 - 2.0 ** -21)         # the factor on a box's squared gap
 EPS = 2.0 ** -24
 WELL_SHAPED = 2.0 ** -6                 # smallest corner-angle sine of a well-shaped triangle
 # The accuracy statement: sqrt(t) >= D - K eps scale (all triangles), sqrt(t) <= D_ws + K eps scale (well-shaped ones), with
@@ -21,10 +21,6 @@ WELL_SHAPED = 2.0 ** -6                 # smallest corner-angle sine of a well-s
 # rounded up to a power of two.
 K_MEASURED = 14.29
 K = 64.0
-
-
-def _dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
 
 
 def closest_triangle(p, v0, e1, e2):
@@ -183,12 +179,6 @@ def accuracy_sides(pts, rows, edges=False):
 
 # ---- scenes and points ----------------------------------------------------------------------------------------------------
 
-def _rows(tris):
-    r = np.zeros((len(tris), 3, 4), f32)
-    r[:, :, :3] = tris
-    return r.reshape(-1, 4)
-
-
 def random_scene(n_tris, seed, offset=(0.0, 0.0, 0.0), size=0.6):
     """n_tris triangles in general position, centres uniform in [-3, 3]^3 + offset."""
     rng = np.random.default_rng(seed)
@@ -311,7 +301,6 @@ def walk_tree_closest(nodes, recs, info, pts, rows, edges=False, spheres=None, r
     out = np.zeros(pts.shape[0], HIT_DTYPE)
     tests = 0
     cap = 3 * max(info["depth"], 1)
-    zero = f32(0)
     with np.errstate(all="ignore"):
         for i in range(pts.shape[0]):
             p, d2max = pts[i, :3], pts[i, 3]
@@ -327,43 +316,20 @@ def walk_tree_closest(nodes, recs, info, pts, rows, edges=False, spheres=None, r
 
             finite = bool(np.isfinite(p).all())
             pmax = np.abs(p).max()
-            stack = []
-            mark = 0
-            cur = 0 if nodes.shape[0] else EMPTY
-            while True:
-                if cur == EMPTY:
-                    if not stack:
-                        break
-                    g, cur = stack.pop()
-                    if (g < -state["t"]) if strict else (g <= -state["t"]):
-                        cur = EMPTY
-                        continue
-                if cur & LEAF:
-                    first, count = leaf_span(cur)
-                    for j in index[first:first + count]:
-                        tests += 1
-                        keep(T[i, j], j)
-                    cur = EMPTY
-                    continue
-                nd = nodes[cur]
-                pad = rho_c * (pmax + nd["cmax"])                                              # (4,) float32
-                gap = np.fmax(np.fmax(np.fmax(nd["lo"] - p[:, None], p[:, None] - nd["hi"]), zero) - pad, zero)   # (3, 4)
-                lb = ((gap[0] * gap[0] + gap[1] * gap[1]) + gap[2] * gap[2]) * DEFLATE
-                assert lb.dtype == f32 and pad.dtype == f32
-                decided = finite & ~np.isnan(lb)
-                skip = (lb > state["t"]) if strict else (lb >= state["t"])
-                kids = []
-                for c in range(4):
-                    ref = int(nd["child"][c])
-                    if ref == EMPTY or (decided[c] and skip[c]):
-                        continue
-                    kids.append((np.fmax(-lb[c], -np.finfo(f32).max) if decided[c] else INF, ref))
-                kids.sort(key=lambda k: -k[0])
-                cur = kids[0][1] if kids else EMPTY
-                for k in reversed(kids[1:]):
-                    stack.append(k)
-                assert len(stack) <= cap
-                mark = max(mark, len(stack))
+
+            def stale(g):
+                return (g < -state["t"]) if strict else (g <= -state["t"])
+
+            def leaf(k):
+                nonlocal tests
+                tests += 1
+                keep(T[i, index[k]], index[k])
+
+            def child(nd):                                               # skipped where its entry would be stale at once
+                lb = box_gap_lb(nd, p, p, pmax, rho_c)
+                return keys_of(-lb, finite & ~np.isnan(lb), stale(-lb))
+
+            mark, _ = walk(nodes, cap, True, child, leaf, stale)
             note_high_water(stats, mark)
             for j in index[n_leaf:]:
                 tests += 1

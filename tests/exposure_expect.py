@@ -3,6 +3,8 @@ float32 operation for operation, the segments the query traces, the packing of p
 unit box with the analytic rule of which directions leave it."""
 import numpy as np
 
+from query_expect import tri_rows as _rows
+
 F32 = np.float32
 ONE = F32(1.0)
 
@@ -68,12 +70,6 @@ def unpack_masks(masks, k=64):
 
 def popcount(masks):
     return np.unpackbits(np.ascontiguousarray(masks, np.uint64).view(np.uint8).reshape(-1, 8), axis=1).sum(axis=1)
-
-
-def _rows(v):
-    r = np.zeros((len(v), 3, 4), F32)
-    r[:, :, :3] = v
-    return r.reshape(-1, 4)
 
 
 def open_box(double_sided=True):

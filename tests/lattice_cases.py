@@ -9,7 +9,7 @@ import numpy as np
 
 from occluded_expect import with_interval
 from query_accel_expect import EMPTY, RHO, populations
-from query_expect import HIT_DTYPE, expected_hits
+from query_expect import HIT_DTYPE, expected_hits, tri_rows as _rows
 
 INF = np.float32(np.inf)
 SHIFT = 1.75                                   # the walls lie on k - SHIFT: the world origin is a quarter point of a cell
@@ -20,12 +20,6 @@ FACE_DIAGONALS = [tuple(float(v) for v in (x, y, z)) for x in (-1, 0, 1) for y i
                   if abs(x) + abs(y) + abs(z) == 2]
 SPACE_DIAGONALS = [(float(x), float(y), float(z)) for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)]
 DIRECTIONS = np.float32(AXES + FACE_DIAGONALS + SPACE_DIAGONALS)               # 6 + 12 + 8, each with its opposite
-
-
-def _rows(v):
-    r = np.zeros((len(v), 3, 4), np.float32)
-    r[:, :, :3] = v
-    return r.reshape(-1, 4)
 
 
 # ---- the scenes ---------------------------------------------------------------------------------------------------------

@@ -5,8 +5,8 @@ helper, not a test.  Everything is deterministic and needs no device."""
 import numpy as np
 
 import closest_expect as ce
-from query_accel_expect import EMPTY, LEAF, leaf_span, note_high_water
 from query_expect import HIT_DTYPE
+from tree_walk_expect import box_gap_lb, keys_of, note_high_water, walk
 
 f32 = np.float32
 INF = ce.INF
@@ -161,7 +161,6 @@ def walk_tree_nearest(nodes, recs, info, pts, rows, max_hits, after=None, edges=
     cur_p = None if after is None else np.asarray(after)["prim"].astype(np.int64)
     tests = 0
     cap = 3 * max(info["depth"], 1)
-    zero = f32(0)
     with np.errstate(all="ignore"):
         for i in range(pts.shape[0]):
             p, d2max = pts[i, :3], pts[i, 3]
@@ -193,44 +192,20 @@ def walk_tree_nearest(nodes, recs, info, pts, rows, max_hits, after=None, edges=
 
             finite = bool(np.isfinite(p).all())
             pmax = np.abs(p).max()
-            stack = []
-            mark = 0
-            cur = 0 if nodes.shape[0] else EMPTY
-            while True:
-                if cur == EMPTY:
-                    if not stack:
-                        break
-                    g, cur = stack.pop()
-                    if (g < -bound()) if strict else (g <= -bound()):
-                        cur = EMPTY
-                        continue
-                if cur & LEAF:
-                    first, count = leaf_span(cur)
-                    for j in index[first:first + count]:
-                        tests += 1
-                        keep(T[i, j], j)
-                    cur = EMPTY
-                    continue
-                nd = nodes[cur]
-                pad = rho_c * (pmax + nd["cmax"])                                              # (4,) float32
-                gap = np.fmax(np.fmax(np.fmax(nd["lo"] - p[:, None], p[:, None] - nd["hi"]), zero) - pad, zero)   # (3, 4)
-                lb = ((gap[0] * gap[0] + gap[1] * gap[1]) + gap[2] * gap[2]) * ce.DEFLATE
-                assert lb.dtype == f32 and pad.dtype == f32
-                decided = finite & ~np.isnan(lb)
-                b = bound()
-                skip = (lb > b) if strict else (lb >= b)
-                kids = []
-                for c in range(4):
-                    ref = int(nd["child"][c])
-                    if ref == EMPTY or (decided[c] and skip[c]):
-                        continue
-                    kids.append((np.fmax(-lb[c], -np.finfo(f32).max) if decided[c] else INF, ref))
-                kids.sort(key=lambda k: -k[0])
-                cur = kids[0][1] if kids else EMPTY
-                for k in reversed(kids[1:]):
-                    stack.append(k)
-                assert len(stack) <= cap
-                mark = max(mark, len(stack))
+
+            def stale(g):
+                return (g < -bound()) if strict else (g <= -bound())
+
+            def leaf(k):
+                nonlocal tests
+                tests += 1
+                keep(T[i, index[k]], index[k])
+
+            def child(nd):                                               # skipped where its entry would be stale at once
+                lb = box_gap_lb(nd, p, p, pmax, rho_c)
+                return keys_of(-lb, finite & ~np.isnan(lb), stale(-lb))
+
+            mark, _ = walk(nodes, cap, True, child, leaf, stale)
             note_high_water(stats, mark)
             for j in index[n_leaf:]:
                 tests += 1

@@ -6,7 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from query_accel_expect import EMPTY, LEAF, RHO, WELL_CONDITIONED, leaf_span, note_box_arithmetic, note_high_water, records_of_rows
+from query_accel_expect import RHO, WELL_CONDITIONED, records_of_rows
+from tree_walk_expect import EMPTY, keys_of, note_box_arithmetic, note_high_water, ray_slab, walk
 
 INF = np.float32(np.inf)
 
@@ -139,8 +140,9 @@ def walk_tree_occluded(orc, nodes, recs, info, segs, rows, spheres=None, contrac
     HitTriangle on the leaves' triangles (absolute rows).  The order of the visits does not change an OR, so the children are
     entered as stored.  Returns ((n,) bool, triangle tests made).  strict=False (for tests of the tests) also skips a child whose
     exit EQUALS tmin or whose enter EQUALS tmax; stats: a dict that receives note_box_arithmetic's counters and
-    note_high_water's marks -- the entries that WAIT: the kernel enters one of a node's children at once and stacks the others,
-    this walk stacks them all and pops one, so the child it pops next is not counted.  kernel_order: the children are entered
+    note_high_water's marks -- the entries that WAIT: one of a node's children is entered at once and the others are stacked.
+    "As stored" is the order of a walk that stacks all of a node's children slot by slot and pops one: the LAST stored slot is
+    entered first, which tree_walk_expect.walk gives with the slot as the key.  kernel_order: the children are entered
     in the kernel's order -- the largest overlap of the child's span with the interval first, +inf where nothing is decided --
     which is what the marks of a device lane follow; the answer is the same OR."""
     contract = orc.FMA if contract is None else contract
@@ -179,44 +181,26 @@ def walk_tree_occluded(orc, nodes, recs, info, segs, rows, spheres=None, contrac
             prunes = bool(np.isfinite(segs[i, :6]).all()) and bool((d != 0).any())
             inv = f32(1.0) / d
             omax = np.abs(o).max()
-            stack = [0] if nodes.shape[0] else []
             seen = {}
-            mark = 0
-            while stack and not done:
-                cur = stack.pop()
-                if cur & LEAF:
-                    first, count = leaf_span(cur)
-                    for j in index[first:first + count]:
-                        tests += 1
-                        if test(j):
-                            done = True
-                            break
-                    continue
-                nd = nodes[cur]
-                pad = rho * (omax + nd["cmax"])                                   # (4,) float32
-                t1 = ((nd["lo"] - pad) - o[:, None]) * inv[:, None]               # (3, 4)
-                t2 = ((nd["hi"] + pad) - o[:, None]) * inv[:, None]
-                assert t1.dtype == np.float32 and pad.dtype == np.float32
-                nan = (np.isnan(t1) | np.isnan(t2)).any(axis=0)
-                enter = np.fmax.reduce(np.fmin(t1, t2), axis=0)
-                exit_ = np.fmin.reduce(np.fmax(t1, t2), axis=0)
+
+            def leaf(k):
+                nonlocal tests, done
+                tests += 1
+                done = test(index[k])
+                return done
+
+            def child(nd):
+                enter, exit_, nan, t1, t2 = ray_slab(nd, o, inv, omax, rho)
                 skip = (exit_ < enter) | (exit_ < tmin) | (enter > tmax)
                 if not strict:
                     skip |= (exit_ == tmin) | (enter == tmax)
                 note_box_arithmetic(stats, seen, t1, t2, nd["child"] != EMPTY)
                 decided = prunes & ~nan
-                below = len(stack)
-                kids = [c for c in range(4) if int(nd["child"][c]) != EMPTY and not (decided[c] and skip[c])]
-                if kernel_order:
-                    good = np.where(decided, np.fmax(np.fmin(exit_, tmax) - np.fmax(enter, tmin), -np.finfo(f32).max), INF)
-                    kids.sort(key=lambda c: -good[c])                    # (stable: equal overlaps stay in slot order)
-                    kids.reverse()                                       # the best on top
-                for c in kids:
-                    stack.append(int(nd["child"][c]))
-                assert len(stack) <= cap + 3
-                waiting = len(stack) - (1 if len(stack) > below else 0)
-                assert waiting <= cap
-                mark = max(mark, waiting)
+                if kernel_order:                                         # (equal overlaps are entered in slot order)
+                    return keys_of(np.fmin(exit_, tmax) - np.fmax(enter, tmin), decided, skip)
+                return [None if (decided[c] and skip[c]) else f32(c) for c in range(4)]      # the slot is the key: the last first
+
+            mark, _ = walk(nodes, cap, not done, child, leaf)
             note_high_water(stats, mark)
             out[i] = done
     return out, tests

@@ -5,7 +5,9 @@ separating-axis test with per-axis margins; and the box populations of the tests
 deterministic and needs no device."""
 import numpy as np
 
-from query_accel_expect import EMPTY, LEAF, leaf_span, note_high_water, records_of_rows
+from query_accel_expect import records_of_rows
+from query_expect import cross3 as _cross, dot3 as _dot, tri_rows as _rows
+from tree_walk_expect import note_high_water, walk
 
 f32 = np.float32
 INF = f32(np.inf)
@@ -20,14 +22,6 @@ HALF = f32(0.5)
 # corner, c and the difference: three roundings of at most EPS * scale each), f (two), two products and a difference (three
 # more, relative), and r likewise; each moves p / |f| by at most EPS * scale, and p and r together make 16.
 K = 16.0
-
-
-def _dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
-def _cross(a, b):
-    return [a[1] * b[2] - b[1] * a[2], a[2] * b[0] - b[2] * a[0], a[0] * b[1] - b[0] * a[1]]
 
 
 def boxes_of(lo, hi):
@@ -186,35 +180,21 @@ def walk_tree(nodes, recs, info, acc, bounds, max_hits, after=None, closed=True,
                 note_high_water(stats, 0)
                 continue
             lo, hi = box
-            stack, mark, overflow = [], 0, False
-            cur = 0 if nodes.shape[0] else EMPTY
-            while True:
-                if cur == EMPTY:
-                    if not stack:
-                        break
-                    cur = stack.pop()
-                if cur & LEAF:
-                    first, count = leaf_span(cur)
-                    for j in index[first:first + count]:
-                        assert not met[i, j]                             # a walk visits every record at most once
-                        met[i, j] = True
-                        tests += 1
-                    cur = EMPTY
-                    continue
-                nd = nodes[cur]
+
+            def leaf(k):
+                nonlocal tests
+                assert not met[i, index[k]]                              # a walk visits every record at most once
+                met[i, index[k]] = True
+                tests += 1
+
+            def child(nd):                                               # no key decides: the children are entered as stored
                 if closed:
                     inn = ((nd["lo"] <= hi[:, None]) & (nd["hi"] >= lo[:, None])).all(axis=0)
                 else:
                     inn = ((nd["lo"] < hi[:, None]) & (nd["hi"] > lo[:, None])).all(axis=0)
-                kids = [int(nd["child"][c]) for c in range(4) if int(nd["child"][c]) != EMPTY and inn[c]]
-                cur = kids[0] if kids else EMPTY
-                for k in reversed(kids[1:]):
-                    if len(stack) < cap:
-                        stack.append(k)
-                    else:
-                        overflow = True
-                assert stack_cap is not None or not overflow             # 3 * depth entries always suffice
-                mark = max(mark, len(stack))
+                return [INF if inn[c] else None for c in range(4)]
+
+            mark, overflow = walk(nodes, cap, True, child, leaf, enforce_cap=stack_cap is None)     # 3 * depth entries always suffice
             note_high_water(stats, mark)
             if overflow:                                                 # from an empty list and count: every leaf record
                 met[i, :n_tris] = False
@@ -275,12 +255,6 @@ def sat64(boxes, rows, edges=False):
 
 
 # ---- scenes and boxes --------------------------------------------------------------------------------------------------------
-
-def _rows(tris):
-    r = np.zeros((len(tris), 3, 4), f32)
-    r[:, :, :3] = tris
-    return r.reshape(-1, 4)
-
 
 def random_scene(n_tris, seed, edge=0.2, span=1.0, snap=None):
     """n_tris triangles of edge about `edge` with centres uniform in [-span, span]^3; snap: every coordinate rounded to a multiple

@@ -6,11 +6,11 @@ import ctypes as C
 import numpy as np
 
 from query_expect import FLT_MAX, HIT_DTYPE
+from tree_walk_expect import EMPTY, LEAF, keys_of, leaf_span, note_box_arithmetic, note_high_water, ray_slab, walk  # noqa: F401  (re-exported)
 
 RHO = np.float32(2.0 ** -8)            # RT_BVH_RHO (csrc/rt_kernels.hpp)
 WELL_CONDITIONED = 2.0 ** -10          # the contract's bound on det / (|d| |e1| |e2|), include/rt_mi355x.h
 EXCLUSION_CAP = 1e-3                   # at most this fraction of a population may use the exclusion
-EMPTY, LEAF = 0xFFFFFFFF, 0x80000000
 
 
 def records_of_rows(rows, edges=False):
@@ -71,10 +71,6 @@ def populations(rows, n, seed):
 
 # ---- the dumped tree ----------------------------------------------------------------------------------------------------
 
-def leaf_span(ref):
-    return int(ref & 0x0FFFFFFF), int((ref >> 28) & 3) + 1
-
-
 def check_tree(nodes, recs, info, rows, edges=False):
     """Every finite triangle in exactly one leaf with its upload index, the non-finite ones only in the always-tested list;
     every leaf box holds its records' corners (float64); every child box lies inside its parent's; depth within the bound."""
@@ -132,29 +128,6 @@ def check_tree(nodes, recs, info, rows, edges=False):
 
 # ---- the traversal's box test, restated -----------------------------------------------------------------------------------
 
-def note_box_arithmetic(stats, seen, t1, t2, present):
-    """Into the dict `stats` of a walk (if given): which branches of the box test this node's present children reach.  seen is
-    the ray's own {"nan": bool, "inf": bool}; stats counts rays ("nan_rays", "inf_rays") and child boxes ("nan_boxes",
-    "inf_boxes") whose t1, t2 hold a NaN (0 * inf: the ray runs inside a slab's plane) or an infinity (parallel, outside)."""
-    if stats is None or (np.isfinite(t1).all() and np.isfinite(t2).all()):
-        return
-    for key, bad in (("nan", np.isnan(t1) | np.isnan(t2)), ("inf", np.isinf(t1) | np.isinf(t2))):
-        boxes = int((bad.any(axis=0) & present).sum())
-        stats[key + "_boxes"] = stats.get(key + "_boxes", 0) + boxes
-        if boxes and not seen.get(key):
-            seen[key] = True
-            stats[key + "_rays"] = stats.get(key + "_rays", 0) + 1
-
-
-def note_high_water(stats, mark):
-    """Into the dict `stats` of a walk (if given): `mark`, the largest number of entries this ray's or point's stack held, is
-    appended to stats["high_water_per"] (one per ray or point, in order; 0 for one that never walks), and stats["high_water"]
-    is the largest of them.  A kernel lane whose capacity is below its mark takes the overflow path."""
-    if stats is not None:
-        stats.setdefault("high_water_per", []).append(int(mark))
-        stats["high_water"] = max(stats.get("high_water", 0), int(mark))
-
-
 def walk_tree(orc, nodes, recs, info, rays, rows, contract=None, nearest=False, rho=RHO, tie_rule=True, strict=True, stats=None):
     """query_bvh_kernel in numpy: the fp32 box test of csrc/rt_bvh.hpp operation by operation, the order-free hit rule, the
     oracle's HitTriangle on the leaves' triangles (absolute rows).  Returns (HIT_DTYPE array, triangle tests made).
@@ -170,7 +143,7 @@ def walk_tree(orc, nodes, recs, info, rays, rows, contract=None, nearest=False, 
     index = recs["index"].astype(np.int64)
     out = np.zeros(rays.shape[0], HIT_DTYPE)
     t, u, v = C.c_float(), C.c_float(), C.c_float()
-    f32, inf = np.float32, np.float32(np.inf)
+    f32 = np.float32
     tests = 0
     cap = 3 * max(info["depth"], 1)
     with np.errstate(all="ignore"):
@@ -192,51 +165,27 @@ def walk_tree(orc, nodes, recs, info, rays, rows, contract=None, nearest=False, 
                 if better or (tie_rule and tj == state["t"] and j < state["i"]):
                     state.update(t=tj, i=int(j), u=f32(u.value), v=f32(v.value))
 
-            stack = []
             seen = {}
-            mark = 0
-            cur = 0 if nodes.shape[0] else EMPTY
-            while True:
-                if cur == EMPTY:
-                    if not stack:
-                        break
-                    g, cur = stack.pop()
-                    lim = -state["t"] if nearest else state["t"]
-                    if (g < lim) if strict else (g <= lim):
-                        cur = EMPTY
-                        continue
-                if cur & LEAF:
-                    first, count = leaf_span(cur)
-                    for j in index[first:first + count]:
-                        tests += 1
-                        test(j)
-                    cur = EMPTY
-                    continue
-                nd = nodes[cur]
-                pad = rho * (omax + nd["cmax"])                                   # (4,) float32
-                t1 = ((nd["lo"] - pad) - o[:, None]) * inv[:, None]               # (3, 4)
-                t2 = ((nd["hi"] + pad) - o[:, None]) * inv[:, None]
-                assert t1.dtype == np.float32 and pad.dtype == np.float32
-                nan = (np.isnan(t1) | np.isnan(t2)).any(axis=0)
-                enter = np.fmax.reduce(np.fmin(t1, t2), axis=0)
-                exit_ = np.fmin.reduce(np.fmax(t1, t2), axis=0)
+
+            def lim():
+                return -state["t"] if nearest else state["t"]
+
+            def stale(g):
+                return (g < lim()) if strict else (g <= lim())
+
+            def leaf(k):
+                nonlocal tests
+                tests += 1
+                test(index[k])
+
+            def child(nd):
+                enter, exit_, nan, t1, t2 = ray_slab(nd, o, inv, omax, rho)
                 good = -enter if nearest else exit_
-                lim = -state["t"] if nearest else state["t"]
-                skip = (exit_ < enter) | ((good < lim) if strict else (good <= lim)) | (nearest & (exit_ <= 0))
+                skip = (exit_ < enter) | stale(good) | (nearest & (exit_ <= 0))
                 note_box_arithmetic(stats, seen, t1, t2, nd["child"] != EMPTY)
-                decided = finite & ~nan
-                kids = []
-                for c in range(4):
-                    ref = int(nd["child"][c])
-                    if ref == EMPTY or (decided[c] and skip[c]):
-                        continue
-                    kids.append((np.fmax(good[c], -FLT_MAX) if decided[c] else inf, ref))
-                kids.sort(key=lambda k: -k[0])
-                cur = kids[0][1] if kids else EMPTY
-                for k in reversed(kids[1:]):
-                    stack.append(k)
-                assert len(stack) <= cap
-                mark = max(mark, len(stack))
+                return keys_of(good, finite & ~nan, skip)
+
+            mark, _ = walk(nodes, cap, True, child, leaf, stale)
             note_high_water(stats, mark)
             for j in index[n_leaf:]:
                 tests += 1

@@ -8,6 +8,23 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), (
 FLT_MAX = np.float32(np.finfo(np.float32).max)
 
 
+def tri_rows(tris):
+    """(n, 3, 3) triangles as (3n, 4) float32 upload rows."""
+    r = np.zeros((len(tris), 3, 4), np.float32)
+    r[:, :, :3] = tris
+    return r.reshape(-1, 4)
+
+
+def dot3(a, b):
+    """a . b of two triples of broadcastable arrays, as the kernels round it: (a0 b0 + a1 b1) + a2 b2."""
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def cross3(a, b):
+    """a x b of two triples of broadcastable arrays, each component two separately rounded products and a difference."""
+    return [a[1] * b[2] - b[1] * a[2], a[2] * b[0] - b[2] * a[0], a[0] * b[1] - b[0] * a[1]]
+
+
 def expected_hits(orc, rays, tri_rows, spheres=None, contract=None, nearest=False):
     """The farthest-hit (or nearest t > 0) scan of Kernels.cuh:73-92 for rays (n, 6) against absolute triangle rows
     (3N, 4) then spheres (M, 4): triangles in order, then spheres, strict comparisons (first scanned wins ties).

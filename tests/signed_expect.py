@@ -7,6 +7,7 @@ import numpy as np
 
 import closest_expect as ce
 from query_accel_expect import records_of_rows
+from query_expect import dot3 as _dot, tri_rows as _rows
 
 f32 = np.float32
 SIDE_DTYPE = np.dtype([("s", np.float32), ("feature", np.int32)])
@@ -71,10 +72,6 @@ def feature_table64(rows, edges=False):
 
 # ---- the side arithmetic, float32 ---------------------------------------------------------------------------------------------
 
-def _dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
 def sides_of(pts, prim, rows, table, edges=False, spheres=None, normal_of=None):
     """rt_side of (point i, primitive prim[i]): pts (n, >=3), prim (n,) int -> SIDE_DTYPE (n,).  The triangle rule of
     closest_expect.closest_triangle gives u, v and the region; r = (ap - u*e1) - v*e2 and s = (r.x*N.x + r.y*N.y) + r.z*N.z in
@@ -131,12 +128,6 @@ def face_normal_of(table):
 
 
 # ---- meshes -------------------------------------------------------------------------------------------------------------------
-
-def _rows(tris):
-    r = np.zeros((len(tris), 3, 4), f32)
-    r[:, :, :3] = tris
-    return r.reshape(-1, 4)
-
 
 def _prism(poly, cap_tris, z0, z1):
     """A closed prism over a counter-clockwise polygon, wound outward: caps from cap_tris (index triples, counter-clockwise),

@@ -7,7 +7,7 @@ import numpy as np
 
 import closest_expect as ce
 from query_accel_expect import records_of_rows
-from query_expect import HIT_DTYPE
+from query_expect import HIT_DTYPE, cross3 as _cross, dot3 as _dot
 
 f32 = np.float32
 INF = f32(np.inf)
@@ -20,14 +20,6 @@ RHO_S = f32(2.0 ** -16)                 # RT_SWEEP_RHO (csrc/rt_kernels.hpp)
 RESIDUAL_MEASURED = 7.67e-05
 DROP_BOUND = {"general r=0.1": 0.0, "general r=0.001": 0.0, "sliver": 0.008, "grazing": 0.0, "far origin": 0.0}
 FEATURES = ("start", "face", "edge AB", "edge AC", "edge BC", "vertex A", "vertex B", "vertex C")
-
-
-def _dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
-def _cross(a, b):
-    return [a[1] * b[2] - b[1] * a[2], a[2] * b[0] - b[2] * a[0], a[0] * b[1] - b[0] * a[1]]
 
 
 def _sub(a, b):

@@ -5,13 +5,7 @@ import numpy as np
 import pytest
 
 from query_accel_expect import check_against_scan, check_tree, walk_tree
-from query_expect import adversarial_rays, adversarial_scene, edge_rows, expected_hits
-
-
-def _rows(v):
-    r = np.zeros((len(v), 3, 4), np.float32)
-    r[:, :, :3] = v
-    return r.reshape(-1, 4)
+from query_expect import adversarial_rays, adversarial_scene, edge_rows, expected_hits, tri_rows as _rows
 
 
 def _slivers(n, seed):

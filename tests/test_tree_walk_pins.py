@@ -1,0 +1,121 @@
+"""The seven restated tree walks, pinned without a device: on the lattice scene and on a random scene of 100 triangles each walk's
+outputs (as a SHA-256 of their bytes), its count of records tested and every query's stack high-water mark are compared with
+tests/golden/tree_walk_pins.json.  The file was recorded from the walks as they stood BEFORE they were moved onto
+tree_walk_expect.walk (its "recorded_from" names the commit), so a change of the shared walk that alters a visiting order, a
+prune or a mark shows here in seven places at once, next to the one that was meant."""
+import hashlib
+import json
+import os
+
+import numpy as np
+import pytest
+
+import closest_expect as ce
+import lattice_cases as lc
+import nearest_expect as ne
+import overlap_expect as oe
+import tridistance_expect as td
+from allhits_expect import walk_tree_all_hits
+from occluded_expect import walk_tree_occluded
+from query_accel_expect import populations, walk_tree
+from query_expect import adversarial_rays
+
+f32 = np.float32
+INF = f32(np.inf)
+PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tree_walk_pins.json")
+SCENES = ("rooms", "random100")
+N = 64                                          # queries per walk, at most
+_cache = {}
+
+
+def _first(a, n=N):
+    """n rows of a, evenly spread."""
+    return np.ascontiguousarray(a[np.linspace(0, a.shape[0] - 1, min(n, a.shape[0])).astype(np.int64)])
+
+
+def scene(name):
+    """The scene, its tree, one sphere the queries can reach, and at most N rays, segments, points, triangles and boxes."""
+    if name in _cache:
+        return _cache[name]
+    from raytracertest_amd import api
+    if name == "rooms":
+        rows = lc.rooms()
+        rays = _first(np.concatenate([lc.axis_rays(4), lc.in_plane_rays(4), lc.vertex_rays(4)]))
+        c = {"points": _first(ce.lattice_points()), "triangles": _first(td.lattice_queries()),
+             "boxes": _first(oe.touching_boxes(rows, range(0, rows.shape[0] // 3, 7))[0]), "sphere": f32([[0.25, 0.25, 0.25, 0.5]])}
+    else:
+        rows = ce.random_scene(100, 61)
+        rays = np.concatenate([_first(np.concatenate(list(populations(rows, 16, 62).values())), 48), _first(adversarial_rays(rows, 0, 63), 16)])
+        c = {"points": ce.points_for(rows, N, 64), "triangles": td.mixed_queries(rows, 48, 65),
+             "boxes": oe.random_boxes(rows, N, 66, width=1.5), "sphere": f32([[0.5, 0.3, -1.0, 0.8]])}
+    c.update(rows=rows, tree=api.bvh_build(rows), rays=rays, segs=lc.ray_segments(rays), points=ce.with_radius(c["points"], INF))
+    assert all(c[k].shape[0] <= N for k in ("rays", "segs", "points", "triangles", "boxes")) and c["tree"][0].shape[0] > 1
+    _cache[name] = c
+    return c
+
+
+def _region(c, stats, stack_cap=None):
+    """overlap_expect.walk_tree as walk_tree_overlap calls it, with a stack_cap."""
+    boxes = c["boxes"]
+
+    def bounds(i):
+        lo, hi = boxes[i, 0:3], boxes[i, 4:7]
+        return (lo, hi) if (lo <= hi).all() else None
+    return oe.walk_tree(*c["tree"], oe.table(boxes, c["rows"], spheres=c["sphere"]), bounds, 16, stack_cap=stack_cap, stats=stats)
+
+
+WALKS = {
+    "intersect farthest": lambda orc, c, st: walk_tree(orc, *c["tree"], c["rays"], c["rows"], stats=st),
+    "intersect nearest": lambda orc, c, st: walk_tree(orc, *c["tree"], c["rays"], c["rows"], nearest=True, stats=st),
+    "all_hits 4": lambda orc, c, st: walk_tree_all_hits(orc, *c["tree"], c["segs"], c["rows"], 4, c["sphere"], stats=st),
+    "occluded as stored": lambda orc, c, st: walk_tree_occluded(orc, *c["tree"], c["segs"], c["rows"], c["sphere"], stats=st),
+    "occluded kernel_order": lambda orc, c, st: walk_tree_occluded(orc, *c["tree"], c["segs"], c["rows"], c["sphere"], stats=st,
+                                                                   kernel_order=True),
+    "closest": lambda orc, c, st: ce.walk_tree_closest(*c["tree"], c["points"], c["rows"], spheres=c["sphere"], stats=st),
+    "nearest 4": lambda orc, c, st: ne.walk_tree_nearest(*c["tree"], c["points"], c["rows"], 4, spheres=c["sphere"], stats=st),
+    "tridistance": lambda orc, c, st: td.walk_tree_tridistance(*c["tree"], c["triangles"], c["rows"], spheres=c["sphere"], stats=st),
+    "region": lambda orc, c, st: _region(c, st),
+    "region stack_cap 1": lambda orc, c, st: _region(c, st, stack_cap=1),
+}
+
+
+def _arrays(x):
+    return [b for y in x for b in _arrays(y)] if isinstance(x, (tuple, list)) else [np.ascontiguousarray(x).tobytes()]
+
+
+def compute(orc, name, walk):
+    """One case as the file holds it: {"sha256": of the outputs' bytes in order, "tests", "high_water_per"}."""
+    stats = {}
+    with np.errstate(all="ignore"):
+        *outs, tests = WALKS[walk](orc, scene(name), stats)
+    return {"sha256": hashlib.sha256(b"".join(_arrays(outs))).hexdigest(), "tests": int(tests),
+            "high_water_per": [int(m) for m in stats["high_water_per"]]}
+
+
+@pytest.fixture(scope="module")
+def pins():
+    with open(PINS) as f:
+        doc = json.load(f)
+    assert doc["recorded_from"] and sorted(doc["cases"]) == sorted("%s / %s" % (s, w) for s in SCENES for w in WALKS)
+    return doc["cases"]
+
+
+@pytest.mark.parametrize("walk", list(WALKS))
+@pytest.mark.parametrize("name", SCENES)
+def test_a_walk_gives_the_recorded_outputs_tests_and_marks(orc, pins, name, walk):
+    want = pins["%s / %s" % (name, walk)]
+    got = compute(orc, name, walk)
+    assert got["tests"] == want["tests"] and got["high_water_per"] == want["high_water_per"]
+    assert got["sha256"] == want["sha256"]
+
+
+def test_the_pinned_cases_push_tie_and_overflow(pins):
+    """What the cases are for: every walk holds waiting entries on both scenes, the lowered capacity is below the region walk's
+    mark (so some walk drops an entry and starts again: more records tested), and the two any-hit orders differ somewhere."""
+    for label, case in pins.items():
+        assert max(case["high_water_per"]) >= (1 if "stack_cap" in label else 2), label
+    for name in SCENES:
+        assert max(pins[name + " / region"]["high_water_per"]) > 1
+        assert pins[name + " / region stack_cap 1"]["tests"] > pins[name + " / region"]["tests"]
+        a, b = pins[name + " / occluded as stored"], pins[name + " / occluded kernel_order"]
+        assert (a["tests"], a["high_water_per"]) != (b["tests"], b["high_water_per"])

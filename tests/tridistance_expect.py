@@ -12,8 +12,9 @@ import numpy as np
 import closest_expect as ce
 import trioverlap_expect as te
 from overlap_expect import corners
-from query_accel_expect import EMPTY, LEAF, leaf_span, note_high_water, records_of_rows
-from query_expect import HIT_DTYPE
+from query_accel_expect import records_of_rows
+from query_expect import HIT_DTYPE, cross3 as _cross, dot3 as _dot
+from tree_walk_expect import box_gap_lb, keys_of, note_high_water, walk
 
 f32 = np.float32
 INF = f32(np.inf)
@@ -28,14 +29,6 @@ EPS = 2.0 ** -24
 # up to a power of two.
 K_MEASURED = 1.983
 K = 8.0
-
-
-def _dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
-def _cross(a, b):
-    return [a[1] * b[2] - b[1] * a[2], a[2] * b[0] - b[2] * a[0], a[0] * b[1] - b[0] * a[1]]
 
 
 def _sub(a, b):
@@ -310,7 +303,6 @@ def walk_tree_tridistance(nodes, recs, info, queries, rows, edges=False, spheres
     wit = np.zeros(queries.shape[0], WITNESS_DTYPE)
     tests = 0
     cap = 3 * max(info["depth"], 1)
-    zero = f32(0)
     with np.errstate(all="ignore"):
         for i in range(queries.shape[0]):
             d2max = queries[i, 3]
@@ -327,43 +319,20 @@ def walk_tree_tridistance(nodes, recs, info, queries, rows, edges=False, spheres
             qmin = np.fmin(np.fmin(P[i, 0], P[i, 1]), P[i, 2])
             qmax = np.fmax(np.fmax(P[i, 0], P[i, 1]), P[i, 2])
             qabs = np.abs(P[i]).max()
-            stack = []
-            mark = 0
-            cur = 0 if nodes.shape[0] else EMPTY
-            while True:
-                if cur == EMPTY:
-                    if not stack:
-                        break
-                    g, cur = stack.pop()
-                    if (g < -state["t"]) if strict else (g <= -state["t"]):
-                        cur = EMPTY
-                        continue
-                if cur & LEAF:
-                    first, count = leaf_span(cur)
-                    for j in index[first:first + count]:
-                        tests += 1
-                        keep(T[i, j], j)
-                    cur = EMPTY
-                    continue
-                nd = nodes[cur]
-                pad = rho_c * (qabs + nd["cmax"])                                                         # (4,) float32
-                gap = np.fmax(np.fmax(np.fmax(nd["lo"] - qmax[:, None], qmin[:, None] - nd["hi"]), zero) - pad, zero)   # (3, 4)
-                lb = ((gap[0] * gap[0] + gap[1] * gap[1]) + gap[2] * gap[2]) * ce.DEFLATE
-                assert lb.dtype == f32 and pad.dtype == f32
-                decided = ~np.isnan(lb)
-                skip = (lb > state["t"]) if strict else (lb >= state["t"])
-                kids = []
-                for c in range(4):
-                    ref = int(nd["child"][c])
-                    if ref == EMPTY or (decided[c] and skip[c]):
-                        continue
-                    kids.append((np.fmax(-lb[c], -np.finfo(f32).max) if decided[c] else INF, ref))
-                kids.sort(key=lambda k: -k[0])
-                cur = kids[0][1] if kids else EMPTY
-                for k in reversed(kids[1:]):
-                    stack.append(k)
-                assert len(stack) <= cap
-                mark = max(mark, len(stack))
+
+            def stale(g):
+                return (g < -state["t"]) if strict else (g <= -state["t"])
+
+            def leaf(k):
+                nonlocal tests
+                tests += 1
+                keep(T[i, index[k]], index[k])
+
+            def child(nd):                                               # skipped where its entry would be stale at once
+                lb = box_gap_lb(nd, qmin, qmax, qabs, rho_c)
+                return keys_of(-lb, ~np.isnan(lb), stale(-lb))
+
+            mark, _ = walk(nodes, cap, True, child, leaf, stale)
             note_high_water(stats, mark)
             for j in index[n_leaf:]:
                 tests += 1
@@ -465,12 +434,6 @@ def accuracy_sides(queries, rows, edges=False):
 
 
 # ---- populations ----------------------------------------------------------------------------------------------------------------
-
-def _rows(tris):
-    r = np.zeros((len(tris), 3, 4), f32)
-    r[:, :, :3] = tris
-    return r.reshape(-1, 4)
-
 
 def near_queries(rows, n, seed, edge=0.6, gap=(1e-4, 0.3), edges=False):
     """n query triangles of edge about `edge` whose centres sit `gap` (log-uniform) off a random point of a random scene

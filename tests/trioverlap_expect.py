@@ -8,18 +8,11 @@ import numpy as np
 import closest_expect as ce
 from overlap_expect import EPS, K, MAX_HITS, NONE, accepted_sets, chain, corners, random_scene, rows_of_table, same, walk_tree  # noqa: F401  (re-exported)
 from query_accel_expect import records_of_rows
+from query_expect import cross3 as _cross, dot3 as _dot
 
 f32 = np.float32
 INF = f32(np.inf)
 NAN = f32(np.nan)
-
-
-def _dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
-def _cross(a, b):
-    return [a[1] * b[2] - b[1] * a[2], a[2] * b[0] - b[2] * a[0], a[0] * b[1] - b[0] * a[1]]
 
 
 def _sub(a, b):
