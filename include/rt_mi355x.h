@@ -470,6 +470,11 @@ int  rt_tracer_intersect_all_device(rt_tracer* t, const float* segs, size_t n, u
  * positives, so a computed closest point never leaves its triangle's box by more than rounding, which the box test's allowance
  * rho_c covers (rt_dbg_query_accel_slack scales it as it scales rho).  A point with a non-finite coordinate takes no pruning
  * decision; triangles with a non-finite record stay in the always-tested list and go through the same rule.
+ * Range.  The rule has no absolute constant, so a scene and its points multiplied by 2^k answer the same u, v and prim and t
+ * times 2^2k -- while the fourth powers of a length it forms (va, vb, vc; region 7 divides by their sum) stay within fp32: for
+ * inputs of order 1, k = -31 .. 31.  Beyond that range the interior region's u and v are the first to go (a sum that is +inf
+ * or whose reciprocal is: the record answers NaN and is not accepted), then t itself below 2^-63 or above 2^63; scan and tree
+ * still agree bit for bit at every scale, and denormals are kept, not flushed (tests/range_cases.py, test_gpu_query_range.py).
  * Accuracy, as measured (K = 64, four times the largest value seen): with scale = max|p| + the largest |vertex
  * coordinate| and eps = 2^-24, sqrt(t) >= D - K*eps*scale for D the true distance to the nearest triangle -- the reported
  * distance is never below the true one by more than rounding -- and sqrt(t) <= D_ws + K*eps*scale for D_ws the true distance to
@@ -506,7 +511,8 @@ int  rt_tracer_closest_point_device(rt_tracer* t, const float* pts, size_t n, rt
  * Scheduling is rt_tracer_closest_point's; a multi-device handle answers from its first band, a band tracer locally.
  * RT_QUERY_SCAN (default): every point tests every candidate.  RT_QUERY_BVH: rt_tracer_closest_point's walk, pruning against
  * min(d2max, the t of the list's last entry once the list is full) instead of against one best; bit for bit the scan's answer,
- * counts included, for every point whose three coordinates are finite.  There is no conditioning clause.  A child is skipped
+ * counts included, for every point whose three coordinates are finite.  There is no conditioning clause, and the range over
+ * which answers rescale with the scene is rt_tracer_closest_point's (fourth powers: k = -31 .. 31).  A child is skipped
  * only when its lower bound lies strictly above that bound, so it holds no record that could enter the list; the cursor takes
  * no pruning decision. */
 /* Host arrays: pts n*4, after n or NULL, hits n*max_hits, counts n.  Returns with the results in host memory. */
@@ -557,7 +563,8 @@ int  rt_tracer_closest_all_device(rt_tracer* t, const float* pts, const rt_hit* 
  * Scheduling is that of the ray queries: never cancels or joins a running Trace, serialised with the other calls, on the query
  * stream or the caller's, waited for by uploads and destroy; a multi-device handle answers from its first band, a band tracer
  * locally.  RT_QUERY_SCAN and RT_QUERY_BVH decide how hits are found, exactly as for rt_tracer_closest_point; sides are a
- * function of (point, record, table) and do not depend on the mode. */
+ * function of (point, record, table) and do not depend on the mode.  Range: rt_tracer_closest_point's (k = -31 .. 31 for
+ * inputs of order 1); s rescales by 2^k, the feature does not change. */
 typedef struct rt_side { float s; int32_t feature; } rt_side;   /* 8 bytes */
 #define RT_FEATURE_NONE   (-1)
 #define RT_FEATURE_FACE   0
@@ -641,7 +648,10 @@ int  rt_tracer_closest_sides_device(rt_tracer* t, const float* pts, const rt_hit
  *   - acceptance is a pure function of (box, record, cursor), and a walk visits every record at most once;
  *   - triangles with a non-finite record sit in the always-tested list and go through the same rule; spheres are never in the
  *     tree and are scanned after the triangles;
- *   - a walk whose stack overflowed recomputes from every leaf record, restarting the list and the count. */
+ *   - a walk whose stack overflowed recomputes from every leaf record, restarting the list and the count.
+ * Range.  The triangle rule compares projections on cross products (cubes of a length) and the sphere rule squares: a scene and
+ * its boxes multiplied by 2^k answer the same rows for k = -62 .. 63 on inputs of order 1; beyond, separations are lost (rows
+ * gain prims) as the products reach +inf or 0.  Scan and tree agree at every scale. */
 /* Host arrays: boxes n*8, after n or NULL, prims n*max_hits (NULL allowed when max_hits = 0), counts n.  Returns with the
  * results in host memory. */
 int  rt_tracer_overlap(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
@@ -696,7 +706,9 @@ int  rt_tracer_overlap_device(rt_tracer* t, const float* boxes, const int32_t* a
  * every input whatsoever, by the argument above: step 1's [tmin, tmax] lies inside the record's tree box, a child the walk skips
  * holds only triangles step 1 rejects, acceptance is a pure function of (query, record, cursor), non-finite records go through
  * the always-tested list, and a walk whose stack overflowed recomputes from every leaf record, restarting the list and the count.
- * There is no rho, no slack and no conditioning clause: rt_dbg_query_accel_slack has no effect on this query either. */
+ * There is no rho, no slack and no conditioning clause: rt_dbg_query_accel_slack has no effect on this query either.
+ * Range.  The rows of a scene and its query triangles multiplied by 2^k are the same rows for k = -36 .. 31 on inputs of order 1
+ * (the sphere rule goes through closest_triangle's fourth powers; the axes' cubes reach further); beyond, separations are lost. */
 /* Host arrays: tris n*12, after n or NULL, prims n*max_hits (NULL allowed when max_hits = 0), counts n.  Returns with the
  * results in host memory. */
 int  rt_tracer_overlap_triangles(rt_tracer* t, const float* tris, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
@@ -770,7 +782,10 @@ int  rt_tracer_overlap_triangles_device(rt_tracer* t, const float* tris, const i
  * every input whatsoever: step 1's [tmin, tmax] lies inside the record's tree box, a child the walk skips holds only triangles
  * step 1 rejects, acceptance is a pure function of (corners, record, cursor), non-finite records go through the always-tested
  * list, and a walk whose stack overflowed recomputes from every leaf record, restarting the list and the count.  There is
- * no rho, no slack and no conditioning clause: rt_dbg_query_accel_slack has no effect on this query either. */
+ * no rho, no slack and no conditioning clause: rt_dbg_query_accel_slack has no effect on this query either.
+ * Range.  The rows of a scene and its regions multiplied by 2^k are the same rows for k = -32 .. 30 on inputs of order 1 (the
+ * sphere rule's d2min goes through closest_triangle's fourth powers, on coordinates up to 2.25 in the measured lattice); beyond,
+ * separations are lost. */
 /* Host arrays: hexa n*32, after n or NULL, prims n*max_hits (NULL allowed when max_hits = 0), counts n.  Returns with the
  * results in host memory. */
 int  rt_tracer_overlap_hexahedra(rt_tracer* t, const float* hexa, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
@@ -845,7 +860,16 @@ int  rt_tracer_overlap_hexahedra_device(rt_tracer* t, const float* hexa, const i
  * clause: an accepted contact is certified to lie within r + s of its record, so the line's span through a child's box grown by
  * r + 4*RT_SWEEP_SLACK*(cmax + r) + rho_s*(max|o| + cmax + r) contains its t, however ill conditioned the root was; a child is
  * skipped only when that span is empty, ends before t = 0 or begins STRICTLY after min(best t, tmax).  A sweep with a non-finite
- * component or a zero direction takes no pruning decision (rt_dbg_query_accel_slack scales the allowance beyond r). */
+ * component or a zero direction takes no pruning decision (rt_dbg_query_accel_slack scales the allowance beyond r).
+ * That holds at the ends of fp32's range too, by a guard computed once per sweep: the box is grown by 2^-72 more than stated
+ * (r*r, (r + s)^2 and the squared distances they are compared with round to multiples of 2^-149 below 2^-126, which can accept
+ * a record up to 2^-74 beyond r + s), and a sweep with max|o| + (the largest |coordinate| of the tree) + r >= 2^62 takes no
+ * pruning decision (there r*r or (r + s)^2 may be +inf, and inf <= inf accepts at any distance).
+ * Range.  No absolute constant enters an answer: a scene and its sweeps multiplied by 2^k answer the same u, v and prim, and t
+ * times 2^k when d is kept, the same t when d is multiplied too -- while the fourth powers of a length the roots and the point
+ * arithmetic form (|e1 x e2|^2, a * disc, va, vb, vc) stay within fp32: for inputs of order 1, k = -31 .. 31 (-30 with d
+ * multiplied).  Beyond, the face root is the first to go (n.n overflows or underflows: contacts with a face's interior are
+ * reported by an edge or vertex root or not at all), then certification; scan and tree still agree bit for bit. */
 /* Host arrays: sweeps n*8, hits n.  Returns with the answers in host memory. */
 int  rt_tracer_sphere_cast(rt_tracer* t, const float* sweeps, size_t n, rt_hit* hits);
 /* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
@@ -918,7 +942,10 @@ int  rt_tracer_sphere_cast_device(rt_tracer* t, const float* sweeps, size_t n, r
  * whose stack overflowed recomputes from every leaf record.  The answer is bit for bit the scan's two arrays under the point
  * query's own invariant (its sliver premise included): every x_k lies in [qmin, qmax], and for every x there each
  * term above is, by the monotonicity of fp32 subtraction, multiplication and max, at most the term the point query computes for
- * x -- so lb is at most the point query's bound, which every record inside the child answers with a t at least as large. */
+ * x -- so lb is at most the point query's bound, which every record inside the child answers with a t at least as large.
+ * Range: the point query's fourth powers (closest_triangle, and a * e - b * b of the segment pairs): a scene and its query
+ * triangles multiplied by 2^k answer the same u, v, prim and `where`, t times 2^2k and the witness times 2^k, for k = -31 .. 31
+ * on inputs of order 1; beyond, interior and crossing candidates answer NaN first.  Scan and tree agree at every scale. */
 typedef struct rt_witness { float x, y, z; int32_t where; } rt_witness;
 /* Host arrays: tris n*12, hits n, witness n.  Returns with the answers in host memory. */
 int  rt_tracer_triangle_distance(rt_tracer* t, const float* tris, size_t n, rt_hit* hits, rt_witness* witness);

@@ -18,11 +18,23 @@
 // Why the walk may prune: an accepted contact is CERTIFIED -- the fp32 point c lies within (r + s) of the record by
 // closest_triangle's own arithmetic, hence (its error bound added) inside the record's box grown by r + s + pad, whatever the
 // conditioning of the root that produced t.  spherecast_bvh_kernel's child() runs bvh_slab on the child's box grown by
-//   g = r + s_box + pad,   s_box = 4 * kSweepSlack * (cmax + r),   pad = rho_s * (max|o| + cmax + r)
+//   g = (r + kSweepTiny) + s_box + pad,   s_box = 4 * kSweepSlack * (cmax + r),   pad = rho_s * (max|o| + cmax + r)
 // (s_box bounds s for every centre inside the grown box; DESIGN.md 4.3k derives rho_s) and skips the child only when the line
 // misses the grown box, leaves it before t = 0, or enters it STRICTLY after min(best, tmax): a tie may hide a lower prim.
 // Nearest entry first; a popped entry that has fallen strictly behind best is dropped.  A sweep with a non-finite component or
 // a zero direction, or a child with a NaN in its slab test, takes no pruning decision.
+//
+// The ends of fp32's range (sweep_range_guard, once per lane; restated by tests/spherecast_expect.py).  The argument above takes
+// "t0 <= r*r" and "d2 <= (r + s)^2" to mean what they say.  Two things break that, and the walk allows for both:
+//   underflow  A square below 2^-149 rounds to a multiple of 2^-149: each of the three products of closest_triangle's t and the
+//              threshold itself is off by at most 2^-150, so an accepted record may lie 2^-74 farther away than the threshold
+//              says (sqrt(x + 4 * 2^-150) <= sqrt(x) + 2^-74), which matters once r + s is that small -- a scene of size 2^-64
+//              or less.  The box is therefore grown by kSweepTiny = 2^-72 more, four times that: the leading r of g is
+//              r + kSweepTiny, formed once per lane.  From r >= 2^-47 the sum is r bit for bit.
+//   overflow   Where r*r or (r + s)^2 is +inf, "inf <= inf" accepts a record at any distance.  (r + s)^2 is finite for every
+//              centre the boxes can hold while m = (max|o| + cmax_root) + r < kSweepHuge = 2^62 (cmax_root: the largest
+//              |coordinate| of the root's four child boxes, so |c| <= cmax_root + g <= 2m, r + s < 2m and its square below
+//              2^126); a sweep with m >= 2^62, or a NaN m, takes no pruning decision.
 //
 // spherecast_kernel (RT_QUERY_SCAN): closest_kernel's shape -- 256-thread blocks, lane = sweep, two 16-byte loads per sweep,
 // the triangles staged through LDS in ascending chunks of kQueryChunk records, spheres after the triangles.
@@ -102,6 +114,17 @@ __device__ __forceinline__ float sweep_face(V3 w, V3 e1, V3 e2, V3 d, float r) {
 __device__ __forceinline__ void sweep_keep(Sweep& q, float t, float u, float v, int prim) {
   if ((t < q.best) | ((t == q.best) & ((q.best_i < 0) | (prim < q.best_i)))) { q.best = t; q.bu = u; q.bv = v; q.best_i = prim; }
 }
+// the two constants of the range guard (the header comment derives them)
+constexpr float kSweepTiny = 0x1p-72f, kSweepHuge = 0x1p62f;
+
+// may this sweep prune at all, as far as fp32's range goes?  m = (max|o| + cmax_root) + r below kSweepHuge
+__device__ __forceinline__ bool sweep_range_guard(const BvhParams& b, float omax, float r) {
+  if (b.n_nodes == 0u) return true;
+  const float4 cm = b.nodes[7];                                    // the root's cmax[4] (an empty child's is 0)
+  const float croot = fmaxf(fmaxf(cm.x, cm.y), fmaxf(cm.z, cm.w));
+  return (omax + croot) + r < kSweepHuge;
+}
+
 // could a contact at t still win?  (t <= best implies t <= tmax: best starts there)
 __device__ __forceinline__ bool sweep_could_win(const Sweep& q, float t, int prim) {
   return (t < q.best) | ((t == q.best) & ((q.best_i < 0) | (prim < q.best_i)));
@@ -234,13 +257,15 @@ __global__ __launch_bounds__(64) void spherecast_bvh_kernel(const TraceParams p,
   const float tmax = s1.w;
 
   const OccludedPrune pr = occluded_prune(q.o, q.d);               // prunes at all?  1 / d, max|o|
+  const bool prunes = pr.prunes && sweep_range_guard(b, pr.omax, q.r);
+  const float rg = q.r + kSweepTiny;                               // (r itself from 2^-47 up)
   const float inf = __builtin_inff();
   auto child = [&](const BvhNode& nd, int c) {
-    const float g = q.r + (ks * (nd.cmax[c] + q.r) + rho_s * ((pr.omax + nd.cmax[c]) + q.r));
+    const float g = rg + (ks * (nd.cmax[c] + q.r) + rho_s * ((pr.omax + nd.cmax[c]) + q.r));
     float enter, exit;
     const bool nan = bvh_slab(nd, c, g, q.o, pr.inv, enter, exit);
     const bool skip = (exit < enter) || (exit < 0.0f) || (enter > q.best);
-    return !(pr.prunes && !nan) ? inf : skip ? -inf : fmaxf(-enter, -FLT_MAX);
+    return !(prunes && !nan) ? inf : skip ? -inf : fmaxf(-enter, -FLT_MAX);
   };
   auto leaf = [&](const float4* rec) { sweep_test_record(rec, q); return false; };
   const bool overflow = bvh_walk<64u, true>(b, s_mem, lane, true, child, leaf, [&](float key) { return key < -q.best; });

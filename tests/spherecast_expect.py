@@ -1,18 +1,20 @@
 """Test side of the swept query (rt_tracer_sphere_cast, csrc/rt_spherecast.hpp): the rule of
 include/rt_mi355x.h in numpy, one operation per operation, in float32 (what the kernels compute, bit for bit) or, through the
 same text, in float64; the expected answer by brute force under the winner rule; float64 distances written independently
-(closest_expect.distance64); the residual and drop-rate measurement behind RT_SWEEP_SLACK; and the sweep populations of the
-tests.  A helper, not a test.  Everything is deterministic and needs no device."""
+(closest_expect.distance64); the residual and drop-rate measurement behind RT_SWEEP_SLACK; the traversal restated over a dumped
+tree; and the sweep populations of the tests.  A helper, not a test.  Everything is deterministic and needs no device."""
 import numpy as np
 
 import closest_expect as ce
 from query_accel_expect import records_of_rows
 from query_expect import HIT_DTYPE, cross3 as _cross, dot3 as _dot
+from tree_walk_expect import keys_of, note_high_water, slab, walk
 
 f32 = np.float32
 INF = f32(np.inf)
 SLACK = f32(2.0 ** -11)                 # RT_SWEEP_SLACK (include/rt_mi355x.h)
 RHO_S = f32(2.0 ** -16)                 # RT_SWEEP_RHO (csrc/rt_kernels.hpp)
+TINY, HUGE = f32(2.0 ** -72), f32(2.0 ** 62)      # kSweepTiny, kSweepHuge (csrc/rt_spherecast.hpp: the range guard)
 # The largest residual (sqrt(d2_float64) - r) / (max|c| + r) of an uncertified candidate that is a genuine first contact, over
 # margin_families() (test_spherecast_expect.py measures it again and prints it per family); SLACK is the smallest power of two
 # >= 4 x that.  DROP_BOUND: the share of genuine contacts certification drops, per family (measured: 23 of 3132 sliver pairs,
@@ -277,6 +279,94 @@ def margin(sweeps, rows, edges=False, block=256):
     return worst, genuine, dropped
 
 
+# ---- the traversal, restated ------------------------------------------------------------------------------------------------
+
+def walk_tree_spherecast(nodes, recs, info, sweeps, rows, edges=False, spheres=None, ks=f32(4.0) * SLACK, rho_s=RHO_S, tie_rule=True,
+                         strict=True, stack_cap=None, stats=None, range_guard=True):
+    """spherecast_bvh_kernel in numpy over a dumped tree (nodes, recs, info of api.bvh_build / query_tree), fp32, operation by
+    operation: sweep_valid first (an invalid sweep answers prim -1 and never walks); occluded_prune's "prunes at all" (every
+    component of o and d finite, d not zero), 1 / d and max|o|; sweep_range_guard: the sweep prunes only while (max|o| + the
+    largest of the root's four cmax) + r < HUGE; best starts at tmax with no prim.  child() grows each child box by
+      g = (r + TINY) + (ks * (cmax + r) + rho_s * ((max|o| + cmax) + r))
+    in that association, runs tree_walk_expect.slab on it and skips the child when exit < enter, exit < 0 or enter > best; its
+    key is -enter (the nearest entry first), and a sweep that does not prune or a child with a NaN among its six products takes
+    no decision.  A popped entry is stale when key < -best.  A leaf's record goes through sweep_keep's order-free rule -- t <
+    best, or t == best and (no prim yet or a lower prim) -- with the pair's entry of table(): the same arithmetic on the same
+    operands.  The kernel skips the certification of a candidate that cannot win and table() certifies every pair; such a
+    candidate is not kept either way, so the answer is the same.  A walk that had to drop an entry (stack_cap; default 3 * depth,
+    which never overflows) starts again from best = tmax over every leaf record, as overlap_expect.walk_tree restates it.  The
+    always-tested list and then the spheres follow the walk.  Returns (HIT_DTYPE array, triangle tests made).  Switches that break
+    one thing each, for tests of the tests: strict=False skips a child at enter >= best and drops a popped entry at key <= -best;
+    tie_rule=False lets the first visited keep a tie; ks = rho_s = 0 grows the box by r alone; range_guard=False is the walk
+    without sweep_range_guard and without TINY, which loses records once r * r or (r + s)^2 underflows or overflows.  stats: a dict that receives
+    tree_walk_expect.note_high_water's marks."""
+    sw = np.asarray(sweeps, f32).reshape(-1, 8)
+    ks, rho_s = f32(ks), f32(rho_s)
+    n_tris = recs.shape[0]
+    T, U, V, _ = table(sw, rows, edges, spheres)
+    n_leaf = n_tris - info["always_tested"]
+    index = recs["index"].astype(np.int64)
+    out = np.zeros(sw.shape[0], HIT_DTYPE)
+    ok = valid(sw)
+    tests = 0
+    cap = 3 * max(info["depth"], 1) if stack_cap is None else stack_cap
+    with np.errstate(all="ignore"):
+        for i in range(sw.shape[0]):
+            if not ok[i]:
+                out[i] = (0, 0, 0, -1)
+                note_high_water(stats, 0)
+                continue
+            o, d, r, tmax = sw[i, 0:3], sw[i, 3:6], sw[i, 6], sw[i, 7]
+            state = {"t": tmax, "i": -1}
+
+            def keep(j):
+                tj = T[i, j]
+                if not tj < INF:                                         # no contact: sweep_triangle returns before sweep_keep
+                    return
+                if tj < state["t"] or (tj == state["t"] and (state["i"] < 0 or (tie_rule and j < state["i"]))):
+                    state.update(t=tj, i=int(j))
+
+            prunes = bool(np.isfinite(sw[i, :6]).all()) and bool((d != 0).any())
+            inv = f32(1.0) / d
+            omax = np.abs(o).max()
+            rg = r
+            if range_guard:
+                if nodes.shape[0]:
+                    prunes = prunes and bool((omax + np.fmax.reduce(nodes[0]["cmax"])) + r < HUGE)
+                rg = r + TINY
+
+            def stale(key):
+                return (key < -state["t"]) if strict else (key <= -state["t"])
+
+            def leaf(k):
+                nonlocal tests
+                tests += 1
+                keep(index[k])
+
+            def child(nd):
+                g = rg + (ks * (nd["cmax"] + r) + rho_s * ((omax + nd["cmax"]) + r))
+                assert g.dtype == f32
+                enter, exit_, nan, _, _ = slab(nd, o, inv, g)
+                skip = (exit_ < enter) | (exit_ < 0) | ((enter > state["t"]) if strict else (enter >= state["t"]))
+                return keys_of(-enter, prunes & ~nan, skip)
+
+            mark, overflow = walk(nodes, cap, True, child, leaf, stale, enforce_cap=stack_cap is None)
+            note_high_water(stats, mark)
+            if overflow:                                                 # every leaf record, from the start
+                state.update(t=tmax, i=-1)
+                for j in index[:n_leaf]:
+                    tests += 1
+                    keep(j)
+            for j in index[n_leaf:]:
+                tests += 1
+                keep(j)
+            for s in range(n_tris, T.shape[1]):                          # the spheres, after the triangles
+                keep(s)
+            j = state["i"]
+            out[i] = (state["t"], U[i, j], V[i, j], j) if j >= 0 else (0, 0, 0, -1)
+    return out, tests
+
+
 # ---- scenes and sweeps ----------------------------------------------------------------------------------------------------
 
 def scene(n_tris, seed=5, bad=True):
@@ -374,6 +464,18 @@ def start_sweeps(rows, n, seed, edges=False, r=0.05):
     k = rng.integers(0, len(v0), n)
     o = v0[k] + 0.25 * e1[k] + 0.25 * e2[k] + _unit(rng.normal(0, 1, (n, 3))) * rng.uniform(0, r, (n, 1))
     return _sweeps(o, rng.normal(0, 1, (n, 3)), r)
+
+
+def whole_scene_sweeps(rows, edges=False):
+    """Four sweeps whose sphere holds the whole scene, or most of it, at t = 0 (radius 3/4 .. 4 of the scene's largest extent,
+    from its middle, the world origin, its lowest corner and one triangle): the records start in overlap and tie at t = 0, every
+    child box is entered, and the walk's stack is as full as the tree lets it be."""
+    v0, e1, e2 = _finite_records(rows, edges)
+    pts = np.concatenate([v0, v0 + e1, v0 + e2])
+    lo, hi = pts.min(axis=0), pts.max(axis=0)
+    ext = (hi - lo).max()
+    at = ((lo + hi) / 2, np.zeros(3), lo, v0[min(5, len(v0) - 1)])
+    return _sweeps(np.asarray(at), np.tile([1.0, 0.5, -0.25], (4, 1)), ext * np.array([2.0, 4.0, 0.75, 1.0]))
 
 
 def tmax_sweeps(base, rows, edges=False, spheres=None):

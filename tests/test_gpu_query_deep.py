@@ -5,7 +5,7 @@ that query's own check, in both layouts, both arithmetic modes and both hit rule
 and with the stack shortened by DebugQueryStackCap every lane that needs one entry more answers from every leaf record -- the
 overflow path, which no tree of the builder reaches on its own -- under the same checks.  The four newer walkers on the same
 bvh_walk (region_bvh_kernel for boxes and triangles, spherecast_bvh_kernel, tridistance_bvh_kernel), each with an overflow
-restart of its own, go through every one of these cases with region_pops' boxes, query triangles and sweeps: they equal the
+restart of its own and a restated walk whose marks say which lanes take it, go through every one of these cases with region_pops' boxes, query triangles and sweeps: they equal the
 scan byte for byte by contract, every row, at every cap."""
 import numpy as np
 import pytest
@@ -75,7 +75,8 @@ def region_pops(rows, seed, n=160):
     ones touch a leaf or nothing, the large ones reach every root child and, on the ladder, cover the origin and with it every
     smaller cluster.  Every sixteenth box and query triangle spans the whole scene, by a different margin each: its walk enters all
     four children at every level, the fullest stack there is (48 of 48 entries on the ladder), beside neighbours in the wave that
-    hold a few; sixteen sweeps of 3 .. 30 extents' radius start in overlap with many records, which all tie at t = 0.  A quarter
+    hold a few; sixteen sweeps of 3 .. 30 extents' radius start in overlap with many records, which all tie at t = 0, and the four
+    of spherecast_expect.whole_scene_sweeps, at the end, with most of the scene (48 of 48 entries on the ladder).  A quarter
     of the query triangles search within half an extent.  Then the rows that accept nothing: an inverted and a NaN box, a NaN corner, a
     negative and a NaN radius, and spherecast_expect.bad_sweeps."""
     rng = np.random.default_rng(seed)
@@ -102,8 +103,9 @@ def region_pops(rows, seed, n=160):
     with np.errstate(over="ignore"):
         sweeps = np.concatenate([spe.random_sweeps(rows, n - 16, seed + 1, rel=True),
                                  spe.random_sweeps(rows, 16, seed + 2, rmin=0.5, rmax=1.5, rel=True)])
+        whole = spe.whole_scene_sweeps(rows)                             # the fullest stack the sweep walk can hold
     return {"boxes": boxes, "tris": np.ascontiguousarray(tris, np.float32),
-            "sweeps": np.ascontiguousarray(np.concatenate([sweeps, spe.bad_sweeps(sweeps[0])]), np.float32)}
+            "sweeps": np.ascontiguousarray(np.concatenate([sweeps, spe.bad_sweeps(sweeps[0]), whole]), np.float32)}
 
 
 def deep_pops(mirror):
@@ -383,7 +385,7 @@ def test_a_shortened_stack_answers_from_every_leaf_record(orc, name):
     print("%s: share of each restated walk's lanes that hold an entry at all: %s" % (name, {k: round(v, 2) for k, v in share.items()}))
     assert all(v > 0.5 for k, v in share.items() if not k.endswith("open lanes")), share
     newer, wide = region_marks(nodes, recs, info, pops, rows, spheres)
-    print("%s: the fullest stacks of the newer walks' restatements (every fourth lane): %s; sweeps whose box meets more than one root child: %d of %d"
+    print("%s: the fullest stacks of the newer walks' restatements (every fourth lane, every sweep): %s; sweeps whose box meets more than one root child: %d of %d"
           % (name, {k: int(m.max()) for k, m in newer.items()}, int(wide.sum()), wide.shape[0]))
     assert all((m > 0).any() for m in newer.values())
     if name == "deep":                                                   # lanes that only the one-entry-short cap overflows
@@ -416,17 +418,18 @@ def test_a_shortened_stack_answers_from_every_leaf_record(orc, name):
 
 
 def region_marks(nodes, recs, info, pops, rows, spheres):
-    """({walk: the most stack entries each lane's restated walk holds}, every fourth box and query triangle, for region_bvh_kernel (boxes, triangles)
-    and tridistance_bvh_kernel; for spherecast_bvh_kernel, which has no restated walk, the sweeps whose
-    box (both ends, widened by the radius) meets more than one child of the root: a device-independent lower bound on the
-    lanes that hold an entry)."""
+    """({walk: the most stack entries each lane's restated walk holds}, every fourth box and query triangle, for region_bvh_kernel
+    (boxes, triangles) and tridistance_bvh_kernel, every sweep for spherecast_bvh_kernel; and, as a cross-check of the sweep
+    walk's marks that no restated walk is needed for, the sweeps whose box (both ends, widened by the radius) meets more than one
+    child of the root)."""
     from query_accel_expect import EMPTY
     out = {}
     boxes, tris, sw = pops["boxes"][::4], pops["tris"][::4], pops["sweeps"]
     with np.errstate(all="ignore"):
         for key, walk in (("overlap16", lambda st: oe.walk_tree_overlap(nodes, recs, info, boxes, rows, 16, spheres=spheres, stats=st)),
                           ("trioverlap16", lambda st: te.walk_tree_triangles(nodes, recs, info, tris, rows, 16, spheres=spheres, stats=st)),
-                          ("tridistance", lambda st: td.walk_tree_tridistance(nodes, recs, info, tris, rows, spheres=spheres, stats=st))):
+                          ("tridistance", lambda st: td.walk_tree_tridistance(nodes, recs, info, tris, rows, spheres=spheres, stats=st)),
+                          ("spherecast", lambda st: spe.walk_tree_spherecast(nodes, recs, info, sw, rows, spheres=spheres, stats=st))):
             stats = {}
             walk(stats)
             out[key] = np.asarray(stats["high_water_per"])

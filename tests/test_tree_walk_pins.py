@@ -1,8 +1,9 @@
-"""The seven restated tree walks, pinned without a device: on the lattice scene and on a random scene of 100 triangles each walk's
+"""The eight restated tree walks, pinned without a device: on the lattice scene and on a random scene of 100 triangles each walk's
 outputs (as a SHA-256 of their bytes), its count of records tested and every query's stack high-water mark are compared with
 tests/golden/tree_walk_pins.json.  The file was recorded from the walks as they stood BEFORE they were moved onto
 tree_walk_expect.walk (its "recorded_from" names the commit), so a change of the shared walk that alters a visiting order, a
-prune or a mark shows here in seven places at once, next to the one that was meant."""
+prune or a mark shows here in seven places at once, next to the one that was meant.  The eighth, spherecast_expect's, was
+written on the shared walk; its cases ("spherecast_recorded_from") pin it as it stood when it first equalled brute force."""
 import hashlib
 import json
 import os
@@ -14,6 +15,7 @@ import closest_expect as ce
 import lattice_cases as lc
 import nearest_expect as ne
 import overlap_expect as oe
+import spherecast_expect as se
 import tridistance_expect as td
 from allhits_expect import walk_tree_all_hits
 from occluded_expect import walk_tree_occluded
@@ -41,15 +43,17 @@ def scene(name):
     if name == "rooms":
         rows = lc.rooms()
         rays = _first(np.concatenate([lc.axis_rays(4), lc.in_plane_rays(4), lc.vertex_rays(4)]))
-        c = {"points": _first(ce.lattice_points()), "triangles": _first(td.lattice_queries()),
+        sw = np.concatenate([np.c_[rays[:, :6], np.full((rays.shape[0], 2), [r, np.inf])] for r in (0.0, 0.25, 0.5)])
+        c = {"points": _first(ce.lattice_points()), "triangles": _first(td.lattice_queries()), "sweeps": _first(sw.astype(f32)),
              "boxes": _first(oe.touching_boxes(rows, range(0, rows.shape[0] // 3, 7))[0]), "sphere": f32([[0.25, 0.25, 0.25, 0.5]])}
     else:
         rows = ce.random_scene(100, 61)
         rays = np.concatenate([_first(np.concatenate(list(populations(rows, 16, 62).values())), 48), _first(adversarial_rays(rows, 0, 63), 16)])
         c = {"points": ce.points_for(rows, N, 64), "triangles": td.mixed_queries(rows, 48, 65),
+             "sweeps": np.concatenate([se.random_sweeps(rows, 40, 67), se.start_sweeps(rows, 12, 68, r=0.5), se.bad_sweeps(se.random_sweeps(rows, 1, 69)[0])[::4]]),
              "boxes": oe.random_boxes(rows, N, 66, width=1.5), "sphere": f32([[0.5, 0.3, -1.0, 0.8]])}
     c.update(rows=rows, tree=api.bvh_build(rows), rays=rays, segs=lc.ray_segments(rays), points=ce.with_radius(c["points"], INF))
-    assert all(c[k].shape[0] <= N for k in ("rays", "segs", "points", "triangles", "boxes")) and c["tree"][0].shape[0] > 1
+    assert all(c[k].shape[0] <= N for k in ("rays", "segs", "points", "triangles", "boxes", "sweeps")) and c["tree"][0].shape[0] > 1
     _cache[name] = c
     return c
 
@@ -76,6 +80,9 @@ WALKS = {
     "tridistance": lambda orc, c, st: td.walk_tree_tridistance(*c["tree"], c["triangles"], c["rows"], spheres=c["sphere"], stats=st),
     "region": lambda orc, c, st: _region(c, st),
     "region stack_cap 1": lambda orc, c, st: _region(c, st, stack_cap=1),
+    "spherecast": lambda orc, c, st: se.walk_tree_spherecast(*c["tree"], c["sweeps"], c["rows"], spheres=c["sphere"], stats=st),
+    "spherecast stack_cap 1": lambda orc, c, st: se.walk_tree_spherecast(*c["tree"], c["sweeps"], c["rows"], spheres=c["sphere"],
+                                                                         stack_cap=1, stats=st),
 }
 
 
@@ -111,11 +118,14 @@ def test_a_walk_gives_the_recorded_outputs_tests_and_marks(orc, pins, name, walk
 
 def test_the_pinned_cases_push_tie_and_overflow(pins):
     """What the cases are for: every walk holds waiting entries on both scenes, the lowered capacity is below the region walk's
-    mark (so some walk drops an entry and starts again: more records tested), and the two any-hit orders differ somewhere."""
+    and the sweep walk's mark (so some walk drops an entry and starts again: more records tested), and the two any-hit orders
+    differ somewhere."""
     for label, case in pins.items():
         assert max(case["high_water_per"]) >= (1 if "stack_cap" in label else 2), label
     for name in SCENES:
         assert max(pins[name + " / region"]["high_water_per"]) > 1
         assert pins[name + " / region stack_cap 1"]["tests"] > pins[name + " / region"]["tests"]
+        assert max(pins[name + " / spherecast"]["high_water_per"]) > 1
+        assert pins[name + " / spherecast stack_cap 1"]["tests"] > pins[name + " / spherecast"]["tests"]
         a, b = pins[name + " / occluded as stored"], pins[name + " / occluded kernel_order"]
         assert (a["tests"], a["high_water_per"]) != (b["tests"], b["high_water_per"])

@@ -3,7 +3,7 @@ plain Python over a dumped tree (nodes, recs, info of api.bvh_build / query_tree
 fp32 child-box arithmetics of the kernels in numpy, operation by operation, and the helpers that note a walk's stats.  The
 candidate rule, the list, the cursor, the spheres, the always-tested list and the count of records tested stay with each query's
 own module (query_accel_expect, allhits_expect, occluded_expect, closest_expect, nearest_expect, tridistance_expect,
-overlap_expect).  A helper, not a test.  Everything is deterministic and needs no device."""
+overlap_expect, spherecast_expect).  A helper, not a test.  Everything is deterministic and needs no device."""
 import numpy as np
 
 from query_expect import FLT_MAX
@@ -67,10 +67,9 @@ def walk(nodes, cap, start, child, leaf, stale=None, enforce_cap=True):
 
 # ---- the two child-box arithmetics -----------------------------------------------------------------------------------------
 
-def ray_slab(nd, o, inv, omax, rho):
-    """bvh_slab for a node's four children at once: the line o + t / inv against each box grown by pad = rho * (omax + cmax).
+def slab(nd, o, inv, pad):
+    """bvh_slab for a node's four children at once: the line o + t / inv against each box grown by the caller's pad (4,).
     -> (enter, exit_, nan, t1, t2): (4,) enter and exit, (4,) bool "a NaN among the six products", and the products (3, 4)."""
-    pad = rho * (omax + nd["cmax"])                                   # (4,) float32
     t1 = ((nd["lo"] - pad) - o[:, None]) * inv[:, None]               # (3, 4)
     t2 = ((nd["hi"] + pad) - o[:, None]) * inv[:, None]
     assert t1.dtype == np.float32 and pad.dtype == np.float32
@@ -78,6 +77,11 @@ def ray_slab(nd, o, inv, omax, rho):
     enter = np.fmax.reduce(np.fmin(t1, t2), axis=0)
     exit_ = np.fmin.reduce(np.fmax(t1, t2), axis=0)
     return enter, exit_, nan, t1, t2
+
+
+def ray_slab(nd, o, inv, omax, rho):
+    """slab with the ray queries' pad = rho * (omax + cmax)."""
+    return slab(nd, o, inv, rho * (omax + nd["cmax"]))
 
 
 def box_gap_lb(nd, qmin, qmax, qabs, rho_c):
