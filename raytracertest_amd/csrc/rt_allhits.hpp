@@ -16,10 +16,13 @@
 // the traversal prunes with -- no runtime index anywhere.  u and v are recomputed from the triangle's record when a row is
 // written out (finish_query_hit's way: same operations as the scan, same bits), so the list holds 8 bytes per hit.
 //
-// allhits_kernel (RT_QUERY_SCAN): occluded_kernel's outer shape -- 256-thread blocks, two 16-byte loads per ray, the triangles
-// staged through LDS in ascending chunks of kQueryChunk 36-byte records, stages A-D with the conservative wave-uniform ballots
-// -- at one ray per lane and without the early exits: nothing is ever finished.  Padding lanes and rays whose interval is empty
-// (a NaN bound, tmin > tmax) stay out of the ballots.
+// allhits_kernel (RT_QUERY_SCAN): the scan of rt_scan.hpp (idle waves skip), lane = ray, two 16-byte loads per ray, stages A-D
+// with the conservative wave-uniform ballots and no early exit: nothing is ever finished.  Padding lanes and rays whose
+// interval is empty (a NaN bound, tmin > tmax) stay out of the ballots.
+//
+// allhits_kernel keeps the scan in its own text -- the chunk loop, the LDS layout, the staging and the barriers are A SECOND
+// COPY of rt_scan.hpp's scan_triangles, which is the first: change them together.  On the shared function this kernel measured
+// slower than its parent by more than the parent's own run-to-run spread.
 //
 // allhits_bvh_kernel (RT_QUERY_BVH): one wave per block, lane = ray, the walk of rt_bvh_walk.hpp with 8-byte stack entries
 // {-enter, reference}.  A child is skipped when  exit < enter,  exit < tmin,  enter > tmax  or, once the list is full,
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(256, 4) void allhits_kernel(const TraceParams p, ui
   int lp[CAP];
   allhits_init<CAP>(lt, lp, max_hits);
 
-  // the triangles, staged into LDS chunk by chunk; every chunk is scanned
+  // the triangles, staged into LDS chunk by chunk; every chunk is scanned (rt_scan.hpp's loop in its SkipIdleWaves mode)
   const uint32_t nt = p.n_tris;
   const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
   float4* const sA = s_mem;                                        // 2 float4 per triangle

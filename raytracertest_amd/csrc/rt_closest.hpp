@@ -11,8 +11,8 @@
 // Accepted: t <= d2max in plain fp32 (a NaN t never; a NaN or negative d2max accepts nothing).  Winner: the smallest (t, prim),
 // equal t (==) to the lowest prim -- a rule that names no visiting order, so the scan and the traversal cannot disagree.
 //
-// closest_kernel (RT_QUERY_SCAN): 256-thread blocks, lane = point, the point is one 16-byte load; the triangles staged through
-// LDS in ascending chunks of kQueryChunk 36-byte records as query_kernel stages them; spheres after the triangles.
+// closest_kernel (RT_QUERY_SCAN): the scan of rt_scan.hpp (idle waves skip), lane = point, the point is one 16-byte load;
+// spheres after the triangles.
 //
 // closest_bvh_kernel (RT_QUERY_BVH): one wave per block, lane = point, the tree and the LDS stack of rt_bvh.hpp (8-byte entries
 // {-lb, reference} at entry * 64 + lane, capacity b.stack_cap, overflow = every leaf record).  Per child, in fp32,
@@ -116,25 +116,12 @@ __global__ __launch_bounds__(256, 4) void closest_kernel(const TraceParams p, ui
   float best = q.w;
   int best_i = -1;
 
-  // the triangles, staged into LDS chunk by chunk; every chunk is scanned
-  const uint32_t nt = p.n_tris;
-  const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
-  float4* const sA = s_mem;                                        // 2 float4 per triangle
-  float* const sB = reinterpret_cast<float*>(s_mem + 2u * cap);    // v0.z
-  for (uint32_t c0 = 0; c0 < nt; c0 += kQueryChunk) {
-    const uint32_t cn = (nt - c0 < kQueryChunk) ? nt - c0 : kQueryChunk;
-    __syncthreads();                                               // the previous chunk is read
-    for (uint32_t i = tid; i < 2u * cn; i += 256u) sA[i] = p.tri_a[2u * c0 + i];
-    for (uint32_t i = tid; i < cn; i += 256u) sB[i] = p.tri_b[c0 + i];
-    __syncthreads();
-    if (__builtin_amdgcn_ballot_w64(active) == 0ull) continue;     // no point of this wave accepts; it still helps staging
-    for (uint32_t j = 0; j < cn; ++j) {
-      const float4 A0 = sA[2u * j], A1 = sA[2u * j + 1u];
-      float t, u, v;
-      closest_triangle(pt, {A1.z, A1.w, sB[j]}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, t, u, v);
-      if (active) closest_keep(t, static_cast<int>(c0 + j), best, best_i);
-    }
-  }
+  // the triangles; every chunk is scanned, by the waves that hold a point that accepts
+  scan_triangles<ScanMode::SkipIdleWaves>(p, s_mem, [&] { return active; }, [&](const float4 A0, const float4 A1, auto z, int prim) {
+    float t, u, v;
+    closest_triangle(pt, {A1.z, A1.w, z()}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, t, u, v);
+    if (active) closest_keep(t, prim, best, best_i);
+  });
   if (tid < nb) {
     float4 h = {0.0f, 0.0f, 0.0f, __int_as_float(-1)};
     if (active) h = closest_finish(p, pt, best, best_i);

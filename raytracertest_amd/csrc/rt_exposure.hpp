@@ -13,9 +13,10 @@
 // rt_dbg_exposure_rays call it.  One arithmetic in both math modes, every operation rounded separately (the build has
 // -ffp-contract=off on both sides), the one division correctly rounded.
 //
-// exposure_kernel (RT_QUERY_SCAN): occluded_kernel<FMA, 1>'s outer shape -- spheres first, the triangles staged through LDS
-// in ascending chunks of kQueryChunk records, a finished wave skips a chunk's loop but still stages, the block leaves through
-// __syncthreads_or.  No thread returns before the last barrier.
+// exposure_kernel (RT_QUERY_SCAN): spheres first, then the scan of rt_scan.hpp in its stop-when-idle mode.  No thread returns
+// before the last barrier.  The kernel keeps the scan in its own text -- the chunk loop, the LDS layout, the staging and the
+// barriers are A SECOND COPY of rt_scan.hpp's scan_triangles, which is the first: change them together.  On the shared
+// function two of its four arms measured slower than the parent by more than the parent's own spread.
 //
 // exposure_bvh_kernel (RT_QUERY_BVH): every lane runs occluded_bvh_kernel's any-hit walk on its own ray -- occluded_child's
 // pruning, spheres and the always-tested list first, the overflow fallback -- with the lane's stack in LDS at entry * 256 + tid.
@@ -93,7 +94,8 @@ __global__ __launch_bounds__(256, 4) void exposure_kernel(const TraceParams p, u
     if (!done[0] && hit_sphere<FMA>(o[0], d[0], p.spheres[si], t) && tmin[0] <= t && t <= tmax[0]) done[0] = true;
   }
 
-  // the triangles, staged into LDS chunk by chunk, until every ray of the block is finished (occluded_kernel's loop)
+  // the triangles, staged into LDS chunk by chunk, until every ray of the block is finished (rt_scan.hpp's loop in its
+  // StopWhenIdle mode)
   const uint32_t nt = p.n_tris;
   const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
   float4* const sA = s_mem;                                        // 2 float4 per triangle

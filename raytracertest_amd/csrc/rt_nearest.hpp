@@ -12,8 +12,7 @@
 // pinned at (-inf, -1), the last slot's t the bound the traversal prunes with (+inf while the list is not full).  u and v are
 // recomputed from the triangle's record when a row is written out: the same operations on the same operands, the same bits.
 //
-// nearest_kernel<CAP> (RT_QUERY_SCAN): closest_kernel's outer shape -- 256-thread blocks, lane = point, the triangles staged
-// through LDS in ascending chunks of kQueryChunk 36-byte records, spheres after the triangles.
+// nearest_kernel<CAP> (RT_QUERY_SCAN): the scan of rt_scan.hpp (idle waves skip), lane = point, spheres after the triangles.
 //
 // nearest_bvh_kernel<CAP> (RT_QUERY_BVH): closest_bvh_kernel's walk -- the same pad, lb, deflation, NaN and non-finite rules,
 // five-exchange ordering, LDS stack and overflow fallback -- against  bound = min(d2max, t_last).  A child is skipped only when
@@ -115,25 +114,12 @@ __global__ __launch_bounds__(256, 4) void nearest_kernel(const TraceParams p, ui
   int lp[CAP];
   allhits_init<CAP>(lt, lp, max_hits);
 
-  // the triangles, staged into LDS chunk by chunk; every chunk is scanned
-  const uint32_t nt = p.n_tris;
-  const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
-  float4* const sA = s_mem;                                        // 2 float4 per triangle
-  float* const sB = reinterpret_cast<float*>(s_mem + 2u * cap);    // v0.z
-  for (uint32_t c0 = 0; c0 < nt; c0 += kQueryChunk) {
-    const uint32_t cn = (nt - c0 < kQueryChunk) ? nt - c0 : kQueryChunk;
-    __syncthreads();                                               // the previous chunk is read
-    for (uint32_t i = tid; i < 2u * cn; i += 256u) sA[i] = p.tri_a[2u * c0 + i];
-    for (uint32_t i = tid; i < cn; i += 256u) sB[i] = p.tri_b[c0 + i];
-    __syncthreads();
-    if (__builtin_amdgcn_ballot_w64(active) == 0ull) continue;     // no point of this wave accepts; it still helps staging
-    for (uint32_t j = 0; j < cn; ++j) {
-      const float4 A0 = sA[2u * j], A1 = sA[2u * j + 1u];
-      float t, u, v;
-      closest_triangle(pt, {A1.z, A1.w, sB[j]}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, t, u, v);
-      if (active) nearest_keep<CAP>(t, static_cast<int>(c0 + j), d2max, cur, lt, lp);
-    }
-  }
+  // the triangles; every chunk is scanned, by the waves that hold a point that accepts
+  scan_triangles<ScanMode::SkipIdleWaves>(p, s_mem, [&] { return active; }, [&](const float4 A0, const float4 A1, auto z, int prim) {
+    float t, u, v;
+    closest_triangle(pt, {A1.z, A1.w, z()}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, t, u, v);
+    if (active) nearest_keep<CAP>(t, prim, d2max, cur, lt, lp);
+  });
   if (active) nearest_spheres<CAP>(p, pt, d2max, cur, lt, lp);
 
   if (tid < nb) nearest_store<CAP>(p, pt, lt, lp, max_hits, hits + (base + tid) * max_hits, counts + base + tid);

@@ -7,12 +7,10 @@
 // of hit_sphere; the interval is closed and compared in plain fp32 (a NaN t or bound, or tmin > tmax, never occludes).  The
 // answer is an OR over the primitives: no winner, no order, no tie rule, and a ray is finished at its first accepted hit.
 //
-// occluded_kernel (RT_QUERY_SCAN): query_kernel's outer shape -- 256-thread blocks, K rays per lane (ray k * 256 + lane of the
-// block), the triangles staged through LDS in ascending chunks of 36-byte records -- with the early exit on top: a finished ray
-// leaves the ballots of the triangle stages, a wave skips a chunk's loop once every ray of it is finished, and the block stops
-// staging once that holds for all its waves (decided by __syncthreads_or in place of the barrier between two chunks: block-
-// uniform, never under divergent control flow).  Rays are two 16-byte loads each, the answers one byte per ray (a wave's 64
-// lanes store 64 consecutive bytes).  Padding lanes (ray index >= n) start finished.
+// occluded_kernel (RT_QUERY_SCAN): the scan of rt_scan.hpp in its stop-when-idle mode, K rays per lane (ray k * 256 + lane of
+// the block): a finished ray leaves the ballots of the triangle stages, and a lane is open while one of its rays is not
+// finished.  Rays are two 16-byte loads each, the answers one byte per ray (a wave's 64 lanes store 64 consecutive bytes).
+// Padding lanes (ray index >= n) start finished.
 //
 // occluded_bvh_kernel (RT_QUERY_BVH): one wave per block, lane = ray, the walk of rt_bvh_walk.hpp as an any-hit traversal.  A
 // child is skipped when  exit < enter,  exit < tmin  or  enter > tmax  (strictly: a tie is visited).  There is no best t, so a
@@ -118,27 +116,16 @@ __global__ __launch_bounds__(256, 4) void occluded_kernel(const TraceParams p, u
     }
   }
 
-  // the triangles, staged into LDS chunk by chunk, until every ray of the block is finished
-  const uint32_t nt = p.n_tris;
-  const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
-  float4* const sA = s_mem;                                        // 2 float4 per triangle
-  float* const sB = reinterpret_cast<float*>(s_mem + 2u * cap);    // v0.z
-  for (uint32_t c0 = 0; c0 < nt; c0 += kQueryChunk) {
-    const uint32_t cn = (nt - c0 < kQueryChunk) ? nt - c0 : kQueryChunk;
-    bool open = false;
+  // the triangles, until every ray of the block is finished
+  const auto open = [&] {
+    bool any = false;
 #pragma unroll
-    for (int k = 0; k < K; ++k) open = open || !done[k];
-    // the barrier between two chunks (the previous one is read) carries the block's verdict: every thread gets the same
-    if (__syncthreads_or(open ? 1 : 0) == 0) break;
-    for (uint32_t i = tid; i < 2u * cn; i += 256u) sA[i] = p.tri_a[2u * c0 + i];
-    for (uint32_t i = tid; i < cn; i += 256u) sB[i] = p.tri_b[c0 + i];
-    __syncthreads();
-    if (__builtin_amdgcn_ballot_w64(open) == 0ull) continue;       // this wave is finished; it still helps staging
-    for (uint32_t j = 0; j < cn; ++j) {
-      const float4 A0 = sA[2u * j], A1 = sA[2u * j + 1u];
-      occluded_test_triangle<FMA, K>(A0, A1, sB[j], o, d, tmin, tmax, done);
-    }
-  }
+    for (int k = 0; k < K; ++k) any = any || !done[k];
+    return any;
+  };
+  scan_triangles<ScanMode::StopWhenIdle>(p, s_mem, open, [&](const float4 A0, const float4 A1, auto z, int) {
+    occluded_test_triangle<FMA, K>(A0, A1, z(), o, d, tmin, tmax, done);
+  });
 
 #pragma unroll
   for (int k = 0; k < K; ++k) {

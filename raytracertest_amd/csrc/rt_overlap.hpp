@@ -20,11 +20,14 @@
 // The kernels are written once for the three region shapes (the box here, the triangle of rt_trioverlap.hpp, the hexahedron of
 // rt_hexoverlap.hpp); a shape is a policy type of static members (BoxRegion below) that states its rule and nothing else.
 //
-// region_kernel<Shape, CAP> (RT_QUERY_SCAN): closest_kernel's outer shape -- 256-thread blocks, lane = query, the query is
-// Shape::kFloat4s 16-byte loads, the triangles staged through LDS in ascending chunks of kQueryChunk 36-byte records, spheres
-// after the triangles.  Prims arrive in ascending order: the first max_hits accepted are stored (compile-time slots, selected by
-// the count), the count runs on.  A record no lane's step 1 passes is left by ballot before steps 2-3.  A padding lane holds a
-// query that accepts nothing and stores nothing.
+// region_kernel<Shape, CAP> (RT_QUERY_SCAN): the scan of rt_scan.hpp (idle waves skip), lane = query, the query is
+// Shape::kFloat4s 16-byte loads, spheres after the triangles.  Prims arrive in ascending order: the first max_hits accepted
+// are stored (compile-time slots, selected by the count), the count runs on.  A record no lane's step 1 passes is left by
+// ballot before steps 2-3.  A padding lane holds a query that accepts nothing and stores nothing.
+// The kernel keeps the scan in its own text -- the chunk loop, the LDS layout, the staging and the barriers are A SECOND COPY
+// of rt_scan.hpp's scan_triangles, which is the first: change them together.  On the shared function one of its 30 arms (the
+// hexahedron at max_hits 16, 1 100 triangles) measured slower than the parent by more than the parent's own spread, and a
+// template has one text.
 //
 // region_bvh_kernel<Shape, CAP> (RT_QUERY_BVH): one wave per block, lane = query, bvh_walk with 4-byte entries and a constant key
 // for a child whose box overlaps the query's bounding box.  Records arrive in tree order: the list is rt_allhits.hpp's idiom on
@@ -215,7 +218,7 @@ __global__ __launch_bounds__(256, Shape::kScanWaves) void region_kernel(const Tr
   OverlapList<CAP> L;
   L.init_scan();
 
-  // the triangles, staged into LDS chunk by chunk; every chunk is scanned
+  // the triangles, staged into LDS chunk by chunk; every chunk is scanned (rt_scan.hpp's loop in its SkipIdleWaves mode)
   const uint32_t nt = p.n_tris;
   const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
   float4* const sA = s_mem;                                        // 2 float4 per triangle

@@ -2,21 +2,18 @@
 // renderer's own arithmetic and hit rule (RayTracer/Kernels.cuh:29-92, ThinLensCamera.cuh:111-130).  Included by
 // rt_kernels.hip only (rt_lists.hpp defines non-template kernels: a second translation unit would define them twice).
 //
-// Shape: 256-thread blocks, each lane holds K rays -- ray k * 256 + lane of the block, so that every load and store of a
-// wave covers one contiguous span.  The block's rays (6 floats each) are read with consecutive threads on consecutive
-// floats into LDS and from there into registers; then the block stages the triangles into the same LDS in ascending
-// chunks of 36-byte records (as TracePath::FullScan does) and every ray scans all of them through rtk::test_triangle --
-// the trace kernel's own code, so the arithmetic is the renderer's by construction.  Spheres follow (the trace kernel's
-// rule), and the winner's u, v are recomputed once from its record with hit_triangle_exact (as the smooth-shading block
-// does: same operations as the scan, same bits).
+// Shape: the scan of rt_scan.hpp (every chunk, every wave), each lane holding K rays -- ray k * 256 + lane of the block, so
+// that every load and store of a wave covers one contiguous span.  The block's rays (6 floats each) are read with
+// consecutive threads on consecutive floats into LDS and from there into registers; the chunks then go through the same LDS
+// and every ray scans all of them through rtk::test_triangle -- the trace kernel's own code, so the arithmetic is the
+// renderer's by construction.  Spheres follow (the trace kernel's rule), and the winner's u, v are recomputed once from its
+// record with hit_triangle_exact (as the smooth-shading block does: same operations as the scan, same bits).
 // Padding lanes (ray index >= n) carry o = d = 0: det = dot(e1, cross(0, e2)) = 0 < 1e-10 culls them at stage A for
 // every finite triangle, so they never keep a triangle alive in the ballots; their results are never stored.
 #pragma once
-#include "rt_trace.hpp"
+#include "rt_scan.hpp"
 
 namespace rtk {
-
-constexpr uint32_t kQueryChunk = 1024u;    // triangles per LDS chunk: 36 KiB, four blocks share a CU's 160 KiB
 
 // Output record: {t, u, v, bits of the int32 primitive} (rt_hit).  prim = triangle index, n_tris + sphere index, or -1.
 template <bool FMA, int K>
@@ -74,24 +71,12 @@ __global__ __launch_bounds__(256, 4) void query_kernel(const TraceParams p, uint
   }
   unsigned long long st_exit[4] = {0, 0, 0, 0}, st_skip[4] = {0, 0, 0, 0};   // (no counters: STATS = false)
 
-  // every triangle, ascending (:75, first-scanned wins ties :84), staged into LDS chunk by chunk
-  const uint32_t nt = p.n_tris;
-  const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
-  float4* const sA = s_mem;                                        // 2 float4 per triangle
-  float* const sB = reinterpret_cast<float*>(s_mem + 2u * cap);    // v0.z
-  for (uint32_t c0 = 0; c0 < nt; c0 += kQueryChunk) {
-    const uint32_t cn = (nt - c0 < kQueryChunk) ? nt - c0 : kQueryChunk;
-    __syncthreads();                                               // the rays / the previous chunk are read
-    for (uint32_t i = tid; i < 2u * cn; i += 256u) sA[i] = p.tri_a[2u * c0 + i];
-    for (uint32_t i = tid; i < cn; i += 256u) sB[i] = p.tri_b[c0 + i];
-    __syncthreads();
-    for (uint32_t j = 0; j < cn; ++j) {
-      const float4 A0 = sA[2u * j], A1 = sA[2u * j + 1u];
-      test_triangle<FMA, K, true, false>(A0, A1, [&] { return sB[j]; }, static_cast<int>(c0 + j), o, d, best_t, best_i,
-                                         nearest, true, static_cast<uint32_t>(K), st_exit, st_skip);
-    }
-  }
+  // every triangle, ascending (:75, first-scanned wins ties :84); the scan's first barrier comes after the rays are read
+  scan_triangles<ScanMode::EveryWave>(p, s_mem, [] { return true; }, [&](const float4 A0, const float4 A1, auto z, int prim) {
+    test_triangle<FMA, K, true, false>(A0, A1, z, prim, o, d, best_t, best_i, nearest, true, static_cast<uint32_t>(K), st_exit, st_skip);
+  });
 
+  const uint32_t nt = p.n_tris;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const uint32_t r = static_cast<uint32_t>(k) * 256u + tid;
@@ -126,11 +111,6 @@ __global__ __launch_bounds__(256, 4) void query_kernel(const TraceParams p, uint
 // What the launch functions of the seven query headers share (host).  Each query has ONE launch function, launch_X(p, b, ...):
 // b == nullptr is the scan, otherwise the walk of *b; it guards its arguments, picks the instantiation and states the launch
 // geometry -- elements per block, threads per block, dynamic LDS -- in its call of launch_blocks.  launch_query is in rt_bvh.hpp.
-
-// the dynamic LDS of a scan kernel's staged chunk: min(n_tris, kQueryChunk) records of 36 bytes
-static uint32_t query_chunk_lds_bytes(uint32_t n_tris) {
-  return (n_tris < kQueryChunk ? n_tris : kQueryChunk) * 36u;
-}
 
 // query_kernel stages its block's rays (24 bytes each) through the same LDS first
 static uint32_t query_lds_bytes(uint32_t n_tris, int K) {

@@ -36,8 +36,8 @@
 //              |coordinate| of the root's four child boxes, so |c| <= cmax_root + g <= 2m, r + s < 2m and its square below
 //              2^126); a sweep with m >= 2^62, or a NaN m, takes no pruning decision.
 //
-// spherecast_kernel (RT_QUERY_SCAN): closest_kernel's shape -- 256-thread blocks, lane = sweep, two 16-byte loads per sweep,
-// the triangles staged through LDS in ascending chunks of kQueryChunk records, spheres after the triangles.
+// spherecast_kernel (RT_QUERY_SCAN): the scan of rt_scan.hpp (idle waves skip), lane = sweep, two 16-byte loads per sweep,
+// spheres after the triangles.
 // spherecast_bvh_kernel (RT_QUERY_BVH): one wave per block, lane = sweep, bvh_walk with keyed entries {-enter, reference}.
 #pragma once
 #include "rt_overlap.hpp"
@@ -211,23 +211,10 @@ __global__ __launch_bounds__(256, 4) void spherecast_kernel(const TraceParams p,
   Sweep q = sweep_load(s0, s1);
   const bool active = sweep_valid(s1.z, s1.w);
 
-  // the triangles, staged into LDS chunk by chunk; every chunk is scanned
-  const uint32_t nt = p.n_tris;
-  const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
-  float4* const sA = s_mem;                                        // 2 float4 per triangle
-  float* const sB = reinterpret_cast<float*>(s_mem + 2u * cap);    // v0.z
-  for (uint32_t c0 = 0; c0 < nt; c0 += kQueryChunk) {
-    const uint32_t cn = (nt - c0 < kQueryChunk) ? nt - c0 : kQueryChunk;
-    __syncthreads();                                               // the previous chunk is read
-    for (uint32_t i = tid; i < 2u * cn; i += 256u) sA[i] = p.tri_a[2u * c0 + i];
-    for (uint32_t i = tid; i < cn; i += 256u) sB[i] = p.tri_b[c0 + i];
-    __syncthreads();
-    if (__builtin_amdgcn_ballot_w64(active) == 0ull) continue;     // no sweep of this wave accepts; it still helps staging
-    for (uint32_t j = 0; j < cn; ++j) {
-      const float4 A0 = sA[2u * j], A1 = sA[2u * j + 1u];
-      if (active) sweep_triangle(q, {A1.z, A1.w, sB[j]}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, static_cast<int>(c0 + j));
-    }
-  }
+  // the triangles; every chunk is scanned, by the waves that hold a sweep that accepts
+  scan_triangles<ScanMode::SkipIdleWaves>(p, s_mem, [&] { return active; }, [&](const float4 A0, const float4 A1, auto z, int prim) {
+    if (active) sweep_triangle(q, {A1.z, A1.w, z()}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}, prim);
+  });
   if (tid < nb) {
     float4 h = {0.0f, 0.0f, 0.0f, __int_as_float(-1)};
     if (active) h = sweep_finish(p, q);

@@ -18,9 +18,9 @@
 // A sphere has four candidates (the corners and the centre's projection) under closest_finish's sphere arithmetic; t = 0 when
 // OverlapTriangles' sphere condition (TriRegion::sphere) holds.  Winner: closest_keep's (t, prim) rule, best starting at d2max.
 //
-// tridistance_kernel (RT_QUERY_SCAN): 256-thread blocks, lane = query, the query is three 16-byte loads; the triangles staged
-// through LDS in ascending chunks of kQueryChunk as closest_kernel stages them; spheres after the triangles.  The loop carries
-// (t, prim) only: the winner's (u, v) and the witness are recomputed from the winning record at the end (td_finish).
+// tridistance_kernel (RT_QUERY_SCAN): the scan of rt_scan.hpp (idle waves skip), lane = query, the query is three 16-byte
+// loads; spheres after the triangles.  The scan carries (t, prim) only: the winner's (u, v) and the witness are recomputed
+// from the winning record at the end (td_finish).
 //
 // tridistance_bvh_kernel (RT_QUERY_BVH): one wave per block, lane = query, bvh_walk<64, true> (keyed entries {-lb, reference}).
 // Per child, in fp32,
@@ -201,24 +201,11 @@ __global__ __launch_bounds__(256, 2) void tridistance_kernel(const TraceParams p
   float best = d.d2max;
   int best_i = -1;
 
-  // the triangles, staged into LDS chunk by chunk; every chunk is scanned
-  const uint32_t nt = p.n_tris;
-  const uint32_t cap = nt < kQueryChunk ? nt : kQueryChunk;
-  float4* const sA = s_mem;                                        // 2 float4 per triangle
-  float* const sB = reinterpret_cast<float*>(s_mem + 2u * cap);    // v0.z
-  for (uint32_t c0 = 0; c0 < nt; c0 += kQueryChunk) {
-    const uint32_t cn = (nt - c0 < kQueryChunk) ? nt - c0 : kQueryChunk;
-    __syncthreads();                                               // the previous chunk is read
-    for (uint32_t i = tid; i < 2u * cn; i += 256u) sA[i] = p.tri_a[2u * c0 + i];
-    for (uint32_t i = tid; i < cn; i += 256u) sB[i] = p.tri_b[c0 + i];
-    __syncthreads();
-    if (__builtin_amdgcn_ballot_w64(d.active) == 0ull) continue;   // no query of this wave accepts; it still helps staging
-    for (uint32_t j = 0; j < cn; ++j) {
-      const float4 A0 = sA[2u * j], A1 = sA[2u * j + 1u];
-      const float t = td_triangle(d, {A1.z, A1.w, sB[j]}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}).t;
-      if (d.active) closest_keep(t, static_cast<int>(c0 + j), best, best_i);
-    }
-  }
+  // the triangles; every chunk is scanned, by the waves that hold a query that accepts
+  scan_triangles<ScanMode::SkipIdleWaves>(p, s_mem, [&] { return d.active; }, [&](const float4 A0, const float4 A1, auto z, int prim) {
+    const float t = td_triangle(d, {A1.z, A1.w, z()}, {A0.w, A1.x, A1.y}, {A0.x, A0.y, A0.z}).t;
+    if (d.active) closest_keep(t, prim, best, best_i);
+  });
   if (tid < nb) {
     float4 h = {0.0f, 0.0f, 0.0f, __int_as_float(-1)}, w = h;
     if (d.active) td_finish(p, d, best, best_i, h, w);

@@ -1,5 +1,5 @@
 """Scenes and populations that put the decisive primitives of every scan-mode query on the seams between the LDS chunks of
-kQueryChunk = 1024 triangle records (csrc/rt_query.hpp; test_seam_cases.py without a device, test_gpu_query_seams.py on one):
+kQueryChunk = 1024 triangle records (csrc/rt_scan.hpp; test_seam_cases.py without a device, test_gpu_query_seams.py on one):
 the last record of a chunk, the first of the next, the last record of the scene, a chunk of exactly 1024 and one of a single
 record.  A helper, not a test.  Everything is deterministic and needs no device.
 
@@ -35,7 +35,7 @@ from query_expect import FLT_MAX, HIT_DTYPE, adversarial_rays, edge_rows  # noqa
 
 f32 = np.float32
 INF = f32(np.inf)
-CHUNK = 1024                                   # rtk::kQueryChunk
+CHUNK = 1024                                   # rtk::kQueryChunk (csrc/rt_scan.hpp)
 SEAMS = (1024, 2048)
 SIZES = (1023, 1024, 1025, 2048, 2049)
 AXES = ((1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1))     # petal k stretches along AXES[k]
