@@ -1,15 +1,20 @@
-// rt_query_api.hpp -- the ray-query entry points of include/rt_mi355x.h (rt_tracer_intersect*, rt_tracer_pick,
-// rt_tracer_focus_at, rt_tracer_occluded*, rt_tracer_exposure*, rt_tracer_intersect_all*) and the point queries (rt_tracer_closest_point*,
-// rt_tracer_closest_all*, rt_tracer_signed_distance*, rt_tracer_closest_sides*) and the region queries (rt_tracer_overlap*, rt_tracer_overlap_triangles*, rt_tracer_overlap_hexahedra*) and the swept query
-// (rt_tracer_sphere_cast*) and the triangle-shaped proximity query (rt_tracer_triangle_distance*).
-// Included by rt_tracer.hip.
+// rt_query_api.hpp -- the query entry points of include/rt_mi355x.h.  Included by rt_tracer.hip.
+//
+// Every query that takes arrays has a host form and a _device form, and both are one call of run_query with the query's
+// description: where the call runs (QueryWhere), its input and output arrays (QueryIn, QueryOut: pointer, bytes, the alignment
+// the _device form demands, whether it may be null), the _device form's alignment message, the query's own argument check,
+// what it prepares (the signed queries' feature table) and what it enqueues on device pointers.  run_query is the path: the
+// checks in one order, all before the lock; query_entry (api_mu, a sharded handle forwarded to its first band); the rest under
+// guarded() -- n = 0 returns, the device made current, the preparation, for the host form the caller's arrays staged through
+// QueryState::in / ::out in the order of the description, the enqueue, and for the host form the copies back and the one wait.
+// rt_tracer_pick, which checks its pixels under the lock, uses the same checks and the same body (query_body).
 //
 // A query is not an exclusive() entry point: it never cancels or joins a running Trace.  It is serialised with the other API
 // calls by api_mu, reads only the scene and a snapshot of the camera (params(), under state_mu), and runs on a stream of its
 // own (QueryState::stream_q, created by the first query) or on the caller's.  QueryState::done, recorded behind every query, is what the scene
 // uploads and destroy wait for before they touch the records a query may still read: every launch goes through enqueue_launch,
-// the one place that waits for and records it.  Every entry point is query_call (or, with a check of its own, query_entry):
-// api_mu, a sharded handle forwarded to its first band, else the body under guarded().
+// the one place that waits for and records it.  The entry points that take no arrays are query_call (or, with a check of their
+// own, query_entry).
 #pragma once
 #include <cmath>
 #include <initializer_list>
@@ -29,12 +34,41 @@ inline int query_k(const rt_tracer* t, size_t n) {
   return n >= 4u * kResidentLanes ? 4 : n >= 2u * kResidentLanes ? 2 : 1;
 }
 
-// The argument checks, made before the lock.  A batch of n != 0 needs every array and a count the kernels' 32-bit indices hold.
-inline bool query_args_ok(rt_tracer* t, size_t n, std::initializer_list<const void*> arrays) {
+// Where a query call runs.  The host form takes host arrays, stages them on the query stream and waits for it; the _device
+// form takes device pointers and enqueues on the caller's stream, of which null is a legitimate one: hence the tag.
+struct QueryWhere { bool device; hipStream_t stream; };
+inline QueryWhere on_host() { return {false, nullptr}; }
+inline QueryWhere on_device(void* stream) { return {true, static_cast<hipStream_t>(stream)}; }
+
+// One array of a query call: the caller's pointer, its bytes (0: nothing to stage), the alignment its kernel's loads and stores
+// need of a _device form's pointer, and whether the caller may pass null.  A call has at most two of each direction.
+template <class Void>
+struct QueryArray { Void* p; size_t bytes; uintptr_t align; bool optional = false; };
+using QueryIn = QueryArray<const void>;
+using QueryOut = QueryArray<void>;
+using QueryIns = std::initializer_list<QueryIn>;
+using QueryOuts = std::initializer_list<QueryOut>;
+
+// The argument checks, made before the lock.  A batch of n != 0 needs its arrays and a count the kernels' 32-bit indices hold.
+inline bool query_args_ok(rt_tracer* t, size_t n, bool arrays_present) {
   if (n == 0u) return true;
-  for (const void* a : arrays)
-    if (!a) { t->set_error("query: null array"); return false; }
+  if (!arrays_present) { t->set_error("query: null array"); return false; }
   if (n > kQueryMaxRays) { t->set_error(fmt("query: %zu rays (at most %zu)", n, kQueryMaxRays)); return false; }
+  return true;
+}
+
+// ... of a described call: every array that is not optional, and for a _device form every pointer on its alignment (null is on
+// any), else `misaligned`, the entry point's own sentence
+inline bool query_arrays_ok(rt_tracer* t, QueryWhere w, size_t n, QueryIns in, QueryOuts out, const char* misaligned) {
+  bool present = true, aligned = true;
+  const auto look = [&](const void* p, uintptr_t align, bool optional) {
+    present = present && (p || optional);
+    aligned = aligned && reinterpret_cast<uintptr_t>(p) % align == 0u;
+  };
+  for (const QueryIn& a : in) look(a.p, a.align, a.optional);
+  for (const QueryOut& a : out) look(a.p, a.align, a.optional);
+  if (!query_args_ok(t, n, present)) return false;
+  if (n != 0u && w.device && !aligned) { t->set_error(misaligned); return false; }
   return true;
 }
 
@@ -44,15 +78,7 @@ inline bool query_row_ok(rt_tracer* t, const char* who, const char* what, uint32
   t->set_error(fmt("%s: %s = %u (1 to %u)", who, what, k, RT_MAX_HITS));
   return false;
 }
-
-// the device pointers of a _device entry point, each with the alignment its kernel's loads and stores need
-struct AlignedTo { const void* p; uintptr_t bytes; };
-inline bool query_aligned_ok(rt_tracer* t, size_t n, std::initializer_list<AlignedTo> ptrs, const char* message) {
-  if (n == 0u) return true;
-  for (const AlignedTo& a : ptrs)
-    if (reinterpret_cast<uintptr_t>(a.p) % a.bytes != 0u) { t->set_error(message); return false; }
-  return true;
-}
+inline bool no_check(rt_tracer*) { return true; }
 
 // An entry point on a non-null handle: its API calls serialised, a sharded handle answered by its first band (whose error text
 // becomes the handle's), any other by rest().
@@ -89,6 +115,44 @@ void staged_out(void* dst, const DevArray<unsigned char>& d, size_t n, hipStream
 }
 // what a host-array entry point starts with: the tracer's device current, the query stream made
 inline hipStream_t host_query_stream(rt_tracer* t) { t->use_device(); return t->queries.stream(); }
+
+// What a described call does under the lock once its arguments are in order.  enqueue(t, in, out, st) gets the device pointers
+// of the arrays in the description's order -- the caller's own in the _device form, the staging buffers of the same index in the
+// host form, null for an array that was left out or has no bytes -- and issues the launches on st.  prepare(t), if any, runs
+// before anything of the call is staged or enqueued (it may wait for the queries in flight).
+using DevIn = const void* const*;
+using DevOut = void* const*;
+template <class Enqueue>
+int query_body(rt_tracer* t, QueryWhere w, size_t n, QueryIns in, QueryOuts out, void (*prepare)(rt_tracer*), const Enqueue& enqueue) {
+  return guarded(t, [&] {
+    if (n == 0u) return;
+    QueryState& q = t->queries;
+    hipStream_t st = w.stream;
+    if (w.device) t->use_device(); else st = host_query_stream(t);
+    if (prepare) prepare(t);
+    const void* d_in[2] = {nullptr, nullptr};
+    void* d_out[2] = {nullptr, nullptr};
+    size_t i = 0;
+    for (const QueryIn& a : in) { d_in[i] = w.device ? a.p : a.p && a.bytes ? staged_in<unsigned char>(q.in[i], a.p, a.bytes, st) : nullptr; ++i; }
+    i = 0;
+    for (const QueryOut& a : out) { d_out[i] = w.device ? a.p : a.p && a.bytes ? room<unsigned char>(q.out[i], a.bytes) : nullptr; ++i; }
+    enqueue(t, d_in, d_out, st);
+    if (w.device) return;
+    i = 0;
+    for (const QueryOut& a : out) { if (d_out[i]) staged_out<unsigned char>(a.p, q.out[i], a.bytes, st); ++i; }
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+// The one path of a query with arrays, in either form: the null handle, the query's own check(t) (whatever n is), the arrays, then
+// the lock; a sharded handle is answered by this same call on its first band.
+template <class Check, class Enqueue>
+int run_query(rt_tracer* t, QueryWhere w, size_t n, QueryIns in, QueryOuts out, const char* misaligned, const Check& check,
+              void (*prepare)(rt_tracer*), const Enqueue& enqueue) {
+  if (!t || !check(t) || !query_arrays_ok(t, w, n, in, out, misaligned)) return RT_ERR_INVALID;
+  return query_entry(t, [&](rt_tracer* band) { return run_query(band, w, n, in, out, misaligned, check, prepare, enqueue); },
+                     [&] { return query_body(t, w, n, in, out, prepare, enqueue); });
+}
 
 // RT_ACCEL_REFIT: the tree of an earlier upload with as many records as the scene has triangles takes the new records and
 // new boxes on the device (rt_refit.hpp), all on the query stream: the gather, one launch per level from the deepest up,
@@ -207,21 +271,6 @@ inline void enqueue_query(rt_tracer* t, size_t n, const float* rays, const uint3
   });
 }
 
-// segments -> one byte per ray.  The hit rule plays no part (an OR over the primitives), so the flags stay 0.
-inline void enqueue_occluded(rt_tracer* t, size_t n, const float* segs, uint8_t* occluded, hipStream_t st) {
-  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return rtk::launch_occluded(p, b, t->fma, query_k(t, n), static_cast<uint32_t>(n), segs, occluded, st);
-  });
-}
-
-// points and a direction table -> one 64-bit mask per point (rt_exposure.hpp).  An OR per ray, as enqueue_occluded: the flags stay 0.
-inline void enqueue_exposure(rt_tracer* t, size_t n, const float* points, const float* dirs, uint32_t n_dirs, uint32_t flags,
-                             uint64_t* masks, hipStream_t st) {
-  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return rtk::launch_exposure(p, b, t->fma, static_cast<uint32_t>(n), points, dirs, n_dirs, flags, masks, st);
-  });
-}
-
 // the direction count and the flags of the exposure entry points, checked whatever n is; t may be null (rt_dbg_exposure_rays)
 inline bool exposure_args_ok(rt_tracer* t, const char* who, uint32_t n_dirs, uint32_t flags) {
   std::string msg;
@@ -232,14 +281,6 @@ inline bool exposure_args_ok(rt_tracer* t, const char* who, uint32_t n_dirs, uin
   return false;
 }
 
-// segments -> rows of max_hits records and one count per ray.  The order rule names no hit rule, so the flags stay 0.
-inline void enqueue_intersect_all(rt_tracer* t, size_t n, const float* segs, uint32_t max_hits, float4* hits, uint32_t* counts,
-                                  hipStream_t st) {
-  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return rtk::launch_allhits(p, b, t->fma, static_cast<uint32_t>(n), segs, max_hits, hits, counts, st);
-  });
-}
-
 // points -> one record per point.  One arithmetic for both math modes and no hit rule: the flags stay 0.  The tree is the ray
 // queries' (ensure_query_tree, so RT_ACCEL_REFIT applies).
 inline void enqueue_closest(rt_tracer* t, size_t n, const float* pts, float4* hits, hipStream_t st) {
@@ -248,91 +289,16 @@ inline void enqueue_closest(rt_tracer* t, size_t n, const float* pts, float4* hi
   });
 }
 
-// points (and their cursors, or nullptr) -> rows of max_hits records and one count per point, with enqueue_closest's tree and rho_c
-inline void enqueue_closest_all(rt_tracer* t, size_t n, const float* pts, const float4* after, uint32_t max_hits, float4* hits,
-                                uint32_t* counts, hipStream_t st) {
-  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return rtk::launch_nearest(p, b, closest_rho(t), static_cast<uint32_t>(n), pts, after, max_hits, hits, counts, st);
-  });
-}
-
 // What the entry points of one region shape (boxes, query triangles, hexahedra) differ in: the floats per query, the array's name in
-// the alignment message, the launch function, and the entry points themselves, which query_call forwards to on a band's tracer.
+// the alignment message and the launch function.
 struct RegionShape {
   size_t floats;
   const char* array;
   hipError_t (*launch)(const rtk::TraceParams&, const rtk::BvhParams*, uint32_t, const float*, const int*, uint32_t, int*, uint32_t*,
                        hipStream_t);
-  int (*host)(rt_tracer*, const float*, const int32_t*, size_t, uint32_t, int32_t*, uint32_t*);
-  int (*device)(rt_tracer*, const float*, const int32_t*, size_t, uint32_t, int32_t*, uint32_t*, void*);
 };
 
-// queries (and their cursors, or nullptr) -> rows of max_hits prims and one total per query (rt_overlap.hpp, rt_trioverlap.hpp,
-// rt_hexoverlap.hpp).  One arithmetic for both math modes: the flags stay 0.  The tree is the ray queries' (ensure_query_tree, so
-// RT_ACCEL_REFIT applies); no rho is passed.
-inline void enqueue_region(rt_tracer* t, const RegionShape& s, size_t n, const float* queries, const int32_t* after, uint32_t max_hits,
-                           int32_t* prims, uint32_t* counts, hipStream_t st) {
-  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return s.launch(p, b, static_cast<uint32_t>(n), queries, after, max_hits, prims, counts, st);
-  });
-}
-
-// sweeps -> one record per sweep (rt_spherecast.hpp).  One arithmetic for both math modes and no hit rule: the flags stay 0.  The
-// tree is the ray queries' (ensure_query_tree, so RT_ACCEL_REFIT applies); the walk's allowance beyond r takes the tracer's slack.
 static_assert(RT_SWEEP_SLACK == rtk::kSweepSlack, "include/rt_mi355x.h and rt_kernels.hpp state one slack");
-inline void enqueue_sphere_cast(rt_tracer* t, size_t n, const float* sweeps, float4* hits, hipStream_t st) {
-  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return rtk::launch_sphere_cast(p, b, static_cast<float>(t->queries.slack_milli) / 1000.0f, static_cast<uint32_t>(n), sweeps, hits, st);
-  });
-}
-
-// query triangles -> one record and one witness per triangle (rt_tridistance.hpp), with enqueue_closest's tree, flags and rho_c
-inline void enqueue_triangle_distance(rt_tracer* t, size_t n, const float* tris, float4* hits, float4* witness, hipStream_t st) {
-  enqueue_launch(t, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
-    return rtk::launch_triangle_distance(p, b, closest_rho(t), static_cast<uint32_t>(n), tris, hits, witness, st);
-  });
-}
-
-// the arguments of the overlap entry points (boxes, query triangles or hexahedra): max_hits checked whatever n is (0 is allowed: counts
-// only), then the arrays
-inline bool overlap_args_ok(rt_tracer* t, const char* who, size_t n, const float* boxes, uint32_t max_hits, const int32_t* prims,
-                            const uint32_t* counts) {
-  if (max_hits > RT_MAX_HITS) { t->set_error(fmt("%s: max_hits = %u (0 to %u)", who, max_hits, RT_MAX_HITS)); return false; }
-  if (!query_args_ok(t, n, {boxes, counts})) return false;
-  if (n != 0u && max_hits != 0u && !prims) { t->set_error("query: null array"); return false; }
-  return true;
-}
-
-// the staged host form of a region query
-inline int region_host(rt_tracer* t, const RegionShape& s, const char* who, const float* queries, const int32_t* after, size_t n,
-                       uint32_t max_hits, int32_t* prims, uint32_t* counts) {
-  if (!t || !overlap_args_ok(t, who, n, queries, max_hits, prims, counts)) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return s.host(b, queries, after, n, max_hits, prims, counts); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_queries = staged_in<float>(t->queries.in[0], queries, n * s.floats, st);
-    const int32_t* d_after = after ? staged_in<int32_t>(t->queries.in[1], after, n, st) : nullptr;
-    int32_t* d_prims = max_hits != 0u ? room<int32_t>(t->queries.out[0], n * max_hits) : nullptr;
-    enqueue_region(t, s, n, d_queries, d_after, max_hits, d_prims, room<uint32_t>(t->queries.out[1], n), st);
-    if (max_hits != 0u) staged_out<int32_t>(prims, t->queries.out[0], n * max_hits, st);
-    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
-}
-
-// and its _device form
-inline int region_device(rt_tracer* t, const RegionShape& s, const char* who, const float* queries, const int32_t* after, size_t n,
-                         uint32_t max_hits, int32_t* prims, uint32_t* counts, void* stream) {
-  if (!t || !overlap_args_ok(t, who, n, queries, max_hits, prims, counts) ||
-      !query_aligned_ok(t, n, {{queries, 16u}, {after, 4u}, {prims, 4u}, {counts, 4u}},
-                        fmt("%s: %s must be 16-byte aligned, after, prims and counts 4-byte aligned", who, s.array).c_str()))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return s.device(b, queries, after, n, max_hits, prims, counts, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_region(t, s, n, queries, after, max_hits, prims, counts, static_cast<hipStream_t>(stream));
-  });
-}
 
 // The signed queries' feature table (rt_features_host.hpp) of the current scene: built on the host from the
 // tracer's copy of the rows of its last upload by the first signed query after that upload, keyed to scene_generation as
@@ -498,76 +464,53 @@ int rt_dbg_query_tree_read(rt_tracer* t, void* nodes, size_t node_capacity_bytes
   });
 }
 
-int rt_tracer_intersect(rt_tracer* t, const float* rays, size_t n, rt_hit* hits) {
-  if (!t || !query_args_ok(t, n, {rays, hits})) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_intersect(b, rays, n, hits); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_rays = staged_in<float>(t->queries.in[0], rays, n * 6u, st);
-    enqueue_query(t, n, d_rays, nullptr, nullptr, room<float4>(t->queries.out[0], n), st);
-    staged_out<float4>(hits, t->queries.out[0], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+// rays -> hits, under the tracer's hit rule
+static int intersect_query(rt_tracer* t, QueryWhere w, const float* rays, size_t n, rt_hit* hits) {
+  return run_query(t, w, n, {{rays, n * 24u, 4u}}, {{hits, n * 16u, 16u}},
+                   "rt_tracer_intersect_device: hits must be 16-byte aligned, rays 4-byte aligned", no_check, nullptr,
+                   [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {
+                     enqueue_query(h, n, static_cast<const float*>(in[0]), nullptr, nullptr, static_cast<float4*>(out[0]), st);
+                   });
 }
-
+int rt_tracer_intersect(rt_tracer* t, const float* rays, size_t n, rt_hit* hits) { return intersect_query(t, on_host(), rays, n, hits); }
 int rt_tracer_intersect_device(rt_tracer* t, const float* rays, size_t n, rt_hit* hits, void* stream) {
-  if (!t || !query_args_ok(t, n, {rays, hits}) ||
-      !query_aligned_ok(t, n, {{hits, 16u}, {rays, 4u}}, "rt_tracer_intersect_device: hits must be 16-byte aligned, rays 4-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_intersect_device(b, rays, n, hits, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_query(t, n, rays, nullptr, nullptr, reinterpret_cast<float4*>(hits), static_cast<hipStream_t>(stream));
-  });
+  return intersect_query(t, on_device(stream), rays, n, hits);
 }
 
-int rt_tracer_occluded(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded) {
-  if (!t || !query_args_ok(t, n, {segs, occluded})) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_occluded(b, segs, n, occluded); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_segs = staged_in<float>(t->queries.in[0], segs, n * 8u, st);
-    enqueue_occluded(t, n, d_segs, room<uint8_t>(t->queries.out[0], n), st);
-    staged_out<uint8_t>(occluded, t->queries.out[0], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+// segments -> one byte per ray.  The hit rule plays no part (an OR over the primitives), so the flags stay 0.
+static int occluded_query(rt_tracer* t, QueryWhere w, const float* segs, size_t n, uint8_t* occluded) {
+  return run_query(t, w, n, {{segs, n * 32u, 16u}}, {{occluded, n, 1u}}, "rt_tracer_occluded_device: segs must be 16-byte aligned",
+                   no_check, nullptr, [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {
+                     enqueue_launch(h, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+                       return rtk::launch_occluded(p, b, h->fma, query_k(h, n), static_cast<uint32_t>(n), static_cast<const float*>(in[0]),
+                                                   static_cast<uint8_t*>(out[0]), st);
+                     });
+                   });
 }
-
+int rt_tracer_occluded(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded) { return occluded_query(t, on_host(), segs, n, occluded); }
 int rt_tracer_occluded_device(rt_tracer* t, const float* segs, size_t n, uint8_t* occluded, void* stream) {
-  if (!t || !query_args_ok(t, n, {segs, occluded}) ||
-      !query_aligned_ok(t, n, {{segs, 16u}}, "rt_tracer_occluded_device: segs must be 16-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_occluded_device(b, segs, n, occluded, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_occluded(t, n, segs, occluded, static_cast<hipStream_t>(stream));
-  });
+  return occluded_query(t, on_device(stream), segs, n, occluded);
 }
 
+// points and a direction table -> one 64-bit mask per point (rt_exposure.hpp).  An OR per ray, as Occluded: the flags stay 0.
+static int exposure_query(rt_tracer* t, QueryWhere w, const char* who, const float* points, size_t n, const float* dirs, uint32_t n_dirs,
+                    uint32_t flags, uint64_t* masks) {
+  return run_query(t, w, n, {{points, n * 32u, 16u}, {dirs, size_t(n_dirs) * 16u, 16u}}, {{masks, n * 8u, 8u}},
+                   "rt_tracer_exposure_device: points and dirs must be 16-byte aligned, masks 8-byte aligned",
+                   [&](rt_tracer* h) { return exposure_args_ok(h, who, n_dirs, flags); }, nullptr,
+                   [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {
+                     enqueue_launch(h, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+                       return rtk::launch_exposure(p, b, h->fma, static_cast<uint32_t>(n), static_cast<const float*>(in[0]),
+                                                   static_cast<const float*>(in[1]), n_dirs, flags, static_cast<uint64_t*>(out[0]), st);
+                     });
+                   });
+}
 int rt_tracer_exposure(rt_tracer* t, const float* points, size_t n, const float* dirs, uint32_t n_dirs, uint32_t flags, uint64_t* masks) {
-  if (!t || !exposure_args_ok(t, "rt_tracer_exposure", n_dirs, flags) || !query_args_ok(t, n, {points, dirs, masks})) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_exposure(b, points, n, dirs, n_dirs, flags, masks); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_points = staged_in<float>(t->queries.in[0], points, n * 8u, st);
-    const float* d_dirs = staged_in<float>(t->queries.in[1], dirs, n_dirs * 4u, st);
-    enqueue_exposure(t, n, d_points, d_dirs, n_dirs, flags, room<uint64_t>(t->queries.out[0], n), st);
-    staged_out<uint64_t>(masks, t->queries.out[0], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+  return exposure_query(t, on_host(), "rt_tracer_exposure", points, n, dirs, n_dirs, flags, masks);
 }
-
 int rt_tracer_exposure_device(rt_tracer* t, const float* points, size_t n, const float* dirs, uint32_t n_dirs, uint32_t flags,
                               uint64_t* masks, void* stream) {
-  if (!t || !exposure_args_ok(t, "rt_tracer_exposure_device", n_dirs, flags) || !query_args_ok(t, n, {points, dirs, masks}) ||
-      !query_aligned_ok(t, n, {{points, 16u}, {dirs, 16u}, {masks, 8u}},
-                        "rt_tracer_exposure_device: points and dirs must be 16-byte aligned, masks 8-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_exposure_device(b, points, n, dirs, n_dirs, flags, masks, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_exposure(t, n, points, dirs, n_dirs, flags, masks, static_cast<hipStream_t>(stream));
-  });
+  return exposure_query(t, on_device(stream), "rt_tracer_exposure_device", points, n, dirs, n_dirs, flags, masks);
 }
 
 int rt_dbg_exposure_rays(rt_tracer* t, const float* points, size_t n, const float* dirs, uint32_t n_dirs, uint32_t flags, float* segs_out) {
@@ -576,7 +519,7 @@ int rt_dbg_exposure_rays(rt_tracer* t, const float* points, size_t n, const floa
     if (n != 0u && (!points || !dirs || !segs_out)) { set_global_error("rt_dbg_exposure_rays: null array"); return RT_ERR_INVALID; }
     return guarded(nullptr, [&] { rtk::exposure_rays_host(n, points, dirs, n_dirs, flags, segs_out); });
   }
-  if (!query_args_ok(t, n, {points, dirs, segs_out})) return RT_ERR_INVALID;
+  if (!query_args_ok(t, n, points && dirs && segs_out)) return RT_ERR_INVALID;
   if (n * static_cast<uint64_t>(n_dirs) >= 0x80000000ull) { t->set_error("rt_dbg_exposure_rays: n * n_dirs must be below 2^31"); return RT_ERR_INVALID; }
   return query_call(t, [&](rt_tracer* b) { return rt_dbg_exposure_rays(b, points, n, dirs, n_dirs, flags, segs_out); }, [&] {
     if (n == 0u) return;
@@ -592,222 +535,174 @@ int rt_dbg_exposure_rays(rt_tracer* t, const float* points, size_t n, const floa
   });
 }
 
-int rt_tracer_intersect_all(rt_tracer* t, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts) {
-  if (!t || !query_row_ok(t, "rt_tracer_intersect_all", "max_hits", max_hits) || !query_args_ok(t, n, {segs, hits, counts})) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_intersect_all(b, segs, n, max_hits, hits, counts); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_segs = staged_in<float>(t->queries.in[0], segs, n * 8u, st);
-    enqueue_intersect_all(t, n, d_segs, max_hits, room<float4>(t->queries.out[0], n * max_hits), room<uint32_t>(t->queries.out[1], n), st);
-    staged_out<float4>(hits, t->queries.out[0], n * max_hits, st);
-    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+// segments -> rows of max_hits records and one count per ray.  The order rule names no hit rule, so the flags stay 0.
+static int intersect_all_query(rt_tracer* t, QueryWhere w, const char* who, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits,
+                               uint32_t* counts) {
+  return run_query(t, w, n, {{segs, n * 32u, 16u}}, {{hits, n * max_hits * 16u, 16u}, {counts, n * 4u, 4u}},
+                   "rt_tracer_intersect_all_device: segs and hits must be 16-byte aligned, counts 4-byte aligned",
+                   [&](rt_tracer* h) { return query_row_ok(h, who, "max_hits", max_hits); }, nullptr,
+                   [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {
+                     enqueue_launch(h, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+                       return rtk::launch_allhits(p, b, h->fma, static_cast<uint32_t>(n), static_cast<const float*>(in[0]), max_hits,
+                                                  static_cast<float4*>(out[0]), static_cast<uint32_t*>(out[1]), st);
+                     });
+                   });
 }
-
+int rt_tracer_intersect_all(rt_tracer* t, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts) {
+  return intersect_all_query(t, on_host(), "rt_tracer_intersect_all", segs, n, max_hits, hits, counts);
+}
 int rt_tracer_intersect_all_device(rt_tracer* t, const float* segs, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts,
                                    void* stream) {
-  if (!t || !query_row_ok(t, "rt_tracer_intersect_all_device", "max_hits", max_hits) || !query_args_ok(t, n, {segs, hits, counts}) ||
-      !query_aligned_ok(t, n, {{segs, 16u}, {hits, 16u}, {counts, 4u}},
-                        "rt_tracer_intersect_all_device: segs and hits must be 16-byte aligned, counts 4-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_intersect_all_device(b, segs, n, max_hits, hits, counts, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_intersect_all(t, n, segs, max_hits, reinterpret_cast<float4*>(hits), counts, static_cast<hipStream_t>(stream));
-  });
+  return intersect_all_query(t, on_device(stream), "rt_tracer_intersect_all_device", segs, n, max_hits, hits, counts);
 }
 
-int rt_tracer_closest_point(rt_tracer* t, const float* pts, size_t n, rt_hit* out) {
-  if (!t || !query_args_ok(t, n, {pts, out})) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_point(b, pts, n, out); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_pts = staged_in<float>(t->queries.in[0], pts, n * 4u, st);
-    enqueue_closest(t, n, d_pts, room<float4>(t->queries.out[0], n), st);
-    staged_out<float4>(out, t->queries.out[0], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+static int closest_point_query(rt_tracer* t, QueryWhere w, const float* pts, size_t n, rt_hit* out) {
+  return run_query(t, w, n, {{pts, n * 16u, 16u}}, {{out, n * 16u, 16u}}, "rt_tracer_closest_point_device: pts and out must be 16-byte aligned",
+                   no_check, nullptr, [&](rt_tracer* h, DevIn in, DevOut d_out, hipStream_t st) {
+                     enqueue_closest(h, n, static_cast<const float*>(in[0]), static_cast<float4*>(d_out[0]), st);
+                   });
 }
-
+int rt_tracer_closest_point(rt_tracer* t, const float* pts, size_t n, rt_hit* out) { return closest_point_query(t, on_host(), pts, n, out); }
 int rt_tracer_closest_point_device(rt_tracer* t, const float* pts, size_t n, rt_hit* out, void* stream) {
-  if (!t || !query_args_ok(t, n, {pts, out}) ||
-      !query_aligned_ok(t, n, {{pts, 16u}, {out, 16u}}, "rt_tracer_closest_point_device: pts and out must be 16-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_point_device(b, pts, n, out, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_closest(t, n, pts, reinterpret_cast<float4*>(out), static_cast<hipStream_t>(stream));
-  });
+  return closest_point_query(t, on_device(stream), pts, n, out);
 }
 
+// points (and their cursors, or nullptr) -> rows of max_hits records and one count per point, with enqueue_closest's tree and rho_c
+static int closest_all_query(rt_tracer* t, QueryWhere w, const char* who, const float* pts, const rt_hit* after, size_t n, uint32_t max_hits,
+                             rt_hit* hits, uint32_t* counts) {
+  return run_query(t, w, n, {{pts, n * 16u, 16u}, {after, n * 16u, 16u, true}}, {{hits, n * max_hits * 16u, 16u}, {counts, n * 4u, 4u}},
+                   "rt_tracer_closest_all_device: pts, after and hits must be 16-byte aligned, counts 4-byte aligned",
+                   [&](rt_tracer* h) { return query_row_ok(h, who, "max_hits", max_hits); }, nullptr,
+                   [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {
+                     enqueue_launch(h, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+                       return rtk::launch_nearest(p, b, closest_rho(h), static_cast<uint32_t>(n), static_cast<const float*>(in[0]),
+                                                  static_cast<const float4*>(in[1]), max_hits, static_cast<float4*>(out[0]),
+                                                  static_cast<uint32_t*>(out[1]), st);
+                     });
+                   });
+}
 int rt_tracer_closest_all(rt_tracer* t, const float* pts, const rt_hit* after, size_t n, uint32_t max_hits, rt_hit* hits,
                           uint32_t* counts) {
-  if (!t || !query_row_ok(t, "rt_tracer_closest_all", "max_hits", max_hits) || !query_args_ok(t, n, {pts, hits, counts})) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_all(b, pts, after, n, max_hits, hits, counts); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_pts = staged_in<float>(t->queries.in[0], pts, n * 4u, st);
-    const float4* d_after = after ? staged_in<float4>(t->queries.in[1], after, n, st) : nullptr;
-    enqueue_closest_all(t, n, d_pts, d_after, max_hits, room<float4>(t->queries.out[0], n * max_hits), room<uint32_t>(t->queries.out[1], n), st);
-    staged_out<float4>(hits, t->queries.out[0], n * max_hits, st);
-    staged_out<uint32_t>(counts, t->queries.out[1], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+  return closest_all_query(t, on_host(), "rt_tracer_closest_all", pts, after, n, max_hits, hits, counts);
 }
-
 int rt_tracer_closest_all_device(rt_tracer* t, const float* pts, const rt_hit* after, size_t n, uint32_t max_hits, rt_hit* hits,
                                  uint32_t* counts, void* stream) {
-  if (!t || !query_row_ok(t, "rt_tracer_closest_all_device", "max_hits", max_hits) || !query_args_ok(t, n, {pts, hits, counts}) ||
-      !query_aligned_ok(t, n, {{pts, 16u}, {after, 16u}, {hits, 16u}, {counts, 4u}},
-                        "rt_tracer_closest_all_device: pts, after and hits must be 16-byte aligned, counts 4-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_all_device(b, pts, after, n, max_hits, hits, counts, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_closest_all(t, n, pts, reinterpret_cast<const float4*>(after), max_hits, reinterpret_cast<float4*>(hits), counts,
-                        static_cast<hipStream_t>(stream));
-  });
+  return closest_all_query(t, on_device(stream), "rt_tracer_closest_all_device", pts, after, n, max_hits, hits, counts);
 }
 
+static int signed_distance_query(rt_tracer* t, QueryWhere w, const float* pts, size_t n, rt_hit* hits, rt_side* sides) {
+  return run_query(t, w, n, {{pts, n * 16u, 16u}}, {{hits, n * 16u, 16u}, {sides, n * 8u, 8u}},
+                   "rt_tracer_signed_distance_device: pts and hits must be 16-byte aligned, sides 8-byte aligned", no_check, ensure_feature_table,
+                   [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {   // the closest kernel's output is the sides kernel's input
+                     enqueue_closest(h, n, static_cast<const float*>(in[0]), static_cast<float4*>(out[0]), st);
+                     enqueue_sides(h, n, 1u, static_cast<const float*>(in[0]), static_cast<const float4*>(out[0]), out[1], st);
+                   });
+}
 int rt_tracer_signed_distance(rt_tracer* t, const float* pts, size_t n, rt_hit* hits, rt_side* sides) {
-  if (!t || !query_args_ok(t, n, {pts, hits, sides})) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_signed_distance(b, pts, n, hits, sides); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    ensure_feature_table(t);
-    const float* d_pts = staged_in<float>(t->queries.in[0], pts, n * 4u, st);
-    float4* const d_hits = room<float4>(t->queries.out[0], n);           // the closest kernel's output is the sides kernel's input
-    enqueue_closest(t, n, d_pts, d_hits, st);
-    enqueue_sides(t, n, 1u, d_pts, d_hits, room<uint2>(t->queries.out[1], n), st);
-    staged_out<float4>(hits, t->queries.out[0], n, st);
-    staged_out<uint2>(sides, t->queries.out[1], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+  return signed_distance_query(t, on_host(), pts, n, hits, sides);
 }
-
 int rt_tracer_signed_distance_device(rt_tracer* t, const float* pts, size_t n, rt_hit* hits, rt_side* sides, void* stream) {
-  if (!t || !query_args_ok(t, n, {pts, hits, sides}) ||
-      !query_aligned_ok(t, n, {{pts, 16u}, {hits, 16u}, {sides, 8u}},
-                        "rt_tracer_signed_distance_device: pts and hits must be 16-byte aligned, sides 8-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_signed_distance_device(b, pts, n, hits, sides, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    ensure_feature_table(t);
-    enqueue_closest(t, n, pts, reinterpret_cast<float4*>(hits), static_cast<hipStream_t>(stream));
-    enqueue_sides(t, n, 1u, pts, reinterpret_cast<const float4*>(hits), sides, static_cast<hipStream_t>(stream));
-  });
+  return signed_distance_query(t, on_device(stream), pts, n, hits, sides);
 }
 
+static int closest_sides_query(rt_tracer* t, QueryWhere w, const char* who, const float* pts, const rt_hit* hits, size_t n, uint32_t per_point,
+                               rt_side* sides) {
+  return run_query(t, w, n, {{pts, n * 16u, 16u}, {hits, n * per_point * 16u, 16u}}, {{sides, n * per_point * 8u, 8u}},
+                   "rt_tracer_closest_sides_device: pts and hits must be 16-byte aligned, sides 8-byte aligned",
+                   [&](rt_tracer* h) { return query_row_ok(h, who, "per_point", per_point); }, ensure_feature_table,
+                   [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {
+                     enqueue_sides(h, n, per_point, static_cast<const float*>(in[0]), static_cast<const float4*>(in[1]), out[0], st);
+                   });
+}
 int rt_tracer_closest_sides(rt_tracer* t, const float* pts, const rt_hit* hits, size_t n, uint32_t per_point, rt_side* sides) {
-  if (!t || !query_row_ok(t, "rt_tracer_closest_sides", "per_point", per_point) || !query_args_ok(t, n, {pts, hits, sides})) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_sides(b, pts, hits, n, per_point, sides); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    ensure_feature_table(t);
-    const float* d_pts = staged_in<float>(t->queries.in[0], pts, n * 4u, st);
-    const float4* d_hits = staged_in<float4>(t->queries.in[1], hits, n * per_point, st);
-    enqueue_sides(t, n, per_point, d_pts, d_hits, room<uint2>(t->queries.out[0], n * per_point), st);
-    staged_out<uint2>(sides, t->queries.out[0], n * per_point, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+  return closest_sides_query(t, on_host(), "rt_tracer_closest_sides", pts, hits, n, per_point, sides);
 }
-
 int rt_tracer_closest_sides_device(rt_tracer* t, const float* pts, const rt_hit* hits, size_t n, uint32_t per_point, rt_side* sides,
                                    void* stream) {
-  if (!t || !query_row_ok(t, "rt_tracer_closest_sides_device", "per_point", per_point) || !query_args_ok(t, n, {pts, hits, sides}) ||
-      !query_aligned_ok(t, n, {{pts, 16u}, {hits, 16u}, {sides, 8u}},
-                        "rt_tracer_closest_sides_device: pts and hits must be 16-byte aligned, sides 8-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_closest_sides_device(b, pts, hits, n, per_point, sides, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    ensure_feature_table(t);
-    enqueue_sides(t, n, per_point, pts, reinterpret_cast<const float4*>(hits), sides, static_cast<hipStream_t>(stream));
-  });
+  return closest_sides_query(t, on_device(stream), "rt_tracer_closest_sides_device", pts, hits, n, per_point, sides);
 }
 
-static const RegionShape kBoxes{8u, "boxes", rtk::launch_overlap, rt_tracer_overlap, rt_tracer_overlap_device};
-static const RegionShape kTriangles{12u, "tris", rtk::launch_overlap_triangles, rt_tracer_overlap_triangles, rt_tracer_overlap_triangles_device};
-static const RegionShape kHexahedra{32u, "hexa", rtk::launch_overlap_hexahedra, rt_tracer_overlap_hexahedra, rt_tracer_overlap_hexahedra_device};   // 128 bytes per query
+// queries (and their cursors, or nullptr) -> rows of max_hits prims and one total per query (rt_overlap.hpp, rt_trioverlap.hpp,
+// rt_hexoverlap.hpp).  One arithmetic for both math modes: the flags stay 0.  The tree is the ray queries' (ensure_query_tree, so
+// RT_ACCEL_REFIT applies); no rho is passed.  max_hits is checked whatever n is; with 0 only the counts are made and prims may be null.
+static int region_query(rt_tracer* t, QueryWhere w, const RegionShape& s, const char* who, const float* queries, const int32_t* after,
+                        size_t n, uint32_t max_hits, int32_t* prims, uint32_t* counts) {
+  const std::string misaligned = w.device ? fmt("%s: %s must be 16-byte aligned, after, prims and counts 4-byte aligned", who, s.array) : std::string();
+  return run_query(t, w, n, {{queries, n * s.floats * 4u, 16u}, {after, n * 4u, 4u, true}},
+                   {{prims, n * max_hits * 4u, 4u, max_hits == 0u}, {counts, n * 4u, 4u}}, misaligned.c_str(),
+                   [&](rt_tracer* h) {
+                     if (max_hits > RT_MAX_HITS) h->set_error(fmt("%s: max_hits = %u (0 to %u)", who, max_hits, RT_MAX_HITS));
+                     return max_hits <= RT_MAX_HITS;
+                   }, nullptr,
+                   [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {
+                     enqueue_launch(h, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+                       return s.launch(p, b, static_cast<uint32_t>(n), static_cast<const float*>(in[0]), static_cast<const int32_t*>(in[1]), max_hits,
+                                       static_cast<int32_t*>(out[0]), static_cast<uint32_t*>(out[1]), st);
+                     });
+                   });
+}
+
+static const RegionShape kBoxes{8u, "boxes", rtk::launch_overlap};
+static const RegionShape kTriangles{12u, "tris", rtk::launch_overlap_triangles};
+static const RegionShape kHexahedra{32u, "hexa", rtk::launch_overlap_hexahedra};   // 128 bytes per query
 
 int rt_tracer_overlap(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                       uint32_t* counts) {
-  return region_host(t, kBoxes, "rt_tracer_overlap", boxes, after, n, max_hits, prims, counts);
+  return region_query(t, on_host(), kBoxes, "rt_tracer_overlap", boxes, after, n, max_hits, prims, counts);
 }
-
 int rt_tracer_overlap_device(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                              uint32_t* counts, void* stream) {
-  return region_device(t, kBoxes, "rt_tracer_overlap_device", boxes, after, n, max_hits, prims, counts, stream);
+  return region_query(t, on_device(stream), kBoxes, "rt_tracer_overlap_device", boxes, after, n, max_hits, prims, counts);
 }
-
 int rt_tracer_overlap_triangles(rt_tracer* t, const float* tris, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                                 uint32_t* counts) {
-  return region_host(t, kTriangles, "rt_tracer_overlap_triangles", tris, after, n, max_hits, prims, counts);
+  return region_query(t, on_host(), kTriangles, "rt_tracer_overlap_triangles", tris, after, n, max_hits, prims, counts);
 }
-
 int rt_tracer_overlap_triangles_device(rt_tracer* t, const float* tris, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                                        uint32_t* counts, void* stream) {
-  return region_device(t, kTriangles, "rt_tracer_overlap_triangles_device", tris, after, n, max_hits, prims, counts, stream);
+  return region_query(t, on_device(stream), kTriangles, "rt_tracer_overlap_triangles_device", tris, after, n, max_hits, prims, counts);
 }
-
 int rt_tracer_overlap_hexahedra(rt_tracer* t, const float* hexa, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                                 uint32_t* counts) {
-  return region_host(t, kHexahedra, "rt_tracer_overlap_hexahedra", hexa, after, n, max_hits, prims, counts);
+  return region_query(t, on_host(), kHexahedra, "rt_tracer_overlap_hexahedra", hexa, after, n, max_hits, prims, counts);
 }
-
 int rt_tracer_overlap_hexahedra_device(rt_tracer* t, const float* hexa, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                                        uint32_t* counts, void* stream) {
-  return region_device(t, kHexahedra, "rt_tracer_overlap_hexahedra_device", hexa, after, n, max_hits, prims, counts, stream);
+  return region_query(t, on_device(stream), kHexahedra, "rt_tracer_overlap_hexahedra_device", hexa, after, n, max_hits, prims, counts);
 }
 
-int rt_tracer_sphere_cast(rt_tracer* t, const float* sweeps, size_t n, rt_hit* hits) {
-  if (!t || !query_args_ok(t, n, {sweeps, hits})) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_sphere_cast(b, sweeps, n, hits); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_sweeps = staged_in<float>(t->queries.in[0], sweeps, n * 8u, st);
-    enqueue_sphere_cast(t, n, d_sweeps, room<float4>(t->queries.out[0], n), st);
-    staged_out<float4>(hits, t->queries.out[0], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+// sweeps -> one record per sweep (rt_spherecast.hpp).  One arithmetic for both math modes and no hit rule: the flags stay 0.  The
+// tree is the ray queries' (ensure_query_tree, so RT_ACCEL_REFIT applies); the walk's allowance beyond r takes the tracer's slack.
+static int sphere_cast_query(rt_tracer* t, QueryWhere w, const float* sweeps, size_t n, rt_hit* hits) {
+  return run_query(t, w, n, {{sweeps, n * 32u, 16u}}, {{hits, n * 16u, 16u}}, "rt_tracer_sphere_cast_device: sweeps and hits must be 16-byte aligned",
+                   no_check, nullptr, [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {
+                     enqueue_launch(h, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+                       return rtk::launch_sphere_cast(p, b, static_cast<float>(h->queries.slack_milli) / 1000.0f, static_cast<uint32_t>(n),
+                                                      static_cast<const float*>(in[0]), static_cast<float4*>(out[0]), st);
+                     });
+                   });
 }
-
+int rt_tracer_sphere_cast(rt_tracer* t, const float* sweeps, size_t n, rt_hit* hits) { return sphere_cast_query(t, on_host(), sweeps, n, hits); }
 int rt_tracer_sphere_cast_device(rt_tracer* t, const float* sweeps, size_t n, rt_hit* hits, void* stream) {
-  if (!t || !query_args_ok(t, n, {sweeps, hits}) ||
-      !query_aligned_ok(t, n, {{sweeps, 16u}, {hits, 16u}}, "rt_tracer_sphere_cast_device: sweeps and hits must be 16-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_sphere_cast_device(b, sweeps, n, hits, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_sphere_cast(t, n, sweeps, reinterpret_cast<float4*>(hits), static_cast<hipStream_t>(stream));
-  });
+  return sphere_cast_query(t, on_device(stream), sweeps, n, hits);
 }
 
+// query triangles -> one record and one witness per triangle (rt_tridistance.hpp), with enqueue_closest's tree, flags and rho_c
+static int triangle_distance_query(rt_tracer* t, QueryWhere w, const float* tris, size_t n, rt_hit* hits, rt_witness* witness) {
+  return run_query(t, w, n, {{tris, n * 48u, 16u}}, {{hits, n * 16u, 16u}, {witness, n * 16u, 16u}},
+                   "rt_tracer_triangle_distance_device: tris, hits and witness must be 16-byte aligned", no_check, nullptr,
+                   [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {
+                     enqueue_launch(h, st, 0u, true, [&](const rtk::TraceParams& p, const rtk::BvhParams* b) {
+                       return rtk::launch_triangle_distance(p, b, closest_rho(h), static_cast<uint32_t>(n), static_cast<const float*>(in[0]),
+                                                            static_cast<float4*>(out[0]), static_cast<float4*>(out[1]), st);
+                     });
+                   });
+}
 int rt_tracer_triangle_distance(rt_tracer* t, const float* tris, size_t n, rt_hit* hits, rt_witness* witness) {
-  if (!t || !query_args_ok(t, n, {tris, hits, witness})) return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_triangle_distance(b, tris, n, hits, witness); }, [&] {
-    if (n == 0u) return;
-    const hipStream_t st = host_query_stream(t);
-    const float* d_tris = staged_in<float>(t->queries.in[0], tris, n * 12u, st);
-    enqueue_triangle_distance(t, n, d_tris, room<float4>(t->queries.out[0], n), room<float4>(t->queries.out[1], n), st);
-    staged_out<float4>(hits, t->queries.out[0], n, st);
-    staged_out<float4>(witness, t->queries.out[1], n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
+  return triangle_distance_query(t, on_host(), tris, n, hits, witness);
 }
-
 int rt_tracer_triangle_distance_device(rt_tracer* t, const float* tris, size_t n, rt_hit* hits, rt_witness* witness, void* stream) {
-  if (!t || !query_args_ok(t, n, {tris, hits, witness}) ||
-      !query_aligned_ok(t, n, {{tris, 16u}, {hits, 16u}, {witness, 16u}},
-                        "rt_tracer_triangle_distance_device: tris, hits and witness must be 16-byte aligned"))
-    return RT_ERR_INVALID;
-  return query_call(t, [&](rt_tracer* b) { return rt_tracer_triangle_distance_device(b, tris, n, hits, witness, stream); }, [&] {
-    if (n == 0u) return;
-    t->use_device();
-    enqueue_triangle_distance(t, n, tris, reinterpret_cast<float4*>(hits), reinterpret_cast<float4*>(witness), static_cast<hipStream_t>(stream));
-  });
+  return triangle_distance_query(t, on_device(stream), tris, n, hits, witness);
 }
 
 int rt_dbg_feature_normals(const rt_float4* rows, size_t count, int edges_layout, void* out, size_t capacity_bytes, uint64_t info[8]) {
@@ -824,7 +719,9 @@ int rt_dbg_feature_normals(const rt_float4* rows, size_t count, int edges_layout
 }
 
 int rt_tracer_pick(rt_tracer* t, const uint32_t* pixels, size_t n, rt_hit* hits, float* rays) {
-  if (!t || !query_args_ok(t, n, {pixels, hits})) return RT_ERR_INVALID;
+  const QueryIns in = {{pixels, n * 8u, 4u}};
+  const QueryOuts out = {{hits, n * 16u, 16u}, {rays, n * 24u, 4u, true}};
+  if (!t || !query_arrays_ok(t, on_host(), n, in, out, nullptr)) return RT_ERR_INVALID;
   const auto forward = [&](rt_tracer* b) {
     multi_push_camera(t);                                                // the camera of the whole frame
     return rt_tracer_pick(b, pixels, n, hits, rays);
@@ -836,14 +733,8 @@ int rt_tracer_pick(rt_tracer* t, const uint32_t* pixels, size_t n, rt_hit* hits,
         return RT_ERR_INVALID;
       }
     }
-    return guarded(t, [&] {
-      if (n == 0u) return;
-      const hipStream_t st = host_query_stream(t);
-      const uint32_t* d_pixels = staged_in<uint32_t>(t->queries.in[0], pixels, n * 2u, st);
-      enqueue_query(t, n, nullptr, d_pixels, rays ? room<float>(t->queries.out[1], n * 6u) : nullptr, room<float4>(t->queries.out[0], n), st);
-      staged_out<float4>(hits, t->queries.out[0], n, st);
-      if (rays) staged_out<float>(rays, t->queries.out[1], n * 6u, st);
-      HIP_CHECK(hipStreamSynchronize(st));
+    return query_body(t, on_host(), n, in, out, nullptr, [&](rt_tracer* h, DevIn d_in, DevOut d_out, hipStream_t st) {
+      enqueue_query(h, n, nullptr, static_cast<const uint32_t*>(d_in[0]), static_cast<float*>(d_out[1]), static_cast<float4*>(d_out[0]), st);
     });
   });
 }

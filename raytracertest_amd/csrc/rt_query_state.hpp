@@ -19,8 +19,9 @@ struct QueryState {
     return stream_q;
   }
   void wait() { if (done) HIP_CHECK(hipEventSynchronize(done)); }
-  // Grow-only staging of the host-array entry points, as bytes: the call says what they hold (staged_in<T>, room<T>, staged_out<T>).
-  // None uses more than two inputs and two outputs (rt_tracer_closest_all) and each waits for its stream before it returns.
+  // Grow-only staging of the host-array entry points, as bytes: query_body (rt_query_api.hpp) stages the i-th input array of a
+  // call's description through in[i] and its i-th output through out[i] (staged_in, room, staged_out).  No query has more than two
+  // inputs and two outputs (rt_tracer_closest_all) and each waits for its stream before it returns.
   DevArray<unsigned char> in[2], out[2];
   // RT_QUERY_BVH (rt_bvh_host.hpp, rt_bvh.hpp): the tree of the scene of generation bvh_scene, built by the first query in
   // that mode after an upload (rt_query_api.hpp, under api_mu).  The buffers are grow-only; a rebuild waits for the queries.
