@@ -10,10 +10,11 @@
  *   - HitTriangle / Ray / normalize(cross)  : pinned bit-exactly by the reference's 8
  *     UnitTests/TriangleHitTest.cpp cases (tests/golden/triangle_hit_kats.json).
  *   - everything else (ray generation, lens sampling, RNG stream, farthest-hit select,
- *     shading, accumulation, BGRA conversion) : PARITY UNPINNED by the reference -- it
- *     ships no golden image, no recorded RGBA and seeds from time(nullptr)
- *     (RayTracer/Random.cu:45).  The reference cannot be compiled here (needs nvcc,
- *     cuRAND, glm, gtest; none present), so the restatement is reviewed line by line.
+ *     shading, accumulation, BGRA conversion) : the reference ships no golden image, no
+ *     recorded RGBA and seeds from time(nullptr) (RayTracer/Random.cu:45).  Pinned, in strict
+ *     arithmetic, by the reference's own kernel headers compiled for the CPU
+ *     (ref_driver.cpp, ref_shim/; tests/test_reference_parity.py), with glm, cuRAND and
+ *     sin / cos as stand-ins; the fma mode stays reviewed line by line.
  *
  * Third-party arithmetic that is not under the reference tree is restated from its
  * published algorithm:
