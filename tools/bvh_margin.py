@@ -17,7 +17,13 @@ tests/spherecast_expect.random_sweeps (narrow and wide radii, a share cut at tma
 rho_c against the query triangle's bounding box: TriangleDistance, hits and witnesses, scan against BVH, on 2^LOG2 queries of
 tests/tridistance_expect.mixed_queries (and the lattice's tie queries), unbounded and within the median distance, C4's scene and
 the lattice scene.
-Usage: bvh_margin.py [--closest | --nearest | --spherecast | --tridistance] [--out FILE.json] [--rays LOG2]"""
+--graze: the sweep on the grazing populations of tests/graze_cases.py (`above` on the general, flat and sliver scenes of 2 000
+triangles, `rivals` on the pairs), whose targeted hits sit at a conditioning of 2^-10 .. 2^-6: Intersect under both hit rules,
+Occluded, IntersectAll (max_hits 4) and Exposure with a world-space table, scan against BVH on the same tracer, with two more
+slacks (0.003, 0.001: rt_dbg_query_accel_slack counts in thousandths).  Per query and
+slack the rows that differ and, of them, the rows the contract does not let differ: the scan winner is well conditioned
+(Intersect, also by distance class), or a well-conditioned in-interval hit of the scan's own first 16 was lost (the others).
+Usage: bvh_margin.py [--closest | --nearest | --spherecast | --tridistance | --graze] [--out FILE.json] [--rays LOG2]"""
 import argparse
 import json
 import os
@@ -30,6 +36,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SLACKS = (1000, 300, 100, 30, 10, 0)
+GRAZE_SLACKS = (1000, 300, 100, 30, 10, 3, 1, 0)        # --graze goes on to the smallest non-zero slack there is
 
 
 def closest_margin(R, scenes, log2_points):
@@ -169,6 +176,89 @@ def spherecast_margin(R, scenes, log2_sweeps):
     return res
 
 
+def graze_margin(R, log2_rays):
+    import exposure_expect as ee
+    import graze_cases as gc
+    from query_accel_expect import WELL_CONDITIONED, conditioning
+    n = min(1 << log2_rays, 1 << 16) // 81 * 81
+    res = {"version": R.api.load_library().rt_version().decode(), "rho": 2.0 ** -8, "slacks": list(GRAZE_SLACKS), "rays": n, "scenes": {}}
+    first_fail = {}
+
+    def well_of(scan, segs, rows):
+        """(n, k) bool: the entries of the scan's lists that are well-conditioned triangle hits."""
+        sh, sc = scan
+        k = sh.shape[1]
+        ratio = np.stack([conditioning(segs[:, :6], rows, sh["prim"][:, j]) for j in range(k)], 1)
+        return (np.arange(k)[None, :] < sc[:, None]) & (ratio >= WELL_CONDITIONED) & np.isfinite(ratio)
+
+    def lists_lost(scan, got, segs, rows, m):
+        """Rows whose tree list lacks a well-conditioned hit of the scan's list that sorts before its end."""
+        sh, sc = scan
+        gh, gcnt = got
+        well = well_of(scan, segs, rows)
+        held = (sh["prim"][:, :, None] == gh["prim"][:, None, :m]).any(axis=2)
+        last = np.clip(gcnt.astype(np.int64) - 1, 0, None)
+        lt, lp = gh["t"][np.arange(len(last)), last], gh["prim"][np.arange(len(last)), last]
+        room = (gcnt < m)[:, None] | (sh["t"] < lt[:, None]) | ((sh["t"] == lt[:, None]) & (sh["prim"] < lp[:, None]))
+        return (well & ~held & room).any(axis=1)
+
+    for name in ("general", "flat", "slivers", "pairs"):
+        if name == "pairs":
+            rows, pop = gc.pairs(999)
+        else:
+            rows = gc.slivers(2000) if name == "slivers" else gc.SCENES[name](2000, size=0.6)
+            pop = gc.rays(rows, "above", n, seed=51)
+        rays, segs = pop["rays"], gc.segments(pop)
+        groups = gc.exposure_groups(pop, 12)
+        xsegs = np.concatenate([ee.exposure_segments(p, d, world=True) for p, d in groups])
+        out = {str(s): {} for s in GRAZE_SLACKS}
+        for nearest in (False, True):
+            g = R.RayTracer((64, 48), (0, 0, 0), (0.0, 0.0), 70.0, 3.0, 0.05, seed=1, nearest_hit=nearest)
+            assert g.UploadScene(rows)
+            scan = g.Intersect(rays)
+            well = conditioning(rays, rows, scan["prim"]) >= WELL_CONDITIONED
+            if not nearest:
+                occ, lists, xocc, xlists = g.Occluded(segs), g.IntersectAll(segs, 16), g.Occluded(xsegs), g.IntersectAll(xsegs, 16)
+                lists4 = (np.ascontiguousarray(lists[0][:, :4]), np.minimum(lists[1], 4))
+                owell, xwell = well_of(lists, segs, rows).any(axis=1), well_of(xlists, xsegs, rows).any(axis=1)
+            g.SetQueryAcceleration(True)
+            for slack in GRAZE_SLACKS:
+                g.DebugQueryAccelSlack(slack)
+                per = out[str(slack)]
+                got = g.Intersect(rays)
+                differ = (got.view(np.uint32).reshape(-1, 4) != scan.view(np.uint32).reshape(-1, 4)).any(axis=1)
+                key = "intersect_nearest" if nearest else "intersect_farthest"
+                per[key] = {"rows": int(rays.shape[0]), "differ": int(differ.sum()), "differ_well_conditioned": int((differ & well).sum()),
+                            "by_distance_class": [int((differ & well & (pop["L"] == c)).sum()) for c in range(len(gc.L_CLASSES))]}
+                if not nearest:
+                    o = g.Occluded(segs)
+                    per["occluded"] = {"rows": int(segs.shape[0]), "differ": int((o != occ).sum()), "invented": int((o & ~occ).sum()),
+                                       "differ_well_conditioned": int((owell & occ & ~o).sum())}
+                    a = g.IntersectAll(segs, 4)
+                    d4 = (a[0].view(np.uint32).reshape(-1, 16) != lists4[0].view(np.uint32).reshape(-1, 16)).any(axis=1) | (a[1] != lists4[1])
+                    per["intersect_all_4"] = {"rows": int(segs.shape[0]), "differ": int(d4.sum()),
+                                              "differ_well_conditioned": int(lists_lost(lists4, a, segs, rows, 4).sum())}
+                    masks = np.concatenate([g.Exposure(p, d, world=True) for p, d in groups])
+                    xo = ~ee.unpack_masks(masks).reshape(-1)
+                    per["exposure"] = {"rows": int(xsegs.shape[0]), "differ": int((xo != xocc).sum()), "invented": int((xo & ~xocc).sum()),
+                                       "differ_well_conditioned": int((xwell & xocc & ~xo).sum())}
+            g.DebugQueryAccelSlack(1000)
+            g.close()
+        res["scenes"][name] = out
+        for slack in GRAZE_SLACKS:
+            for q, v in out[str(slack)].items():
+                if v["differ_well_conditioned"]:
+                    first_fail[q] = max(first_fail.get(q, -1), slack)
+    # per query the largest slack at which a row the contract protects differed (absent: at none, not even bare boxes)
+    res["largest_slack_milli_with_a_well_conditioned_difference"] = first_fail
+    worst = max(first_fail.values(), default=-1)
+    clean = min(s for s in GRAZE_SLACKS if s > worst)                     # the smallest probed slack above it: still the scan
+    res["smallest_clean_slack_milli"] = clean
+    res["allowance_over_reach"] = {"at_least": 1000.0 / clean, "below": (1000.0 / worst) if worst > 0 else None,
+                                   "bare_boxes_differ": worst >= 0}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -177,9 +267,17 @@ def main():
     ap.add_argument("--nearest", action="store_true")
     ap.add_argument("--spherecast", action="store_true")
     ap.add_argument("--tridistance", action="store_true")
+    ap.add_argument("--graze", action="store_true")
     a = ap.parse_args()
     import raytracertest_amd as R
     from raytracertest_amd import scenes
+    if a.graze:
+        txt = json.dumps(graze_margin(R, a.rays), indent=1)
+        print(txt)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(txt + "\n")
+        return
     if a.closest or a.nearest or a.spherecast or a.tridistance:
         margin = tridistance_margin if a.tridistance else spherecast_margin if a.spherecast else nearest_margin if a.nearest else closest_margin
         txt = json.dumps(margin(R, scenes, a.rays), indent=1)
