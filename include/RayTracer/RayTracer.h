@@ -266,6 +266,34 @@ public:
     if (!OverlapHexahedra(hexa, maxHits, prims, counts)) counts.clear();
     return counts;
   }
+  // Section query (rt_mi355x.h, rt_tracer_section): planes holds 8 floats per plane or slab, n.x n.y n.z d0 d1 _ _ _ (the pads are
+  // never read): the region d0 <= n.x <= d1, a plane when d0 == d1, a half-space when one end is infinite; n is used as given.
+  // prims, counts, after and maxHits are Overlap's: row i holds the min(counts[i], maxHits) lowest primitives slab i cuts, then
+  // RT_PRIM_NONE; counts[i] is their TOTAL behind the cursor.  Closed: touching counts; a non-finite normal, a NaN or d0 > d1
+  // cuts nothing.  A vector whose size is no multiple of 8, or an after of another length: false, the outputs untouched.
+  bool Section(const std::vector<float>& planes, uint32_t maxHits, std::vector<int32_t>& prims, std::vector<uint32_t>& counts,
+               const std::vector<int32_t>& after = std::vector<int32_t>()) {
+    return Region(rt_tracer_section, 8, planes, maxHits, prims, counts, after);
+  }
+  // The same, returning the counts: empty when the arguments were rejected or the call failed (LastError()).
+  std::vector<uint32_t> Section(const std::vector<float>& planes, uint32_t maxHits = 0) {
+    std::vector<int32_t> prims;
+    std::vector<uint32_t> counts;
+    if (!Section(planes, maxHits, prims, counts)) counts.clear();
+    return counts;
+  }
+  // Where the plane n.x = d0 (side 0) or d1 (side 1) cuts the prims Section returned (rt_mi355x.h, rt_tracer_section_segments):
+  // prims holds perPlane ints per plane (a row of Section with maxHits = perPlane); cuts[j] is the rt_cut of prims[j] --
+  // RT_CUT_SEGMENT from p0 to p1, RT_CUT_TOUCH, RT_CUT_COPLANAR, RT_CUT_CIRCLE or RT_CUT_NONE.  Sizes that do not fit: false,
+  // cuts untouched.
+  bool SectionSegments(const std::vector<float>& planes, const std::vector<int32_t>& prims, uint32_t perPlane, uint32_t side,
+                       std::vector<rt_cut>& cuts) {
+    if (!mImpl || planes.size() % 8 != 0 || perPlane == 0 || prims.size() != planes.size() / 8 * perPlane) return false;
+    std::vector<rt_cut> out(prims.size());
+    if (rt_tracer_section_segments(mImpl, planes.data(), prims.data(), planes.size() / 8, perPlane, side, out.data()) != RT_OK) return false;
+    cuts.swap(out);
+    return true;
+  }
   // Swept query (rt_mi355x.h, rt_tracer_sphere_cast): sweeps holds 8 floats per sweep -- origin, direction (used as given), the
   // sphere's radius, tmax; the centre runs along o + t*d for 0 <= t <= tmax.  hits[i].t = the time of first contact, u, v the
   // barycentrics of the contact point on triangle prim (0, 0 for a sphere), prim = RT_PRIM_NONE when nothing is touched.  A

@@ -660,8 +660,8 @@ int  rt_tracer_overlap(rt_tracer* t, const float* boxes, const int32_t* after, s
  * synchronisation.  boxes must be 16-byte aligned; otherwise RT_ERR_INVALID. */
 int  rt_tracer_overlap_device(rt_tracer* t, const float* boxes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
                               uint32_t* counts, void* stream);
-/* Which primitives of the tracer's scene touch a TRIANGLE (the narrow phase of mesh against mesh, a cut plane or a portal given
- * as two triangles, a scene's own self-intersections).
+/* Which primitives of the tracer's scene touch a TRIANGLE (the narrow phase of mesh against mesh, a portal given as two
+ * triangles, a scene's own self-intersections; for a cut PLANE see rt_tracer_section, under section queries).
  *   tris        n x 12 floats: P0.x P0.y P0.z _ P1.x P1.y P1.z _ P2.x P2.y P2.z _ (three 16-byte loads).  The three pad floats
  *               are never read into any arithmetic: NaNs there change nothing.
  *   max_hits, after, prims, counts
@@ -952,6 +952,98 @@ int  rt_tracer_triangle_distance(rt_tracer* t, const float* tris, size_t n, rt_h
 /* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
  * synchronisation.  tris, hits and witness must be 16-byte aligned; otherwise RT_ERR_INVALID. */
 int  rt_tracer_triangle_distance_device(rt_tracer* t, const float* tris, size_t n, rt_hit* hits, rt_witness* witness, void* stream);
+
+/* ---- section queries ------------------------------------------------------------------------------
+ * The region query for a plane or a slab, and where the plane cuts what it returned.  Both follow the conventions of the region
+ * queries (rt_tracer_overlap): host and _device forms, the cursor, scheduling -- a query never cancels or joins a running Trace --
+ * and a multi-device handle answers from its first band. */
+/* Which primitives of the tracer's scene a PLANE or a SLAB cuts (a cross-section, a contour slice, clipping by a half-space, the
+ * layer between two heights): the region d0 <= n.x <= d1, a plane when d0 == d1, a half-space when one end is infinite.
+ *   planes      n x 8 floats: nx ny nz d0 d1 _ _ _ (two 16-byte loads).  The three pad floats are never read into any arithmetic:
+ *               NaNs there change nothing.  n is used as given, NOT normalised.  The query is valid when nx, ny, nz are finite
+ *               and d0 <= d1 as a plain comparison (-inf and +inf ends are allowed); any other query -- a NaN anywhere among
+ *               the five, an infinite normal component, d0 > d1 -- accepts NOTHING, spheres included.  n = 0 is not special: it
+ *               gets what the arithmetic gives (every projection is 0, so everything is accepted when d0 <= 0 <= d1).
+ *   max_hits, after, prims, counts
+ *               exactly as in rt_tracer_overlap: max_hits 0 .. RT_MAX_HITS (above that RT_ERR_INVALID; 0: counts only, prims
+ *               may be NULL); row i holds the min(counts[i], max_hits) LOWEST accepted prims in ascending order, then
+ *               RT_PRIM_NONE; counts[i] is the TOTAL behind the cursor, not capped; after[i] = the row's last prim continues:
+ *               nothing repeats and nothing is lost.
+ *   triangle    one arithmetic in RT_MATH_FMA and RT_MATH_STRICT: every operation is one separately rounded fp32 operation; min
+ *               and max are IEEE minNum / maxNum.  On the record the renderer intersects (v0, e1, e2; for edge-format scenes the
+ *               uploaded rows), with corners A = v0, B = fl(v0 + e1), C = fl(v0 + e2), and
+ *                 p(X) = (nx*X.x + ny*X.y) + nz*X.z
+ *               the triangle is accepted when the query is valid, none of p(A), p(B), p(C) is a NaN,
+ *                 min(min(p(A), p(B)), p(C)) <= d1  and  max(max(p(A), p(B)), p(C)) >= d0.
+ *               Plain comparisons, closed: touching counts.  There is no second step: a triangle meets a slab exactly when its
+ *               corners' projections meet the interval.
+ *   sphere      a sphere of the scene is its surface.  Centre S, radius r:  pc = p(S), rn = r * sqrt((nx*nx + ny*ny) + nz*nz), the
+ *               square root correctly rounded.  Accepted when the query is valid, pc - rn <= d1 and pc + rn >= d0.  A slab is
+ *               unbounded, so the ball touches it exactly when the surface does.
+ * Everything else -- no scene, spheres alone, n = 0, NULL arrays (RT_ERR_INVALID, outputs untouched), scheduling, multi-device
+ * handles, RT_ACCEL_REFIT -- is rt_tracer_overlap's.
+ * RT_QUERY_BVH: for a child box [lo, hi] take per axis xlo = (n_axis >= 0 ? lo : hi) and xhi the other end, and pmin = p(xlo),
+ * pmax = p(xhi) by the same expression.  The child is skipped only when pmin > d1 or pmax < d0 (a NaN never skips); there is NO
+ * inflation, and the result is bit for bit the scan's rows and counts for every input whatsoever.  Why: rounding is monotone --
+ * x -> fl(n_axis * x) is monotone in the direction of n_axis's sign, fl(a + b) is monotone in both operands, and flushing
+ * denormals keeps both -- so for every fp32 point P with lo <= P <= hi componentwise pmin <= p(P) <= pmax whenever no value is
+ * a NaN; A, B and C lie inside the record's tree box (rt_tracer_overlap, above) and inside every ancestor's child box, so a
+ * skipped child holds only records the rule rejects.  Non-finite records go through the always-tested list, and a walk whose
+ * stack overflowed recomputes from every leaf record.  rt_dbg_query_accel_slack has no effect on this query.
+ * Range.  Only second powers enter (a product of a normal component and a coordinate, the sphere rule's dot(n, n)): the rows of
+ * a scene and its planes multiplied by 2^k -- every length and the normal times s, d0 and d1 times s*s -- are the same rows for
+ * k = -61 .. 62 on inputs of order 1 (tests/test_section_range.py); beyond, the products reach +inf or the subnormals.  Scan and
+ * tree agree at every scale. */
+/* Host arrays: planes n*8, after n or NULL, prims n*max_hits (NULL allowed when max_hits = 0), counts n.  Returns with the
+ * results in host memory. */
+int  rt_tracer_section(rt_tracer* t, const float* planes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                       uint32_t* counts);
+/* Device pointers on the tracer's device: only enqueues on `stream` (a hipStream_t; NULL is HIP's default stream), no host
+ * synchronisation.  planes must be 16-byte aligned; otherwise RT_ERR_INVALID. */
+int  rt_tracer_section_device(rt_tracer* t, const float* planes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                              uint32_t* counts, void* stream);
+/* WHERE the plane n.x = d0 (side = 0) or n.x = d1 (side = 1) cuts the primitives rt_tracer_section returned: a post-pass over its
+ * rows, one record per prim.
+ *   planes      the n planes of the section query, as above.
+ *   prims       n * per_plane int32, record j belongs to plane j / per_plane: a row of rt_tracer_section with max_hits =
+ *               per_plane, or any prims of the caller's.  per_plane 1 .. RT_MAX_HITS and side 0 or 1; otherwise RT_ERR_INVALID.
+ *   cuts        n * per_plane rt_cut.  One arithmetic in both math modes, every operation rounded separately, the division and
+ *               the square roots correctly rounded.  With d the chosen offset and sX = p(X) - d for X = A, B, C (the sign of an
+ *               fp32 difference is exact) a corner is above (s > 0), below (s < 0) or on the plane (s == 0).
+ *     RT_CUT_NONE      the prim is RT_PRIM_NONE or outside the scene (nothing is read), the plane is invalid, some s is a NaN, or
+ *                      all corners are strictly on one side.  The record is all zeros.
+ *     RT_CUT_COPLANAR  all three corners are on the plane.  The points are zero.
+ *     RT_CUT_TOUCH     no corner is above, or none is below, and one or two corners are on the plane.  p0, p1 are the on-corners,
+ *                      bit for bit; one on-corner: both points are that corner; two: in the order of the walk A -> B -> C -> A
+ *                      (A, B), (B, C) or (C, A).
+ *     RT_CUT_SEGMENT   at least one corner above and one below.  The endpoints are the on-corner (bit for bit), if there is one,
+ *                      and the crossings of the edges whose ends are strictly opposite.  A crossing is always computed from the
+ *                      below end L towards the above end U:  t = sL / (sL - sU),  X = L + t*(U - L) per component (a
+ *                      subtraction, a product, a sum).  Two records that share an edge with bit-equal corners therefore give
+ *                      bit-equal points, whichever way each one walks the edge.  p0 is where the walk A -> B -> C -> A leaves the
+ *                      above side, p1 where it enters it: the segment p0 -> p1 runs along n x (e1 x e2), so the contour of an
+ *                      outward-wound solid runs counter-clockwise seen from the tip of n, holes clockwise.
+ *     features         f0 | f1 << 8, f0 of p0 and f1 of p1: 0 / 1 / 2 the edge AB / BC / CA, 4 / 5 / 6 the corner A / B / C.  A
+ *                      caller with adjacency can chain contours without comparing floats.  0 for NONE, COPLANAR and CIRCLE.
+ *     RT_CUT_CIRCLE    a sphere (centre S, radius r) with |pc - d| <= rn, pc and rn as in the section rule, nn = dot(n, n):
+ *                      p0 = S + ((d - pc) / nn) * n, the circle's centre; p1 = {sqrt(max(r*r - ((d - pc)*(d - pc)) / nn, 0)), 0, 0},
+ *                      its radius.  Otherwise RT_CUT_NONE.
+ * No tree is walked and no scene is needed (every record is then RT_CUT_NONE); n = 0 is a no-op; a NULL array with n > 0 is
+ * RT_ERR_INVALID.  Chaining segments into polylines with a tolerance, capping cut solids and regions bounded by several planes
+ * are not offered: corners of neighbouring records need not be bit-equal in general, because B = fl(v0 + e1). */
+#define RT_CUT_NONE     0
+#define RT_CUT_SEGMENT  1
+#define RT_CUT_TOUCH    2
+#define RT_CUT_COPLANAR 3
+#define RT_CUT_CIRCLE   4
+typedef struct rt_cut { float p0[3]; int32_t kind; float p1[3]; int32_t features; } rt_cut;   /* 32 bytes */
+/* Host arrays: planes n*8, prims n*per_plane, cuts n*per_plane. */
+int  rt_tracer_section_segments(rt_tracer* t, const float* planes, const int32_t* prims, size_t n, uint32_t per_plane, uint32_t side,
+                                rt_cut* cuts);
+/* Device pointers on the tracer's device: only enqueues on `stream`.  planes and cuts must be 16-byte aligned; otherwise
+ * RT_ERR_INVALID. */
+int  rt_tracer_section_segments_device(rt_tracer* t, const float* planes, const int32_t* prims, size_t n, uint32_t per_plane,
+                                       uint32_t side, rt_cut* cuts, void* stream);
 
 /* ---- one frame sharded over several GPUs, continued: the entry points --------------------------- */
 /* Same constructor, device list added: band k runs on devices[k] (ordinals may repeat: several bands per

@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "rt_tracer_overlap", "rt_tracer_overlap_device",
     "rt_tracer_overlap_triangles", "rt_tracer_overlap_triangles_device",
     "rt_tracer_overlap_hexahedra", "rt_tracer_overlap_hexahedra_device",
+    "rt_tracer_section", "rt_tracer_section_device", "rt_tracer_section_segments", "rt_tracer_section_segments_device",
     "rt_tracer_sphere_cast", "rt_tracer_sphere_cast_device",
     "rt_tracer_triangle_distance", "rt_tracer_triangle_distance_device",
     "rt_tracer_set_query_accel", "rt_tracer_query_accel_info", "rt_dbg_bvh_build", "rt_dbg_query_accel_slack",
@@ -133,6 +134,9 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), (
 # rt_side: the side half of a signed point query's answer
 SIDE_DTYPE = np.dtype([("s", np.float32), ("feature", np.int32)])
 FEATURE_NONE, FEATURE_FACE, FEATURE_SPHERE = -1, 0, 7
+# rt_cut: where a plane cuts one primitive (rt_tracer_section_segments)
+CUT_DTYPE = np.dtype([("p0", np.float32, 3), ("kind", np.int32), ("p1", np.float32, 3), ("features", np.int32)])
+CUT_NONE, CUT_SEGMENT, CUT_TOUCH, CUT_COPLANAR, CUT_CIRCLE = 0, 1, 2, 3, 4
 # rt_witness: the query-side half of a triangle distance query's answer
 WITNESS_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("where", np.int32)])
 _FEATURE_KEYS = ("triangles", "vertices", "edges", "contributing", "build_us", "bytes")
@@ -377,6 +381,11 @@ def load_library():
         if hasattr(L, "rt_tracer_overlap_hexahedra"):     # (an older build selected by RT_MI355X_LIB for an A/B has no hexahedron regions)
             L.rt_tracer_overlap_hexahedra.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
             L.rt_tracer_overlap_hexahedra_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
+        if hasattr(L, "rt_tracer_section"):               # (an older build selected by RT_MI355X_LIB for an A/B has no section queries)
+            L.rt_tracer_section.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
+            L.rt_tracer_section_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
+            L.rt_tracer_section_segments.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp]
+            L.rt_tracer_section_segments_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp]
         if hasattr(L, "rt_tracer_sphere_cast"):           # (an older build selected by RT_MI355X_LIB for an A/B has no swept query)
             L.rt_tracer_sphere_cast.argtypes = [vp, vp, C.c_size_t, vp]
             L.rt_tracer_sphere_cast_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
@@ -1320,6 +1329,102 @@ class RayTracer:
         exceeds max_hits (1 <= max_hits <= RT_MAX_HITS is the row length of one round).  Returns (prims, offsets) as OverlapAll
         does: region i's prims, ascending, are prims[offsets[i]:offsets[i + 1]]."""
         return self._region_all(self.OverlapHexahedra, self._hexahedra_array, "OverlapHexahedraAll", corners, max_hits)
+
+    # ---- planes and slabs (rt_tracer_section / rt_tracer_section_segments, and their _device forms) -------------------------
+    @staticmethod
+    def plane_rows(normal, d0, d1=None):
+        """(n, 8) float32 {nx, ny, nz, d0, d1, 0, 0, 0}: the slabs d0 <= normal.x <= d1 of Section, a plane where d1 is None (d1 =
+        d0).  normal (3,) or (n, 3), used as given (not normalised); d0, d1 scalars or (n,); the three broadcast to the longest."""
+        nrm = np.asarray(normal, np.float32).reshape(-1, 3)
+        a = np.asarray(d0, np.float32).reshape(-1)
+        b = a if d1 is None else np.asarray(d1, np.float32).reshape(-1)
+        sizes = (nrm.shape[0], a.shape[0], b.shape[0])
+        out = np.zeros((0 if 0 in sizes else max(sizes), 8), np.float32)
+        out[:, 0:3], out[:, 3], out[:, 4] = nrm, a, b
+        return out
+
+    @staticmethod
+    def _planes_array(who, planes):
+        """-> contiguous (n, 8) float32 {nx, ny, nz, d0, d1, 0, 0, 0}: from (n, 8) as it is (the pads are never read), from (n, 5)
+        {n xyz, d0, d1}, or from (n, 4) {n xyz, d}, a plane."""
+        p = np.asarray(planes, np.float32)
+        if p.ndim == 0 or p.shape[-1] not in (4, 5, 8):
+            raise ValueError("%s: expected (n, 4), (n, 5) or (n, 8) float32 planes, got shape %s" % (who, p.shape))
+        if p.shape[-1] != 8:
+            w = p.shape[-1]
+            p = p.reshape(-1, w)
+            q = np.zeros((p.shape[0], 8), np.float32)
+            q[:, :w] = p
+            if w == 4:
+                q[:, 4] = p[:, 3]
+            p = q
+        return np.ascontiguousarray(p).reshape(-1, 8)
+
+    def Section(self, planes, max_hits=RT_MAX_HITS, after=None):
+        """The primitives each plane or slab cuts (rt_tracer_section): the region d0 <= n.x <= d1, a plane when d0 == d1, a
+        half-space when one end is infinite (plane_rows builds the rows).  planes: (n, 8) float32 {nx, ny, nz, d0, d1, -, -, -},
+        (n, 5) {n xyz, d0, d1} or (n, 4) {n xyz, d}; closed, touching counts; a non-finite normal, a NaN or d0 > d1 cuts nothing.
+        max_hits, after and the returned (prims (n, max_hits) int32, counts (n,) uint32) are Overlap's: the lowest cut prims in
+        ascending order, then PRIM_NONE, and the TOTAL behind the cursor (SectionAll chains it).  Independent of the tracer's
+        arithmetic mode and hit rule; a sphere is its surface.  numpy in, numpy out, on return.  A contiguous (n, 8) float32
+        torch tensor on the tracer's device -> ((n, max_hits) int32, (n,) int32) tensors, enqueued on
+        torch.cuda.current_stream() without a host synchronisation; after is then a contiguous (n,) int32 tensor."""
+        if type(planes).__module__.startswith("torch"):
+            return self._region_tensor("Section", "planes", 8, self._lib.rt_tracer_section_device, planes, max_hits, after)
+        return self._region_query("Section", "plane", self._planes_array, self._lib.rt_tracer_section, planes, max_hits, after)
+
+    def SectionAll(self, planes, max_hits=RT_MAX_HITS):
+        """Every primitive each plane or slab cuts, numpy only: Section repeated with the cursor while a count exceeds max_hits
+        (1 <= max_hits <= RT_MAX_HITS is the row length of one round).  Returns (prims, offsets) as OverlapAll does: plane i's
+        prims, ascending, are prims[offsets[i]:offsets[i + 1]]."""
+        return self._region_all(self.Section, self._planes_array, "SectionAll", planes, max_hits)
+
+    def SectionSegments(self, planes, prims, side=0):
+        """Where the plane n.x = d0 (side 0) or n.x = d1 (side 1) cuts the prims Section returned (rt_tracer_section_segments):
+        prims of shape (n,) or (n, per_plane) int32, per_plane <= RT_MAX_HITS -> CUT_DTYPE of the same shape {p0, kind, p1,
+        features}: CUT_SEGMENT from p0 to p1 along n x (e1 x e2), CUT_TOUCH (the on-corners), CUT_COPLANAR, CUT_CIRCLE (a
+        sphere: p0 the circle's centre, p1[0] its radius) or CUT_NONE (PRIM_NONE, a prim outside the scene, no cut).  features
+        = f0 | f1 << 8 names the edge (0 AB, 1 BC, 2 CA) or corner (4 A, 5 B, 6 C) each point lies on.  torch: planes a
+        contiguous (n, 8) float32 tensor, prims a contiguous (n,) or (n, per_plane) int32 tensor on its device -> (..., 8)
+        float32 {p0 xyz, kind bits, p1 xyz, features bits}, enqueued on torch.cuda.current_stream()."""
+        side = int(side)
+        if type(planes).__module__.startswith("torch"):
+            import torch
+            if planes.dtype != torch.float32 or planes.dim() != 2 or planes.shape[1] != 8 or not planes.is_contiguous():
+                raise ValueError("SectionSegments: expected a contiguous (n, 8) float32 tensor")
+            stream = self._stream_of("SectionSegments", "planes", planes)
+            n = planes.shape[0]
+            if (not type(prims).__module__.startswith("torch") or prims.dtype != torch.int32 or prims.dim() not in (1, 2) or
+                    prims.shape[0] != n or not prims.is_contiguous() or prims.device != planes.device):
+                raise ValueError("SectionSegments: prims must be a contiguous (n,) or (n, per_plane) int32 tensor on the planes' device")
+            k = 1 if prims.dim() == 1 else self._max_hits("SectionSegments", prims.shape[1])
+            cuts = torch.empty(tuple(prims.shape) + (8,), dtype=torch.float32, device=planes.device)
+            self._check(self._lib.rt_tracer_section_segments_device(self._h, planes.data_ptr(), prims.data_ptr(), n, k, side,
+                                                                    cuts.data_ptr(), stream))
+            return cuts
+        q = self._planes_array("SectionSegments", planes)
+        r = np.ascontiguousarray(prims, np.int32)
+        if r.ndim not in (1, 2) or r.shape[0] != q.shape[0]:
+            raise ValueError("SectionSegments: expected the int32 prims (n,) or (n, per_plane) of these %d planes" % q.shape[0])
+        k = 1 if r.ndim == 1 else self._max_hits("SectionSegments", r.shape[1])
+        cuts = np.zeros(r.shape, CUT_DTYPE)
+        self._check(self._lib.rt_tracer_section_segments(self._h, q.ctypes.data, r.ctypes.data, q.shape[0], k, side, cuts.ctypes.data))
+        return cuts
+
+    def Slice(self, normal, offsets):
+        """The contour segments of the scene in the planes normal.x = offsets[i], numpy only: a plane per offset (plane_rows),
+        SectionAll, then SectionSegments on every returned prim.  Returns (cuts, layer_offsets): the CUT_DTYPE records of kind
+        CUT_SEGMENT of all layers, flat; layer i's are cuts[layer_offsets[i]:layer_offsets[i + 1]], layer_offsets (n + 1,)
+        int64.  Touching and coplanar triangles and spheres' circles are left out (SectionSegments returns them)."""
+        planes = self.plane_rows(normal, np.asarray(offsets, np.float32).reshape(-1))
+        n = planes.shape[0]
+        prims, po = self.SectionAll(planes)
+        owner = np.repeat(np.arange(n), np.diff(po))
+        cuts = self.SectionSegments(planes[owner], prims) if prims.size else np.zeros(0, CUT_DTYPE)
+        keep = cuts["kind"] == CUT_SEGMENT
+        layer_offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(np.bincount(owner[keep], minlength=n), out=layer_offsets[1:])
+        return cuts[keep], layer_offsets
 
     @staticmethod
     def box_corners(lo, hi):

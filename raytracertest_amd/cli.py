@@ -1,6 +1,6 @@
 """Headless front end: `python -m raytracertest_amd.cli`.  The reference's command line
 (OpenGLView/App.cpp:62-184: -w -h -s -i -u -cx -cy -cz -cxa -cya -f -l -a, integer values,
-defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --tri-distance / --spherecast / --focus; the image is saved
+defaults App.cpp:11-23) without the GUI, plus scene/seed/output options and --pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --section / --tri-distance / --spherecast / --focus; the image is saved
 in the reference's BMP format (Common/Bitmap.h).  Same options as tools/rt_cli.cpp."""
 import argparse
 import math
@@ -67,10 +67,13 @@ def build_parser():
     p.add_argument("--overlap-hexa", type=_overlap_hexa, default=None, metavar="X0,Y0,Z0,...,X7,Y7,Z7[,K]", dest="overlap_hexa",
                    help="print `overlap-hexa count`, the number of primitives that touch the hexahedron with those eight corners in "
                         "box-like order, then one line `prim` for each of the K lowest (default 8)")
+    p.add_argument("--section", type=_section, default=None, metavar="NX,NY,NZ,D0[,D1[,K]]",
+                   help="print `section count`, the number of primitives the slab D0 <= N.x <= D1 cuts (D1 defaults to D0: a plane), "
+                        "then for each of the K lowest (default 8) one line `prim kind features x0 y0 z0 x1 y1 z1`: its cut at D0")
     p.add_argument("--select", type=_select, default=None, metavar="X0,Y0,X1,Y1,FAR[,NEAR]",
                    help="print `select count`, then one line `prim` for every primitive that touches the frustum of the pixel "
                         "rectangle X0,Y0 .. X1,Y1 between the ray parameters NEAR (default 0) and FAR")
-    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --tri-distance / --spherecast / --focus through the scene's BVH instead of the scan")
+    p.add_argument("--accel", action="store_true", help="--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --section / --tri-distance / --spherecast / --focus through the scene's BVH instead of the scan")
     p.add_argument("--focus", type=_xy, default=None, metavar="X,Y",
                    help="before the trace, set the focal length to the distance to what pixel X,Y sees; prints it")
     return p
@@ -140,6 +143,17 @@ def _tri_distance(s):
 
 def _overlap_hexa(s):
     return _overlap(s, 24)
+
+
+def _section(s):
+    v = s.split(",")
+    if len(v) not in (4, 5, 6):
+        raise ValueError(s)
+    k = int(v[5]) if len(v) == 6 else 8
+    if k < 0:
+        raise ValueError(s)
+    f = [float(x) for x in v[:5]]
+    return tuple(f[:4]) + (f[4] if len(f) == 5 else f[3], k)
 
 
 def _select(s):
@@ -283,6 +297,16 @@ def main(argv=None):
         print("overlap-hexa %d" % counts[0])
         for prim in prims[0, :min(int(counts[0]), a.overlap_hexa[24])]:
             print("%d" % prim)
+    if a.section is not None:
+        try:
+            planes = g.plane_rows(a.section[:3], a.section[3], a.section[4])
+            prims, counts = g.Section(planes, a.section[5])
+            cuts = g.SectionSegments(planes, prims)[0] if a.section[5] else ()
+        except Exception as e:
+            sys.exit("--section: %s" % e)
+        print("section %d" % counts[0])
+        for prim, c in zip(prims[0, :min(int(counts[0]), a.section[5])], cuts):
+            print("%d %d %d %.9g %.9g %.9g %.9g %.9g %.9g" % ((prim, c["kind"], c["features"]) + tuple(c["p0"]) + tuple(c["p1"])))
     if a.select is not None:
         try:
             prims = g.SelectRect(*a.select[:4], near=a.select[5], far=a.select[4])

@@ -14,6 +14,8 @@
 //   nearest_*kernel    <- a point's k nearest primitives in order, with a continuation cursor (rt_nearest.hpp)
 //   region_*kernel     <- the primitives that touch a caller's box (rt_overlap.hpp, which holds the two kernels), triangle
 //                         (rt_trioverlap.hpp) or hexahedron (frustum, oriented box; rt_hexoverlap.hpp), lowest first, and how many
+//   section_*kernel   <- the primitives a plane or slab cuts (region_kernel and a tree kernel of its own), and the cut segments
+//                         (rt_section.hpp)
 //   tridistance_*kernel <- the primitive nearest to a caller's triangle, and where on both (rt_tridistance.hpp)
 //   spherecast_*kernel <- a moving sphere's first contact with the scene (rt_spherecast.hpp)
 //   sides_kernel       <- the side of the surface a point query's records lie on (rt_sides.hpp)
@@ -32,6 +34,7 @@
 #include "rt_overlap.hpp"
 #include "rt_trioverlap.hpp"
 #include "rt_hexoverlap.hpp"
+#include "rt_section.hpp"
 #include "rt_tridistance.hpp"
 #include "rt_spherecast.hpp"
 #include "rt_sides.hpp"

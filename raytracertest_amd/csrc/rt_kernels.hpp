@@ -226,6 +226,17 @@ hipError_t launch_overlap_triangles(const TraceParams& p, const BvhParams* b, ui
 hipError_t launch_overlap_hexahedra(const TraceParams& p, const BvhParams* b, uint32_t n, const float* hexa, const int* after,
                                     uint32_t max_hits, int* prims, uint32_t* counts, hipStream_t st);
 
+// The section query (rt_section.hpp): n slabs {nx, ny, nz, d0, d1, -, -, -}, 16-byte aligned; after, max_hits, prims and counts as
+// launch_overlap's.  One arithmetic for both math modes; one slab per lane in both forms.  The tree form (a kernel of its own)
+// reads neither b->rho nor a slack: its prune is exact.
+hipError_t launch_section(const TraceParams& p, const BvhParams* b, uint32_t n, const float* planes, const int* after, uint32_t max_hits,
+                          int* prims, uint32_t* counts, hipStream_t st);
+
+// The cut post-pass (rt_section.hpp): n slabs, n * per_plane prims of them (as launch_section wrote them) -> as many 32-byte records
+// {p0 xyz, kind, p1 xyz, features}, 16-byte aligned, of the plane n.x = d0 (side 0) or d1 (side 1).  No tree.
+hipError_t launch_section_segments(const TraceParams& p, uint32_t n, uint32_t per_plane, uint32_t side, const float* planes, const int* prims,
+                                   void* cuts, hipStream_t st);
+
 // The triangle-shaped proximity query (rt_tridistance.hpp): n query triangles {P0 xyz, d2max, P1 xyz, -, P2 xyz, -}, 16-byte
 // aligned; hits[i] as launch_closest's for the nearest primitive of the triangle, witness[i] = {the winning point on the query
 // triangle, bits of its int32 candidate index}, or {0, 0, 0, -1} in both.  One arithmetic for both math modes; one query per lane

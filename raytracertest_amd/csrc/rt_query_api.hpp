@@ -671,6 +671,42 @@ int rt_tracer_overlap_hexahedra_device(rt_tracer* t, const float* hexa, const in
   return region_query(t, on_device(stream), kHexahedra, "rt_tracer_overlap_hexahedra_device", hexa, after, n, max_hits, prims, counts);
 }
 
+// slabs: the region query of rt_section.hpp, a RegionShape as the three above (the tree form is a kernel of its own)
+static const RegionShape kPlanes{8u, "planes", rtk::launch_section};
+int rt_tracer_section(rt_tracer* t, const float* planes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                      uint32_t* counts) {
+  return region_query(t, on_host(), kPlanes, "rt_tracer_section", planes, after, n, max_hits, prims, counts);
+}
+int rt_tracer_section_device(rt_tracer* t, const float* planes, const int32_t* after, size_t n, uint32_t max_hits, int32_t* prims,
+                             uint32_t* counts, void* stream) {
+  return region_query(t, on_device(stream), kPlanes, "rt_tracer_section_device", planes, after, n, max_hits, prims, counts);
+}
+
+// slabs and n * per_plane prims of them -> as many rt_cut (rt_section.hpp); no tree and nothing to prepare
+static int section_segments_query(rt_tracer* t, QueryWhere w, const char* who, const float* planes, const int32_t* prims, size_t n,
+                                  uint32_t per_plane, uint32_t side, rt_cut* cuts) {
+  return run_query(t, w, n, {{planes, n * 32u, 16u}, {prims, n * per_plane * 4u, 4u}}, {{cuts, n * per_plane * 32u, 16u}},
+                   "rt_tracer_section_segments_device: planes and cuts must be 16-byte aligned, prims 4-byte aligned",
+                   [&](rt_tracer* h) {
+                     if (side > 1u) { h->set_error(fmt("%s: side = %u (0 or 1)", who, side)); return false; }
+                     return query_row_ok(h, who, "per_plane", per_plane);
+                   }, nullptr,
+                   [&](rt_tracer* h, DevIn in, DevOut out, hipStream_t st) {
+                     enqueue_launch(h, st, 0u, false, [&](const rtk::TraceParams& p, const rtk::BvhParams*) {
+                       return rtk::launch_section_segments(p, static_cast<uint32_t>(n), per_plane, side, static_cast<const float*>(in[0]),
+                                                           static_cast<const int32_t*>(in[1]), out[0], st);
+                     });
+                   });
+}
+int rt_tracer_section_segments(rt_tracer* t, const float* planes, const int32_t* prims, size_t n, uint32_t per_plane, uint32_t side,
+                               rt_cut* cuts) {
+  return section_segments_query(t, on_host(), "rt_tracer_section_segments", planes, prims, n, per_plane, side, cuts);
+}
+int rt_tracer_section_segments_device(rt_tracer* t, const float* planes, const int32_t* prims, size_t n, uint32_t per_plane, uint32_t side,
+                                      rt_cut* cuts, void* stream) {
+  return section_segments_query(t, on_device(stream), "rt_tracer_section_segments_device", planes, prims, n, per_plane, side, cuts);
+}
+
 // sweeps -> one record per sweep (rt_spherecast.hpp).  One arithmetic for both math modes and no hit rule: the flags stay 0.  The
 // tree is the ray queries' (ensure_query_tree, so RT_ACCEL_REFIT applies); the walk's allowance beyond r takes the tracer's slack.
 static int sphere_cast_query(rt_tracer* t, QueryWhere w, const float* sweeps, size_t n, rt_hit* hits) {

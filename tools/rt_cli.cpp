@@ -42,6 +42,9 @@ struct Args {
   bool overlap_hexa = false;
   float overlap_h[24] = {0};                        // --overlap-hexa 24 floats[,K]: the eight corners C0 .. C7
   uint32_t overlap_hexa_k = 8;
+  bool section = false;
+  float section_p[5] = {0, 0, 0, 0, 0};             // --section NX,NY,NZ,D0[,D1[,K]]: the normal and the slab's ends
+  uint32_t section_k = 8;
   bool select = false;
   float select_v[6] = {0, 0, 0, 0, 0, 0};           // --select X0,Y0,X1,Y1,FAR[,NEAR]
   bool tri_distance = false;
@@ -159,6 +162,17 @@ bool parse_overlap(const char* s, float* out, uint32_t& k, int m = 6) {
   }
 }
 
+// "NX,NY,NZ,D0", "...,D1" or "...,D1,K": a plane (D1 = D0) or slab and an optional row length
+bool parse_section(const char* s, float out[5], uint32_t& k) {
+  int commas = 0;
+  for (const char* q = s; *q; ++q) commas += *q == ',';
+  if (commas == 4 || commas == 5) return parse_overlap(s, out, k, 5);    // (without K the fifth float ends the string)
+  uint32_t none = 0;
+  if (commas != 3 || !parse_overlap(s, out, none, 4)) return false;
+  out[4] = out[3];
+  return true;
+}
+
 // "X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2" or "...,R": the three corners of a triangle and an optional search distance (out[9] keeps its
 // value when R is absent)
 bool parse_tri_distance(const char* s, float out[10]) {
@@ -248,13 +262,16 @@ void usage() {
             "                      that found it, the nearest point on the triangle and on the scene; `tri-distance -1` when there is none)\n"
             "       [--overlap-hexa X0,Y0,Z0,...,X7,Y7,Z7[,K]] (prints `overlap-hexa count`, the number of primitives that touch the hexahedron\n"
             "                      with those eight corners in box-like order, then one line `prim` for each of the K lowest, default 8)\n"
+            "       [--section NX,NY,NZ,D0[,D1[,K]]] (prints `section count`, the number of primitives the slab D0 <= N.x <= D1 cuts, D1\n"
+            "                      defaults to D0: a plane; then for each of the K lowest, default 8, one line\n"
+            "                      `prim kind features x0 y0 z0 x1 y1 z1`: its cut at D0)\n"
             "       [--select X0,Y0,X1,Y1,FAR[,NEAR]] (prints `select count`, then one line `prim` for every primitive that touches the frustum\n"
             "                      of the pixel rectangle X0,Y0 .. X1,Y1 between the ray parameters NEAR, default 0, and FAR)\n"
             "       [--focus X,Y] (focal length := distance to what pixel X,Y sees, before the trace; prints it)\n"
             "       [--spherecast X,Y,Z,DX,DY,DZ,R[,TMAX]] (prints `spherecast prim t u v x y z`: the first contact of a sphere of radius\n"
             "                      R whose centre moves from X,Y,Z along DX,DY,DZ for 0 <= t <= TMAX, and the contact point;\n"
             "                      `spherecast -1` when there is none)\n"
-            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --tri-distance / --spherecast / --focus through the scene's BVH instead of the scan)");
+            "       [--accel]     (--pick / --hits / --closest / --signed / --exposure / --nearest X,Y,Z / --overlap / --overlap-tri / --section / --tri-distance / --spherecast / --focus through the scene's BVH instead of the scan)");
 }
 
 // one region query of the command line: `label count`, then up to k of its prims; false, with the error line, when it fails
@@ -330,6 +347,10 @@ int main(int argc, char** argv) {
     else if (k == "--tri-distance") {
       if (!parse_tri_distance(next("--tri-distance"), a.tri_distance_t)) { std::fprintf(stderr, "--tri-distance wants X0,Y0,Z0,X1,Y1,Z1,X2,Y2,Z2[,R]\n"); return 2; }
       a.tri_distance = true;
+    }
+    else if (k == "--section") {
+      if (!parse_section(next("--section"), a.section_p, a.section_k)) { std::fprintf(stderr, "--section wants NX,NY,NZ,D0[,D1[,K]]\n"); return 2; }
+      a.section = true;
     }
     else if (k == "--overlap-hexa") {
       if (!parse_overlap(next("--overlap-hexa"), a.overlap_h, a.overlap_hexa_k, 24)) { std::fprintf(stderr, "--overlap-hexa wants X0,Y0,Z0,...,X7,Y7,Z7[,K]\n"); return 2; }
@@ -547,6 +568,22 @@ int main(int argc, char** argv) {
     for (int k = 0; k < 8; ++k)
       for (int c = 0; c < 3; ++c) hexa[4 * k + c] = a.overlap_h[3 * k + c];
     if (!print_region(tracer, &rt::RayTracer::OverlapHexahedra, "overlap-hexa", hexa, a.overlap_hexa_k)) return 1;
+  }
+  if (a.section) {
+    const float* c = a.section_p;
+    const std::vector<float> planes = {c[0], c[1], c[2], c[3], c[4], 0.0f, 0.0f, 0.0f};
+    std::vector<int32_t> prims;
+    std::vector<uint32_t> counts;
+    std::vector<rt_cut> cuts;
+    if (!tracer.Section(planes, a.section_k, prims, counts) || (a.section_k != 0 && !tracer.SectionSegments(planes, prims, a.section_k, 0, cuts))) {
+      std::fprintf(stderr, "rt_cli: --section: %s\n", a.section_k > RT_MAX_HITS ? "K out of range" : tracer.LastError().c_str());
+      return 1;
+    }
+    std::printf("section %u\n", counts[0]);
+    for (uint32_t j = 0; j < a.section_k && j < counts[0]; ++j) {
+      const rt_cut& x = cuts[j];
+      std::printf("%d %d %d %.9g %.9g %.9g %.9g %.9g %.9g\n", prims[j], x.kind, x.features, x.p0[0], x.p0[1], x.p0[2], x.p1[0], x.p1[1], x.p1[2]);
+    }
   }
   if (a.select) {
     // the frustum between the pinhole rays of the four corner pixels (x0,y0), (x1,y0), (x0,y1), (x1,y1) that holds everything
